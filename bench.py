@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Headline benchmark: clips/s of the AdaFocus offline-inference hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
-  N > 1 from a bare shell: bench.py re-executes itself under `python -m torch.distributed.run --nnodes=1
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+  N > 1 from a bare shell: bench.py runs itself as a child `python -m torch.distributed.run --nnodes=1
   --nproc-per-node N --master-addr 127.0.0.1 --master-port <free>` (one rank per GPU, RCCL), the counterpart of the
   reference's own `mp.spawn` + `init_process_group` (ACT/main_dist.py:59,79-80); launched under torchrun already
   (WORLD_SIZE set), it just joins.  `--dry-run` exercises the same launch / barrier / max-over-ranks / gather / JSON
@@ -17,8 +17,14 @@ Glancer features and policy actions are producers upstream of the path and are g
 before the timed region (the actions are a forced uniform-random 7x7 grid sequence so the gather
 addresses scatter).
 
-Prints ONE JSON line (rank 0) with the contract fields plus:
+A plain run sets up, warms up, times K steps, writes the outputs (--dump-outputs) and prints ONE JSON line (rank 0) with
+the contract fields (`value` in clips/s, `ms_per_step` = milliseconds of one timed step) and nothing else measured.
+--dump-outputs DIR: the arrays the last timed step handed its caller (hot_path's logits, last-step logits and features), as
+DIR/<name>.npy in float32; inputs and weights are seeded, so two builds compare output for output.
+--full adds everything else, measured after the headline steps:
+  sustained / serial_value -- the same step soaked for >= 3 s / on one stream
   roofline     -- dominant kernel (implicit-GEMM conv on fp32 MFMA): algorithmic FLOP / HIP-event time
+  gather, also, next_rows, full_forward -- the other configurations, precisions and pieces of the forward
   cpu_baseline -- the oracle (torch-CPU restatement of the reference) timed on this box's host cores
 """
 import argparse
@@ -519,11 +525,30 @@ def free_port():
 
 
 def self_launch(n):
-    """`python bench.py --gpus N` from a bare shell: become `torch.distributed.run` with N local ranks."""
+    """`python bench.py --gpus N` from a bare shell: run `torch.distributed.run` with N local ranks as a fresh child process (this
+    process may have opened the HIP runtime while counting devices) and exit with its status."""
+    import subprocess
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1",
            "--master-port", str(free_port()), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush()
-    os.execv(sys.executable, cmd)
+    raise SystemExit(subprocess.call(cmd))
+
+
+# --dump-outputs writes at most this many bytes of array data in all
+DUMP_BYTES = 60 * 1000 * 1000
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as `path`/<name>.npy in float32.  When they hold more than DUMP_BYTES in all, each one is cut to the same
+    fixed, seeded sample of its flattened elements (the sample depends only on the shapes), so two builds still compare element for element."""
+    os.makedirs(path, exist_ok=True)
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items() if v is not None}
+    total = sum(v.nbytes for v in host.values())
+    for name, v in host.items():
+        if total > DUMP_BYTES:
+            keep = v.size * DUMP_BYTES // total
+            v = v.reshape(-1)[np.sort(np.random.Generator(np.random.PCG64(2024)).choice(v.size, keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(v, dtype=np.float32))
 
 
 class DryModel:
@@ -551,14 +576,17 @@ def main():
     ap.add_argument("--cpu-clips", type=int, default=None, help="(deprecated) 0 = skip the CPU baseline leg")
     ap.add_argument("--cpu-threads", type=int, default=0)
     ap.add_argument("--profile-steps", type=int, default=5, help="per-launch HIP-event passes for the roofline (median per launch)")
-    ap.add_argument("--sustained-steps", type=int, default=240, help="extra soak after the timed region (>= 3 s); 0 = skip")
-    ap.add_argument("--full", action="store_true", help="also time the full forward (glancer + policy + hot path)")
+    ap.add_argument("--sustained-steps", type=int, default=240, help="(--full) extra soak after the timed region (>= 3 s); 0 = skip")
+    ap.add_argument("--full", action="store_true", help="after the headline steps also measure everything else: sustained and serial rates, "
+                    "roofline and gather pricing, the other configurations and precisions, the full forward, the CPU baseline")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="write what the last timed step computed (logits, last, feature) as DIR/<name>.npy, float32")
     ap.add_argument("--math", choices=["f32", "split_bf16"], default="f32",
                     help="conv arithmetic: f32 = fp32 matrix pipe (default, the reported configuration); split_bf16 = opt-in, "
                          "fp32 operands as three exact bf16 parts on the bf16 matrix pipe, fp32 accumulate")
     ap.add_argument("--tiles", type=str, default="", help="comma list of per-conv tile overrides (tuning)")
     ap.add_argument("--fuse", type=int, default=-1, help="trunk layer fusion: -1 = library default, 0 = off, 1 = on")
-    ap.add_argument("--skip-extras", action="store_true", help="only the timed steps + roofline pass (for rocprofv3 runs)")
+    ap.add_argument("--skip-extras", action="store_true", help="with --full: only the timed steps + roofline pass (for rocprofv3 runs)")
     ap.add_argument("--streams", type=int, default=3, help="HIP streams the steps are round-robined over (batch i+1's "
                     "trunk overlaps batch i's latency-bound GRU scan); 1 = strictly serial steps")
     ap.add_argument("--dry-run", action="store_true", help="CPU/gloo stand-in for the step: tests the launcher and the protocol")
@@ -654,11 +682,13 @@ def main():
     comm_stream = torch.cuda.Stream(device=dev) if (world > 1 and not dry) else None
 
     b, t, p = a.batch, a.frames, a.patch
+    # every input is seeded (per rank): the same arguments give the same inputs, run after run
     if dry:
         model, sd, trunk = DryModel(b, t), None, None
-        frames = torch.randn(b * t, 3, 8, 8)
-        actions = torch.rand(b * t, 2)
-        gvec = torch.randn(b, t, 1280)
+        gen = torch.Generator().manual_seed(100 + rank)
+        frames = torch.randn(b * t, 3, 8, 8, generator=gen)
+        actions = torch.rand(b * t, 2, generator=gen)
+        gvec = torch.randn(b, t, 1280, generator=gen)
         streams = [None] * max(a.streams, 1)
     else:
         from adafocus_amd.gfv_net import GFV
@@ -670,7 +700,7 @@ def main():
         frames = torch.from_numpy(synth.synth_frames(b, t, 224, seed=100 + rank)).to(dev).view(b * t, 3, 224, 224)
         _, act_np = synth.synth_actions(b * t, 7, seed=2 + rank)
         actions = torch.from_numpy(act_np).to(dev)
-        gvec = torch.randn((b, t, 1280), device=dev)
+        gvec = torch.from_numpy(np.random.Generator(np.random.PCG64(300 + rank)).standard_normal((b, t, 1280), dtype=np.float32)).to(dev)
         model.focuser.net.set_math(a.math)
         trunk = model.focuser.net._sync()
         if a.tiles:
@@ -681,15 +711,16 @@ def main():
 
     def step(i):
         # consecutive batches are independent: enqueue them on alternating streams (software pipelining of
-        # the eval loop); every step still does all of its work, and the timed region ends with a device sync
+        # the eval loop); every step still does all of its work, and the timed region ends with a device sync.
+        # Returns what the caller of the path receives: hot_path's (logits, last, feature), `last` gathered over the ranks
         if dry:
-            last = model.hot_path(frames, gvec, actions, b, t)[1]
-            return gather_logits(last) if world > 1 else last
+            logits, last, feature = model.hot_path(frames, gvec, actions, b, t)
+            return {"logits": logits, "last": gather_logits(last) if world > 1 else last, "feature": feature}
         with torch.no_grad(), torch.cuda.stream(streams[i % len(streams)]):
-            logits, last, _ = model.hot_path(frames, gvec, actions, b, t)
+            logits, last, feature = model.hot_path(frames, gvec, actions, b, t)
             if world > 1:      # the logits all-gather on its own stream, ordered after this step's scan; the next trunk does not wait for it
                 last = gather_logits_async(last, comm_stream)
-        return last
+        return {"logits": logits, "last": last, "feature": feature}
 
     def timed_steps(n):
         sync()
@@ -716,9 +747,12 @@ def main():
     for i in range(a.warmup):
         step(i)
     elapsed, per_rank_s, out = timed_steps(a.steps)
-    assert torch.isfinite(out).all()
+    assert torch.isfinite(out["last"]).all()
     if world > 1:
-        assert out.shape[0] == world * b, out.shape      # the gathered logits of every rank's shard
+        assert out["last"].shape[0] == world * b, out["last"].shape      # the gathered logits of every rank's shard
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, out)
+    del out
 
     value = b * world * a.steps / elapsed
     res = {
@@ -742,13 +776,14 @@ def main():
     if dry:
         res["dry_run"] = True
 
-    if a.sustained_steps > 0 and not a.skip_extras:
+    # ---- everything below the headline is --full only ----------------------------------------------
+    if a.full and a.sustained_steps > 0 and not a.skip_extras:
         # the same step for >= 3 s: the 30-step figure above is a ~0.4 s sample
         s_el, _, _ = timed_steps(a.sustained_steps)
         res["sustained"] = {"value": round(b * world * a.sustained_steps / s_el, 2), "unit": "clips/s", "steps": a.sustained_steps,
                             "seconds": round(s_el, 3), "ms_per_step": round(1e3 * s_el / a.sustained_steps, 3)}
 
-    if not dry and len(streams) > 1 and not a.skip_extras:
+    if a.full and not dry and len(streams) > 1 and not a.skip_extras:
         # the same steps strictly serial (one stream): `value` overlaps batch i+1's trunk with batch i's latency-bound GRU scan
         # and launch tails across %d streams, each with its own trunk workspace; this is what a single stream gets
         saved = streams
@@ -762,7 +797,7 @@ def main():
                                "note": "`value` uses %d streams (and %d trunk workspaces of %.1f GB); this is the strictly serial rate" % (
                                    len(saved), len(saved), (trunk._lib.adaf_resnet50_workspace_bytes(trunk._net, b * t, p) / 1e9) if trunk is not None else 0.0)}
 
-    if rank == 0 and not dry:
+    if a.full and rank == 0 and not dry:
         # ---- roofline of the dominant kernel: per-launch HIP events on the launch stream -------------
         conv_ms = conv_fl = tot_ms = conv_by = 0.0
         nconv = 0
@@ -934,7 +969,7 @@ def main():
                 res.setdefault("also", {})["config5_T16_P144_efficientnet_b3"] = {"error": repr(exc)[:300]}
         if os.environ.get("ADAF_BENCH_LAUNCHES"):
             res["launches"] = [{k: (round(v, 4) if isinstance(v, float) else v) for k, v in e.items()} for e in per_launch]
-        if a.full and not a.skip_extras:
+        if not a.skip_extras:
             try:
                 scan = frames.view(b, t * 3, 224, 224)
                 with torch.no_grad():

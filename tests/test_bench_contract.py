@@ -1,5 +1,5 @@
-"""bench.py's output contract (one JSON line on stdout with the driver's keys plus `roofline` and `cpu_baseline`),
-checked by running it for two short steps on the GPU."""
+"""bench.py's output contract (one JSON line on stdout with the driver's keys; with --full also `roofline` and `cpu_baseline`),
+checked by running it for a few short steps on the GPU."""
 import json
 import os
 import subprocess
@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.gpu
 def test_bench_emits_one_json_line_with_the_contract_keys():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--cpu-clips", "2",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--cpu-clips", "2",
                           "--cpu-threads", "8", "--batch", "8", "--profile-steps", "1"],
                          capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -54,13 +54,35 @@ def test_bench_emits_one_json_line_with_the_contract_keys():
 
 
 @pytest.mark.gpu
+def test_bench_plain_run_dumps_what_the_last_step_computed(tmp_path):
+    """A plain run on the GPU: the headline only, and --dump-outputs writes hot_path's logits, last-step logits and features of the last
+    timed step as float32 .npy files (B = 8, T = 16, 2048 + 1280 features), finite and within the 64 MB cap."""
+    import numpy as np
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "8",
+                          "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.strip().startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    r = json.loads(lines[0])
+    assert r["steps"] == 3 and r["warmup"] == 1 and r["dtype"] == "f32" and r["value"] > 0
+    assert abs(r["value"] - 8 * 3 / (r["ms_per_step"] * 3e-3)) / r["value"] < 0.01
+    for k in ("sustained", "serial_value", "roofline", "also", "next_rows", "cpu_baseline"):
+        assert k not in r, k
+    assert sorted(os.listdir(tmp_path)) == ["feature.npy", "last.npy", "logits.npy"]
+    d = {n: np.load(tmp_path / (n + ".npy")) for n in ("feature", "last", "logits")}
+    assert d["last"].shape == (8, 200) and d["feature"].shape == (8, 16, 2048 + 1280) and d["logits"].size % 200 == 0
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in d.values())
+    assert sum(v.nbytes for v in d.values()) <= 64e6
+
+
+@pytest.mark.gpu
 def test_bench_two_ranks_sharing_one_gpu():
     """`python bench.py --gpus 2 --share-gpu` from a bare shell: the launcher spawns two ranks, both run the REAL hot path on
     GPU 0 (their persistent GRU scans and trunks co-run on one device) and all-gather their logits (over gloo: RCCL refuses
     two ranks on one device).  Proves the N > 1 code path on hardware; the throughput is not a scaling figure."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--steps", "6", "--warmup", "2",
-                          "--batch", "16", "--skip-extras", "--sustained-steps", "0", "--profile-steps", "1"],
+                          "--batch", "16", "--full", "--skip-extras", "--sustained-steps", "0", "--profile-steps", "1"],
                          capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip().startswith("{")]

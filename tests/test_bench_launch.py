@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def _run(extra, env_drop=("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")):
     env = {k: v for k, v in os.environ.items() if k not in env_drop}
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run", "--steps", "3", "--warmup", "1",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run", "--full", "--steps", "3", "--warmup", "1",
                           "--sustained-steps", "4", "--batch", "4", "--frames", "2"] + extra,
                          capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -55,7 +55,7 @@ def test_bench_summary_is_the_tail_of_the_line():
     """The driver keeps only the last few KB of bench.py's stdout: the compact `summary` object must be the LAST key of the line and parse
     back from its last 2 KB on its own -- from a dry run, and from a full line of the previous round (every row filled)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run", "--steps", "3", "--warmup", "1", "--sustained-steps", "4",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run", "--full", "--steps", "3", "--warmup", "1", "--sustained-steps", "4",
                           "--batch", "4", "--frames", "2"], capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
 
@@ -87,6 +87,62 @@ def test_bench_summary_is_the_tail_of_the_line():
     assert s["evaluate_loop"] == full["next_rows"]["evaluate_loop"]["value"]
     assert s["sth_shipped"]["full_forward"] == full["also"]["sth_shipped_T8_12_P144"]["full_forward_from_uint8"]["value"]
     assert s["config3"]["clips_per_s"] == full["also"]["config3_T16_P128_act"]["clips_per_s"]
+
+
+def test_bench_plain_run_is_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """A plain run (no --full) measures the headline and nothing else: --steps sets the timed steps, `ms_per_step` is one of them, and none of
+    the --full entries is in the line.  --dump-outputs writes what the last timed step returned as float32 .npy files, the same from run to
+    run (the inputs are seeded)."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+
+    def run(d):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run", "--steps", "5", "--warmup", "2", "--batch", "4",
+                              "--frames", "2", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.strip().startswith("{")]
+        assert len(lines) == 1, out.stdout[-2000:]
+        return json.loads(lines[0])
+
+    r = run(tmp_path / "a")
+    assert r["steps"] == 5 and r["warmup"] == 2 and r["ms_per_step"] > 0 and r["unit"] == "clips/s" and r["higher_is_better"] is True
+    assert abs(r["ms_per_step"] - 1e3 * 4 / r["value"]) <= 6e-4 + 1e-3 * r["ms_per_step"]      # (ms_per_step is rounded to 3 decimals)
+    for k in ("sustained", "serial_value", "roofline", "gather", "also", "next_rows", "full_forward", "cpu_baseline"):
+        assert k not in r, k
+    assert list(r.keys())[-1] == "summary" and r["summary"]["value"] == r["value"]
+    run(tmp_path / "b")
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["last.npy", "logits.npy"] and sorted(os.listdir(tmp_path / "b")) == names      # (the stand-in returns no features)
+    for n in names:
+        x, y = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert x.dtype == np.float32 and np.isfinite(x).all() and np.array_equal(x, y), n
+    assert np.load(tmp_path / "a" / "last.npy").shape == (4, 200) and np.load(tmp_path / "a" / "logits.npy").shape == (8, 200)
+
+
+def test_dump_outputs_takes_a_fixed_sample_over_the_cap(tmp_path, monkeypatch):
+    """Outputs larger than the cap are cut to the same seeded sample of their elements every time, within the cap in all."""
+    import importlib
+
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    monkeypatch.setattr(bench, "DUMP_BYTES", 4000)
+    arrays = {"a": torch.arange(3000, dtype=torch.float32).view(30, 100), "b": torch.arange(1000, dtype=torch.float64), "c": None}
+    bench.dump_outputs(str(tmp_path / "x"), arrays)
+    bench.dump_outputs(str(tmp_path / "y"), arrays)
+    assert sorted(os.listdir(tmp_path / "x")) == ["a.npy", "b.npy"]
+    total = 0
+    for n in ("a", "b"):
+        x, y = np.load(tmp_path / "x" / (n + ".npy")), np.load(tmp_path / "y" / (n + ".npy"))
+        assert x.dtype == np.float32 and x.ndim == 1 and np.array_equal(x, y) and x.size > 0
+        assert np.all(np.diff(x) > 0) and np.all(x == np.round(x))          # a sorted subset of the elements, in their order
+        total += x.nbytes
+    assert total <= 4000
+    small = {"a": torch.ones(2, 3, dtype=torch.float64)}
+    bench.dump_outputs(str(tmp_path / "z"), small)                            # under the cap: the whole array, its shape kept
+    z = np.load(tmp_path / "z" / "a.npy")
+    assert z.dtype == np.float32 and z.shape == (2, 3)
 
 
 def test_bench_distributed_init_failure_leaves_one_diagnosable_line():

@@ -9,8 +9,8 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$R/gpurun_out
 cd /tmp && export TMPDIR=/tmp
 run() { local name=$1; shift; rocprofv3 "$@" > $OUT/r5_$name.log 2>&1; }
-SPLIT="python $R/bench.py --steps 20 --warmup 4 --skip-extras --streams 1 --cpu-baseline 0 --math split_bf16"
-SPLITPMC="python $R/bench.py --steps 4 --warmup 2 --skip-extras --profile-steps 1 --streams 1 --cpu-baseline 0 --math split_bf16"
+SPLIT="python $R/bench.py --full --steps 20 --warmup 4 --skip-extras --streams 1 --cpu-baseline 0 --math split_bf16"
+SPLITPMC="python $R/bench.py --full --steps 4 --warmup 2 --skip-extras --profile-steps 1 --streams 1 --cpu-baseline 0 --math split_bf16"
 run split_trace --kernel-trace --stats --output-format csv -d $OUT/prof_r5_split_trace -- $SPLIT
 run split_mfma --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_INSTS_VALU --output-format csv -d $OUT/prof_r5_split_mfma -- $SPLITPMC
 cd $R

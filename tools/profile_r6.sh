@@ -11,8 +11,8 @@ mkdir -p $OUT
 bash $R/tools/profile_r6_glancer.sh r6
 cd /tmp && export TMPDIR=/tmp
 run() { local name=$1; shift; rocprofv3 "$@" > $OUT/r6_$name.log 2>&1; }
-SPLIT="python $R/bench.py --steps 20 --warmup 4 --skip-extras --streams 1 --cpu-baseline 0 --math split_bf16"
-SPLITPMC="python $R/bench.py --steps 4 --warmup 2 --skip-extras --profile-steps 1 --streams 1 --cpu-baseline 0 --math split_bf16"
+SPLIT="python $R/bench.py --full --steps 20 --warmup 4 --skip-extras --streams 1 --cpu-baseline 0 --math split_bf16"
+SPLITPMC="python $R/bench.py --full --steps 4 --warmup 2 --skip-extras --profile-steps 1 --streams 1 --cpu-baseline 0 --math split_bf16"
 run split_trace --kernel-trace --stats --output-format csv -d $OUT/prof_r6_split_trace -- $SPLIT
 run split_mfma --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_INSTS_VALU --output-format csv -d $OUT/prof_r6_split_mfma -- $SPLITPMC
 run split_lds --pmc SQ_INSTS_LDS SQ_LDS_IDX_ACTIVE SQ_LDS_ADDR_CONFLICT SQ_LDS_DATA_FIFO_FULL SQ_INSTS_MFMA SQ_WAIT_INST_LDS GRBM_GUI_ACTIVE --output-format csv -d $OUT/prof_r6_split_lds -- $SPLITPMC
