@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("ADAF_LIB") or os.path.join(_HERE, "csrc", "libadafocu
 
 LAYOUT_NCHW, LAYOUT_NHWC, LAYOUT_NHWC4 = 0, 1, 2
 ACT_NONE, ACT_RELU, ACT_RELU6, ACT_SIGMOID, ACT_SWISH = 0, 1, 2, 3, 4
-MATH_F32, MATH_F32_SPLIT_BF16 = 0, 1
+MATH_F32, MATH_F32_SPLIT_BF16, MATH_F16 = 0, 1, 2
 DTYPE_F32, DTYPE_F16 = 0, 1
 CONV_TILES = 4
 

@@ -255,6 +255,9 @@ int adaf_pick_conv_tile(int M, int N, int K, int cus);
 int adaf_launch_conv_lat(const ConvArgs& a, hipStream_t s);   // conv_lat.hip: small-batch form (tile id 95), 1 = launched, 0 = not eligible
 int adaf_launch_conv_pool(ConvArgs a, int hw, float* pool_out, int pool_ld, hipStream_t s);   // 1 = launched (tile id 96), 0 = not eligible
 int adaf_launch_conv_pool16(ConvArgs a, int hw, float* pool_out, int pool_ld, hipStream_t s); // fp16 operands (EfficientNet's head); same return
+// fp16 operands + fp16 residual, the activated values ROUNDED to fp16 before they are averaged (the fp16 ResNet trunk's last conv3): the bits
+// of conv (fp16 store) + adaf_launch_avgpool_f16.  Same return
+int adaf_launch_conv_pool16_rounded(ConvArgs a, int hw, float* pool_out, int pool_ld, hipStream_t s);
 bool adaf_conv_tile_exists(int tile);   // is `tile` an id adaf_launch_conv_gemm has a kernel for
 void adaf_launch_conv_naive(const ConvArgs& a, hipStream_t s);
 // conv2 3x3 (64 -> 64) -> conv3 1x1 (+ identity, ReLU) [-> the next block's conv1 1x1] in one launch (stage 1 of the trunk);
@@ -300,6 +303,10 @@ void adaf_launch_pack_weight_f16(const float* w, int cout, int cin, int kh, int 
 void adaf_launch_cast(const void* x, long long count, void* o, int to_f16, hipStream_t s);
 void adaf_launch_dwconv3x3_f16(const void* x, int n, int h, int w, int c, int stride, const float* wt, const float* scale,
                                const float* bias, int act, void* o, hipStream_t s);
+// fp16 trunk (ADAF_MATH_F16): max-pool of the fp32 stem map with an fp16 store, global average pool of an fp16 map (fp32 features), NHWC fp16 shift
+void adaf_launch_maxpool_f16out(const float* x, int n, int h, int w, int c, void* o, hipStream_t s);
+void adaf_launch_avgpool_f16(const void* x, int n, int hw, int c, float* o, int ldo, hipStream_t s);
+void adaf_launch_tshift_f16(const void* x, int nt, int c, int hw, int T, int div, void* o, hipStream_t s);
 // stem.hip
 void adaf_launch_pack_stem_weight(const float* w_oihw, float* wr, hipStream_t s);
 size_t adaf_stem_weight_floats();
@@ -307,8 +314,9 @@ void adaf_launch_stem7x7(const float* x4, int n, int P, const float* wr, const f
                          int cus, hipStream_t s);
 bool adaf_stem7x7_rows_ok(int P, int n, int cus);   // the strip-walking stem + pool kernel exists for this patch size and there are enough images to fill the device
 // the same launch gathering its own windows from planar frames [n, 3, H, W] at floor(action * (H - P)) (get_patch folded in); false = not available
+// out16: the pooled map is stored as fp16 (one rounding of the fp32 result; ADAF_MATH_F16), `out` then holds halfs
 bool adaf_launch_stem7x7_pool_frames(const float* frames, bool pixel_major, int nframes, const float* act, int fpa, int H, int W, int n, int P,
-                                     const float* wr, const float* scale, const float* bias, float* out, int cus, hipStream_t s);
+                                     const float* wr, const float* scale, const float* bias, float* out, int cus, hipStream_t s, bool out16 = false);
 bool adaf_stem7x7_pool_pays(int P);     // does the fused stem + max-pool launch beat the two separate ones at this patch size
 void adaf_launch_stem7x7_pool(const float* x4, int n, int P, const float* wr, const float* scale, const float* bias, float* out,
-                              int cus, hipStream_t s);
+                              int cus, hipStream_t s, bool out16 = false);

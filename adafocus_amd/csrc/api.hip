@@ -354,6 +354,8 @@ int adaf_conv2d_bn_act_f16(adaf_handle* h, const adaf_conv_params* p, const void
     a.out16 = out_dtype == ADAF_DTYPE_F16;
     a.res16 = residual_f16 != nullptr;
     if (a.in16 && (p->cin % 8 || a.ldx % 8)) return fail(h, ADAF_E_LAYOUT, "conv_f16: fp16 operands need cin %% 8 == 0 (16-byte chunks)");
+    if (a.in16 && a.tsm_T > 0 && a.tsm_fold % 8)
+        return fail(h, ADAF_E_LAYOUT, "conv_f16: temporal-shift fold=%d must be a multiple of 8 with fp16 operands (whole 16-byte chunks)", a.tsm_fold);
     if (!a.in16 && residual_f16) return fail(h, ADAF_E_BADARG, "conv_f16: a residual needs fp16 operands");
     if (p->tile && (p->tile < 81 || p->tile > 88)) return fail(h, ADAF_E_BADARG, "conv_f16: tile ids are 81..84, 88");
     if (adaf_launch_conv_gemm(a, p->tile, h->cus, (hipStream_t)stream) < 0)
@@ -467,6 +469,7 @@ struct ConvLayer {
     int cin_pad;
     float* w = nullptr;    // packed OHWI
     unsigned short* wsp = nullptr;   // the same as three bf16 planes (ADAF_MATH_F32_SPLIT_BF16 only)
+    unsigned short* w16 = nullptr;   // the same rounded to fp16, nearest-even (ADAF_MATH_F16 only; not for the stem)
     float* scale = nullptr;
     float* bias = nullptr;
 };
@@ -481,6 +484,7 @@ struct adaf_resnet50 {
     float* l10_w = nullptr;
     float* l10_scale = nullptr;
     float* l10_bias = nullptr;
+    unsigned short* l10_w16 = nullptr;   // l10_w rounded to fp16 (ADAF_MATH_F16)
     int math = ADAF_MATH_F32;      // ADAF_MATH_*: which matrix pipe the (non-stem) convs use
     bool fuse = true;              // stage 1: conv2 -> conv3 (-> next conv1) in one launch; stem + max-pool in one launch
     bool fuse_stem_always = false; // (tests, set_fusion(2)) take every fused launch at every size, not only where it is the faster plan
@@ -530,6 +534,178 @@ struct FrameSrc {
     int fpa;
 };
 
+// The fp16 trunk (ADAF_MATH_F16, include/adafocus.h: numerics contract).  Same slabs as the fp32 plan (an fp16 map takes half of one), same
+// block walk: stem + max-pool with an fp16 store, then every conv on the fp16-operand tiles (conv_gemm.hip, tile ids 81..84 / 88: fp16
+// activations and filters, v_mfma_f32_32x32x16_f16, fp32 BN affine / residual / ReLU, one rounding to fp16 in the epilogue).  Fused forms
+// (fusion on): stem + max-pool in one launch, layer1.0's conv1 + downsample as one GEMM, the global average pool in the last conv3's
+// epilogue where whole images fill its tiles -- each gives the bits of the unfused launches.
+int run_trunk16(adaf_resnet50* net, const float* x4, int n, int P, int tsm_T, int tsm_div, float* feat, int ldfeat, float* const* buf,
+                hipStream_t st, std::vector<hipEvent_t>* rec, std::vector<Launch>* info, float* featmap, const FrameSrc* src) {
+    adaf_handle* h = net->h;
+    if (!net->convs[1].w16) return fail(h, ADAF_E_STATE, "resnet50: fp16 filters missing (finalize() did not complete)");
+    const bool tsm_block = net->tsm_block && tsm_T > 0;
+    const int tsm_c1 = tsm_block ? 0 : tsm_T;     // the temporal shift conv1's operand load carries
+    if (tsm_T > 0 && tsm_div <= 0) return fail(h, ADAF_E_BADARG, "resnet50: tsm_div must be positive");
+    if (tsm_c1 > 0)
+        for (size_t i = 1; i < net->convs.size(); ++i) {
+            const ConvLayer& L = net->convs[i];
+            if (L.name.size() > 5 && L.name.compare(L.name.size() - 5, 5, "conv1") == 0 && (L.cin / tsm_div) % 8)
+                return fail(h, ADAF_E_LAYOUT, "resnet50 (fp16): temporal-shift fold = %d / %d = %d of %s must be a multiple of 8", L.cin, tsm_div,
+                            L.cin / tsm_div, L.name.c_str());
+        }
+    auto mark = [&](double flops, double bytes, int tile) {
+        if (rec) {
+            (void)hipEventRecord((*rec)[info->size()], st);
+            info->push_back({flops, bytes, tile});
+        }
+    };
+    auto f16 = [](const void* p) { return static_cast<const float*>(p); };   // fp16 buffers travel as float* through ConvArgs
+    int li = 0;
+    auto conv = [&](const void* in, int hh, int ww, int act, const void* res, void* out, bool tsm, int* oh, int* ow) -> int {
+        const ConvLayer& L = net->convs[li];
+        adaf_conv_params p;
+        memset(&p, 0, sizeof(p));
+        p.n = n; p.h = hh; p.w = ww; p.cin = L.cin_pad; p.cout = L.cout; p.kh = p.kw = L.k; p.stride = L.stride; p.pad = L.pad;
+        p.act = act; p.tsm_segments = tsm ? tsm_T : 0; p.tsm_div = tsm_div;
+        ConvArgs a;
+        int rc = make_conv_args(h, &p, f16(in), f16(L.w16), L.scale, L.bias, f16(res), static_cast<float*>(out), &a);
+        if (rc) return rc;
+        a.in16 = 1; a.out16 = 1; a.res16 = res != nullptr;
+        const double macs = (double)a.M * L.cout * L.k * L.k * L.cin;
+        const double bytes = 2.0 * ((double)n * hh * ww * L.cin + (double)a.M * L.cout * (res ? 2 : 1) + (double)L.cout * L.k * L.k * L.cin);
+        mark(2.0 * macs, bytes, 0);
+        const int used = adaf_launch_conv_gemm(a, net->tiles[li], h->cus, st);
+        if (used < 0) return fail(h, ADAF_E_LAUNCH, "resnet50 (fp16): no kernel for conv launch %d (tile id %d)", li, net->tiles[li]);
+        if (info && !info->empty()) info->back().tile = used;
+        *oh = a.OH; *ow = a.OW;
+        ++li;
+        return ADAF_OK;
+    };
+
+    // ---- stem: conv 7x7/2 + BN + ReLU (fp32) -> max-pool 3x3/2 -> ONE rounding to fp16, into buf[1]
+    const ConvLayer& L0 = net->convs[0];
+    const int s1 = conv_out(P, 7, 2, 3), ph = conv_out(s1, 3, 2, 1);
+    const double stem_flops = 2.0 * (double)n * s1 * s1 * 64 * 147;
+    bool gathered = false;
+    if (src) {
+        if (net->fuse && adaf_stem7x7_rows_ok(P, n, h->cus)) {
+            mark(stem_flops, 4.0 * ((double)n * P * P * 3 + 64.0 * 147) + 2.0 * (double)n * ph * ph * 64, 94);
+            gathered = adaf_launch_stem7x7_pool_frames(src->frames, src->pixel_major, src->nframes, src->act, src->fpa, src->H, src->W, n, P,
+                                                       net->stem_w, L0.scale, L0.bias, buf[1], h->cus, st, true);
+            if (!gathered && rec) info->pop_back();
+        }
+        if (!gathered) {
+            mark(0.0, 4.0 * 2.0 * (double)n * P * P * 3, 0);
+            for (int g = 0; g * src->nframes < n; ++g) {
+                const float* act = src->act + (size_t)g * (src->nframes / src->fpa) * 2;
+                float* dst = buf[2] + (size_t)g * src->nframes * P * P * 4;
+                if (src->pixel_major) adaf_launch_crop_nhwc4(src->frames, src->nframes, src->H, src->W, act, src->fpa, P, dst, nullptr, st);
+                else if (adaf_launch_crop(src->frames, src->nframes, 3, src->H, src->W, act, src->fpa, P, dst, ADAF_LAYOUT_NHWC4, nullptr, st) != hipSuccess)
+                    return fail(h, ADAF_E_LAUNCH, "resnet50: gather launch");
+            }
+            x4 = buf[2];
+        }
+    }
+    if (gathered) {
+    } else if (net->fuse && (adaf_stem7x7_pool_pays(P) || adaf_stem7x7_rows_ok(P, n, h->cus) || net->fuse_stem_always)) {
+        mark(stem_flops, 4.0 * ((double)n * P * P * 3 + 64.0 * 147) + 2.0 * (double)n * ph * ph * 64, 90);
+        adaf_launch_stem7x7_pool(x4, n, P, net->stem_w, L0.scale, L0.bias, buf[1], h->cus, st, true);
+    } else {
+        mark(stem_flops, 4.0 * ((double)n * P * P * 3 + (double)n * s1 * s1 * 64 + 64.0 * 147), 40);
+        adaf_launch_stem7x7(x4, n, P, net->stem_w, L0.scale, L0.bias, buf[0], h->cus, st);
+        mark(0.0, 4.0 * (double)n * s1 * s1 * 64 + 2.0 * (double)n * ph * ph * 64, 0);
+        adaf_launch_maxpool_f16out(buf[0], n, s1, s1, 64, buf[1], st);
+    }
+    li = 1;
+    int hh = ph, ww = ph;
+
+    void* cur = buf[1];
+    void* nxt = buf[0];
+    void* t1 = buf[2];
+    void* t2 = buf[3];
+    void* dsb = buf[4];
+    void* shb = tsm_block ? buf[5] : nullptr;
+    bool pooled = false;
+    int rc;
+    for (int s = 0; s < 4; ++s) {
+        for (int b = 0; b < kStageBlocks[s]; ++b) {
+            int h1 = hh, w1 = ww, h2, w2, h3, w3;
+            if (tsm_block) {       // the block's input, shifted along its clip: conv1, downsample and identity all read this copy
+                const int cin = net->convs[li].cin;
+                mark(0.0, 4.0 * (double)n * hh * ww * cin, 0);
+                adaf_launch_tshift_f16(cur, n, cin, hh * ww, tsm_T, tsm_div, shb, st);
+                void* t = cur; cur = shb; shb = t;
+            }
+            const int i_c2 = li + 1, i_ds = li + 3;
+            const int i_next = li + 3 + (b == 0 ? 1 : 0);
+            bool ds_done = false;
+            if (s == 0 && b == 0 && net->fuse && net->l10_w16 && tsm_c1 == 0 && !net->tiles[li] && !net->tiles[i_ds]) {
+                // layer1.0: conv1 (64) and the downsample conv (256) as ONE GEMM over the same map; 128 x 64 tiles: column tile 0 is conv1
+                const ConvLayer &C1 = net->convs[li], &DS = net->convs[i_ds];
+                adaf_conv_params p;
+                memset(&p, 0, sizeof(p));
+                p.n = n; p.h = hh; p.w = ww; p.cin = C1.cin_pad; p.cout = C1.cout + DS.cout; p.kh = p.kw = 1; p.stride = 1; p.pad = 0;
+                p.act = ADAF_ACT_RELU;
+                ConvArgs am;
+                if ((rc = make_conv_args(h, &p, f16(cur), f16(net->l10_w16), net->l10_scale, net->l10_bias, nullptr, static_cast<float*>(t1), &am))) return rc;
+                am.in16 = 1; am.out16 = 1;
+                am.ldo = C1.cout;
+                am.split_n = C1.cout;
+                am.out_b = reinterpret_cast<float*>(static_cast<_Float16*>(dsb) - C1.cout);   // column n of the merged GEMM: channel n - 64 of the downsample
+                am.ldo_b = DS.cout;
+                am.act_b = ADAF_ACT_NONE;
+                const double M = (double)am.M;
+                mark(2.0 * M * (C1.cout + DS.cout) * C1.cin, 2.0 * (M * C1.cin + M * (C1.cout + DS.cout) + (double)(C1.cout + DS.cout) * C1.cin), 93);
+                if (adaf_launch_conv_gemm(am, 82, h->cus, st) < 0) return fail(h, ADAF_E_LAUNCH, "resnet50 (fp16): merged layer1.0 launch");
+                h1 = am.OH; w1 = am.OW;
+                ++li;
+                ds_done = true;
+            } else if ((rc = conv(cur, hh, ww, ADAF_ACT_RELU, nullptr, t1, tsm_c1 > 0, &h1, &w1))) return rc;
+            const void* identity = cur;
+            if (b == 0) {
+                if (!ds_done) {
+                    li = i_ds;
+                    int hd, wd;
+                    if ((rc = conv(cur, hh, ww, ADAF_ACT_NONE, nullptr, dsb, false, &hd, &wd))) return rc;
+                }
+                identity = dsb;
+            }
+            li = i_c2;
+            if ((rc = conv(t1, h1, w1, ADAF_ACT_RELU, nullptr, t2, false, &h2, &w2))) return rc;
+            const bool last = s == 3 && b == kStageBlocks[3] - 1;
+            if (last && net->fuse && !rec && !featmap && !net->tiles[li]) {
+                // the trunk's last conv3 with the global average pool in its epilogue: the fp16-rounded values are averaged (conv + pool bits)
+                const ConvLayer& L3 = net->convs[li];
+                adaf_conv_params p;
+                memset(&p, 0, sizeof(p));
+                p.n = n; p.h = h2; p.w = w2; p.cin = L3.cin_pad; p.cout = L3.cout; p.kh = p.kw = 1; p.stride = 1; p.pad = 0;
+                p.act = ADAF_ACT_RELU;
+                ConvArgs a3;
+                if ((rc = make_conv_args(h, &p, f16(t2), f16(L3.w16), L3.scale, L3.bias, f16(identity), static_cast<float*>(nxt), &a3))) return rc;
+                a3.in16 = 1; a3.res16 = 1;
+                if (adaf_launch_conv_pool16_rounded(a3, h2 * w2, feat, ldfeat, st)) {
+                    pooled = true;
+                    h3 = h2; w3 = w2;
+                    ++li;
+                }
+            }
+            if (!pooled && (rc = conv(t2, h2, w2, ADAF_ACT_RELU, identity, nxt, false, &h3, &w3))) return rc;
+            li = i_next;
+            hh = h3; ww = w3;
+            void* t = cur; cur = nxt; nxt = t;
+        }
+    }
+    if (featmap)        // get_featmap(pooled=False): the exact fp32 widening of the fp16 map (NHWC)
+        adaf_launch_cast(cur, (long long)n * hh * ww * 2048, featmap, 0, st);
+    if (!pooled) {
+        mark(0.0, 2.0 * (double)n * hh * ww * 2048 + 4.0 * (double)n * 2048, 0);
+        adaf_launch_avgpool_f16(cur, n, hh * ww, 2048, feat, ldfeat, st);
+    }
+    if (rec) (void)hipEventRecord((*rec)[info->size()], st);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? ADAF_OK : hip_fail(h, e, "resnet50 forward (fp16)");
+}
+
 // Walks the trunk; `rec` (optional) gets one hipEvent before each launch plus one at the end.
 int run_trunk(adaf_resnet50* net, const float* x4, int n, int P, int tsm_T, int tsm_div, float* feat, int ldfeat,
               void* ws, size_t ws_bytes, hipStream_t st, std::vector<hipEvent_t>* rec, std::vector<Launch>* info, float* featmap = nullptr,
@@ -567,6 +743,7 @@ int run_trunk(adaf_resnet50* net, const float* x4, int n, int P, int tsm_T, int 
     const size_t slab = adaf_resnet50_workspace_bytes(net, n, P) / (nslab * sizeof(float));  // largest activation, floats
     float* buf[6];
     for (int i = 0; i < nslab; ++i) buf[i] = static_cast<float*>(ws) + i * slab;
+    if (net->math == ADAF_MATH_F16) return run_trunk16(net, x4, n, P, tsm_T, tsm_div, feat, ldfeat, buf, st, rec, info, featmap, src);
 
     auto mark = [&](double flops, double bytes, int tile) {
         if (rec) {   // events are created up front by the caller: recording is the only work between launches
@@ -796,9 +973,11 @@ int adaf_resnet50_destroy(adaf_resnet50* net) {
     if (net->l10_w) (void)hipFree(net->l10_w);
     if (net->l10_scale) (void)hipFree(net->l10_scale);
     if (net->l10_bias) (void)hipFree(net->l10_bias);
+    if (net->l10_w16) (void)hipFree(net->l10_w16);
     for (auto& L : net->convs) {
         if (L.w) (void)hipFree(L.w);
         if (L.wsp) (void)hipFree(L.wsp);
+        if (L.w16) (void)hipFree(L.w16);
         if (L.scale) (void)hipFree(L.scale);
         if (L.bias) (void)hipFree(L.bias);
     }
@@ -826,6 +1005,30 @@ static int split_weights(adaf_resnet50* net, void* stream) {
     }
     hipError_t e = hipStreamSynchronize(st);
     if (e != hipSuccess) return hip_fail(h, e, "resnet50 split weights");
+    return ADAF_OK;
+}
+
+// Every packed filter bank except the stem's rounded to fp16, nearest-even (ADAF_MATH_F16; idempotent).  The packed fp32 bank is a copy of
+// the parameters, so this is the rounding of the fp32 parameters themselves.
+static int f16_weights(adaf_resnet50* net, void* stream) {
+    adaf_handle* h = net->h;
+    hipStream_t st = (hipStream_t)stream;
+    for (size_t i = 1; i < net->convs.size(); ++i) {
+        ConvLayer& L = net->convs[i];
+        const size_t wn = (size_t)L.cout * L.k * L.k * L.cin_pad;
+        if (!L.w16 && hipMalloc(reinterpret_cast<void**>(&L.w16), wn * sizeof(unsigned short)) != hipSuccess)
+            return fail(h, ADAF_E_NOMEM, "resnet50: hipMalloc fp16 weights");
+        adaf_launch_cast(L.w, (long long)wn, L.w16, 1, st);
+    }
+    if (net->l10_w) {
+        const ConvLayer &C1 = net->convs[1], &DS = net->convs[4];
+        const size_t wn = (size_t)C1.cout * C1.cin_pad + (size_t)DS.cout * DS.cin_pad;
+        if (!net->l10_w16 && hipMalloc(reinterpret_cast<void**>(&net->l10_w16), wn * sizeof(unsigned short)) != hipSuccess)
+            return fail(h, ADAF_E_NOMEM, "resnet50: hipMalloc merged fp16 filters");
+        adaf_launch_cast(net->l10_w, (long long)wn, net->l10_w16, 1, st);
+    }
+    hipError_t e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return hip_fail(h, e, "resnet50 fp16 weights");
     return ADAF_OK;
 }
 
@@ -882,6 +1085,7 @@ int adaf_resnet50_finalize(adaf_resnet50* net, void* stream) {
     if (e != hipSuccess) return hip_fail(h, e, "resnet50 finalize");
     net->finalized = true;
     if (net->math == ADAF_MATH_F32_SPLIT_BF16) return split_weights(net, stream);
+    if (net->math == ADAF_MATH_F16) return f16_weights(net, stream);
     return ADAF_OK;
 }
 
@@ -974,11 +1178,14 @@ int adaf_resnet50_forward_profiled(adaf_resnet50* net, const float* patches_nhwc
 
 int adaf_resnet50_set_tiles(adaf_resnet50* net, const int* tile, int count) {
     if (!net || !tile || count != (int)net->convs.size()) return ADAF_E_BADARG;
+    const bool f16 = net->math == ADAF_MATH_F16;
     for (int i = 0; i < count; ++i) {
-        if (tile[i] < 0 || tile[i] > 80 || (tile[i] && !adaf_conv_tile_exists(tile[i])))
-            return fail(net->h, ADAF_E_BADARG, "set_tiles: no kernel variant with id %d", tile[i]);
-        net->tiles[i] = tile[i];
+        // fp16 trunk: the fp16-operand tiles for the convs after the stem (the stem is fp32 and has its own kernels: 0 only)
+        const bool ok = f16 ? (tile[i] == 0 || (i > 0 && ((tile[i] >= 81 && tile[i] <= 84) || tile[i] == 88)))
+                            : !(tile[i] < 0 || tile[i] > 80 || (tile[i] && !adaf_conv_tile_exists(tile[i])));
+        if (!ok) return fail(net->h, ADAF_E_BADARG, "set_tiles: no kernel variant with id %d for conv launch %d in math mode %d", tile[i], i, net->math);
     }
+    for (int i = 0; i < count; ++i) net->tiles[i] = tile[i];
     return ADAF_OK;
 }
 
@@ -1004,9 +1211,12 @@ int adaf_resnet50_set_latency_rows(adaf_resnet50* net, int rows) {
 
 int adaf_resnet50_set_math(adaf_resnet50* net, int mode) {
     if (!net) return ADAF_E_BADARG;
-    if (mode != ADAF_MATH_F32 && mode != ADAF_MATH_F32_SPLIT_BF16) return fail(net->h, ADAF_E_BADARG, "set_math: unknown mode %d", mode);
+    if (mode != ADAF_MATH_F32 && mode != ADAF_MATH_F32_SPLIT_BF16 && mode != ADAF_MATH_F16) return fail(net->h, ADAF_E_BADARG, "set_math: unknown mode %d", mode);
+    // tile overrides name kernels of one storage type: entering or leaving the fp16 trunk clears them
+    if ((mode == ADAF_MATH_F16) != (net->math == ADAF_MATH_F16)) net->tiles.assign(net->convs.size(), 0);
     net->math = mode;
     if (mode == ADAF_MATH_F32_SPLIT_BF16 && net->finalized) return split_weights(net, nullptr);
+    if (mode == ADAF_MATH_F16 && net->finalized) return f16_weights(net, nullptr);
     return ADAF_OK;
 }
 

@@ -298,7 +298,10 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a0, float* smem, f
 // bit-identical to conv + separate pool (tests/test_hip_parity_r3.py).  Saves the 75 MB map's round trip and a launch.
 // SIG (fp16-operand launches: EfficientNet's head conv, adaf_launch_conv_pool16): the activation may be swish / sigmoid, finished by
 // finish_act exactly as conv_epilogue does (clamp bounds open for them), so the pooled features are the bits of conv + avgpool_kernel.
-template <int TM, int TN, int BM, int BN, int NW, bool SIG = false>
+// RND (the fp16 ResNet trunk's last conv3, adaf_launch_conv_pool16_rounded): the residual is fp16 (widened), and every activated value is
+// ROUNDED to fp16 (adaf_f16_of, the conv's fp16 store) and widened back before it is parked -- the pool averages the values the unfused
+// conv would have stored, in pixel order, as avgpool_f16_kernel (misc_ops.hip) does: the same bits.
+template <int TM, int TN, int BM, int BN, int NW, bool SIG = false, bool RND = false>
 __device__ __forceinline__ void conv_epilogue_pool(const ConvArgs& a, float* smem, f32x16 (&acc)[TM][TN], int m0, int n0, int wm, int wn,
                                                    int lane, int wave, int tile_m) {
     constexpr int WM = TM * 32, WN = TN * 32, SP = WN + 4, PP = BN + 4;
@@ -330,7 +333,13 @@ __device__ __forceinline__ void conv_epilogue_pool(const ConvArgs& a, float* sme
             const int lrow = wm * WM + i * 32 + row;                 // row inside the tile
             const int ml = m0 + lrow;
             const bool ok = n_ok && lrow < a.pool_rows && ml < a.M;
-            const f32x4 rv = (ok && a.res) ? *reinterpret_cast<const f32x4*>(a.res + (size_t)ml * a.ldr + n) : zero4;
+            f32x4 rv = zero4;
+            if (RND) {
+                if (ok && a.res) {
+                    const f16x4 hv = *reinterpret_cast<const f16x4*>(reinterpret_cast<const _Float16*>(a.res) + (size_t)ml * a.ldr + n);
+                    rv = f32x4{(float)hv.x, (float)hv.y, (float)hv.z, (float)hv.w};
+                }
+            } else if (ok && a.res) rv = *reinterpret_cast<const f32x4*>(a.res + (size_t)ml * a.ldr + n);
             const f32x4 v = *reinterpret_cast<const f32x4*>(st + row * SP + 4 * c4);
             f32x4 o;
             o.x = fminf(fmaxf(fmaf(v.x, sc.x, bi.x) + rv.x, act_lo), act_hi);
@@ -338,6 +347,9 @@ __device__ __forceinline__ void conv_epilogue_pool(const ConvArgs& a, float* sme
             o.z = fminf(fmaxf(fmaf(v.z, sc.z, bi.z) + rv.z, act_lo), act_hi);
             o.w = fminf(fmaxf(fmaf(v.w, sc.w, bi.w) + rv.w, act_lo), act_hi);
             if constexpr (SIG) { o.x = finish_act(o.x, sig); o.y = finish_act(o.y, sig); o.z = finish_act(o.z, sig); o.w = finish_act(o.w, sig); }
+            if constexpr (RND) {
+                o.x = (float)adaf_f16_of(o.x); o.y = (float)adaf_f16_of(o.y); o.z = (float)adaf_f16_of(o.z); o.w = (float)adaf_f16_of(o.w);
+            }
             *reinterpret_cast<f32x4*>(P + lrow * PP + wn * WN + 4 * c4) = o;
         }
     }
@@ -576,7 +588,8 @@ template <int BM, int BN, int WGM, int WGN, bool DENSE, int PIPE, bool SPECIAL, 
           bool LEAN = false, bool POOL = false>
 __global__ __launch_bounds__(64 * WGM * WGN, (BM == 128 && BN == 128 && WGM * WGN == 4) ? 2 : 1)   // 128x128: two blocks per CU
 void conv_gemm_glds_kernel(const ConvArgs a) {
-    static_assert(!POOL || (DENSE && !SPECIAL && ((LEAN && DT == 0) || (!LEAN && DT == 4))), "pooled epilogue: the lean dense fp32 kernel, or the dense fp16-operand kernel with fp32 features");
+    static_assert(!POOL || (DENSE && !SPECIAL && ((LEAN && DT == 0) || (!LEAN && (DT == 4 || DT == 6)))),
+                  "pooled epilogue: the lean dense fp32 kernel, or the dense fp16-operand kernel with fp32 features (DT 6: fp16 residual, rounded values)");
     static_assert(!PM || (!DENSE && (EMU == 0 || BSP) && PIPE == 1), "position-major tiles: k x k filters on the fp32 pipe, or split tiles with pre-split weights");
     static_assert(!LEAN || ((DENSE || PM) && PIPE == 1 && ((EMU == 0 && !BSP) || (EMU != 0 && BSP)) &&
                             (!SPECIAL || (DENSE && EMU == 0 && DT == 0 && !POOL))),
@@ -1163,7 +1176,7 @@ void conv_gemm_glds_kernel(const ConvArgs a) {
     }
     __syncthreads();   // all fragment reads done before the slabs overwrite the stage buffers
     if constexpr (POOL) {
-        conv_epilogue_pool<TM, TN, BM, BN, NW, (DT & 4) != 0>(a, smem, acc, m0, n0, wm, wn, lane, wave, tile_m);
+        conv_epilogue_pool<TM, TN, BM, BN, NW, DT == 4, DT == 6>(a, smem, acc, m0, n0, wm, wn, lane, wave, tile_m);
         return;
     }
     if (PM) conv_epilogue<TM, TN, (DT & 3)>(a, smem, acc, m0, n0, wm, wn, lane, wave, a.OH * a.OW, pm_p, a.pm_images);
@@ -2015,6 +2028,23 @@ int adaf_launch_conv_pool16(ConvArgs a, int hw, float* pool_out, int pool_ld, hi
     a.nblocks = ((a.M + a.pool_rows - 1) / a.pool_rows) * a.tiles_n;
     a.K /= 2; a.cin /= 2; a.ldx /= 2;
     hipLaunchKernelGGL((conv_gemm_glds_kernel<128, 64, 2, 2, true, 1, false, 0, false, 4, false, false, true>), dim3(a.nblocks), dim3(256), 0, s, a);
+    return 1;
+}
+
+// The fp16 ResNet trunk's last conv3 (ADAF_MATH_F16): 1x1 fp16 operands, fp16 identity, ReLU, global average pool of the fp16-ROUNDED
+// activated values (conv_epilogue_pool RND).  Every fp16 tile shape walks k in the same order per output, so this 128 x 64 tile gives the
+// bits of whichever tile the unfused conv takes; with the rounding and the pixel-order sum the features are those of conv + pool.  1 = launched.
+int adaf_launch_conv_pool16_rounded(ConvArgs a, int hw, float* pool_out, int pool_ld, hipStream_t s) {
+    if (!adaf_options().conv_pool) return 0;
+    if (!a.in16 || a.out16 || (a.res && !a.res16) || a.split_n || a.tsm_T > 0 || a.wsp || !conv_glds16_ok(a)) return 0;
+    if (a.KH != 1 || a.KW != 1 || a.stride != 1 || a.pad != 0 || (a.K & 63) || (a.N & 3) || (a.ldr & 3) || !a.vec_epi) return 0;
+    if (a.act != ADAF_ACT_NONE && a.act != ADAF_ACT_RELU && a.act != ADAF_ACT_RELU6) return 0;
+    if (hw <= 0 || hw > 128 || a.M % hw || (128 / hw) * hw * 10 < 128 * 9 || (pool_ld & 3) || (reinterpret_cast<size_t>(pool_out) & 15)) return 0;
+    a.pool_hw = hw; a.pool_rows = (128 / hw) * hw; a.pool_out = pool_out; a.pool_ld = pool_ld;
+    a.tiles_n = (a.N + 63) / 64;
+    a.nblocks = ((a.M + a.pool_rows - 1) / a.pool_rows) * a.tiles_n;
+    a.K /= 2; a.cin /= 2; a.ldx /= 2;
+    hipLaunchKernelGGL((conv_gemm_glds_kernel<128, 64, 2, 2, true, 1, false, 0, false, 6, false, false, true>), dim3(a.nblocks), dim3(256), 0, s, a);
     return 1;
 }
 

@@ -124,6 +124,79 @@ __global__ void tshift_kernel(const float* __restrict__ x, long long total, int 
     o[idx] = v;
 }
 
+// ---- fp16 trunk (ADAF_MATH_F16) ----------------------------------------------------------------------------------
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+
+// MaxPool2d(3, 2, 1) of the fp32 stem map with an fp16 store: the maximum, then ONE rounding (rounding is monotone, so this is the
+// rounded fp32 max-pool -- the bits of the fused stem + pool's fp16 form).  Same window walk as maxpool_kernel.
+__global__ void maxpool_f16out_kernel(const float* __restrict__ x, int n, int h, int w, int c4, int oh, int ow, _Float16* __restrict__ o) {
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long total = (long long)n * oh * ow * c4;
+    if (idx >= total) return;
+    const int cq = (int)(idx % c4);
+    long long t = idx / c4;
+    const int ox = (int)(t % ow);
+    t /= ow;
+    const int oy = (int)(t % oh);
+    const int img = (int)(t / oh);
+    const float ninf = -__builtin_inff();
+    f32x4 best = {ninf, ninf, ninf, ninf};
+#pragma unroll
+    for (int ky = 0; ky < 3; ++ky) {
+        const int iy = min(max(2 * oy - 1 + ky, 0), h - 1);
+#pragma unroll
+        for (int kx = 0; kx < 3; ++kx) {
+            const int ix = min(max(2 * ox - 1 + kx, 0), w - 1);
+            const f32x4 v = *reinterpret_cast<const f32x4*>(x + (((size_t)img * h + iy) * w + ix) * (size_t)(4 * c4) + 4 * cq);
+            best.x = fmaxf(best.x, v.x); best.y = fmaxf(best.y, v.y); best.z = fmaxf(best.z, v.z); best.w = fmaxf(best.w, v.w);
+        }
+    }
+    *reinterpret_cast<f16x4*>(o + (size_t)idx * 4) = f16x4{adaf_f16_of(best.x), adaf_f16_of(best.y), adaf_f16_of(best.z), adaf_f16_of(best.w)};
+}
+
+// AdaptiveAvgPool2d(1) of an fp16 map: the stored values widened to fp32, summed in pixel order, divided by hw -- the order and the
+// operations of avgpool_kernel and of the pooled fp16 conv3 epilogue (conv_gemm.hip conv_epilogue_pool, RND form): the same bits.
+__global__ void avgpool_f16_kernel(const _Float16* __restrict__ x, int n, int hw, int c4, float* __restrict__ o, int ldo) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= n * c4) return;
+    const int cq = idx % c4, img = idx / c4;
+    f32x4 s = {0.f, 0.f, 0.f, 0.f};
+    const _Float16* p = x + (size_t)img * hw * (4 * c4) + 4 * cq;
+    for (int i = 0; i < hw; ++i) {
+        const f16x4 v = *reinterpret_cast<const f16x4*>(p + (size_t)i * (4 * c4));
+        s += f32x4{(float)v.x, (float)v.y, (float)v.z, (float)v.w};
+    }
+    const float inv = (float)hw;
+    f32x4 r = {s.x / inv, s.y / inv, s.z / inv, s.w / inv};
+    *reinterpret_cast<f32x4*>(o + (size_t)img * ldo + 4 * cq) = r;
+}
+
+// TemporalShift.shift of an NHWC fp16 map (shift_place = 'block' of the fp16 trunk): eight channels (16 bytes) per thread.  c % 8 == 0
+// and fold % 8 == 0 keep a chunk on one side of the fold boundaries; otherwise one channel per thread.  A move: exact.
+__global__ void tshift_f16_kernel(const _Float16* __restrict__ x, long long total, int c, int hw, int T, int fold, int vec,
+                                  _Float16* __restrict__ o) {
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const int per = vec ? 8 : 1;
+    if (idx * per >= total) return;
+    const long long e = idx * per;                      // first element of this thread
+    const long long frame_elems = (long long)c * hw;
+    const long long f = e / frame_elems;
+    const int ch = (int)((e - f * frame_elems) % c);
+    const int t = (int)(f % T);
+    long long src = e;
+    bool zero = false;
+    if (ch < fold) { src = e + frame_elems; zero = t == T - 1; }          // from t+1
+    else if (ch < 2 * fold) { src = e - frame_elems; zero = t == 0; }     // from t-1
+    if (vec) {
+        f16x8 v = {};
+        if (!zero) v = *reinterpret_cast<const f16x8*>(x + src);
+        *reinterpret_cast<f16x8*>(o + e) = v;
+    } else {
+        o[e] = zero ? (_Float16)0.f : x[src];
+    }
+}
+
 __device__ __forceinline__ float sigmoidf_(float v) { return 1.f / (1.f + expf(-v)); }
 
 // One GRU step's gate math (PyTorch order r,z,n):  gi = W_ih x_t + b_ih (precomputed for all t),
@@ -425,4 +498,23 @@ void adaf_launch_dwconv3x3_f16(const void* x, int n, int h, int w, int c, int st
         hipLaunchKernelGGL((dwconv3x3_kernel<2, 2, 1, _Float16>), dim3(blocks_for(total)), dim3(256), 0, s, xi, n, h, w, c / 4, oh, ow, wt,
                            scale, bias, lo, hi, oo);
     }
+}
+
+void adaf_launch_maxpool_f16out(const float* x, int n, int h, int w, int c, void* o, hipStream_t s) {
+    const int oh = (h + 2 - 3) / 2 + 1, ow = (w + 2 - 3) / 2 + 1;
+    const long long total = (long long)n * oh * ow * (c / 4);
+    hipLaunchKernelGGL(maxpool_f16out_kernel, dim3(blocks_for(total)), dim3(256), 0, s, x, n, h, w, c / 4, oh, ow, static_cast<_Float16*>(o));
+}
+
+void adaf_launch_avgpool_f16(const void* x, int n, int hw, int c, float* o, int ldo, hipStream_t s) {
+    hipLaunchKernelGGL(avgpool_f16_kernel, dim3(blocks_for((long long)n * (c / 4))), dim3(256), 0, s, static_cast<const _Float16*>(x), n, hw,
+                       c / 4, o, ldo);
+}
+
+void adaf_launch_tshift_f16(const void* x, int nt, int c, int hw, int T, int div, void* o, hipStream_t s) {
+    const long long total = (long long)nt * c * hw;
+    const int fold = c / div;
+    const int vec = (c % 8 == 0 && fold % 8 == 0) ? 1 : 0;
+    hipLaunchKernelGGL(tshift_f16_kernel, dim3(blocks_for(vec ? total / 8 : total)), dim3(256), 0, s, static_cast<const _Float16*>(x), total, c, hw,
+                       T, fold, vec, static_cast<_Float16*>(o));
 }

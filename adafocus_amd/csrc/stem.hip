@@ -16,14 +16,26 @@
 //                        a real, non-negative value, so 0 is as good as the -inf padding of nn.MaxPool2d) and 256 threads
 //                        take the 3 x 3 maxima with 16-byte reads and stores.  The 604 MB conv map (1024 patches of 96^2)
 //                        is never written: 151 MB of pooled output instead, one launch instead of two.
+// Both pooled forms also come with an fp16 store (O16, the fp16 trunk ADAF_MATH_F16): the same fp32 chain, BN, ReLU and maxima, then ONE
+// rounding of each pooled value (rounding is monotone: the rounded pool of the fp32 map, bit for bit).
 // Both are persistent (a block loops over tiles) and software-pipelined: the next tile's window is fetched into registers
 // before the current tile's MFMAs and written to LDS after them, so no global latency sits between two tiles.
 #include "adaf_internal.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
 namespace {
+
+// a pooled 4-channel quad -> the output map: fp32, or (O16, the fp16 trunk ADAF_MATH_F16) ONE rounding of the fp32 maximum per value
+template <bool O16>
+__device__ __forceinline__ void store_quad(float* out, size_t at, const f32x4 m) {
+    if constexpr (O16)
+        *reinterpret_cast<f16x4*>(reinterpret_cast<_Float16*>(out) + at) = f16x4{adaf_f16_of(m.x), adaf_f16_of(m.y), adaf_f16_of(m.z), adaf_f16_of(m.w)};
+    else
+        *reinterpret_cast<f32x4*>(out + at) = m;
+}
 
 constexpr int KS = 74;                    // MFMA steps (k pairs): k = j | 74 + j
 
@@ -45,7 +57,7 @@ struct StemArgs {
     const float* w;      // Wr [2][74][64]
     const float* scale;  // [64]
     const float* bias;
-    float* out;          // [n, OH, OW, 64] (conv map) or [n, PH, PW, 64] (pooled map)
+    float* out;          // [n, OH, OW, 64] (conv map) or [n, PH, PW, 64] (pooled map; fp16 in the O16 forms)
     int n, P, OH, OW, PH, PW, tiles_y, tiles_x, ntiles;
 };
 
@@ -188,7 +200,7 @@ struct PoolCfg {
                                                                       // instead of 128 + 6 spilled -- the tile form now only runs where blocks are scarce)
 };
 
-template <int TPH>
+template <int TPH, bool O16 = false>
 __global__ __launch_bounds__(PoolCfg<TPH>::NT) __attribute__((amdgpu_waves_per_eu(PoolCfg<TPH>::WPE, PoolCfg<TPH>::WPE)))
 void stem7x7_pool_kernel(const StemArgs a) {
     using C = PoolCfg<TPH>;
@@ -279,7 +291,7 @@ void stem7x7_pool_kernel(const StemArgs a) {
                         m.x = fmaxf(m.x, v.x); m.y = fmaxf(m.y, v.y); m.z = fmaxf(m.z, v.z); m.w = fmaxf(m.w, v.w);
                     }
                 if (py0 + py < a.PH && px0 + px < a.PW)
-                    *reinterpret_cast<f32x4*>(a.out + (((size_t)img * a.PH + py0 + py) * a.PW + px0 + px) * 64 + 32 * half + 4 * c4) = m;
+                    store_quad<O16>(a.out, (((size_t)img * a.PH + py0 + py) * a.PW + px0 + px) * 64 + 32 * half + 4 * c4, m);
             }
             if (half == 0) __syncthreads();   // the second half overwrites the staging image
         }
@@ -318,7 +330,7 @@ struct RowsCfg {
     static_assert(NPX % 32 == 0 && OW % 2 == 0 && R % 2 == 0 && OW % R == 0 && PR * PW * 8 == NT, "strip geometry");
 };
 
-template <int OW, int R, int FR, int G = (RowsCfg<OW, R>::WPE >= 3 ? 4 : 8)>
+template <int OW, int R, int FR, int G = (RowsCfg<OW, R>::WPE >= 3 ? 4 : 8), bool O16 = false>
 __global__ __launch_bounds__((RowsCfg<OW, R>::NT)) __attribute__((amdgpu_waves_per_eu((RowsCfg<OW, R>::WPE), (RowsCfg<OW, R>::WPE))))
 void stem7x7_pool_rows_kernel(const StemArgs a) {
     using C = RowsCfg<OW, R>;
@@ -456,20 +468,25 @@ void stem7x7_pool_rows_kernel(const StemArgs a) {
                 m.z = fmaxf(fmaxf(top.z, mid.z), bot.z); m.w = fmaxf(fmaxf(top.w, mid.w), bot.w);
                 if (je == C::PR - 1) carry[half] = bot;
                 const int py = st * C::PR + je;
-                *reinterpret_cast<f32x4*>(a.out + (((size_t)img * C::PW + py) * C::PW + px) * 64 + 32 * half + 4 * c4) = m;
+                store_quad<O16>(a.out, (((size_t)img * C::PW + py) * C::PW + px) * 64 + 32 * half + 4 * c4, m);
             }
             if (half == 0) __syncthreads();   // the second half overwrites the staging image
         }
     }
 }
 
-template <int OW, int R, int FR, int G = (RowsCfg<OW, R>::WPE >= 3 ? 4 : 8)>
-void launch_rows(StemArgs a, int cus, hipStream_t s) {
+template <int OW, int R, int FR, int G, bool O16>
+void launch_rows_t(StemArgs a, int cus, hipStream_t s) {
     using C = RowsCfg<OW, R>;
     const int grid = a.n < cus * C::BPC ? a.n : cus * C::BPC;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&stem7x7_pool_rows_kernel<OW, R, FR, G>), hipFuncAttributeMaxDynamicSharedMemorySize,
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&stem7x7_pool_rows_kernel<OW, R, FR, G, O16>), hipFuncAttributeMaxDynamicSharedMemorySize,
                               C::LDSF * 4);
-    hipLaunchKernelGGL((stem7x7_pool_rows_kernel<OW, R, FR, G>), dim3(grid), dim3(C::NT), C::LDSF * 4, s, a);
+    hipLaunchKernelGGL((stem7x7_pool_rows_kernel<OW, R, FR, G, O16>), dim3(grid), dim3(C::NT), C::LDSF * 4, s, a);
+}
+template <int OW, int R, int FR, int G = (RowsCfg<OW, R>::WPE >= 3 ? 4 : 8)>
+void launch_rows(StemArgs a, int cus, hipStream_t s, bool out16) {
+    if (out16) launch_rows_t<OW, R, FR, G, true>(a, cus, s);
+    else launch_rows_t<OW, R, FR, G, false>(a, cus, s);
 }
 
 // Strip height R and operand-group size G per patch size, from tools/stem_probe.py sweeps on 1024 patches (ms per launch, tile form first):
@@ -477,23 +494,24 @@ void launch_rows(StemArgs a, int cus, hipStream_t s) {
 //   128^2: 1.53 (0.98 as two launches) -> R = 2 (two 4-wave blocks) 0.69, R = 4 / 8 0.70-0.73;  144^2: 1.27 -> R = 4 (one 9-wave block) 1.07;
 //   64^2: 0.39 -> 0.18.  Taller strips amortise the four barriers of a strip; a 16-wave block is the limit (R * OW <= 512).
 template <int FR>
-bool launch_rows_for(const StemArgs& a, int cus, hipStream_t s) {
+bool launch_rows_for(const StemArgs& a, int cus, hipStream_t s, bool out16) {
     switch (a.P) {
-        case 64: launch_rows<32, 4, FR, 8>(a, cus, s); return true;
-        case 96: launch_rows<48, 8, FR, 2>(a, cus, s); return true;
-        case 128: launch_rows<64, 2, FR, 8>(a, cus, s); return true;
-        case 144: launch_rows<72, 4, FR, 2>(a, cus, s); return true;
+        case 64: launch_rows<32, 4, FR, 8>(a, cus, s, out16); return true;
+        case 96: launch_rows<48, 8, FR, 2>(a, cus, s, out16); return true;
+        case 128: launch_rows<64, 2, FR, 8>(a, cus, s, out16); return true;
+        case 144: launch_rows<72, 4, FR, 2>(a, cus, s, out16); return true;
         default: return false;
     }
 }
 
 template <int TPH>
-void launch_pool(StemArgs a, int cus, hipStream_t s) {
+void launch_pool(StemArgs a, int cus, hipStream_t s, bool out16) {
     using C = PoolCfg<TPH>;
     a.tiles_y = (a.PH + TPH - 1) / TPH; a.tiles_x = (a.PW + C::TPW - 1) / C::TPW;
     a.ntiles = a.n * a.tiles_y * a.tiles_x;
     const int grid = a.ntiles < cus * 2 ? a.ntiles : cus * 2;
-    hipLaunchKernelGGL((stem7x7_pool_kernel<TPH>), dim3(grid), dim3(C::NT), 0, s, a);
+    if (out16) hipLaunchKernelGGL((stem7x7_pool_kernel<TPH, true>), dim3(grid), dim3(C::NT), 0, s, a);
+    else hipLaunchKernelGGL((stem7x7_pool_kernel<TPH>), dim3(grid), dim3(C::NT), 0, s, a);
 }
 
 }  // namespace
@@ -530,23 +548,23 @@ bool adaf_stem7x7_rows_ok(int P, int n, int cus) {
 }
 
 bool adaf_launch_stem7x7_pool_frames(const float* frames, bool pixel_major, int nframes, const float* act, int fpa, int H, int W, int n, int P,
-                                     const float* wr, const float* scale, const float* bias, float* out, int cus, hipStream_t s) {
+                                     const float* wr, const float* scale, const float* bias, float* out, int cus, hipStream_t s, bool out16) {
     if (!adaf_stem7x7_rows_ok(P, n, cus) || !act || fpa < 1 || nframes < 1 || H < P || W < P) return false;
     StemArgs a;
     a.x = frames; a.act = act; a.fpa = fpa; a.H = H; a.W = W; a.nframes = nframes; a.w = wr; a.scale = scale; a.bias = bias; a.out = out;
     a.n = n; a.P = P; a.OH = P / 2; a.OW = a.OH; a.PH = a.OH / 2; a.PW = a.PH; a.tiles_y = a.tiles_x = a.ntiles = 0;
-    return pixel_major ? launch_rows_for<2>(a, cus, s) : launch_rows_for<1>(a, cus, s);
+    return pixel_major ? launch_rows_for<2>(a, cus, s, out16) : launch_rows_for<1>(a, cus, s, out16);
 }
 
 // conv 7x7/2 + BN + ReLU + max-pool 3x3/2/1 in one launch: out [n, PH, PW, 64] with PH = (OH - 1) / 2 + 1
 void adaf_launch_stem7x7_pool(const float* x4, int n, int P, const float* wr, const float* scale, const float* bias, float* out,
-                              int cus, hipStream_t s) {
+                              int cus, hipStream_t s, bool out16) {
     StemArgs a;
     a.x = x4; a.w = wr; a.scale = scale; a.bias = bias; a.out = out; a.act = nullptr; a.fpa = 1; a.H = a.W = 0; a.nframes = n;
     a.n = n; a.P = P; a.OH = (P + 6 - 7) / 2 + 1; a.OW = a.OH; a.PH = (a.OH - 1) / 2 + 1; a.PW = a.PH;
-    if (adaf_stem7x7_rows_ok(P, n, cus) && launch_rows_for<0>(a, cus, s)) return;
+    if (adaf_stem7x7_rows_ok(P, n, cus) && launch_rows_for<0>(a, cus, s, out16)) return;
     // rows of pooled pixels per tile: 4 (5 waves) or 6 (7 waves), whichever computes fewer conv pixels for this map
     const int cost4 = ((a.PH + 3) / 4) * PoolCfg<4>::NWV, cost6 = ((a.PH + 5) / 6) * PoolCfg<6>::NWV;
-    if (cost6 < cost4) launch_pool<6>(a, cus, s);
-    else launch_pool<4>(a, cus, s);
+    if (cost6 < cost4) launch_pool<6>(a, cus, s, out16);
+    else launch_pool<4>(a, cus, s, out16);
 }

@@ -28,7 +28,7 @@ from torch import nn
 from . import hip_ops
 from .mobilenet import mobilenet_v2
 from .ppo import PPO, Memory
-from .resnet import resnet50
+from .resnet import check_local_math, resnet50
 from .synth import grid_table
 from .utils import get_patch, get_patch_nhwc4
 
@@ -64,6 +64,13 @@ class GFV(nn.Module):
         self.focuser = Focuser(args.patch_size, args.random_patch, policy_params, self.num_class,
                                local_arch=getattr(args, "local_arch", "resnet50"), local_dtype=getattr(args, "local_dtype", "f16"),
                                local_image_size=getattr(args, "local_image_size", "native"))
+        # build-specific: local_math = the ResNet-50 local CNN's arithmetic, "f32" (default) | "split_bf16" | "f16" (include/adafocus.h
+        # ADAF_MATH_*; the glancer, policy and classifier stay fp32 whatever it is)
+        local_math = getattr(args, "local_math", None)
+        if local_math is not None:
+            check_local_math(local_math, getattr(args, "local_arch", "resnet50"))
+            if getattr(args, "local_arch", "resnet50") == "resnet50":
+                self.focuser.net.set_math(local_math)
         self.dropout = nn.Dropout(p=args.dropout)
         feat_dim = self.focuser.feature_dim + (self.glancer.feature_dim if self.with_glancer else 0)
         if args.consensus == "gru":

@@ -18,6 +18,7 @@ from .basic_ops import ConsensusModule
 from .mobilenetv2 import InvertedResidual, mobilenet_v2
 from .ppo import PPO, Memory
 from .ppo_continuous import PPO_Continuous
+from .resnet import check_local_math
 from .synth import grid_table
 from .temporal_shift import TemporalShift
 from .tsn import TSN
@@ -81,6 +82,11 @@ class GFV(nn.Module):
                     shift_place=args.shift_place, fc_lr5=args.fc_lr5, temporal_pool=args.temporal_pool,
                     non_local=args.non_local)
         self.focuser = Focuser(args.patch_size, args.random_patch, policy_params, base)
+        # build-specific: local_math = the TSN local CNN's (ResNet-50) arithmetic, "f32" (default) | "split_bf16" | "f16" (include/adafocus.h
+        # ADAF_MATH_*; the glancer, policy and classifier stay fp32 whatever it is)
+        local_math = getattr(args, "local_math", None)
+        if local_math is not None:
+            self.focuser.net.base_model.set_math(check_local_math(local_math, getattr(args, "local_arch", "resnet50")))
         self.dropout = nn.Dropout(p=args.dropout)
         self.classifier = nn.Linear(in_features=self.focuser.feature_dim, out_features=args.num_classes)
         self.consensus = ConsensusModule(consensus_type="avg")

@@ -9,7 +9,7 @@ import torch
 
 from . import _lib as L
 from ._lib import ACT_NONE, ACT_RELU, ACT_RELU6, ACT_SIGMOID, ACT_SWISH, LAYOUT_NCHW, LAYOUT_NHWC, LAYOUT_NHWC4  # noqa: F401
-from ._lib import MATH_F32, MATH_F32_SPLIT_BF16  # noqa: F401
+from ._lib import MATH_F16, MATH_F32, MATH_F32_SPLIT_BF16  # noqa: F401
 from ._lib import DTYPE_F32, DTYPE_F16  # noqa: F401
 
 
@@ -347,9 +347,11 @@ class ResNet50Trunk:
         L.check(self._lib.adaf_resnet50_set_tiles(self._net, arr, len(tiles)), self._h)
 
     def set_math(self, mode):
-        """"f32" (default: fp32 MFMA, exact FMA chain) or "split_bf16" (opt-in: fp32 operands decomposed into three
-        bf16 parts, six bf16 MFMA products per element pair, fp32 accumulate -- include/adafocus.h ADAF_MATH_*)."""
-        code = {"f32": MATH_F32, "split_bf16": MATH_F32_SPLIT_BF16}.get(mode, mode)
+        """"f32" (default: fp32 MFMA, exact FMA chain), "split_bf16" (opt-in: fp32 operands decomposed into three
+        bf16 parts, six bf16 MFMA products per element pair, fp32 accumulate) or "f16" (opt-in: fp16 activations and
+        filters on the f16 matrix pipe, fp32 accumulate / BN / residual, one rounding per stored value; the stem and the
+        pooled features stay fp32) -- include/adafocus.h ADAF_MATH_*.  Switching into or out of "f16" clears tile overrides."""
+        code = {"f32": MATH_F32, "split_bf16": MATH_F32_SPLIT_BF16, "f16": MATH_F16}.get(mode, mode)
         L.check(self._lib.adaf_resnet50_set_math(self._net, int(code)), self._h)
 
 

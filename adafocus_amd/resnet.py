@@ -17,7 +17,18 @@ from .utils import nchw_to_nhwc4
 __all__ = ["ResNet", "resnet50", "Bottleneck"]
 
 _STAGES = ((64, 3, 1), (128, 4, 2), (256, 6, 2), (512, 3, 2))
-DEFAULT_MATH = "f32"      # arithmetic of newly built trunks ("f32" | "split_bf16"); ResNet.set_math overrides per model
+DEFAULT_MATH = "f32"      # arithmetic of newly built trunks ("f32" | "split_bf16" | "f16"); ResNet.set_math overrides per model
+MATH_MODES = ("f32", "split_bf16", "f16")
+
+
+def check_local_math(mode, local_arch="resnet50"):
+    """Validates the build-specific ``args.local_math`` of the GFV models: the ResNet-50 local CNN's arithmetic ("f32" default,
+    "split_bf16", "f16").  An EfficientNet local CNN keeps its own ``local_dtype``: any value but "f32" is refused there."""
+    if mode not in MATH_MODES:
+        raise ValueError("local_math must be one of %s, got %r" % (", ".join(MATH_MODES), mode))
+    if local_arch != "resnet50" and mode != "f32":
+        raise ValueError("local_math=%r applies to the ResNet-50 local CNN only (local_arch=%r: use local_dtype)" % (mode, local_arch))
+    return mode
 
 
 class Bottleneck(nn.Module):
@@ -96,11 +107,20 @@ class ResNet(nn.Module):
             self._trunk.set_fusion(on)
 
     def set_math(self, mode):
-        """Opt-in arithmetic of the convolutions: "f32" (default, fp32 matrix pipe) or "split_bf16" (fp32 operands
-        as three exact bf16 parts on the bf16 matrix pipe, fp32 accumulate); no reference counterpart."""
+        """Opt-in arithmetic of the convolutions: "f32" (default, fp32 matrix pipe), "split_bf16" (fp32 operands
+        as three exact bf16 parts on the bf16 matrix pipe, fp32 accumulate) or "f16" (fp16 activations and filters on
+        the f16 matrix pipe with fp32 accumulation; fp32 stem and pooled features -- include/adafocus.h ADAF_MATH_F16);
+        no reference counterpart."""
+        if mode not in MATH_MODES:
+            raise ValueError("math must be one of %s, got %r" % (", ".join(MATH_MODES), mode))
         self._math = mode
         if self._trunk is not None:
             self._trunk.set_math(mode)
+
+    @property
+    def math(self):
+        """The arithmetic the trunk runs with ("f32" | "split_bf16" | "f16")."""
+        return getattr(self, "_math", None) or DEFAULT_MATH
 
     # ---- reference surface --------------------------------------------------------------
     def features_nhwc4(self, patches_nhwc4, out=None):

@@ -167,7 +167,7 @@ typedef struct adaf_conv_params {
     int tsm_segments;   /* > 0: temporal shift (STH/ops/temporal_shift.py:28-46) of the INPUT, fused into the
                            operand load; images are (clip, t) with t fastest, n % tsm_segments == 0;
                            only for kh = kw = 1, stride 1, pad 0 */
-    int tsm_div;        /* fold = cin / tsm_div, must be a multiple of 4 */
+    int tsm_div;        /* fold = cin / tsm_div, must be a multiple of 4 (of 8 with fp16 operands) */
     int ldx, ldo, ldr;  /* pixel strides in floats of x / out / residual; 0 = dense (cin / cout / cout) */
     int tile;           /* 0 = choose automatically; otherwise force a kernel variant (tuning / tests):
                            1..4 = 128x128, 128x64, 64x64, 64x128 block tiles with register staging,
@@ -320,8 +320,29 @@ int adaf_resnet50_set_shift_place(adaf_resnet50* net, int place);
  *                            pipe, the rest runs the six-product form; the global option "split_stage1_f32" = 0 puts every conv but
  *                            the stem on split tiles (NOT bit-identical to the default hybrid plan, both fp32-accurate; results of
  *                            split_bf16 callers changed by <= 2e-5 when the hybrid plan became the default).  adaf_resnet50_set_fusion
- *                            applies to the fp32-pipe launches of either mode. */
-enum { ADAF_MATH_F32 = 0, ADAF_MATH_F32_SPLIT_BF16 = 1 };
+ *                            applies to the fp32-pipe launches of either mode.
+ *   ADAF_MATH_F16            (opt-in)  fp16 STORAGE on the f16 matrix pipe.  Numerics contract:
+ *                            - stem: the 7x7/2 conv on fp32 operands (3-channel input, fp32 weights, an exact fp32 chain), BN, ReLU and
+ *                              the 3x3/2 max-pool exactly as ADAF_MATH_F32; the pooled map is rounded ONCE to fp16 (rounding is
+ *                              monotone: the fused stem + pool equals rounding the fp32 stem output, bit for bit);
+ *                            - every later conv (conv1/2/3, downsample): fp16 activations, fp16 weights rounded to nearest-even from the
+ *                              fp32 parameters at finalize, products on v_mfma_f32_32x32x16_f16 with fp32 accumulation, BN as the fp32
+ *                              (scale, bias) affine (not folded into the filters), conv3: + the fp16 residual widened to fp32, ReLU,
+ *                              then ONE rounding to fp16;
+ *                            - global average pool: the fp16-rounded values of the last block's map, widened to fp32, summed in pixel
+ *                              order and divided by the pixel count -- fp32 features feat[i * ldfeat + c]; the pooled conv3 epilogue and
+ *                              the separate pool launch give the same bits (a patch's features do not depend on its batch);
+ *                            - temporal shift: a move of fp16 values with zeros at clip ends (exact).  'blockres' needs
+ *                              fold = cin / tsm_div to be a multiple of 8 (ADAF_E_LAYOUT otherwise; every ResNet conv1 with tsm_div 8 or 4
+ *                              qualifies); 'block' materialises the shifted fp16 map in the sixth slab as the fp32 plan does;
+ *                            - adaf_resnet50_forward_map writes the exact fp32 widening of the fp16 final map.
+ *                            Everything outside the trunk (GRU / FC, fc_meanpool, glancer, policy) stays fp32.  The fp16 filter planes
+ *                            are packed at finalize, or by set_math(ADAF_MATH_F16) after finalize.  adaf_resnet50_set_tiles accepts 0 and
+ *                            81..84 / 88 (adaf_conv_params.tile) for the convs after the stem, 0 for the stem; switching between
+ *                            ADAF_MATH_F16 and an fp32 mode resets the overrides to 0.  adaf_resnet50_set_latency_rows has no effect (the
+ *                            small-batch form is fp32 only); adaf_resnet50_set_fusion applies to the stem + max-pool launch, the merged
+ *                            layer1.0 conv1 + downsample GEMM and the pooled last conv3 (bit-identical either way). */
+enum { ADAF_MATH_F32 = 0, ADAF_MATH_F32_SPLIT_BF16 = 1, ADAF_MATH_F16 = 2 };
 int adaf_resnet50_set_math(adaf_resnet50* net, int mode);
 
 /* ---- a10: MobileNetV2 building blocks and the glancer as one object ---------------------
