@@ -467,6 +467,7 @@ struct ConvLayer {
     std::string bn;        // e.g. "layer1.0.bn1"
     int cin, cout, k, stride, pad;
     int cin_pad;
+    bool tsm = false;      // a Bottleneck conv1 that the 'blockres' temporal shift wraps (make_temporal_shift's n_round rule)
     float* w = nullptr;    // packed OHWI
     unsigned short* wsp = nullptr;   // the same as three bf16 planes (ADAF_MATH_F32_SPLIT_BF16 only)
     unsigned short* w16 = nullptr;   // the same rounded to fp16, nearest-even (ADAF_MATH_F16 only; not for the stem)
@@ -479,6 +480,7 @@ struct adaf_resnet50 {
     std::map<std::string, std::pair<const float*, size_t>> params;
     std::vector<ConvLayer> convs;  // [0] = stem, then per block conv1, conv2, conv3, (downsample)
     std::vector<int> tiles;        // per conv launch override
+    int blocks[4] = {3, 4, 6, 3};  // Bottlenecks per stage: ResNet-50, -101 or -152 (inferred from the parameter names at finalize)
     // layer1.0's conv1 (64 -> 64) and downsample (64 -> 256) read the same map with the same 1x1 / stride-1 geometry: their
     // filter banks and BN affines concatenated along the output channels, for one launch instead of two (run_trunk)
     float* l10_w = nullptr;
@@ -496,21 +498,27 @@ struct adaf_resnet50 {
 
 namespace {
 
-const int kStageBlocks[4] = {3, 4, 6, 3};
 const int kStagePlanes[4] = {64, 128, 256, 512};
+// the Bottleneck depths the trunk runs (torchvision's resnet50 / resnet101 / resnet152, ACT/models/resnet.py:280-315)
+const int kDepths[3][4] = {{3, 4, 6, 3}, {3, 4, 23, 3}, {3, 8, 36, 3}};
+
+int total_blocks(const adaf_resnet50* net) { return net->blocks[0] + net->blocks[1] + net->blocks[2] + net->blocks[3]; }
 
 void build_layers(adaf_resnet50* net) {
     net->convs.clear();
     net->convs.push_back({"conv1", "bn1", 3, 64, 7, 2, 3, 4});
+    // make_temporal_shift, place 'blockres' (STH/ops/temporal_shift.py:122-136): a layer3 of 23 or more blocks gives n_round = 2,
+    // and block i of every stage has its conv1 shifted iff i % n_round == 0
+    const int n_round = net->blocks[2] >= 23 ? 2 : 1;
     int inplanes = 64;
     for (int s = 0; s < 4; ++s) {
         const int planes = kStagePlanes[s];
-        for (int b = 0; b < kStageBlocks[s]; ++b) {
+        for (int b = 0; b < net->blocks[s]; ++b) {
             char pre[32];
             snprintf(pre, sizeof(pre), "layer%d.%d.", s + 1, b);
             const int stride = (b == 0 && s > 0) ? 2 : 1;
             const std::string p(pre);
-            net->convs.push_back({p + "conv1", p + "bn1", inplanes, planes, 1, 1, 0, inplanes});
+            net->convs.push_back({p + "conv1", p + "bn1", inplanes, planes, 1, 1, 0, inplanes, b % n_round == 0});
             net->convs.push_back({p + "conv2", p + "bn2", planes, planes, 3, stride, 1, planes});
             net->convs.push_back({p + "conv3", p + "bn3", planes, planes * 4, 1, 1, 0, planes});
             if (b == 0) net->convs.push_back({p + "downsample.0", p + "downsample.1", inplanes, planes * 4, 1, stride, 0, inplanes});
@@ -549,7 +557,7 @@ int run_trunk16(adaf_resnet50* net, const float* x4, int n, int P, int tsm_T, in
     if (tsm_c1 > 0)
         for (size_t i = 1; i < net->convs.size(); ++i) {
             const ConvLayer& L = net->convs[i];
-            if (L.name.size() > 5 && L.name.compare(L.name.size() - 5, 5, "conv1") == 0 && (L.cin / tsm_div) % 8)
+            if (L.tsm && (L.cin / tsm_div) % 8)
                 return fail(h, ADAF_E_LAYOUT, "resnet50 (fp16): temporal-shift fold = %d / %d = %d of %s must be a multiple of 8", L.cin, tsm_div,
                             L.cin / tsm_div, L.name.c_str());
         }
@@ -628,7 +636,7 @@ int run_trunk16(adaf_resnet50* net, const float* x4, int n, int P, int tsm_T, in
     bool pooled = false;
     int rc;
     for (int s = 0; s < 4; ++s) {
-        for (int b = 0; b < kStageBlocks[s]; ++b) {
+        for (int b = 0; b < net->blocks[s]; ++b) {
             int h1 = hh, w1 = ww, h2, w2, h3, w3;
             if (tsm_block) {       // the block's input, shifted along its clip: conv1, downsample and identity all read this copy
                 const int cin = net->convs[li].cin;
@@ -660,7 +668,7 @@ int run_trunk16(adaf_resnet50* net, const float* x4, int n, int P, int tsm_T, in
                 h1 = am.OH; w1 = am.OW;
                 ++li;
                 ds_done = true;
-            } else if ((rc = conv(cur, hh, ww, ADAF_ACT_RELU, nullptr, t1, tsm_c1 > 0, &h1, &w1))) return rc;
+            } else if ((rc = conv(cur, hh, ww, ADAF_ACT_RELU, nullptr, t1, tsm_c1 > 0 && net->convs[li].tsm, &h1, &w1))) return rc;
             const void* identity = cur;
             if (b == 0) {
                 if (!ds_done) {
@@ -672,7 +680,7 @@ int run_trunk16(adaf_resnet50* net, const float* x4, int n, int P, int tsm_T, in
             }
             li = i_c2;
             if ((rc = conv(t1, h1, w1, ADAF_ACT_RELU, nullptr, t2, false, &h2, &w2))) return rc;
-            const bool last = s == 3 && b == kStageBlocks[3] - 1;
+            const bool last = s == 3 && b == net->blocks[3] - 1;
             if (last && net->fuse && !rec && !featmap && !net->tiles[li]) {
                 // the trunk's last conv3 with the global average pool in its epilogue: the fp16-rounded values are averaged (conv + pool bits)
                 const ConvLayer& L3 = net->convs[li];
@@ -838,7 +846,7 @@ int run_trunk(adaf_resnet50* net, const float* x4, int n, int P, int tsm_T, int 
     float* t2 = buf[3];            // conv2 output (or, after a fused launch, the NEXT block's conv1 output)
     bool c1_done = false;          // the previous fused launch already produced this block's conv1 output (in t1)
     for (int s = 0; s < 4; ++s) {
-        for (int b = 0; b < kStageBlocks[s]; ++b) {
+        for (int b = 0; b < net->blocks[s]; ++b) {
             int h1 = hh, w1 = ww, h2, w2, h3, w3;
             if (tsm_block) {       // the block's input, shifted along its clip: conv1, downsample and identity all read this copy
                 const int cin = net->convs[li].cin;
@@ -873,7 +881,7 @@ int run_trunk(adaf_resnet50* net, const float* x4, int n, int P, int tsm_T, int 
                 ++li;
                 ds_done = true;
             } else if (!c1_done) {
-                if ((rc = conv(cur, hh, ww, ADAF_ACT_RELU, nullptr, t1, tsm_c1 > 0, &h1, &w1, 0))) return rc;
+                if ((rc = conv(cur, hh, ww, ADAF_ACT_RELU, nullptr, t1, tsm_c1 > 0 && net->convs[li].tsm, &h1, &w1, 0))) return rc;
             } else ++li;
             c1_done = false;
             const float* identity = cur;
@@ -904,7 +912,7 @@ int run_trunk(adaf_resnet50* net, const float* x4, int n, int P, int tsm_T, int 
                 //  with the shift as a row offset inside the tile, whole clips per tile -- adaf_fused_tail_shift_ok)
                 const ConvLayer* Ln = ((tsm_T == 0 || tsm_c1 > 0) && i_next < (int)net->convs.size() && !net->tiles[i_next]) ? &net->convs[i_next] : nullptr;
                 if (Ln && !(Ln->k == 1 && Ln->stride == 1 && Ln->cin == L3.cout && (Ln->cout == 64 || Ln->cout == 128))) Ln = nullptr;
-                const int tsm_n1 = (Ln && tsm_c1 > 0) ? tsm_c1 : 0, fold_n1 = Ln ? Ln->cin / (tsm_div > 0 ? tsm_div : 8) : 0;
+                const int tsm_n1 = (Ln && tsm_c1 > 0 && Ln->tsm) ? tsm_c1 : 0, fold_n1 = Ln ? Ln->cin / (tsm_div > 0 ? tsm_div : 8) : 0;
                 if (tsm_n1 && !adaf_fused_tail_shift_ok(a2, L3.cout, L3.cout, tsm_n1, fold_n1)) Ln = nullptr;
                 const double M = (double)a2.M;
                 double macs = M * 64 * 9 * 64 + M * L3.cout * 64 + (Ln ? M * Ln->cout * L3.cout : 0.0);
@@ -918,7 +926,7 @@ int run_trunk(adaf_resnet50* net, const float* x4, int n, int P, int tsm_T, int 
                 if (Ln) { float* t = t1; t1 = t2; t2 = t; c1_done = true; }
             } else {
                 if ((rc = conv(t1, h1, w1, ADAF_ACT_RELU, nullptr, t2, 0, &h2, &w2, 0))) return rc;
-                const bool last = s == 3 && b == kStageBlocks[3] - 1;
+                const bool last = s == 3 && b == net->blocks[3] - 1;
                 if (last && fuse && !rec && !featmap && net->math == ADAF_MATH_F32 && !net->tiles[li] && !(lat_ok && n * h2 * w2 <= lat_rows)) {
                     // the trunk's last conv3: the global average pool rides in its epilogue (conv_epilogue_pool) -- no 2048-channel map,
                     // no pooling launch -- when whole images fill its row tiles (3x3 / 4x4 / 5x5 maps); bit-identical to conv + pool
@@ -1044,6 +1052,30 @@ int adaf_resnet50_finalize(adaf_resnet50* net, void* stream) {
         *p = it->second.first;
         return ADAF_OK;
     };
+    // the depth: the highest "layerS.B." block index registered per stage
+    int found[4] = {0, 0, 0, 0};
+    for (const auto& kv : net->params) {
+        int s = 0, b = 0, len = 0;
+        if (sscanf(kv.first.c_str(), "layer%d.%d.%n", &s, &b, &len) == 2 && len > 0 && s >= 1 && s <= 4 && b >= 0 && b + 1 > found[s - 1])
+            found[s - 1] = b + 1;
+    }
+    int depth = -1;
+    for (int d = 0; d < 3; ++d)
+        if (!memcmp(found, kDepths[d], sizeof(found))) depth = d;
+    if (depth < 0)
+        return fail(h, ADAF_E_BADARG, "resnet50: parameters name {%d, %d, %d, %d} Bottlenecks per stage; the trunk runs {3, 4, 6, 3} (ResNet-50), "
+                    "{3, 4, 23, 3} (ResNet-101) or {3, 8, 36, 3} (ResNet-152)", found[0], found[1], found[2], found[3]);
+    if (memcmp(found, net->blocks, sizeof(found))) {   // another depth than the plan holds: drop its packed filters, rebuild the plan
+        for (auto& L : net->convs) {
+            if (L.w) (void)hipFree(L.w);
+            if (L.wsp) (void)hipFree(L.wsp);
+            if (L.w16) (void)hipFree(L.w16);
+            if (L.scale) (void)hipFree(L.scale);
+            if (L.bias) (void)hipFree(L.bias);
+        }
+        memcpy(net->blocks, found, sizeof(found));
+        build_layers(net);
+    }
     for (auto& L : net->convs) {
         const float *w, *g, *b, *m, *v;
         int rc;
@@ -1144,7 +1176,7 @@ int adaf_resnet50_forward_map(adaf_resnet50* net, const float* patches_nhwc4, in
                      featmap_nhwc);
 }
 
-int adaf_resnet50_launch_count(const adaf_resnet50* net) { return net ? (int)net->convs.size() + 2 + (net->tsm_block ? 16 : 0) : 0; }
+int adaf_resnet50_launch_count(const adaf_resnet50* net) { return net ? (int)net->convs.size() + 2 + (net->tsm_block ? total_blocks(net) : 0) : 0; }
 
 int adaf_resnet50_forward_profiled(adaf_resnet50* net, const float* patches_nhwc4, int n, int patch, int tsm_segments,
                                    int tsm_div, float* feat, int ldfeat, void* ws, size_t ws_bytes, void* stream,

@@ -1,12 +1,12 @@
-"""Local CNN: ResNet-50 with the reference's parameter names, executed by the HIP trunk.
+"""Local CNN: a Bottleneck ResNet (50, 101 or 152 layers) with the reference's parameter names, executed by the HIP trunk.
 
-Mirrors the surface of ACT/models/resnet.py that the hot path uses -- ``resnet50()``,
+Mirrors the surface of ACT/models/resnet.py that the hot path uses -- ``resnet50()``, ``resnet101()``, ``resnet152()`` (:280-315),
 ``ResNet.get_featmap(x, pooled)`` (:211-225), ``get_featvec`` (:227-239), ``forward`` (:196-209),
 ``feature_dim`` (:241-243) and the torchvision state-dict keys -- while the nn.Conv2d / BatchNorm2d
 children only hold parameters: their ``forward`` is never called.  All arithmetic runs in
 ``adaf_resnet50_forward`` (implicit-GEMM MFMA convs with the BN affine, residual add and ReLU in
-the epilogue).  Only ResNet-50 is built: the other depths are never instantiated by the reference
-drivers.
+the epilogue).  The Bottleneck depths are built (the reference's Something-Something TSN takes any torchvision
+``resnet*`` by name, STH/models/tsn.py:109-145); the BasicBlock ResNet-18 / -34 are not (TSN.feature_dim is 2048).
 """
 import torch
 from torch import nn
@@ -14,20 +14,22 @@ from torch import nn
 from . import hip_ops
 from .utils import nchw_to_nhwc4
 
-__all__ = ["ResNet", "resnet50", "Bottleneck"]
+__all__ = ["ResNet", "resnet50", "resnet101", "resnet152", "Bottleneck", "DEPTHS"]
 
-_STAGES = ((64, 3, 1), (128, 4, 2), (256, 6, 2), (512, 3, 2))
+DEPTHS = {"resnet50": (3, 4, 6, 3), "resnet101": (3, 4, 23, 3), "resnet152": (3, 8, 36, 3)}   # Bottlenecks per stage
+_PLANES = ((64, 1), (128, 2), (256, 2), (512, 2))          # (planes, stride of the stage's first block)
 DEFAULT_MATH = "f32"      # arithmetic of newly built trunks ("f32" | "split_bf16" | "f16"); ResNet.set_math overrides per model
 MATH_MODES = ("f32", "split_bf16", "f16")
 
 
 def check_local_math(mode, local_arch="resnet50"):
-    """Validates the build-specific ``args.local_math`` of the GFV models: the ResNet-50 local CNN's arithmetic ("f32" default,
-    "split_bf16", "f16").  An EfficientNet local CNN keeps its own ``local_dtype``: any value but "f32" is refused there."""
+    """Validates the build-specific ``args.local_math`` of the GFV models: the ResNet local CNN's arithmetic ("f32" default,
+    "split_bf16", "f16"), at every depth of DEPTHS.  An EfficientNet local CNN keeps its own ``local_dtype``: any value but "f32" is
+    refused there."""
     if mode not in MATH_MODES:
         raise ValueError("local_math must be one of %s, got %r" % (", ".join(MATH_MODES), mode))
-    if local_arch != "resnet50" and mode != "f32":
-        raise ValueError("local_math=%r applies to the ResNet-50 local CNN only (local_arch=%r: use local_dtype)" % (mode, local_arch))
+    if local_arch not in DEPTHS and mode != "f32":
+        raise ValueError("local_math=%r applies to the ResNet local CNN only (local_arch=%r: use local_dtype)" % (mode, local_arch))
     return mode
 
 
@@ -54,12 +56,16 @@ class Bottleneck(nn.Module):
 
 
 class ResNet(nn.Module):
-    def __init__(self, num_classes=1000):
+    def __init__(self, num_classes=1000, layers=DEPTHS["resnet50"]):
         super().__init__()
+        if tuple(layers) not in DEPTHS.values():
+            raise NotImplementedError("adafocus_amd.ResNet: Bottleneck layers %s; the trunk runs %s" % (
+                list(layers), ", ".join("%s %s" % (k, list(v)) for k, v in DEPTHS.items())))
+        self.layers = tuple(int(b) for b in layers)
         self.conv1 = nn.Conv2d(3, 64, 7, 2, 3, bias=False)
         self.bn1 = nn.BatchNorm2d(64)
         inplanes = 64
-        for i, (planes, blocks, stride) in enumerate(_STAGES, start=1):
+        for i, ((planes, stride), blocks) in enumerate(zip(_PLANES, self.layers), start=1):
             seq = [Bottleneck(inplanes, planes, stride, True)]
             inplanes = planes * 4
             seq += [Bottleneck(inplanes, planes, 1, False) for _ in range(blocks - 1)]
@@ -68,11 +74,21 @@ class ResNet(nn.Module):
         for m in self.modules():  # same initialisation family as the reference (resnet.py:152-157)
             if isinstance(m, nn.Conv2d):
                 nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
-        self.tsm_segments = 0     # > 0: temporal shift before every Bottleneck conv1 (TSM, STH)
+        self.tsm_segments = 0     # > 0: temporal shift before the Bottleneck conv1s (TSM, STH; which ones: shifted_blocks)
         self.tsm_div = 8
-        self.tsm_place = "blockres"   # 'blockres': shift inside every Bottleneck conv1; 'block': in front of the whole Bottleneck
+        self.tsm_place = "blockres"   # 'blockres': shift inside the Bottleneck conv1s; 'block': in front of every whole Bottleneck
         self._trunk = None
         self._sig = None
+
+    @property
+    def n_round(self):
+        """make_temporal_shift's stride over the blocks of a stage under 'blockres' (STH/ops/temporal_shift.py:123-127): 2 when layer3
+        has 23 or more blocks (ResNet-101 / -152), else 1."""
+        return 2 if self.layers[2] >= 23 else 1
+
+    def shifted_blocks(self, stage):
+        """Indices of the blocks of layer<stage> whose conv1 the 'blockres' shift wraps (the library derives the same set itself)."""
+        return [i for i in range(self.layers[stage - 1]) if i % self.n_round == 0]
 
     # ---- weight hand-off to the library -------------------------------------------------
     def _trunk_params(self):
@@ -162,4 +178,14 @@ class ResNet(nn.Module):
 def resnet50(pretrained=False, progress=True, **kwargs):
     """ACT/models/resnet.py:280.  There is no network here: `pretrained` weights must be supplied
     through load_state_dict (the reference's checkpoints load unchanged)."""
-    return ResNet(**kwargs)
+    return ResNet(layers=DEPTHS["resnet50"], **kwargs)
+
+
+def resnet101(pretrained=False, progress=True, **kwargs):
+    """ACT/models/resnet.py:292 (Bottleneck, [3, 4, 23, 3]); weights through load_state_dict, as resnet50."""
+    return ResNet(layers=DEPTHS["resnet101"], **kwargs)
+
+
+def resnet152(pretrained=False, progress=True, **kwargs):
+    """ACT/models/resnet.py:304 (Bottleneck, [3, 8, 36, 3]); weights through load_state_dict, as resnet50."""
+    return ResNet(layers=DEPTHS["resnet152"], **kwargs)

@@ -35,15 +35,18 @@ class TemporalShift(nn.Module):
 
 
 def make_temporal_shift(net, n_segment, n_div=8, place="blockres", temporal_pool=False):
-    """temporal_shift.py:99-142 for ResNet-50 without temporal pooling.  place='blockres' (every shipped configuration,
-    :123-140): every Bottleneck conv1 sees the shifted block input -- fused into that conv's operand load.  place='block'
-    (:104-121): TemporalShift wraps the whole Bottleneck, so conv1, the downsample conv and the identity all see it -- the shifted
-    map is materialised once per block (adaf_resnet50_set_shift_place)."""
+    """temporal_shift.py:99-142 for a Bottleneck ResNet without temporal pooling.  place='blockres' (every shipped configuration,
+    :123-140): n_round = 2 if layer3 has 23 or more blocks (ResNet-101 / -152), else 1, and block i of every stage has its conv1 see
+    the shifted block input iff i % n_round == 0 -- fused into that conv's operand load (the library applies the same rule from the
+    depth).  place='block' (:104-121): TemporalShift wraps every whole Bottleneck, so conv1, the downsample conv and the identity all see
+    it -- the shifted map is materialised once per block (adaf_resnet50_set_shift_place)."""
     if temporal_pool:
         raise NotImplementedError("temporal_pool is unused by the reference drivers")
     if place == "block":
         net.tsm_place = "block"
     elif "blockres" in place:
+        n_round = 2 if len(list(net.layer3.children())) >= 23 else 1
+        assert n_round == net.n_round, (n_round, net.n_round)
         net.tsm_place = "blockres"
     else:
         # (the reference silently inserts NO shift for any other string -- its `else: raise` belongs to the isinstance test,

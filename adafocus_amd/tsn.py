@@ -1,10 +1,10 @@
-"""TSN wrapper of the local CNN -- host mirror of STH/models/tsn.py for the one configuration the
-Something-Something drivers use (ResNet-50, RGB, TSM 'blockres', no temporal pooling).
+"""TSN wrapper of the local CNN -- host mirror of STH/models/tsn.py for the configurations the
+Something-Something drivers use (base_model resnet50 / resnet101 / resnet152, RGB, TSM, no temporal pooling).
 
-``forward(input, no_reshape=True)`` (tsn.py:215-241) = TSM-ResNet-50 trunk -> (N, 2048), executed by
+``forward(input, no_reshape=True)`` (tsn.py:215-241) = TSM-ResNet trunk -> (N, 2048), executed by
 ``adaf_resnet50_forward`` with the shift fused into conv1.  State-dict compatibility: the reference
-wraps every Bottleneck conv1 in ``TemporalShift`` (key ``...conv1.net.weight``; with shift_place='block' the
-whole Bottleneck: ``layer1.0.net.conv1.weight``) and
+wraps the shifted Bottleneck conv1s in ``TemporalShift`` (key ``...conv1.net.weight``; an unshifted block of a ResNet-101 / -152,
+n_round = 2, keeps ``...conv1.weight``; with shift_place='block' every whole Bottleneck: ``layer1.0.net.conv1.weight``) and
 STH/evaluate.py:83 re-wraps the children in a Sequential to drop fc (keys ``base_model.4.0.conv1.net.
 weight``); both spellings load and save here.
 """
@@ -13,7 +13,7 @@ import re
 import torch
 from torch import nn
 
-from .resnet import ResNet
+from .resnet import DEPTHS, ResNet
 from .temporal_shift import make_temporal_shift
 
 __all__ = ["TSN"]
@@ -27,14 +27,16 @@ class TSN(nn.Module):
                  partial_bn=True, print_spec=False, pretrain="imagenet", is_shift=False, shift_div=8,
                  shift_place="blockres", fc_lr5=False, temporal_pool=False, non_local=False):
         super().__init__()
-        if modality != "RGB" or "resnet50" not in base_model or non_local or temporal_pool:
-            raise NotImplementedError("adafocus_amd.TSN: RGB ResNet-50 without non-local / temporal pooling only")
+        if base_model not in DEPTHS:
+            raise NotImplementedError("adafocus_amd.TSN: base_model %r is not supported; supported: %s" % (base_model, ", ".join(DEPTHS)))
+        if modality != "RGB" or non_local or temporal_pool:
+            raise NotImplementedError("adafocus_amd.TSN: RGB without non-local / temporal pooling only")
         self.modality, self.num_segments, self.reshape = modality, num_segments, False
         self.is_shift, self.shift_div, self.shift_place = is_shift, shift_div, shift_place
         self.new_length = 1
         self._stripped = False
         object.__setattr__(self, "_in_init", True)
-        self.base_model = ResNet(num_classes=1000)
+        self.base_model = ResNet(num_classes=1000, layers=DEPTHS[base_model])
         object.__setattr__(self, "_in_init", False)
         if is_shift:
             make_temporal_shift(self.base_model, num_segments, n_div=shift_div, place=shift_place)
@@ -72,12 +74,14 @@ class TSN(nn.Module):
 
     def _reference_keys(self, module, state_dict, prefix, local_metadata):
         p = prefix + "base_model."
+        shifted = {s: set(self.base_model.shifted_blocks(s)) for s in range(1, 5)}
         for k in [k for k in state_dict if k.startswith(p)]:
             rest = k[len(p):]
             if self.is_shift and self.shift_place == "block":
                 rest = re.sub(r"^(layer\d\.\d+)\.", r"\1.net.", rest)
-            elif self.is_shift:
-                rest = re.sub(r"^(layer\d\.\d+\.conv1)\.", r"\1.net.", rest)
+            elif self.is_shift:       # only the blocks make_temporal_shift wrapped (n_round)
+                rest = re.sub(r"^layer(\d)\.(\d+)\.conv1\.", lambda m: m.group(0) + "net." if int(m.group(2)) in shifted[int(m.group(1))]
+                              else m.group(0), rest)
             if self._stripped:
                 head, _, tail = rest.partition(".")
                 if head == "fc":

@@ -233,18 +233,24 @@ int adaf_global_avgpool_f32(adaf_handle* h, const float* x, int n, int hw, int c
 int adaf_temporal_shift_f32(adaf_handle* h, const float* x, int nt, int c, int hw, int n_segment, int fold_div,
                             int layout, float* out, void* stream);
 
-/* ---- a4/a5: ResNet-50 trunk as one object ----------------------------------------------
+/* ---- a4/a5: ResNet-50 / -101 / -152 trunk as one object ---------------------------------
  * Replaces ResNet.get_featmap(x, pooled=True) -- ACT/models/resnet.py:211-225 -- and
- * TSN.forward(input, no_reshape=True) -- STH/models/tsn.py:215-241 (TSM on every Bottleneck
- * conv1, STH/ops/temporal_shift.py:123-140).  Parameter names are torchvision's
+ * TSN.forward(input, no_reshape=True) -- STH/models/tsn.py:215-241 (TSM on the Bottleneck
+ * conv1s, STH/ops/temporal_shift.py:123-140).  Parameter names are torchvision's
  * ("conv1.weight", "bn1.running_var", "layer3.4.conv2.weight", "layer2.0.downsample.1.bias").
+ * The adaf_resnet50_* object runs the three Bottleneck depths of torchvision (resnet50 [3, 4, 6, 3],
+ * resnet101 [3, 4, 23, 3], resnet152 [3, 8, 36, 3]); every depth ends in the same 2048-wide
+ * features and the same largest map, so the workspace, ldfeat and forward_map do not depend on it.
  */
 int adaf_resnet50_create(adaf_handle* h, adaf_resnet50** out);
 int adaf_resnet50_destroy(adaf_resnet50* net);
 /* Registers a device pointer to a parameter / buffer in PyTorch layout; the data is read by
  * adaf_resnet50_finalize() and not needed afterwards. */
 int adaf_resnet50_set_param(adaf_resnet50* net, const char* name, const float* dev_ptr, size_t numel);
-/* Packs weights (OIHW -> OHWI, stem cin 3 -> 4), folds BN, on `stream`; synchronises that stream. */
+/* Packs weights (OIHW -> OHWI, stem cin 3 -> 4), folds BN, on `stream`; synchronises that stream.  The depth is read from the
+ * registered names: the highest "layerS.B." block index per stage.  {3,4,6,3}, {3,4,23,3} and {3,8,36,3} are accepted, anything else
+ * is ADAF_E_BADARG (the message names the counts found).  A new depth rebuilds the launch plan: adaf_resnet50_launch_count and the
+ * adaf_resnet50_set_tiles table follow it, and tile overrides reset to 0. */
 int adaf_resnet50_finalize(adaf_resnet50* net, void* stream);
 size_t adaf_resnet50_workspace_bytes(const adaf_resnet50* net, int n, int patch);
 /* patches_nhwc4 [n, patch, patch, 4] (adaf_crop_gather_f32 with ADAF_LAYOUT_NHWC4);
@@ -300,10 +306,13 @@ int adaf_resnet50_set_fusion(adaf_resnet50* net, int on);
  * published latency is a CPU bs = 1 figure). */
 int adaf_resnet50_set_latency_rows(adaf_resnet50* net, int rows);
 /* Where the temporal shift sits (make_temporal_shift(net, n_segment, n_div, place), STH/ops/temporal_shift.py:99-142):
- *   ADAF_SHIFT_BLOCKRES (default; every shipped configuration, the STH/conf yaml files: `shift_place: blockres`): TemporalShift wraps the
- *                       conv1 of every Bottleneck (:123-140) -- fused into that conv's operand load, no shifted tensor exists;
+ *   ADAF_SHIFT_BLOCKRES (default; every shipped configuration, the STH/conf yaml files: `shift_place: blockres`): TemporalShift wraps
+ *                       Bottleneck conv1s (:123-140) -- fused into that conv's operand load, no shifted tensor exists.  Which ones is
+ *                       the reference's n_round rule: n_round = 2 if layer3 has 23 or more blocks (ResNet-101 / -152), else 1, and
+ *                       block i of EVERY stage has its conv1 shifted iff i % n_round == 0 (ResNet-50: all of them; ResNet-101 / -152:
+ *                       blocks 0, 2, 4, ...).  The fused stage-1 tail and the lean conv1 form follow the flag per block;
  *   ADAF_SHIFT_BLOCK    TemporalShift wraps the WHOLE Bottleneck (:104-121): conv1, the downsample conv and the identity all see
- *                       the shifted block input.  The shifted map is materialised once per block (adaf_temporal_shift_f32's
+ *                       the shifted block input, for EVERY block at every depth (no n_round).  The shifted map is materialised once per block (adaf_temporal_shift_f32's
  *                       kernel) in a sixth workspace slab -- adaf_resnet50_workspace_bytes(net, ...) grows accordingly, so set
  *                       the placement before sizing the workspace.
  * Only read when a forward is called with tsm_segments > 0. */
@@ -333,8 +342,8 @@ int adaf_resnet50_set_shift_place(adaf_resnet50* net, int place);
  *                              order and divided by the pixel count -- fp32 features feat[i * ldfeat + c]; the pooled conv3 epilogue and
  *                              the separate pool launch give the same bits (a patch's features do not depend on its batch);
  *                            - temporal shift: a move of fp16 values with zeros at clip ends (exact).  'blockres' needs
- *                              fold = cin / tsm_div to be a multiple of 8 (ADAF_E_LAYOUT otherwise; every ResNet conv1 with tsm_div 8 or 4
- *                              qualifies); 'block' materialises the shifted fp16 map in the sixth slab as the fp32 plan does;
+ *                              fold = cin / tsm_div to be a multiple of 8 at every SHIFTED conv1 (n_round rule above; ADAF_E_LAYOUT
+ *                              otherwise; every ResNet conv1 with tsm_div 8 or 4 qualifies); 'block' materialises the shifted fp16 map in the sixth slab as the fp32 plan does;
  *                            - adaf_resnet50_forward_map writes the exact fp32 widening of the fp16 final map.
  *                            Everything outside the trunk (GRU / FC, fc_meanpool, glancer, policy) stays fp32.  The fp16 filter planes
  *                            are packed at finalize, or by set_math(ADAF_MATH_F16) after finalize.  adaf_resnet50_set_tiles accepts 0 and
