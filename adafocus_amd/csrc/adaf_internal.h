@@ -24,6 +24,7 @@ struct adaf_handle {
     int scan_next = 0;
     int scan_resident = 0;   // scan blocks the device can hold at once (occupancy query)
     int scan_slots = 1;      // min(4, scan_resident / blocks per scan)
+    int bptt_resident = 0;   // blocks of the persistent GRU backward scan (gru_bptt.hip) the device can hold at once
     std::string err;
 };
 
@@ -248,6 +249,20 @@ AdafGruScanPlan adaf_gru_scan_plan(int batch, int steps, size_t bar_words, int r
 hipError_t adaf_launch_gru_scan_persistent(const float* gi, const float* whh, const float* bhh, const float* h0, float* hs,
                                            unsigned* bar, const AdafGruScanPlan& plan, int batch, int steps, const float* fcw, const float* fcb,
                                            float* logits, float* last, int classes, bool cooperative, unsigned* timeouts, hipStream_t s);
+
+// gru_bptt.hip (stage-3 backward of the GRU classifier)
+int adaf_gru_bptt_blocks_per_cu();
+bool adaf_gru_bptt_persistent_ok(int batch, int hidden, int resident_blocks);
+hipError_t adaf_launch_gru_bptt(const float* dy, const float* gi, const float* gh, const float* bhh, const float* hs, const float* whh,
+                                float* dgi, float* dgh, float* carry, unsigned* bar, unsigned* timeouts, int batch, int steps, int hidden,
+                                bool persistent, bool cooperative, hipStream_t s);
+// C[m, n] = sum_k A[m * a_m + k * a_k] B[k * b_k + n * b_n] (* mul[m * ldm + n] when mul != nullptr); deterministic (no atomics)
+void adaf_launch_gemm_strided(const float* A, long long a_m, long long a_k, const float* B, long long b_k, long long b_n, float* C, int ldc,
+                              const float* mul, int ldm, int M, int N, int K, hipStream_t s);
+size_t adaf_colsum_partial_floats(int cols);
+void adaf_launch_colsum(const float* x, int rows, int cols, int ld, float* part, float* out, hipStream_t s);
+// out = x * mask (mask == nullptr: a copy), or with shift: out[b, t] = x[b, t - 1], out[b, 0] = 0 (rows = B * steps of `width` floats)
+void adaf_launch_rows_scale(const float* x, const float* mask, float* out, int rows, int width, int steps, bool shift, hipStream_t s);
 
 // conv_gemm.hip
 int adaf_launch_conv_gemm(const ConvArgs& a, int tile, int cus, hipStream_t s);  // returns chosen tile (>0) or <0

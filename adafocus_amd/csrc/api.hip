@@ -121,6 +121,8 @@ int adaf_create(int device, adaf_handle** out) {
         h->scan_resident = (per_cu > 1 ? per_cu - 1 : per_cu) * h->cus;
         const int slots = h->scan_resident / 128;
         h->scan_slots = slots < 1 ? 1 : (slots > 4 ? 4 : slots);
+        const int bptt_per_cu = adaf_gru_bptt_blocks_per_cu();
+        h->bptt_resident = (bptt_per_cu > 1 ? bptt_per_cu - 1 : bptt_per_cu) * h->cus;
     }
     (void)hipSetDevice(cur);
     if (e != hipSuccess) { delete h; return ADAF_E_NOMEM; }
@@ -1376,6 +1378,110 @@ int adaf_gru_cls_forward_f32(adaf_handle* h, const float* x, int ldx, int batch,
     if (rc) return rc;
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? ADAF_OK : hip_fail(h, e, "gru_cls forward");
+}
+
+// ---- stage-3 training of the GRU classifier (gru_bptt.hip) -------------------------------------------------------------------------
+size_t adaf_gru_cls_train_workspace_bytes(int batch, int steps, int hidden) {
+    if (batch <= 0 || steps <= 0 || hidden <= 0) return 0;
+    // gh [B, 3H] (the forward scan's per-step product / barrier words) + the dropped-out states [B*T, H]
+    return ((size_t)batch * 3 * hidden + (size_t)batch * steps * hidden) * sizeof(float);
+}
+
+int adaf_gru_cls_train_forward_f32(adaf_handle* h, const float* x, int ldx, int batch, int steps, int feat, int hidden, int classes,
+                                   const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, const float* fc_w,
+                                   const float* fc_b, const float* mask, float* gi_out, float* hs_out, float* logits_all, float* last,
+                                   void* ws, size_t ws_bytes, void* stream) {
+    if (!h) return ADAF_E_BADARG;
+    if (batch == 0) return ADAF_OK;
+    if (!x || !w_ih || !w_hh || !b_ih || !b_hh || !fc_w || !fc_b || !gi_out || !hs_out || !logits_all || !ws)
+        return fail(h, ADAF_E_BADARG, "gru_cls_train: null pointer");
+    if (batch < 0 || steps <= 0 || feat <= 0 || hidden <= 0 || classes <= 0) return fail(h, ADAF_E_BADARG, "gru_cls_train: non-positive extent");
+    if (ldx == 0) ldx = feat;
+    if (feat % 4 || hidden % 16 || ldx % 4) return fail(h, ADAF_E_LAYOUT, "gru_cls_train: feat %% 4, hidden %% 16, ldx %% 4 must be 0");
+    if (ws_bytes < adaf_gru_cls_train_workspace_bytes(batch, steps, hidden)) return fail(h, ADAF_E_NOMEM, "gru_cls_train: workspace too small");
+    hipStream_t st = (hipStream_t)stream;
+    float* gh = static_cast<float*>(ws);
+    float* hd = gh + (size_t)batch * 3 * hidden;
+    const int rows = batch * steps;
+    int rc = gru_scan(h, x, ldx, batch, steps, feat, hidden, w_ih, w_hh, b_ih, b_hh, nullptr, gi_out, gh, hs_out, nullptr, nullptr, 0, nullptr,
+                      nullptr, st);
+    if (rc) return rc;
+    const float* fc_in = hs_out;
+    if (mask) {
+        adaf_launch_rows_scale(hs_out, mask, hd, rows, hidden, steps, false, st);
+        fc_in = hd;
+    }
+    if ((rc = linear_launch(h, fc_in, rows, hidden, hidden, classes, fc_w, fc_b, logits_all, 0, st))) return rc;
+    if (last) adaf_launch_copy2d(logits_all + (size_t)(steps - 1) * classes, steps * classes, last, classes, batch, classes, st);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? ADAF_OK : hip_fail(h, e, "gru_cls_train forward");
+}
+
+size_t adaf_gru_cls_backward_workspace_bytes(int batch, int steps, int hidden, int classes) {
+    if (batch <= 0 || steps <= 0 || hidden <= 0 || classes <= 0) return 0;
+    const size_t bt = (size_t)batch * steps, h3 = 3 * (size_t)hidden;
+    const size_t cols = h3 > (size_t)classes ? h3 : (size_t)classes;
+    // dropped-out / shifted states + dY [B*T, H] each, gh + dgi + dgh [B*T, 3H] each, carry [B, H], column-sum partials, barrier words
+    const size_t floats = 2 * bt * hidden + 3 * bt * h3 + (size_t)batch * hidden + adaf_colsum_partial_floats((int)cols);
+    return (floats + ((size_t)steps + 64) / 64 * 64) * sizeof(float);
+}
+
+int adaf_gru_cls_backward_f32(adaf_handle* h, const float* x, int ldx, int batch, int steps, int feat, int hidden, int classes,
+                              const float* w_ih, const float* w_hh, const float* b_hh, const float* fc_w, const float* gi,
+                              const float* hs, const float* mask, const float* dlogits, float* dx, float* dw_ih, float* dw_hh,
+                              float* db_ih, float* db_hh, float* dw_fc, float* db_fc, void* ws, size_t ws_bytes, void* stream) {
+    if (!h) return ADAF_E_BADARG;
+    if (!x || !w_ih || !w_hh || !b_hh || !fc_w || !gi || !hs || !dlogits || !dw_ih || !dw_hh || !db_ih || !db_hh || !dw_fc || !db_fc || !ws)
+        return fail(h, ADAF_E_BADARG, "gru_cls_backward: null pointer");
+    if (batch <= 0 || steps <= 0 || feat <= 0 || hidden <= 0 || classes <= 0) return fail(h, ADAF_E_BADARG, "gru_cls_backward: non-positive extent");
+    if (ldx == 0) ldx = feat;
+    if (feat % 4 || hidden % 16 || ldx % 4 || ldx < feat) return fail(h, ADAF_E_LAYOUT, "gru_cls_backward: feat %% 4, hidden %% 16, ldx %% 4 must be 0");
+    if (ws_bytes < adaf_gru_cls_backward_workspace_bytes(batch, steps, hidden, classes)) return fail(h, ADAF_E_NOMEM, "gru_cls_backward: workspace too small");
+    hipStream_t st = (hipStream_t)stream;
+    const int rows = batch * steps, h3 = 3 * hidden;
+    float* hd = static_cast<float*>(ws);
+    float* dy = hd + (size_t)rows * hidden;
+    float* gh = dy + (size_t)rows * hidden;
+    float* dgi = gh + (size_t)rows * h3;
+    float* dgh = dgi + (size_t)rows * h3;
+    float* carry = dgh + (size_t)rows * h3;
+    float* part = carry + (size_t)batch * hidden;
+    unsigned* bar = reinterpret_cast<unsigned*>(part + adaf_colsum_partial_floats(h3 > classes ? h3 : classes));
+    // FC + dropout: dW_fc = dlogits^T (hs * mask), db_fc = column sums, dY = (dlogits W_fc) * mask
+    adaf_launch_rows_scale(hs, mask, hd, rows, hidden, steps, false, st);
+    adaf_launch_gemm_strided(dlogits, 1, classes, hd, hidden, 1, dw_fc, hidden, nullptr, 0, classes, hidden, rows, st);
+    adaf_launch_colsum(dlogits, rows, classes, classes, part, db_fc, st);
+    adaf_launch_gemm_strided(dlogits, classes, 1, fc_w, hidden, 1, dy, hidden, mask, hidden, rows, hidden, classes, st);
+    // gh = W_hh h_t + b_hh of every step in one engine GEMM (row (b, t) is step t+1's hidden projection)
+    int rc = linear_launch(h, hs, rows, hidden, hidden, h3, w_hh, b_hh, gh, 0, st);
+    if (rc) return rc;
+    // the T-sequential part: persistent under the forward scan's rules (not under capture unless "gru_graph_persistent"), and it takes
+    // EVERY scan slot -- its 104 KB of LDS leave room for one block per CU, so no forward scan of this handle may run beside it
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    (void)hipStreamIsCapturing(st, &cap);
+    const bool capturing = cap != hipStreamCaptureStatusNone;
+    const bool persistent = h->gru_persistent && (!capturing || adaf_options().gru_graph_persistent) &&
+                            adaf_gru_bptt_persistent_ok(batch, hidden, h->bptt_resident);
+    if (persistent && !capturing)
+        for (int i = 0; i < h->scan_slots; ++i)
+            if (h->scan_used[i]) (void)hipStreamWaitEvent(st, h->scan_done[i], 0);
+    hipError_t e = adaf_launch_gru_bptt(dy, gi, gh, b_hh, hs, w_hh, dgi, dgh, carry, bar, h->scan_timeouts, batch, steps, hidden, persistent,
+                                        h->gru_persistent == 2, st);
+    if (e != hipSuccess) return hip_fail(h, e, "gru bptt launch");
+    if (persistent && !capturing)
+        for (int i = 0; i < h->scan_slots; ++i) {
+            (void)hipEventRecord(h->scan_done[i], st);
+            h->scan_used[i] = true;
+        }
+    // weight gradients: dW_ih = dgi^T x, dW_hh = dgh^T h_{t-1} (h_{-1} = 0), bias gradients, dx = dgi W_ih
+    adaf_launch_rows_scale(hs, nullptr, hd, rows, hidden, steps, true, st);
+    adaf_launch_gemm_strided(dgi, 1, h3, x, ldx, 1, dw_ih, feat, nullptr, 0, h3, feat, rows, st);
+    adaf_launch_gemm_strided(dgh, 1, h3, hd, hidden, 1, dw_hh, hidden, nullptr, 0, h3, hidden, rows, st);
+    adaf_launch_colsum(dgi, rows, h3, h3, part, db_ih, st);
+    adaf_launch_colsum(dgh, rows, h3, h3, part, db_hh, st);
+    if (dx) adaf_launch_gemm_strided(dgi, h3, 1, w_ih, feat, 1, dx, feat, nullptr, 0, rows, feat, h3, st);
+    e = hipGetLastError();
+    return e == hipSuccess ? ADAF_OK : hip_fail(h, e, "gru_cls backward");
 }
 
 int adaf_fc_meanpool_forward_f32(adaf_handle* h, const float* feat, int batch, int steps, int feat_dim, int classes,

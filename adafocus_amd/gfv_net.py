@@ -14,8 +14,9 @@ execution plan of ``GFV.forward(one_step=True)`` (gfv_net.py:95-133):
              ONE batched HIP gather of B*T patches (NHWC4) -> ONE ResNet-50 trunk pass over B*T
              patches whose avgpool writes straight into the GRU input matrix -> HIP GRU + FC
 
-which reproduces the reference logits.  Training branches (stage 0-2 forward
-modes, PPO update) are out of scope and raise.  ``GFV.one_step_act(training=False)`` -- the body of the
+which reproduces the reference logits.  Stage-3 training (``train_mode`` with
+train_stage 3: only ``classifier.*`` learns) runs the frozen part on the same HIP path and the classifier with a HIP backward
+(csrc/gru_bptt.hip); the other training branches (stage 0-2 forward modes, PPO update) are out of scope and raise.  ``GFV.one_step_act(training=False)`` -- the body of the
 stage-2 VALIDATION loop (ACT/main_dist.py:346-362), reward baseline included -- keeps the reference's
 per-step structure on the same HIP ops (round 6, pinned by G15).
 """
@@ -95,6 +96,8 @@ class GFV(nn.Module):
         if kwargs.get("training"):
             raise NotImplementedError("only training=False (offline inference / validation) is implemented")
         if not kwargs.get("one_step"):
+            if self.training:
+                raise NotImplementedError("the stage-1 form in train mode is stage-1 training: out of scope (stage 3 is one_step=True)")
             # the stage-1 form (gfv_net.py:135-150) in eval mode, as validate() runs it at train_stage 1 (ACT/main_dist.py:334-340): glancer and
             # focuser over all B*T frames at once -- random crops when the model was built with random_patch (the stage-1 configuration),
             # else ONE policy step over the B*T frames as a batch, exactly as the reference's call does -- then the classifier
@@ -108,12 +111,24 @@ class GFV(nn.Module):
                 return self.classifier(feature.view(b, t, -1))
         if self.focuser.random:
             return None          # (gfv_net.py:108: the one_step form only has a body for a policy-driven focuser)
+        if self.training:
+            # stage 3 (train_mode(train_stage=3), gfv_net.py:95-133): the frozen glancer / policy / local CNN under no_grad on the HIP path up to
+            # the (B, T, F) feature matrix, then the classifier ONCE with grad (dropout + GRU + FC with a HIP backward)
+            with torch.no_grad():
+                frames, fvec, actions, _, b, t = self._frozen_inputs(kwargs["input"], kwargs["scan"])
+                feature = self.hot_path_features(frames, fvec, actions, b, t)
+            return self.classifier(feature)
         return self.offline_forward(kwargs["input"], kwargs["scan"])[:2]
 
     @torch.no_grad()
     def offline_forward(self, images, scan, forced_action_idx=None):
         """images, scan: (B, T*3, H, W) fp32 on the GPU.  Returns (logits (B*T,C), last (B,C),
         feature matrix (B,T,F), action indices (B,T))."""
+        frames, fvec, actions, idx, b, t = self._frozen_inputs(images, scan, forced_action_idx)
+        return self.hot_path(frames, fvec, actions, b, t) + (idx,)
+
+    def _frozen_inputs(self, images, scan, forced_action_idx=None):
+        """The hot path's inputs: frames (B*T,3,H,W), glancer vectors (B,T,1280) or None, actions (B*T,2), action indices, B, T."""
         b, tc, hh, ww = images.shape
         t = tc // 3
         # glancer (adaf_mobilenetv2) -> pixel-major map + 1280-d vectors; policy over all T steps at once
@@ -123,8 +138,7 @@ class GFV(nn.Module):
         if forced_action_idx is not None:
             idx = forced_action_idx.to(idx.device)
             actions = table[idx.reshape(-1)]
-        return self.hot_path(images.view(b * t, 3, hh, ww), fvec.view(b, t, -1) if self.with_glancer else None, actions,
-                             b, t) + (idx,)
+        return images.view(b * t, 3, hh, ww), fvec.view(b, t, -1) if self.with_glancer else None, actions, idx, b, t
 
     def glancer_input(self, images):
         """`input_prime = F.interpolate(images, (glance_size, glance_size))` of the reference's drivers (nearest mode,
@@ -211,6 +225,12 @@ class GFV(nn.Module):
         """Batched crop -> local CNN -> concat -> classifier: the benchmarked slice.
         frames (B*T,3,H,W) [reference layout] or (B*T,H,W,4) [pixel-major], global_feat (B,T,1280) or
         None, actions (B*T,2)."""
+        feature = self.hot_path_features(frames, global_feat, actions, b, t)
+        logits, last = self.classifier(feature)
+        return logits, last, feature
+
+    def hot_path_features(self, frames, global_feat, actions, b, t):
+        """hot_path up to the classifier: the (B,T,F) feature matrix [glancer vector | local feature]."""
         gdim = global_feat.shape[2] if global_feat is not None else 0
         feature = torch.empty((b, t, gdim + self.focuser.feature_dim), device=frames.device, dtype=torch.float32)
         flat = feature.view(b * t, -1)
@@ -226,8 +246,7 @@ class GFV(nn.Module):
             net.features_nhwc4(patches, out=flat[:, gdim:])
         if gdim:
             hip_ops.copy2d(global_feat.reshape(b * t, gdim), flat[:, :gdim])
-        logits, last = self.classifier(feature)
-        return logits, last, feature
+        return feature
 
     def capture_hot_path(self, b, t, frame_shape=None, exclusive=False, check_every=16):
         """Latency mode for small batches (BASELINE config 1 is B = 2; the reference's published CPU figure is a bs = 1
@@ -280,7 +299,17 @@ class GFV(nn.Module):
         return logits, last_out, patch_size_list, action_list, baseline_logits
 
     def train_mode(self, args):
-        raise NotImplementedError("training modes are out of scope; use .eval()")
+        """gfv_net.py:62-81 for train_stage == 3 (call after model.train(), as ACT/main_dist.py does): the glancer, the focuser and
+        both policies go to eval mode; only the classifier trains (dropout on, HIP backward).  Stages 0-2 (the backbones' and the
+        policy's training) are out of scope and raise."""
+        if args.train_stage != 3:
+            raise NotImplementedError("train_mode: train_stage %r is out of scope (only stage 3, classifier training, is implemented)"
+                                      % (args.train_stage,))
+        self.train()
+        self.glancer.eval()
+        self.focuser.eval()
+        self.focuser.policy.policy.eval()
+        self.focuser.policy.policy_old.eval()
 
     @property
     def scale_size(self):
@@ -507,10 +536,23 @@ class RecurrentClassifier(nn.Module):
         self.fc = nn.Linear(hidden_dim, num_classes)
         self.dropout = nn.Dropout(dropout)
 
-    def forward(self, feature):
-        if self.training:
-            raise RuntimeError("RecurrentClassifier: eval mode only (dropout must be the identity)")
+    def forward(self, feature, mask=None):
+        """(logits (B*T,C), last_out (B,C)).  Train mode (stage 3): dropout on the GRU outputs (gfv_net.py:432) and a HIP backward for
+        x and every parameter (hip_ops.GruClassifierFn).  The dropout multipliers (0 or 1/(1-p), shape (B,T,H)) are drawn from torch's
+        device generator unless `mask` gives them."""
         g = self.gru
+        if self.training:
+            b, t, _ = feature.shape
+            p = self.dropout.p
+            if mask is None and p > 0:
+                keep = 1.0 - p
+                mask = torch.empty((b, t, self.hidden_dim), device=feature.device, dtype=torch.float32).bernoulli_(keep)
+                mask = mask.mul_(1.0 / keep) if keep > 0 else mask
+            logits = hip_ops.GruClassifierFn.apply(feature, g.weight_ih_l0, g.weight_hh_l0, g.bias_ih_l0, g.bias_hh_l0, self.fc.weight,
+                                                   self.fc.bias, mask)
+            return logits, logits.view(b, t, -1)[:, -1, :].reshape(b, -1)
+        if mask is not None:
+            raise ValueError("RecurrentClassifier: a dropout mask in eval mode")
         return hip_ops.gru_cls_forward(feature, g.weight_ih_l0.detach(), g.weight_hh_l0.detach(), g.bias_ih_l0.detach(),
                                        g.bias_hh_l0.detach(), self.fc.weight.detach(), self.fc.bias.detach())
 

@@ -157,6 +157,84 @@ def gru_cls_forward(x, w_ih, w_hh, b_ih, b_hh, fc_w, fc_b):
     return logits, last
 
 
+def gru_cls_train_forward(x, w_ih, w_hh, b_ih, b_hh, fc_w, fc_b, mask=None):
+    """Stage-3 training forward of RecurrentClassifier (adaf_gru_cls_train_forward_f32): x (B,T,F), mask (B,T,H) dropout multipliers
+    (0 or 1/(1-p)) or None -> (logits (B*T,C), gi (B*T,3H), hs (B,T,H)); gi and hs are what gru_cls_backward needs."""
+    L.need_gpu_f32(x, w_ih, w_hh, b_ih, b_hh, fc_w, fc_b, mask)
+    b, t, f = x.shape
+    if x.stride(2) != 1 or x.stride(0) != t * x.stride(1):
+        x = x.contiguous()
+    hid, ncls = w_hh.shape[1], fc_w.shape[0]
+    if mask is not None:
+        mask = mask.contiguous()
+    lib = L.load_library()
+    ws_bytes = lib.adaf_gru_cls_train_workspace_bytes(b, t, hid)
+    ws = torch.empty(max(ws_bytes // 4, 1), device=x.device, dtype=torch.float32)
+    gi = torch.empty((b * t, 3 * hid), device=x.device, dtype=torch.float32)
+    hs = torch.empty((b, t, hid), device=x.device, dtype=torch.float32)
+    logits = torch.empty((b * t, ncls), device=x.device, dtype=torch.float32)
+    h = _h(x)
+    L.check(lib.adaf_gru_cls_train_forward_f32(h, L.ptr(x), x.stride(1), b, t, f, hid, ncls, L.ptr(w_ih.contiguous()),
+                                               L.ptr(w_hh.contiguous()), L.ptr(b_ih.contiguous()), L.ptr(b_hh.contiguous()),
+                                               L.ptr(fc_w.contiguous()), L.ptr(fc_b.contiguous()), L.ptr(mask), L.ptr(gi), L.ptr(hs),
+                                               L.ptr(logits), None, L.ptr(ws), ws_bytes, L.stream_ptr()), h)
+    return logits, gi, hs
+
+
+def gru_cls_backward(x, w_ih, w_hh, b_hh, fc_w, gi, hs, mask, dlogits, want_dx=True):
+    """adaf_gru_cls_backward_f32: gradients of the GRU classifier from dlogits (B*T,C) and the activations of gru_cls_train_forward (same
+    mask).  Returns (dx (B,T,F) or None, dW_ih, dW_hh, db_ih, db_hh, dW_fc, db_fc); deterministic (same inputs, same bits)."""
+    L.need_gpu_f32(x, w_ih, w_hh, b_hh, fc_w, gi, hs, mask, dlogits)
+    b, t, f = x.shape
+    if x.stride(2) != 1 or x.stride(0) != t * x.stride(1):
+        x = x.contiguous()
+    hid, ncls = w_hh.shape[1], fc_w.shape[0]
+    dlogits = dlogits.contiguous()
+    if mask is not None:
+        mask = mask.contiguous()
+    lib = L.load_library()
+    ws_bytes = lib.adaf_gru_cls_backward_workspace_bytes(b, t, hid, ncls)
+    ws = torch.empty(max(ws_bytes // 4, 1), device=x.device, dtype=torch.float32)
+    dev, fp = x.device, torch.float32
+    dx = torch.empty((b, t, f), device=dev, dtype=fp) if want_dx else None
+    dw_ih = torch.empty((3 * hid, f), device=dev, dtype=fp)
+    dw_hh = torch.empty((3 * hid, hid), device=dev, dtype=fp)
+    db_ih = torch.empty((3 * hid,), device=dev, dtype=fp)
+    db_hh = torch.empty((3 * hid,), device=dev, dtype=fp)
+    dw_fc = torch.empty((ncls, hid), device=dev, dtype=fp)
+    db_fc = torch.empty((ncls,), device=dev, dtype=fp)
+    h = _h(x)
+    L.check(lib.adaf_gru_cls_backward_f32(h, L.ptr(x), x.stride(1), b, t, f, hid, ncls, L.ptr(w_ih.contiguous()), L.ptr(w_hh.contiguous()),
+                                          L.ptr(b_hh.contiguous()), L.ptr(fc_w.contiguous()), L.ptr(gi), L.ptr(hs), L.ptr(mask),
+                                          L.ptr(dlogits), L.ptr(dx), L.ptr(dw_ih), L.ptr(dw_hh), L.ptr(db_ih), L.ptr(db_hh), L.ptr(dw_fc),
+                                          L.ptr(db_fc), L.ptr(ws), ws_bytes, L.stream_ptr()), h)
+    return dx, dw_ih, dw_hh, db_ih, db_hh, dw_fc, db_fc
+
+
+class GruClassifierFn(torch.autograd.Function):
+    """logits (B*T,C) of GRU -> dropout(mask) -> Linear with a HIP backward (stage 3 of ACT/main_dist.py trains classifier.* only).
+    apply(x, w_ih, w_hh, b_ih, b_hh, fc_w, fc_b, mask): grads for x (when it requires grad) and the six parameters, so they land in
+    the .grad of nn.GRU / nn.Linear.  Runs in fp32 under autocast (inputs are cast; the logits stay fp32).  Nothing is cached across
+    calls: every forward reads the parameters as they are, so the step after optimizer.step() sees the new weights."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, x, w_ih, w_hh, b_ih, b_hh, fc_w, fc_b, mask):
+        w_ih, w_hh, b_ih, b_hh, fc_w, fc_b = (p.detach() for p in (w_ih, w_hh, b_ih, b_hh, fc_w, fc_b))
+        x = x.detach()
+        logits, gi, hs = gru_cls_train_forward(x, w_ih, w_hh, b_ih, b_hh, fc_w, fc_b, mask)
+        ctx.save_for_backward(x, w_ih, w_hh, b_hh, fc_w, gi, hs, mask)
+        return logits
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, g):
+        x, w_ih, w_hh, b_hh, fc_w, gi, hs, mask = ctx.saved_tensors
+        dx, dw_ih, dw_hh, db_ih, db_hh, dw_fc, db_fc = gru_cls_backward(x, w_ih, w_hh, b_hh, fc_w, gi, hs, mask, g.float(),
+                                                                        want_dx=ctx.needs_input_grad[0])
+        return dx, dw_ih, dw_hh, db_ih, db_hh, dw_fc, db_fc, None
+
+
 def fc_meanpool_forward(feat, batch, fc_w, fc_b, global_logit=None):
     """mean_t FC(f_t) (+ mean_t glancer logits) -- STH/models/gfv_net.py:164-174.
     feat (B*T,F); global_logit (B,Tg,C) or None -> (B,C)."""

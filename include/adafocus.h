@@ -495,6 +495,38 @@ int adaf_gru_cls_forward_f32(adaf_handle* h, const float* x, int ldx, int batch,
                              const float* b_hh, const float* fc_w, const float* fc_b, float* logits_all,
                              float* last, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- a7 training (stage 3): GRU classifier forward that keeps its activations, and its backward ------------------------------
+ * Stage 3 of ACT/main_dist.py trains classifier.* only (GRU(F -> H) + dropout + Linear(H -> C), ACT/models/gfv_net.py:427-435).
+ *
+ * adaf_gru_cls_train_forward_f32: as adaf_gru_cls_forward_f32 with the dropout of gfv_net.py:432 and the activations the backward needs.
+ *   mask [B, T, H] multipliers of the GRU outputs (0 or 1 / (1 - p), drawn by the caller) or NULL (= identity);
+ *   gi_out [B*T, 3H] = W_ih x + b_ih, hs_out [B, T, H] the hidden states (both caller buffers: the backward reads them);
+ *   logits_all [B*T, C] = (hs * mask) W_fc^T + b_fc; last [B, C] (the rows of step T-1) or NULL.
+ *   The recurrence is the forward scan of adaf_gru_seq_forward_f32 (same kernels, same bits of hs).
+ *   Workspace: adaf_gru_cls_train_workspace_bytes(batch, steps, hidden) bytes.
+ *
+ * adaf_gru_cls_backward_f32: every parameter gradient (and optionally dx) from dlogits [B*T, C], fp32 throughout.
+ *   Inputs: x/ldx, the weights, gi/hs of the training forward and the SAME mask (or NULL).  Outputs (overwritten, not accumulated):
+ *   dw_ih [3H, F], dw_hh [3H, H], db_ih [3H], db_hh [3H], dw_fc [C, H], db_fc [C]; dx [B, T, F] (row stride F) or NULL = not wanted.
+ *   Plan: dW_fc / db_fc and dY = (dlogits W_fc) * mask on a strided fp32 MFMA GEMM; gh = W_hh h_t + b_hh for every step in ONE engine
+ *   GEMM (no per-step gate storage in the forward); the T-sequential part as ONE persistent kernel with a grid barrier per step when
+ *   hidden == 1024 and batch <= 256 (same scan-slot throttle, co-residency check, bounded spin and time-out counter as the forward scan,
+ *   adaf_gru_scan_timeouts; a block that times out NaN-poisons the gradients), else -- and under stream capture -- one launch per step
+ *   with the SAME arithmetic (bit-identical; adaf_set_gru_persistent(0) selects it); then dW_ih = dgi^T x, dW_hh = dgh^T h_{t-1},
+ *   dx = dgi W_ih on the same GEMM and the bias gradients as two-pass column sums.  No atomics: identical inputs give identical bits.
+ *   hidden % 16 == 0, feat % 4 == 0, ldx % 4 == 0.  Workspace: adaf_gru_cls_backward_workspace_bytes(batch, steps, hidden, classes).
+ * Both workspace queries are plain arithmetic (no device needed); both return 0 for a non-positive extent. */
+size_t adaf_gru_cls_train_workspace_bytes(int batch, int steps, int hidden);
+int adaf_gru_cls_train_forward_f32(adaf_handle* h, const float* x, int ldx, int batch, int steps, int feat, int hidden, int classes,
+                                   const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, const float* fc_w,
+                                   const float* fc_b, const float* mask, float* gi_out, float* hs_out, float* logits_all, float* last,
+                                   void* ws, size_t ws_bytes, void* stream);
+size_t adaf_gru_cls_backward_workspace_bytes(int batch, int steps, int hidden, int classes);
+int adaf_gru_cls_backward_f32(adaf_handle* h, const float* x, int ldx, int batch, int steps, int feat, int hidden, int classes,
+                              const float* w_ih, const float* w_hh, const float* b_hh, const float* fc_w, const float* gi,
+                              const float* hs, const float* mask, const float* dlogits, float* dx, float* dw_ih, float* dw_hh,
+                              float* db_ih, float* db_hh, float* dw_fc, float* db_fc, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- a8: linear classifier + temporal mean ---------------------------------------------
  * nn.Linear + ConsensusModule('avg') (+ glancer mean logits) -- STH/models/gfv_net.py:164-174,
  * STH/ops/basic_ops.py:17-26.  feat [B*T, F]; global_logit [B, Tg, C] or NULL; out [B, C];
