@@ -95,7 +95,7 @@ struct AdafOptions {
     unsigned effnet_fused_blocks = 0xffffffffu;   // "effnet_fused_blocks": MBConv blocks (bit = block index) the fused expand + depthwise launch may take
     int effnet_chunk = 1024;      // "effnet_chunk": frames per chunk of the EfficientNet forward
     int stem_rows = 1;            // "stem_rows": stem + max-pool over whole-width strips walked down the image (stem.hip, round 5); 0 = the tile form, 2 = also below one image per CU (tests)
-    int split_stage1_f32 = 1;     // "split_stage1_f32": the split-bf16 trunk takes the fp32 pipe's fused stage-1 launches (api.hip run_trunk)
+    int split_stage1_f32 = 1;     // "split_stage1_f32": the split-bf16 trunk takes the fp32 pipe's fused stage-1 launches (resnet_trunk.hip run_trunk)
     int split_lean = 1;           // "split_lean": the split tiles' K loop with scalar-base DMA (conv_gemm.hip launch_glds; 0 = the pointer-per-lane form, A/B)
     int tsm_lean = 1;             // "tsm_lean": a conv1 with the fused temporal shift on the lean K loop (range-checked buffer DMA; conv_gemm.hip launch_glds; 0 = the per-lane select form, A/B)
     int gru_graph_persistent = 0; // "gru_graph_persistent": 1 = a stream capture keeps the persistent GRU scan (the caller guarantees exclusive use of the device
@@ -149,6 +149,15 @@ struct ConvArgs {
     int pool_hw, pool_rows, pool_ld;
     float* pool_out;
 };
+
+// api.hip: helpers of the C-ABI layer's host code (api.hip, resnet_trunk.hip)
+int adaf_fail(adaf_handle* h, int code, const char* fmt, ...);       // stores the formatted message in the handle, returns `code`
+int adaf_hip_fail(adaf_handle* h, hipError_t e, const char* what);   // ADAF_E_LAUNCH with the runtime's error string
+bool adaf_aligned16(const void* p);
+int adaf_conv_out(int in, int k, int stride, int pad);
+// Validates a conv description and flattens it; returns ADAF_OK or an error code.
+int adaf_make_conv_args(adaf_handle* h, const adaf_conv_params* p, const float* x, const float* w, const float* scale,
+                        const float* bias, const float* res, float* out, ConvArgs* a);
 
 // mbconv.hip: fused expand 1x1 -> depthwise 3x3 of an inverted-residual block
 struct MbFuseArgs {
