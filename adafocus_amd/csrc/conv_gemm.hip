@@ -1605,7 +1605,8 @@ __global__ __launch_bounds__(256, N1 == 128 ? 2 : 3) void conv_fused_tail_kernel
                     for (int i = 0; i < TM; ++i) {
                         const int arow = wm * 64 + i * 32 + (lane & 31);
                         const int t = (m0 + arow) % fa.tsm_T1;
-                        const bool ok = tsm_dr > 0 ? t < fa.tsm_T1 - 1 : t > 0;
+                        // (idle rows of a group of fewer than 128 images are not-ok: their frame index would send row 127 to row 128, past the image)
+                        const bool ok = arow < fa.pm_gstride && (tsm_dr > 0 ? t < fa.tsm_T1 - 1 : t > 0);
                         const int nrow = ok ? arow + tsm_dr : arow;
                         const int swn = (nrow >> 1) & 7;
                         const f32x4 v = *reinterpret_cast<const f32x4*>(A2 + nrow * 32 + (((2 * kk + (lane >> 5)) ^ swn) << 2));

@@ -291,7 +291,10 @@ int adaf_mobilenetv2_forward(adaf_mobilenetv2* net, const float* frames_nhwc4, i
                 // the expand -> depthwise strip kernel, whose lanes load whole 4-channel groups of one shift kind (fold % 4 == 0: the 64- / 96-channel blocks):
                 // the shift rides in their pixel loads (MbFuseArgs::tsm_T), nothing is materialised and the identity rows are the input itself
                 // (the whole-block strip kernel of the 32-channel blocks has no register left for the frame offset: 252 of 256; its input stays materialised)
-                const bool strip_shift = tsm && strip_xd && (b.inp / tsm_div) % 4 == 0;
+                // (the kernel gives a frame offset to the first CIN / 4 channels of a pixel only, mbstrip.hip dsh[]: both shifted folds must lie inside them
+                //  -- shift_div >= 8; a wider fold falls through to the materialised copy the whole-block strips read)
+                const int fold = tsm_div > 0 ? b.inp / tsm_div : 0;
+                const bool strip_shift = tsm && strip_xd && fold % 4 == 0 && 2 * fold <= b.inp / 4;
                 if (strip_shift) strip_T = tsm_segments;
                 else if (tsm) {
                     if (!fused && (b.inp / tsm_div) % 4 == 0) fused_T = tsm_segments;   // shift fused into the operand load

@@ -701,9 +701,10 @@ def pack_conv_weight_f16(w_oihw, cin_pad=None):
 
 
 def conv2d_bn_act_f16(x, w_ohwi, scale=None, bias=None, residual=None, stride=1, pad=0, act=ACT_NONE, out_dtype=torch.float16,
-                      tile=0):
+                      tile=0, tsm_segments=0, tsm_div=8):
     """adaf_conv2d_bn_act_f16: x (N,H,W,Cin) fp16 with fp16 weights (or fp32 x / w with an fp16 store), fp32 accumulate and
-    epilogue, `out_dtype` store."""
+    epilogue, `out_dtype` store.  `tsm_segments` > 0: the temporal shift fused into a 1x1 conv's operand load, as conv2d_bn_act
+    (fp16 operands move whole 16-byte chunks: cin / tsm_div a multiple of 8)."""
     _need_gpu(x, w_ohwi, scale, bias, residual)
     x = x.contiguous()
     w_ohwi = w_ohwi.contiguous()
@@ -720,8 +721,8 @@ def conv2d_bn_act_f16(x, w_ohwi, scale=None, bias=None, residual=None, stride=1,
         if residual.dtype != torch.float16:
             raise ValueError("conv2d_bn_act_f16: the residual is fp16")
         residual = residual.contiguous()
-    p = L.ConvParams(n=n, h=hh, w=ww, cin=cin, cout=cout, kh=kh, kw=kw, stride=stride, pad=pad, act=act, tsm_segments=0,
-                     tsm_div=8, ldx=0, ldo=0, ldr=0, tile=tile)
+    p = L.ConvParams(n=n, h=hh, w=ww, cin=cin, cout=cout, kh=kh, kw=kw, stride=stride, pad=pad, act=act, tsm_segments=int(tsm_segments),
+                     tsm_div=int(tsm_div), ldx=0, ldo=0, ldr=0, tile=tile)
     h = _h(x)
     L.check(L.load_library().adaf_conv2d_bn_act_f16(h, C.byref(p), L.ptr(x), DTYPE_F16 if x.dtype == torch.float16 else DTYPE_F32,
                                                     L.ptr(w_ohwi), L.ptr(scale), L.ptr(bias), L.ptr(residual), L.ptr(out),
