@@ -37,6 +37,8 @@ SYMBOLS = (
     "adaf_effnet_create", "adaf_effnet_destroy", "adaf_effnet_feature_dim", "adaf_effnet_block_count", "adaf_effnet_block_info",
     "adaf_effnet_set_dtype", "adaf_effnet_set_fusion", "adaf_effnet_whole_blocks", "adaf_effnet_fused_expand_blocks", "adaf_effnet_set_param", "adaf_effnet_finalize", "adaf_effnet_workspace_bytes", "adaf_effnet_forward",
     "adaf_gru_cls_train_workspace_bytes", "adaf_gru_cls_train_forward_f32", "adaf_gru_cls_backward_workspace_bytes", "adaf_gru_cls_backward_f32",
+    "adaf_ppo_sample_f32", "adaf_ppo_returns_f32", "adaf_ppo_head_workspace_bytes", "adaf_ppo_head_f32", "adaf_ppo_rows_transpose_f32",
+    "adaf_ppo_wenc_grad_workspace_bytes", "adaf_ppo_wenc_grad_f32", "adaf_ppo_encoder_backward_workspace_bytes", "adaf_ppo_encoder_backward_f32",
 )
 
 
@@ -122,6 +124,18 @@ def load_library():
     lib.adaf_gru_cls_backward_workspace_bytes.restype = C.c_size_t
     lib.adaf_gru_cls_backward_workspace_bytes.argtypes = [ip, ip, ip, ip]
     lib.adaf_gru_cls_backward_f32.argtypes = [vp, vp, ip, ip, ip, ip, ip, ip] + [vp] * 16 + [C.c_size_t, vp]
+    lib.adaf_ppo_sample_f32.argtypes = [vp, vp, ip, ip, ip, vp, vp, vp, vp, vp]
+    lib.adaf_ppo_returns_f32.argtypes = [vp, vp, ip, ip, fp, vp, vp]
+    lib.adaf_ppo_head_workspace_bytes.restype = C.c_size_t
+    lib.adaf_ppo_head_workspace_bytes.argtypes = [ip, ip]
+    lib.adaf_ppo_head_f32.argtypes = [vp, vp, ip, ip, ip, ip, vp, vp, vp, fp] + [vp] * 9 + [C.c_size_t, vp]
+    lib.adaf_ppo_rows_transpose_f32.argtypes = [vp, vp, ip, ip, ip, vp, vp]
+    lib.adaf_ppo_wenc_grad_workspace_bytes.restype = C.c_size_t
+    lib.adaf_ppo_wenc_grad_workspace_bytes.argtypes = [ip, ip, ip]
+    lib.adaf_ppo_wenc_grad_f32.argtypes = [vp, vp, vp, vp, ip, ip, ip, ip, vp, vp, C.c_size_t, vp]
+    lib.adaf_ppo_encoder_backward_workspace_bytes.restype = C.c_size_t
+    lib.adaf_ppo_encoder_backward_workspace_bytes.argtypes = [ip, ip, ip, ip, ip, ip]
+    lib.adaf_ppo_encoder_backward_f32.argtypes = [vp, vp, vp, vp, vp, ip, ip, ip, ip, ip, ip, vp, vp, vp, vp, vp, C.c_size_t, vp]
     lib.adaf_crop_gather_nhwc4_f32.argtypes = [vp, vp, ip, ip, ip, vp, ip, ip, ip, vp, vp, vp]
     lib.adaf_ingest_u8_f32.argtypes = [vp, vp, ip, ip, ip, ip, C.POINTER(C.c_float), C.POINTER(C.c_float), vp, vp]
     lib.adaf_crop_resize_f32.argtypes = [vp, vp, ip, ip, ip, ip, ip, vp, ip, ip, vp, ip, ip, vp, ip, vp, vp]

@@ -1,0 +1,487 @@
+// Stage-2 training (ACT/models/ppo.py:84-92,98-122,147-178): what PPO needs around the GRU + Linear forward / backward of gru_bptt.hip.
+//
+//   ppo_sample_kernel        Categorical(softmax(logits)).sample() from caller-drawn uniforms, its log-probability, the probabilities
+//   ppo_returns_kernel       R_t = r_t + gamma R_{t+1}, then (R - mean) / (std + 1e-5) over all T*B entries (unbiased std), one block
+//   ppo_head_kernel          per row of the stacked head output [actor logits | critic value]: log-softmax, log-probability of the stored
+//                            action, entropy, value, the clipped-surrogate loss terms AND d loss.mean() / d head in the same pass
+//   ppo_loss_sum_kernel      the scalar loss from the per-row terms, summed in a fixed order
+//   ppo_wenc_splitk_kernel   dW_enc [32, C] = (relu-masked dE1)^T S over all T*B*h*w pixels: the state tensor S (257 MB at B = 64, T = 16) is
+//                            read ONCE with 16-byte loads; a block owns a pixel slice and a 128- or 256-channel chunk and keeps its 32 x chunk
+//                            partial in MFMA accumulators; ppo_wenc_reduce_kernel adds the slices in slice order
+//   small layout kernels     (T, B) <-> (B, T) row permutation (with the ReLU mask), the Linear gradient's pixel-major -> nn.Linear permutation
+//
+// fp32 throughout, no atomics: the same inputs give the same bits.  Every kernel compiles to zero scratch.
+#include "adaf_internal.h"
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+namespace {
+
+// ---- sampling ---------------------------------------------------------------------------------------------------------------------------
+// One thread per row (rows = clips of one roll-out step, A <= a few dozen): max, sum of exponentials and the running sum all in index order.
+// The sampled index is the first a whose running sum exceeds u * total; the last index if rounding leaves none.
+__global__ void ppo_sample_kernel(const float* logits, int ld, int rows, int A, const float* u, long long* action, float* logprob,
+                                  float* probs) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= rows) return;
+    const float* l = logits + (size_t)r * ld;
+    float mx = l[0];
+    for (int a = 1; a < A; ++a) mx = fmaxf(mx, l[a]);
+    float total = 0.f;
+    for (int a = 0; a < A; ++a) total += expf(l[a] - mx);
+    const float thr = u[r] * total;
+    float run = 0.f;
+    int pick = A - 1;
+    for (int a = 0; a < A; ++a) {
+        const float e = expf(l[a] - mx);
+        run += e;
+        if (probs) probs[(size_t)r * A + a] = e / total;
+        if (run > thr && pick == A - 1) pick = a;
+    }
+    action[r] = pick;
+    logprob[r] = (l[pick] - mx) - logf(total);
+}
+
+// ---- returns ----------------------------------------------------------------------------------------------------------------------------
+// sum of v over the block's 256 threads in a fixed order (a binary tree over thread indices); every thread gets the result
+__device__ __forceinline__ float block_sum_256(float v, float* red) {
+    const int tid = threadIdx.x;
+    red[tid] = v;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s) red[tid] = red[tid] + red[tid + s];
+        __syncthreads();
+    }
+    const float out = red[0];
+    __syncthreads();
+    return out;
+}
+
+__global__ __launch_bounds__(256) void ppo_returns_kernel(const float* rewards, int T, int B, float gamma, float* out) {
+    __shared__ float red[256];
+    const int tid = threadIdx.x, n = T * B;
+    for (int b = tid; b < B; b += 256) {
+        float R = 0.f;
+        for (int t = T - 1; t >= 0; --t) {
+            R = rewards[(size_t)t * B + b] + gamma * R;
+            out[(size_t)t * B + b] = R;
+        }
+    }
+    __syncthreads();
+    float s = 0.f;
+    for (int i = tid; i < n; i += 256) s += out[i];
+    const float mean = block_sum_256(s, red) / (float)n;
+    float q = 0.f;
+    for (int i = tid; i < n; i += 256) {
+        const float d = out[i] - mean;
+        q += d * d;
+    }
+    const float sd = sqrtf(block_sum_256(q, red) / (float)(n - 1));
+    const float inv = 1.f / (sd + 1e-5f);
+    for (int i = tid; i < n; i += 256) out[i] = (out[i] - mean) * inv;
+}
+
+// ---- PPO head ---------------------------------------------------------------------------------------------------------------------------
+struct HeadArgs {
+    const float* head;        // [T*B, A + 1]: row b * T + t when head_bt, else row t * B + b
+    const long long* action;  // [T, B]
+    const float* old_logprob; // [T, B] (loss mode)
+    const float* returns;     // [T, B] (loss mode)
+    const float* g_logprob;   // [T, B] upstream gradients (plain backward mode; any may be null = 0)
+    const float* g_value;
+    const float* g_entropy;
+    float* logprob;           // [T, B] outputs (may be null)
+    float* value;
+    float* entropy;
+    float* terms;             // [2, T*B]: -min(surr1, surr2) - 0.01 entropy, (value - return)^2   (loss mode)
+    float* dhead;             // [T*B, A + 1] in the head's row order (may be null)
+    int T, B, A, head_bt, mode;   // mode 0: statistics only, 1: PPO loss + its gradient, 2: gradient from g_*
+    float eps_clip;
+};
+
+__global__ void ppo_head_kernel(const HeadArgs h) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x, n = h.T * h.B;
+    if (i >= n) return;
+    const int t = i / h.B, b = i - t * h.B, A = h.A;
+    const size_t hrow = (size_t)(h.head_bt ? b * h.T + t : i) * (A + 1);
+    const float* l = h.head + hrow;
+    float mx = l[0];
+    for (int a = 1; a < A; ++a) mx = fmaxf(mx, l[a]);
+    float total = 0.f;
+    for (int a = 0; a < A; ++a) total += expf(l[a] - mx);
+    const float lse = logf(total);
+    float ent = 0.f;
+    for (int a = 0; a < A; ++a) {
+        const float lp = (l[a] - mx) - lse;
+        ent -= expf(lp) * lp;
+    }
+    const int act = (int)h.action[i];
+    const float lp_act = (l[act] - mx) - lse, v = l[A];
+    if (h.logprob) h.logprob[i] = lp_act;
+    if (h.value) h.value[i] = v;
+    if (h.entropy) h.entropy[i] = ent;
+    if (h.mode == 0) return;
+    float g_lp, g_v, g_ent;
+    if (h.mode == 1) {
+        const float inv_n = 1.f / (float)n;
+        const float ratio = expf(lp_act - h.old_logprob[i]);
+        const float R = h.returns[i], adv = R - v;
+        const float lo = 1.f - h.eps_clip, hi = 1.f + h.eps_clip;
+        const float surr1 = ratio * adv, surr2 = fminf(fmaxf(ratio, lo), hi) * adv;
+        h.terms[i] = -fminf(surr1, surr2) - 0.01f * ent;
+        h.terms[n + i] = (v - R) * (v - R);
+        // autograd through torch.min / torch.clamp: an unclamped ratio carries the whole advantage (half through each equal branch); a clamped
+        // one carries it only when surr1 wins the min (half of it on an exact tie)
+        float g_ratio = adv;
+        if (ratio < lo || ratio > hi) g_ratio = surr1 < surr2 ? adv : (surr1 == surr2 ? 0.5f * adv : 0.f);
+        g_lp = -g_ratio * ratio * inv_n;
+        g_v = (v - R) * inv_n;            // 0.5 * MSE, a mean over all rows, broadcast into every row's loss
+        g_ent = -0.01f * inv_n;
+    } else {
+        g_lp = h.g_logprob ? h.g_logprob[i] : 0.f;
+        g_v = h.g_value ? h.g_value[i] : 0.f;
+        g_ent = h.g_entropy ? h.g_entropy[i] : 0.f;
+    }
+    if (!h.dhead) return;
+    float* d = h.dhead + hrow;
+    for (int a = 0; a < A; ++a) {
+        const float lp = (l[a] - mx) - lse, p = expf(lp);
+        d[a] = g_lp * ((a == act ? 1.f : 0.f) - p) - g_ent * p * (lp + ent);
+    }
+    d[A] = g_v;
+}
+
+// loss.mean() = mean(-min(surr1, surr2) - 0.01 entropy) + 0.5 * mean((value - return)^2): per-thread strided partial sums in index order,
+// then the fixed tree of block_sum_256
+__global__ __launch_bounds__(256) void ppo_loss_sum_kernel(const float* terms, int n, float* loss) {
+    __shared__ float red[256];
+    float s = 0.f, q = 0.f;
+    for (int i = threadIdx.x; i < n; i += 256) {
+        s += terms[i];
+        q += terms[n + i];
+    }
+    const float a = block_sum_256(s, red), m = block_sum_256(q, red);
+    if (threadIdx.x == 0) *loss = a / (float)n + 0.5f * (m / (float)n);
+}
+
+// ---- layout kernels ---------------------------------------------------------------------------------------------------------------------
+// out[(j * ni + i), :] = in[(i * nj + j), :] (* (gate[(i * nj + j), :] > 0) when gate != nullptr): (T, B) <-> (B, T) rows of `width` floats
+__global__ void ppo_rows_transpose_kernel(const float* in, const float* gate, float* out, int ni, int nj, int width) {
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x, n = (size_t)ni * nj * width;
+    if (idx >= n) return;
+    const size_t orow = idx / width;
+    const int c = (int)(idx - orow * width), j = (int)(orow / ni), i = (int)(orow - (size_t)j * ni);
+    const size_t src = ((size_t)i * nj + j) * width + c;
+    out[idx] = gate ? (gate[src] > 0.f ? in[src] : 0.f) : in[src];
+}
+
+// dW_lin in the nn.Linear layout (column c * hw + p) from the engine's pixel-major one (column p * cmid + c)
+__global__ void ppo_lin_grad_permute_kernel(const float* pm, float* out, int rows, int hw, int cmid) {
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x, cols = (size_t)hw * cmid;
+    if (idx >= rows * cols) return;
+    const size_t r = idx / cols;
+    const int k = (int)(idx - r * cols), c = k / hw, p = k - c * hw;
+    out[idx] = pm[r * cols + (size_t)p * cmid + c];
+}
+
+// x * (gate > 0): the masked operand of the single-chain form of the weight gradient
+__global__ void ppo_relu_mask_kernel(const float* x, const float* gate, float* out, size_t n) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = gate[i] > 0.f ? x[i] : 0.f;
+}
+
+// ---- split-K weight gradient of the 1x1 conv --------------------------------------------------------------------------------------------
+// grid (C / (128 NQ), slices), 512 threads.  A block owns pixels [slice * pps, (slice + 1) * pps) and channels [chunk * 128 NQ, ...).  Its
+// pixels go to its 8 waves in groups of 8 (group g to wave g % 8, ascending); a wave walks its groups with v_mfma_f32_32x32x2_f32 products:
+// M = the 32 conv outputs, N = 32 lanes x 4 channels of a 16-byte load (MFMA q takes component q: output column nl of accumulator 4 j + q is
+// channel 128 j + 4 nl + q of the chunk), K = 2 pixels per product (lane half = pixel parity).  The eight wave partials meet in LDS in the
+// fixed order ((w0 + w4) + (w2 + w6)) + ((w1 + w5) + (w3 + w7)) and wave 0 writes the block's partial [32, chunk] into part[slice].
+//
+// Property (2) of DESIGN 3 (a returning load is not interlocked against an MFMA that still reads or writes its landing register): a group's
+// loads are requested behind a VALU read (an add into `fence`) of the youngest MFMA result -- every product that read the landing registers
+// has retired by then --, pinned by scheduling barriers.
+constexpr int kSkThreads = 512, kSkWaves = 8, kSkU = 4;      // kSkU pixel pairs per group
+
+template <int NQ>
+struct SkStage {
+    f32x4 b[kSkU][NQ];
+    float d[kSkU], e[kSkU];
+    bool ok[kSkU];
+};
+
+template <int NQ>
+__global__ __launch_bounds__(kSkThreads) void ppo_wenc_splitk_kernel(const float* __restrict__ S, const float* __restrict__ dE1,
+                                                                      const float* __restrict__ E1, float* __restrict__ part, int npix,
+                                                                      int cin, int pps) {
+    constexpr int NA = 4 * NQ;
+    __shared__ float red[2][NA * 16 * 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, nl = lane & 31;
+    const int c0 = blockIdx.x * 128 * NQ;
+    const int p0 = blockIdx.y * pps, p1 = min(npix, p0 + pps);
+    const int ngroups = (p1 - p0 + 2 * kSkU - 1) / (2 * kSkU);
+    f32x16 acc[NA];
+#pragma unroll
+    for (int q = 0; q < NA; ++q)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[q][r] = 0.f;
+
+    // branch-free: a pixel past the slice reads the slice's last pixel (a cache hit) and takes a zero gradient
+    auto load = [&](int g, SkStage<NQ>& s) {
+#pragma unroll
+        for (int u = 0; u < kSkU; ++u) {
+            const int pix = p0 + (g * kSkU + u) * 2 + half, pc = min(pix, p1 - 1);
+            const float* sp = S + (size_t)pc * cin + c0 + 4 * nl;
+#pragma unroll
+            for (int j = 0; j < NQ; ++j) s.b[u][j] = *reinterpret_cast<const f32x4*>(sp + 128 * j);
+            s.d[u] = dE1[(size_t)pc * 32 + nl];
+            s.e[u] = E1[(size_t)pc * 32 + nl];
+            s.ok[u] = pix < p1;
+        }
+    };
+
+    auto products = [&](const SkStage<NQ>& s) {
+#pragma unroll
+        for (int u = 0; u < kSkU; ++u) {
+            const float a = s.ok[u] && s.e[u] > 0.f ? s.d[u] : 0.f;     // the ReLU mask of the conv output, applied on the way in
+#pragma unroll
+            for (int j = 0; j < NQ; ++j)
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+                    acc[4 * j + q] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, s.b[u][j][q], acc[4 * j + q], 0, 0, 0);
+        }
+    };
+    // per group: requests, products, then a VALU read (an add into `fence`) of the youngest MFMA result, pinned by scheduling barriers: the
+    // next group's loads are requested only after every product that read the landing registers has retired.  The latency of a group's
+    // loads is covered by the block's other seven waves
+    SkStage<NQ> st;
+    float fence = 0.f;
+    for (int g = wave; g < ngroups; g += kSkWaves) {
+        load(g, st);
+        __builtin_amdgcn_sched_barrier(0);
+        products(st);
+#pragma unroll
+        for (int q = 0; q < NA; ++q) fence += acc[q][15];      // (every accumulator: the compiler orders the independent chains as it likes)
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    asm volatile("" ::"v"(fence));      // (keeps the fence adds alive; no instruction, the result is untouched)
+
+    // the eight partials, pairwise through two LDS buffers
+    auto put = [&](int buf) {
+#pragma unroll
+        for (int q = 0; q < NA; ++q)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) red[buf][(q * 16 + r) * 64 + lane] = acc[q][r];
+    };
+    auto add = [&](int buf) {
+#pragma unroll
+        for (int q = 0; q < NA; ++q)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[q][r] = acc[q][r] + red[buf][(q * 16 + r) * 64 + lane];
+    };
+    // (writers, readers) per phase: w4, w5 -> w0, w1;  w6, w7 -> w2, w3;  w2, w3 -> w0, w1;  w1 -> w0
+    const int wr0[4] = {4, 6, 2, 1}, rd0[4] = {0, 2, 0, 0};
+#pragma unroll
+    for (int ph = 0; ph < 4; ++ph) {
+        const int pairs = ph == 3 ? 1 : 2;
+        if (wave >= wr0[ph] && wave < wr0[ph] + pairs) put(wave - wr0[ph]);
+        __syncthreads();
+        if (wave >= rd0[ph] && wave < rd0[ph] + pairs) add(wave - rd0[ph]);
+        __syncthreads();
+    }
+    if (wave == 0) {
+        float* o = part + (size_t)blockIdx.y * 32 * cin + c0 + 4 * nl;
+#pragma unroll
+        for (int j = 0; j < NQ; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int m = (r & 3) + 8 * (r >> 2) + 4 * half;
+                const f32x4 v = {acc[4 * j][r], acc[4 * j + 1][r], acc[4 * j + 2][r], acc[4 * j + 3][r]};
+                *reinterpret_cast<f32x4*>(o + (size_t)m * cin + 128 * j) = v;
+            }
+    }
+}
+
+// dW[i] = part[0][i] + part[1][i] + ... in slice order
+__global__ void ppo_wenc_reduce_kernel(const float* part, int slices, int n, float* out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float v = 0.f;
+    for (int s = 0; s < slices; ++s) v += part[(size_t)s * n + i];
+    out[i] = v;
+}
+
+// pixel slices of the split-K launch: about one block per CU, at least 64 pixels per slice (plain arithmetic: the workspace query uses it)
+int sk_slices(int npix, int cin, int cus) {
+    const int chunks = cin % 256 == 0 ? cin / 256 : cin / 128;
+    int s = cus / (chunks > 0 ? chunks : 1);
+    const int most = (npix + 63) / 64;
+    if (s > most) s = most;
+    return s < 1 ? 1 : s;
+}
+constexpr int kSkCus = 256;     // the workspace is sized for the MI355X's 256 CUs whatever the device reports (never fewer slices than used)
+
+int launch_wenc_grad(adaf_handle* h, const float* states, const float* de1, const float* e1, int npix, int cin, int cmid, int split_k,
+                     float* dw, float* ws, hipStream_t st) {
+    if (split_k) {
+        if (cmid != 32 || cin % 128) return adaf_fail(h, ADAF_E_LAYOUT, "ppo_wenc_grad: the split-K form needs 32 conv outputs and channels %% 128 == 0");
+        const int cus = h->cus < kSkCus ? h->cus : kSkCus;
+        const int slices = sk_slices(npix, cin, cus), pps = ((npix + slices - 1) / slices + 1) / 2 * 2;
+        const int used = (npix + pps - 1) / pps;
+        if (cin % 256 == 0)
+            hipLaunchKernelGGL(ppo_wenc_splitk_kernel<2>, dim3(cin / 256, used), dim3(kSkThreads), 0, st, states, de1, e1, ws, npix, cin, pps);
+        else
+            hipLaunchKernelGGL(ppo_wenc_splitk_kernel<1>, dim3(cin / 128, used), dim3(kSkThreads), 0, st, states, de1, e1, ws, npix, cin, pps);
+        hipLaunchKernelGGL(ppo_wenc_reduce_kernel, dim3((32 * cin + 255) / 256), dim3(256), 0, st, ws, used, 32 * cin, dw);
+    } else {
+        // the single-chain form: the masked gradient as a tensor, then dW[m, c] = sum_i masked[i, m] S[i, c] as one ascending chain per output
+        const size_t n = (size_t)npix * cmid;
+        hipLaunchKernelGGL(ppo_relu_mask_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, de1, e1, ws, n);
+        adaf_launch_gemm_strided(ws, 1, cmid, states, cin, 1, dw, cin, nullptr, 0, cmid, cin, npix, st);
+    }
+    return ADAF_OK;
+}
+
+size_t wenc_sk_floats(int npix, int cin, int cmid) {
+    return (cmid == 32 && cin % 128 == 0) ? (size_t)sk_slices(npix, cin, kSkCus) * 32 * cin : 0;
+}
+size_t wenc_ws_floats(int npix, int cin, int cmid) {      // either form of adaf_ppo_wenc_grad_f32: the partials, or the masked gradient
+    const size_t sk = wenc_sk_floats(npix, cin, cmid), chain = (size_t)npix * cmid;
+    return sk > chain ? sk : chain;
+}
+
+}  // namespace
+
+extern "C" {
+
+int adaf_ppo_sample_f32(adaf_handle* h, const float* logits, int ld, int rows, int n_actions, const float* uniforms, int64_t* action_out,
+                        float* logprob_out, float* probs_out, void* stream) {
+    if (!h) return ADAF_E_BADARG;
+    if (rows == 0) return ADAF_OK;
+    if (!logits || !uniforms || !action_out || !logprob_out) return adaf_fail(h, ADAF_E_BADARG, "ppo_sample: null pointer");
+    if (rows < 0 || n_actions <= 0) return adaf_fail(h, ADAF_E_BADARG, "ppo_sample: non-positive extent");
+    if (ld == 0) ld = n_actions;
+    if (ld < n_actions) return adaf_fail(h, ADAF_E_BADARG, "ppo_sample: ld < n_actions");
+    hipLaunchKernelGGL(ppo_sample_kernel, dim3((rows + 63) / 64), dim3(64), 0, (hipStream_t)stream, logits, ld, rows, n_actions, uniforms,
+                       reinterpret_cast<long long*>(action_out), logprob_out, probs_out);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? ADAF_OK : adaf_hip_fail(h, e, "ppo_sample launch");
+}
+
+int adaf_ppo_returns_f32(adaf_handle* h, const float* rewards, int steps, int batch, float gamma, float* returns_out, void* stream) {
+    if (!h) return ADAF_E_BADARG;
+    if (!rewards || !returns_out) return adaf_fail(h, ADAF_E_BADARG, "ppo_returns: null pointer");
+    if (steps <= 0 || batch <= 0) return adaf_fail(h, ADAF_E_BADARG, "ppo_returns: non-positive extent");
+    hipLaunchKernelGGL(ppo_returns_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, rewards, steps, batch, gamma, returns_out);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? ADAF_OK : adaf_hip_fail(h, e, "ppo_returns launch");
+}
+
+size_t adaf_ppo_head_workspace_bytes(int steps, int batch) {
+    if (steps <= 0 || batch <= 0) return 0;
+    return 2 * (size_t)steps * batch * sizeof(float);      // the two per-row loss terms
+}
+
+int adaf_ppo_head_f32(adaf_handle* h, const float* head, int head_batch_major, int steps, int batch, int n_actions, const int64_t* actions,
+                      const float* old_logprobs, const float* returns, float eps_clip, const float* g_logprob, const float* g_value,
+                      const float* g_entropy, float* logprobs_out, float* values_out, float* entropy_out, float* loss_out, float* dhead_out,
+                      void* ws, size_t ws_bytes, void* stream) {
+    if (!h) return ADAF_E_BADARG;
+    if (!head || !actions) return adaf_fail(h, ADAF_E_BADARG, "ppo_head: null pointer");
+    if (steps <= 0 || batch <= 0 || n_actions <= 0) return adaf_fail(h, ADAF_E_BADARG, "ppo_head: non-positive extent");
+    const bool loss_mode = old_logprobs || returns || loss_out;
+    const bool grad_mode = g_logprob || g_value || g_entropy;
+    if (loss_mode && (!old_logprobs || !returns || !loss_out || !ws)) return adaf_fail(h, ADAF_E_BADARG, "ppo_head: the loss needs old_logprobs, returns, loss_out and a workspace");
+    if (loss_mode && grad_mode) return adaf_fail(h, ADAF_E_BADARG, "ppo_head: either the PPO loss or upstream gradients");
+    if (grad_mode && !dhead_out) return adaf_fail(h, ADAF_E_BADARG, "ppo_head: upstream gradients without dhead_out");
+    if (loss_mode && ws_bytes < adaf_ppo_head_workspace_bytes(steps, batch)) return adaf_fail(h, ADAF_E_NOMEM, "ppo_head: workspace too small");
+    hipStream_t st = (hipStream_t)stream;
+    HeadArgs a;
+    a.head = head; a.action = reinterpret_cast<const long long*>(actions); a.old_logprob = old_logprobs; a.returns = returns;
+    a.g_logprob = g_logprob; a.g_value = g_value; a.g_entropy = g_entropy;
+    a.logprob = logprobs_out; a.value = values_out; a.entropy = entropy_out; a.terms = static_cast<float*>(ws); a.dhead = dhead_out;
+    a.T = steps; a.B = batch; a.A = n_actions; a.head_bt = head_batch_major ? 1 : 0; a.mode = loss_mode ? 1 : (grad_mode ? 2 : 0);
+    a.eps_clip = eps_clip;
+    const int n = steps * batch;
+    hipLaunchKernelGGL(ppo_head_kernel, dim3((n + 63) / 64), dim3(64), 0, st, a);
+    if (loss_mode) hipLaunchKernelGGL(ppo_loss_sum_kernel, dim3(1), dim3(256), 0, st, a.terms, n, loss_out);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? ADAF_OK : adaf_hip_fail(h, e, "ppo_head launch");
+}
+
+int adaf_ppo_rows_transpose_f32(adaf_handle* h, const float* in, int ni, int nj, int width, float* out, void* stream) {
+    if (!h) return ADAF_E_BADARG;
+    if (!in || !out) return adaf_fail(h, ADAF_E_BADARG, "ppo_rows_transpose: null pointer");
+    if (ni <= 0 || nj <= 0 || width <= 0) return adaf_fail(h, ADAF_E_BADARG, "ppo_rows_transpose: non-positive extent");
+    const size_t n = (size_t)ni * nj * width;
+    hipLaunchKernelGGL(ppo_rows_transpose_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, in, nullptr, out, ni, nj, width);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? ADAF_OK : adaf_hip_fail(h, e, "ppo_rows_transpose launch");
+}
+
+size_t adaf_ppo_wenc_grad_workspace_bytes(int pixels, int channels, int conv_out) {
+    if (pixels <= 0 || channels <= 0 || conv_out <= 0) return 0;
+    return wenc_ws_floats(pixels, channels, conv_out) * sizeof(float);
+}
+
+int adaf_ppo_wenc_grad_f32(adaf_handle* h, const float* states, const float* de1, const float* e1, int pixels, int channels, int conv_out,
+                           int split_k, float* dw_out, void* ws, size_t ws_bytes, void* stream) {
+    if (!h) return ADAF_E_BADARG;
+    if (!states || !de1 || !e1 || !dw_out || !ws) return adaf_fail(h, ADAF_E_BADARG, "ppo_wenc_grad: null pointer");
+    if (pixels <= 0 || channels <= 0 || conv_out <= 0) return adaf_fail(h, ADAF_E_BADARG, "ppo_wenc_grad: non-positive extent");
+    if (!adaf_aligned16(states) || !adaf_aligned16(ws) || !adaf_aligned16(dw_out)) return adaf_fail(h, ADAF_E_LAYOUT, "ppo_wenc_grad: 16-byte alignment");
+    if (ws_bytes < adaf_ppo_wenc_grad_workspace_bytes(pixels, channels, conv_out)) return adaf_fail(h, ADAF_E_NOMEM, "ppo_wenc_grad: workspace too small");
+    int rc = launch_wenc_grad(h, states, de1, e1, pixels, channels, conv_out, split_k, dw_out, static_cast<float*>(ws), (hipStream_t)stream);
+    if (rc) return rc;
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? ADAF_OK : adaf_hip_fail(h, e, "ppo_wenc_grad launch");
+}
+
+size_t adaf_ppo_encoder_backward_workspace_bytes(int steps, int batch, int map_pixels, int channels, int conv_out, int hidden) {
+    if (steps <= 0 || batch <= 0 || map_pixels <= 0 || channels <= 0 || conv_out <= 0 || hidden <= 0) return 0;
+    const size_t rows = (size_t)steps * batch, mid = (size_t)map_pixels * conv_out;
+    // dE [rows, hidden] + dE1 [rows, hw * cmid] + the pixel-major dW_lin [hidden, hw * cmid] + column-sum partials + the split-K slice partials
+    const size_t floats = rows * hidden + rows * mid + (size_t)hidden * mid + adaf_colsum_partial_floats(hidden) +
+                          wenc_sk_floats((int)(rows * map_pixels), channels, conv_out);
+    return floats * sizeof(float);
+}
+
+int adaf_ppo_encoder_backward_f32(adaf_handle* h, const float* states, const float* e1, const float* e_bt, const float* dx_bt, int steps,
+                                  int batch, int map_pixels, int channels, int conv_out, int hidden, const float* w_lin_pm, float* dw_enc,
+                                  float* dw_lin, float* db_lin, void* ws, size_t ws_bytes, void* stream) {
+    if (!h) return ADAF_E_BADARG;
+    if (!states || !e1 || !e_bt || !dx_bt || !w_lin_pm || !dw_enc || !dw_lin || !db_lin || !ws)
+        return adaf_fail(h, ADAF_E_BADARG, "ppo_encoder_backward: null pointer");
+    if (steps <= 0 || batch <= 0 || map_pixels <= 0 || channels <= 0 || conv_out <= 0 || hidden <= 0)
+        return adaf_fail(h, ADAF_E_BADARG, "ppo_encoder_backward: non-positive extent");
+    if (conv_out != 32 || channels % 128) return adaf_fail(h, ADAF_E_LAYOUT, "ppo_encoder_backward: 32 conv outputs and channels %% 128 == 0 expected");
+    if (!adaf_aligned16(states) || !adaf_aligned16(ws)) return adaf_fail(h, ADAF_E_LAYOUT, "ppo_encoder_backward: 16-byte alignment");
+    if (ws_bytes < adaf_ppo_encoder_backward_workspace_bytes(steps, batch, map_pixels, channels, conv_out, hidden))
+        return adaf_fail(h, ADAF_E_NOMEM, "ppo_encoder_backward: workspace too small");
+    hipStream_t st = (hipStream_t)stream;
+    const int rows = steps * batch, mid = map_pixels * conv_out;
+    float* de = static_cast<float*>(ws);
+    float* de1 = de + (size_t)rows * hidden;
+    float* dwl = de1 + (size_t)rows * mid;
+    float* part = dwl + (size_t)hidden * mid;
+    float* wws = part + adaf_colsum_partial_floats(hidden);
+    // dE[t * B + b] = dx[b * T + t] * (E[b * T + t] > 0): the GRU's (B, T) rows back to the states' (T, B) order, ReLU mask on the way
+    {
+        const size_t n = (size_t)rows * hidden;
+        hipLaunchKernelGGL(ppo_rows_transpose_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dx_bt, e_bt, de, batch, steps, hidden);
+    }
+    // Linear: dW_lin = dE^T E1 (pixel-major columns, then permuted), db_lin = column sums, dE1 = dE W_lin
+    adaf_launch_gemm_strided(de, 1, hidden, e1, mid, 1, dwl, mid, nullptr, 0, hidden, mid, rows, st);
+    {
+        const size_t n = (size_t)hidden * mid;
+        hipLaunchKernelGGL(ppo_lin_grad_permute_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dwl, dw_lin, hidden, map_pixels, conv_out);
+    }
+    adaf_launch_colsum(de, rows, hidden, hidden, part, db_lin, st);
+    adaf_launch_gemm_strided(de, hidden, 1, w_lin_pm, mid, 1, de1, mid, nullptr, 0, rows, mid, hidden, st);
+    int rc = launch_wenc_grad(h, states, de1, e1, rows * map_pixels, channels, conv_out, 1, dw_enc, wws, st);
+    if (rc) return rc;
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? ADAF_OK : adaf_hip_fail(h, e, "ppo_encoder_backward launch");
+}
+
+}  // extern "C"

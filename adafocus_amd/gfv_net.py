@@ -16,7 +16,9 @@ execution plan of ``GFV.forward(one_step=True)`` (gfv_net.py:95-133):
 
 which reproduces the reference logits.  Stage-3 training (``train_mode`` with
 train_stage 3: only ``classifier.*`` learns) runs the frozen part on the same HIP path and the classifier with a HIP backward
-(csrc/gru_bptt.hip); the other training branches (stage 0-2 forward modes, PPO update) are out of scope and raise.  ``GFV.one_step_act(training=False)`` -- the body of the
+(csrc/gru_bptt.hip).  Stage-2 training (``policy_train_mode()``: only ``focuser.policy.policy`` learns) runs the roll-out through
+``one_step_act(training=True)`` and the PPO update through ``Focuser.update()`` with a HIP backward (csrc/ppo_train.hip; the loop body is
+``adafocus_amd.train.train_stage2_batch``).  The other training branches (stages 0 and 1) are out of scope and raise.  ``GFV.one_step_act(training=False)`` -- the body of the
 stage-2 VALIDATION loop (ACT/main_dist.py:346-362), reward baseline included -- keeps the reference's
 per-step structure on the same HIP ops (round 6, pinned by G15).
 """
@@ -276,11 +278,17 @@ class GFV(nn.Module):
         the classifier's CURRENT state (`test_single_forward`, gfv_net.py:448-457) -- for reward = 'random' a random crop per clip
         (`Focuser.random_patching`; origins drawn like utils.py:31-32, from numpy's global generator), for 'padding' | 'prev' | 'conf'
         zeros in place of the local feature.  Returns (logits (B,C), last_out (B,C), None, standard action (B,2), baseline logits (B,C)).
-        training=True is the PPO roll-out of stage-2 TRAINING (memory of log-probabilities, sampled actions): out of scope."""
-        if training:
-            raise NotImplementedError("one_step_act(training=True) is the stage-2 (PPO) training loop body: out of scope")
+        training=True is the PPO roll-out step of stage-2 TRAINING (ACT/main_dist.py:507-509): the same body with an action SAMPLED from
+        policy_old (state, action and log-probability go to focuser.memory), returning the reference's four-tuple (logits, last_out, None,
+        baseline logits).  It needs `policy_train_mode()` first: on a model whose policy_old is in eval mode it raises."""
+        if training and self.focuser.policy is None:
+            raise NotImplementedError("one_step_act(training=True) is the stage-2 (PPO) roll-out: this is a random-patch model, it has no "
+                                      "policy to roll out (use training=False)")
+        if training and not self.focuser.policy.policy_old.training:
+            raise NotImplementedError("one_step_act(training=True) is the stage-2 (PPO) roll-out: call model.policy_train_mode() first "
+                                      "(focuser.policy.policy_old is in eval mode)")
         b = img.shape[0]
-        local_feat, pack = self.focuser(input=img, state=global_feat_map, restart_batch=restart_batch, training=False)
+        local_feat, pack = self.focuser(input=img, state=global_feat_map, restart_batch=restart_batch, training=bool(training))
         patch_size_list, action_list = pack if pack is not None else (None, None)
         local_feat = local_feat.view(b, -1)
         if self.rew == "random":
@@ -296,20 +304,33 @@ class GFV(nn.Module):
             feature, baseline_feature = local_feat, base_local
         baseline_logits, _ = self.classifier.test_single_forward(baseline_feature.unsqueeze(1), reset=restart_batch)
         logits, last_out = self.classifier.single_forward(feature.unsqueeze(1), reset=restart_batch)
+        if training:
+            return logits, last_out, patch_size_list, baseline_logits
         return logits, last_out, patch_size_list, action_list, baseline_logits
 
     def train_mode(self, args):
         """gfv_net.py:62-81 for train_stage == 3 (call after model.train(), as ACT/main_dist.py does): the glancer, the focuser and
-        both policies go to eval mode; only the classifier trains (dropout on, HIP backward).  Stages 0-2 (the backbones' and the
-        policy's training) are out of scope and raise."""
+        both policies go to eval mode; only the classifier trains (dropout on, HIP backward).  Stages 0 and 1 (the backbones' training) are
+        out of scope and raise; stage 2 (the policy's training) is entered through `policy_train_mode()` and raises here too."""
         if args.train_stage != 3:
-            raise NotImplementedError("train_mode: train_stage %r is out of scope (only stage 3, classifier training, is implemented)"
-                                      % (args.train_stage,))
+            raise NotImplementedError("train_mode: train_stage %r is not entered here (stage 3, classifier training, is; stage 2, policy "
+                                      "training, is entered with policy_train_mode(); stages 0 and 1 are out of scope)" % (args.train_stage,))
         self.train()
         self.glancer.eval()
         self.focuser.eval()
         self.focuser.policy.policy.eval()
         self.focuser.policy.policy_old.eval()
+
+    def policy_train_mode(self):
+        """gfv_net.py:70-75, what the reference's train_mode does for train_stage == 2: everything in eval mode, then both policies in
+        train mode.  Only focuser.policy.policy learns (Focuser.update); `one_step_act(training=True)` checks for this mode."""
+        if self.focuser.policy is None:
+            raise NotImplementedError("policy_train_mode: a random-patch model has no policy to train")
+        self.eval()
+        self.glancer.eval()
+        self.focuser.eval()
+        self.focuser.policy.policy.train()
+        self.focuser.policy.policy_old.train()
 
     @property
     def scale_size(self):
@@ -465,7 +486,9 @@ class Focuser(nn.Module):
         return self.net(input)
 
     def update(self):
-        raise NotImplementedError("policy update is training code")
+        """gfv_net.py:341-343: one PPO update from the roll-out in `memory`, then the memory is cleared."""
+        self.policy.update(self.memory)
+        self.memory.clear_memory()
 
     @property
     def feature_dim(self):

@@ -235,6 +235,129 @@ class GruClassifierFn(torch.autograd.Function):
         return dx, dw_ih, dw_hh, db_ih, db_hh, dw_fc, db_fc, None
 
 
+# ---- stage-2 training: PPO roll-out and policy update (csrc/ppo_train.hip) -------------------------------------------------------------
+def ppo_sample(logits, uniforms, want_probs=False):
+    """Categorical(softmax(logits)).sample() from caller-drawn uniforms in [0, 1): logits (rows, A), uniforms (rows,) ->
+    (action int64 (rows,), logprob (rows,)[, probs (rows, A)])."""
+    L.need_gpu_f32(logits, uniforms)
+    logits, uniforms = logits.contiguous(), uniforms.contiguous()
+    rows, a = logits.shape
+    if uniforms.numel() != rows:
+        raise ValueError("ppo_sample: one uniform per row expected")
+    action = torch.empty((rows,), device=logits.device, dtype=torch.int64)
+    logprob = torch.empty((rows,), device=logits.device, dtype=torch.float32)
+    probs = torch.empty((rows, a), device=logits.device, dtype=torch.float32) if want_probs else None
+    h = _h(logits)
+    L.check(L.load_library().adaf_ppo_sample_f32(h, L.ptr(logits), a, rows, a, L.ptr(uniforms), L.ptr(action), L.ptr(logprob), L.ptr(probs),
+                                                 L.stream_ptr()), h)
+    return (action, logprob, probs) if want_probs else (action, logprob)
+
+
+def ppo_returns(rewards, gamma):
+    """rewards (T, B) -> discounted returns, normalised over all T*B entries (ACT/models/ppo.py:148-157)."""
+    L.need_gpu_f32(rewards)
+    rewards = rewards.contiguous()
+    t, b = rewards.shape
+    out = torch.empty_like(rewards)
+    h = _h(rewards)
+    L.check(L.load_library().adaf_ppo_returns_f32(h, L.ptr(rewards), t, b, C.c_float(gamma), L.ptr(out), L.stream_ptr()), h)
+    return out
+
+
+def _ppo_head(head, actions, batch_major, old_logprobs=None, returns=None, eps_clip=0.2, grads=None, want_dhead=True):
+    L.need_gpu_f32(head, old_logprobs, returns, *(grads or ()))
+    head = head.contiguous()
+    t, b = actions.shape
+    a = head.shape[1] - 1
+    if head.shape[0] != t * b or actions.dtype != torch.int64 or not actions.is_cuda:
+        raise ValueError("ppo head: head (T*B, A+1) and int64 GPU actions (T, B) expected")
+    actions = actions.contiguous()
+    dev, fp = head.device, torch.float32
+    logprobs, values, entropy = (torch.empty((t, b), device=dev, dtype=fp) for _ in range(3))
+    loss_mode = old_logprobs is not None
+    loss = torch.empty((1,), device=dev, dtype=fp) if loss_mode else None
+    dhead = torch.empty_like(head) if (want_dhead and (loss_mode or grads is not None)) else None
+    lib = L.load_library()
+    ws_bytes = lib.adaf_ppo_head_workspace_bytes(t, b) if loss_mode else 0
+    ws = torch.empty(max(ws_bytes // 4, 1), device=dev, dtype=fp)
+    g = [None if x is None else x.contiguous() for x in (grads or (None, None, None))]
+    if loss_mode:
+        old_logprobs, returns = old_logprobs.contiguous(), returns.contiguous()
+    h = _h(head)
+    L.check(lib.adaf_ppo_head_f32(h, L.ptr(head), int(batch_major), t, b, a, L.ptr(actions), L.ptr(old_logprobs), L.ptr(returns),
+                                  C.c_float(eps_clip), L.ptr(g[0]), L.ptr(g[1]), L.ptr(g[2]), L.ptr(logprobs), L.ptr(values), L.ptr(entropy),
+                                  L.ptr(loss), L.ptr(dhead), L.ptr(ws), ws_bytes, L.stream_ptr()), h)
+    return logprobs, values, entropy, loss, dhead
+
+
+def ppo_head_stats(head, actions, batch_major=True):
+    """head (T*B, A+1) [actor logits | critic value] (rows b*T+t when batch_major) -> (logprobs, values, entropy), each (T, B)."""
+    return _ppo_head(head, actions, batch_major)[:3]
+
+
+def ppo_head_backward(head, actions, g_logprob, g_value, g_entropy, batch_major=True):
+    """Pull-back of upstream gradients of (logprobs, values, entropy) (each (T, B) or None) to the head output."""
+    if g_logprob is None and g_value is None and g_entropy is None:
+        return torch.zeros_like(head)
+    return _ppo_head(head, actions, batch_major, grads=(g_logprob, g_value, g_entropy))[4]
+
+
+def ppo_loss_head(head, actions, old_logprobs, returns, eps_clip, batch_major=True):
+    """The PPO loss head, forward and backward in one pass (ACT/models/ppo.py:114-122,166-175):
+    -> (logprobs, values, entropy (T, B), loss.mean() (1,), d loss.mean() / d head (T*B, A+1))."""
+    return _ppo_head(head, actions, batch_major, old_logprobs=old_logprobs, returns=returns, eps_clip=eps_clip)
+
+
+def rows_transpose(x, ni, nj):
+    """x (ni*nj, W) with rows i*nj+j -> rows j*ni+i."""
+    L.need_gpu_f32(x)
+    x = x.contiguous()
+    w = x.shape[-1]
+    out = torch.empty_like(x)
+    h = _h(x)
+    L.check(L.load_library().adaf_ppo_rows_transpose_f32(h, L.ptr(x), int(ni), int(nj), w, L.ptr(out), L.stream_ptr()), h)
+    return out
+
+
+def ppo_wenc_grad(states, de1, e1, split_k=True):
+    """The 1x1 conv's weight gradient: states (pixels, C), de1 / e1 (pixels, 32) -> (32, C) = (de1 where e1 > 0)^T states.
+    split_k=False: the single-chain cross-check on the strided GEMM."""
+    L.need_gpu_f32(states, de1, e1)
+    states, de1, e1 = states.contiguous(), de1.contiguous(), e1.contiguous()
+    npix, cin = states.shape
+    cmid = de1.shape[1]
+    lib = L.load_library()
+    ws_bytes = lib.adaf_ppo_wenc_grad_workspace_bytes(npix, cin, cmid)
+    ws = torch.empty(max(ws_bytes // 4, 4), device=states.device, dtype=torch.float32)
+    dw = torch.empty((cmid, cin), device=states.device, dtype=torch.float32)
+    h = _h(states)
+    L.check(lib.adaf_ppo_wenc_grad_f32(h, L.ptr(states), L.ptr(de1), L.ptr(e1), npix, cin, cmid, int(bool(split_k)), L.ptr(dw), L.ptr(ws),
+                                       ws_bytes, L.stream_ptr()), h)
+    return dw
+
+
+def ppo_encoder_backward(states, e1, e_bt, dx_bt, t, b, w_lin_pm):
+    """Backward of the policy's state encoder (1x1 conv -> ReLU -> flatten -> Linear -> ReLU): states (T*B, h, w, C) pixel-major, e1
+    (T*B, h*w*32) and e_bt (B*T, H) its stored activations, dx_bt (B, T, H) the GRU's input gradient -> (dW_enc (32, C), dW_lin (H, 32*h*w)
+    in the nn.Linear layout, db_lin (H,))."""
+    L.need_gpu_f32(states, e1, e_bt, dx_bt, w_lin_pm)
+    hw, cin = states.shape[1] * states.shape[2], states.shape[3]
+    hid = w_lin_pm.shape[0]
+    cmid = w_lin_pm.shape[1] // hw
+    lib = L.load_library()
+    ws_bytes = lib.adaf_ppo_encoder_backward_workspace_bytes(t, b, hw, cin, cmid, hid)
+    ws = torch.empty(max(ws_bytes // 4, 4), device=states.device, dtype=torch.float32)
+    dev, fp = states.device, torch.float32
+    dw_enc = torch.empty((cmid, cin), device=dev, dtype=fp)
+    dw_lin = torch.empty((hid, cmid * hw), device=dev, dtype=fp)
+    db_lin = torch.empty((hid,), device=dev, dtype=fp)
+    h = _h(states)
+    L.check(lib.adaf_ppo_encoder_backward_f32(h, L.ptr(states.contiguous()), L.ptr(e1.contiguous()), L.ptr(e_bt.contiguous()),
+                                              L.ptr(dx_bt.contiguous()), t, b, hw, cin, cmid, hid, L.ptr(w_lin_pm.contiguous()), L.ptr(dw_enc),
+                                              L.ptr(dw_lin), L.ptr(db_lin), L.ptr(ws), ws_bytes, L.stream_ptr()), h)
+    return dw_enc, dw_lin, db_lin
+
+
 def fc_meanpool_forward(feat, batch, fc_w, fc_b, global_logit=None):
     """mean_t FC(f_t) (+ mean_t glancer logits) -- STH/models/gfv_net.py:164-174.
     feat (B*T,F); global_logit (B,Tg,C) or None -> (B,C)."""

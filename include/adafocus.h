@@ -527,6 +527,54 @@ int adaf_gru_cls_backward_f32(adaf_handle* h, const float* x, int ldx, int batch
                               const float* hs, const float* mask, const float* dlogits, float* dx, float* dw_ih, float* dw_hh,
                               float* db_ih, float* db_hh, float* dw_fc, float* db_fc, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- a11 training (stage 2): PPO roll-out and policy update (csrc/ppo_train.hip) ----------------------------------------------
+ * Stage 2 of ACT/main_dist.py trains focuser.policy.policy only (ACT/models/ppo.py:27-62: 1x1 conv C -> 32, Linear, GRU, actor, critic).
+ * The GRU with both heads is adaf_gru_cls_train_forward_f32 / adaf_gru_cls_backward_f32 with the actor and critic weights stacked into
+ * one (A + 1)-row Linear and mask = NULL; the calls below are what surrounds it.  fp32, no atomics: the same inputs give the same bits.
+ *
+ * adaf_ppo_sample_f32: Categorical(softmax(logits)).sample() (ppo.py:84-92) from caller-drawn uniforms u [rows] in [0, 1).
+ *   logits [rows, A] with row stride ld (0 = A).  action_out [rows] int64 = the first a whose running sum of exp(l - max), in index
+ *   order, exceeds u * total (the last index if rounding leaves none); logprob_out [rows]; probs_out [rows, A] or NULL.
+ * adaf_ppo_returns_f32: rewards [T, B] -> R_t = r_t + gamma R_{t+1}, then (R - mean) / (std + 1e-5) over all T*B entries with the
+ *   unbiased standard deviation (ppo.py:148-157), sums in a fixed order.  returns_out [T, B].
+ * adaf_ppo_head_f32: per row of the stacked head output head [T*B, A + 1] (row b * T + t when head_batch_major, else t * B + b; columns
+ *   0..A-1 actor logits, column A the critic value) with actions [T, B] int64: logprobs_out / values_out / entropy_out [T, B] (each may be
+ *   NULL) as ActorCritic.evaluate returns them (ppo.py:114-122).  Then one of
+ *     - the PPO loss (old_logprobs, returns [T, B], loss_out [1] all given): ppo.py:166-172's loss.mean() into loss_out and
+ *       d loss.mean() / d head into dhead_out [T*B, A + 1] (head's row order; may be NULL).  Advantages take the value as a constant; the
+ *       gradient through min / clamp is autograd's (zero through a clamped ratio that wins the min).
+ *       Workspace: adaf_ppo_head_workspace_bytes(steps, batch) = 2 * steps * batch * 4 bytes.
+ *     - upstream gradients g_logprob / g_value / g_entropy [T, B] (any may be NULL = 0): dhead_out is their pull-back.
+ *     - neither: statistics only.
+ * adaf_ppo_rows_transpose_f32: out[j * ni + i, :] = in[i * nj + j, :] for rows of `width` floats ((T, B) <-> (B, T) row order).
+ * adaf_ppo_wenc_grad_f32: the 1x1 conv's weight gradient dw_out [conv_out, channels] = sum over pixels of
+ *   (de1[pixel, :] where e1[pixel, :] > 0, else 0) (x) states[pixel, :]; states [pixels, channels], de1 / e1 [pixels, conv_out].
+ *   split_k = 1: the streaming form (conv_out == 32, channels % 128 == 0): one read of `states` with 16-byte loads, block partials in
+ *   MFMA accumulators, slices added in slice order.  split_k = 0: the masked gradient as a tensor + one ascending chain per output on the
+ *   strided GEMM (the cross-check).  Workspace: adaf_ppo_wenc_grad_workspace_bytes(pixels, channels, conv_out).
+ * adaf_ppo_encoder_backward_f32: the state encoder's backward from dx_bt [B, T, hidden] (the dx of adaf_gru_cls_backward_f32).
+ *   states [T*B*map_pixels, channels] pixel-major, e1 [T*B, map_pixels * conv_out] the conv output after ReLU (rows t * B + b), e_bt
+ *   [B, T, hidden] the encoder output after ReLU (the GRU's x), w_lin_pm [hidden, map_pixels * conv_out] the Linear weight with pixel-major
+ *   columns.  Outputs: dw_enc [conv_out, channels], dw_lin [hidden, conv_out * map_pixels] in the nn.Linear layout (channel-major
+ *   columns), db_lin [hidden].  Workspace: adaf_ppo_encoder_backward_workspace_bytes(steps, batch, map_pixels, channels, conv_out, hidden).
+ * The workspace queries are plain arithmetic (no device needed) and return 0 for a non-positive extent. */
+int adaf_ppo_sample_f32(adaf_handle* h, const float* logits, int ld, int rows, int n_actions, const float* uniforms, int64_t* action_out,
+                        float* logprob_out, float* probs_out, void* stream);
+int adaf_ppo_returns_f32(adaf_handle* h, const float* rewards, int steps, int batch, float gamma, float* returns_out, void* stream);
+size_t adaf_ppo_head_workspace_bytes(int steps, int batch);
+int adaf_ppo_head_f32(adaf_handle* h, const float* head, int head_batch_major, int steps, int batch, int n_actions, const int64_t* actions,
+                      const float* old_logprobs, const float* returns, float eps_clip, const float* g_logprob, const float* g_value,
+                      const float* g_entropy, float* logprobs_out, float* values_out, float* entropy_out, float* loss_out, float* dhead_out,
+                      void* ws, size_t ws_bytes, void* stream);
+int adaf_ppo_rows_transpose_f32(adaf_handle* h, const float* in, int ni, int nj, int width, float* out, void* stream);
+size_t adaf_ppo_wenc_grad_workspace_bytes(int pixels, int channels, int conv_out);
+int adaf_ppo_wenc_grad_f32(adaf_handle* h, const float* states, const float* de1, const float* e1, int pixels, int channels, int conv_out,
+                           int split_k, float* dw_out, void* ws, size_t ws_bytes, void* stream);
+size_t adaf_ppo_encoder_backward_workspace_bytes(int steps, int batch, int map_pixels, int channels, int conv_out, int hidden);
+int adaf_ppo_encoder_backward_f32(adaf_handle* h, const float* states, const float* e1, const float* e_bt, const float* dx_bt, int steps,
+                                  int batch, int map_pixels, int channels, int conv_out, int hidden, const float* w_lin_pm, float* dw_enc,
+                                  float* dw_lin, float* db_lin, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- a8: linear classifier + temporal mean ---------------------------------------------
  * nn.Linear + ConsensusModule('avg') (+ glancer mean logits) -- STH/models/gfv_net.py:164-174,
  * STH/ops/basic_ops.py:17-26.  feat [B*T, F]; global_logit [B, Tg, C] or NULL; out [B, C];
