@@ -11,6 +11,7 @@ import torch
 
 from adafocus_amd import synth
 from tests.helpers import golden, rnd, synth_sd
+from tests.strided import conv_f16_bound
 
 pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("trunk_math")]
 
@@ -476,7 +477,7 @@ def test_conv_f16_operands_vs_fp32_reference(dev, ops, tile):
                                         pad=pad, act=ops.ACT_RELU, out_dtype=odt, tile=tile)
             assert got.dtype == odt
             err = (got.float().cpu() - ref).abs().max().item()
-            assert err < (2e-4 if odt == torch.float32 else 2e-3 * max(1.0, ref.abs().max().item())), (cin, cout, k, odt, err)
+            assert err < conv_f16_bound(odt, ref), (cin, cout, k, odt, err)
 
 
 def test_dwconv_f16_and_casts(dev, ops):
