@@ -158,6 +158,7 @@ int adaf_conv_out(int in, int k, int stride, int pad);
 // Validates a conv description and flattens it; returns ADAF_OK or an error code.
 int adaf_make_conv_args(adaf_handle* h, const adaf_conv_params* p, const float* x, const float* w, const float* scale,
                         const float* bias, const float* res, float* out, ConvArgs* a);
+int adaf_set_conv_dtypes(adaf_handle* h, bool in16, bool out16, ConvArgs* a);   // adaf_conv2d_bn_act_f16's dtype checks on top of it
 
 // mbconv.hip: fused expand 1x1 -> depthwise 3x3 of an inverted-residual block
 struct MbFuseArgs {

@@ -64,6 +64,16 @@ int adaf_make_conv_args(adaf_handle* h, const adaf_conv_params* p, const float* 
     return ADAF_OK;
 }
 
+// The half-precision part of the validation: which of a flattened conv's operands are fp16 (a residual, if there is one, always is).
+int adaf_set_conv_dtypes(adaf_handle* h, bool in16, bool out16, ConvArgs* a) {
+    a->in16 = in16; a->out16 = out16; a->res16 = a->res != nullptr;
+    if (in16 && (a->cin % 8 || a->ldx % 8)) return adaf_fail(h, ADAF_E_LAYOUT, "conv_f16: fp16 operands need cin %% 8 == 0 (16-byte chunks)");
+    if (in16 && a->tsm_T > 0 && a->tsm_fold % 8)
+        return adaf_fail(h, ADAF_E_LAYOUT, "conv_f16: temporal-shift fold=%d must be a multiple of 8 with fp16 operands (whole 16-byte chunks)", a->tsm_fold);
+    if (!in16 && a->res) return adaf_fail(h, ADAF_E_BADARG, "conv_f16: a residual needs fp16 operands");
+    return ADAF_OK;
+}
+
 AdafOptions& adaf_options() {
     static AdafOptions o;
     return o;
@@ -346,13 +356,7 @@ int adaf_conv2d_bn_act_f16(adaf_handle* h, const adaf_conv_params* p, const void
     int rc = adaf_make_conv_args(h, p, static_cast<const float*>(x), static_cast<const float*>(w_ohwi), scale, bias,
                             static_cast<const float*>(residual_f16), static_cast<float*>(out), &a);
     if (rc) return rc;
-    a.in16 = x_dtype == ADAF_DTYPE_F16;
-    a.out16 = out_dtype == ADAF_DTYPE_F16;
-    a.res16 = residual_f16 != nullptr;
-    if (a.in16 && (p->cin % 8 || a.ldx % 8)) return adaf_fail(h, ADAF_E_LAYOUT, "conv_f16: fp16 operands need cin %% 8 == 0 (16-byte chunks)");
-    if (a.in16 && a.tsm_T > 0 && a.tsm_fold % 8)
-        return adaf_fail(h, ADAF_E_LAYOUT, "conv_f16: temporal-shift fold=%d must be a multiple of 8 with fp16 operands (whole 16-byte chunks)", a.tsm_fold);
-    if (!a.in16 && residual_f16) return adaf_fail(h, ADAF_E_BADARG, "conv_f16: a residual needs fp16 operands");
+    if ((rc = adaf_set_conv_dtypes(h, x_dtype == ADAF_DTYPE_F16, out_dtype == ADAF_DTYPE_F16, &a))) return rc;
     if (p->tile && (p->tile < 81 || p->tile > 88)) return adaf_fail(h, ADAF_E_BADARG, "conv_f16: tile ids are 81..84, 88");
     if (adaf_launch_conv_gemm(a, p->tile, h->cus, (hipStream_t)stream) < 0)
         return adaf_fail(h, ADAF_E_LAYOUT, "conv_f16: shape not eligible (1x1: cin %% 8 == 0; k x k: cin %% 64 == 0)");

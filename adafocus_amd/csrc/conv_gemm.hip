@@ -17,6 +17,7 @@
 // same permutation on A and W, hence an exact (re-ordered) fp32 fma chain.
 #include <cstdlib>
 #include <type_traits>
+#include <utility>
 
 #include "adaf_internal.h"
 
@@ -1674,60 +1675,149 @@ __global__ void conv_naive_kernel(const ConvArgs a) {
     a.out[(size_t)m * a.ldo + n] = v;
 }
 
-struct TileShape { int bm, bn; float eff; };
-// eff: relative MFMA efficiency of the main loop; refined from profiles/ measurements.
-// Tile ids (adaf_conv_params.tile / adaf_resnet50_set_tiles):
-//    1..5   register-staged kernel: 128x128, 128x64, 64x64, 64x128, 256x128 (the fallback for shapes the DMA form cannot take)
-//   21..27  direct-to-LDS kernel, DMA issued at the top of a slice (kept for A/B)
-//   31..39  direct-to-LDS kernel, DMA issued between the MFMA groups  <- what the cost model picks (id + 30);
-//           38 / 39 = 128x32 / 256x32 for cout <= 32 (MobileNetV2 project convs)
-//   40      automatic choice among the split tiles; 41..47 split (6 products), operands split on the fly; 51..54 9 products
-//   61..67  split (6 products) with the weights pre-split at load time (ConvArgs::wsp; trunk only)
-//   71..74  fp32 pipe with the barrier between steps 2 and 3 of a slice (measured variant, not the default)
-// Everything above 4 is reachable only through an explicit override (tools/conv_probe.py, tests).
-const TileShape kTiles[ADAF_CONV_TILES + 1] = {
-    {0, 0, 0.f}, {128, 128, 1.00f}, {128, 64, 1.02f}, {64, 64, 0.98f}, {64, 128, 0.99f}};
+// ---- host side: which kernel instantiation a conv gets ---------------------------------------------------------------------------------
+// Three steps: kTileTable says which tiles exist, plan_conv decides -- without touching the device -- the tile and the kernel form a conv
+// takes, launch_row is the one place that spells the kernels' template arguments.  adaf_conv_plan_debug shows a plan to the host tests.
+enum TileFamily {
+    TF_REG,        // register-staged kernel (conv_gemm_kernel): takes every shape, the fallback of all the others
+    TF_DMA_TOP,    // direct-to-LDS kernel, DMA issued at the top of a slice (kept for A/B)
+    TF_DMA_MID,    // direct-to-LDS kernel, DMA issued between the MFMA groups  <- what the cost model picks
+    TF_BAR23,      // fp32 pipe with the barrier between steps 2 and 3 of a slice (next slice's first fragments prefetched; measured variant)
+    TF_SPLIT6,     // fp32 operands split on the fly into bf16 parts on the bf16 matrix pipe, 6 products per element pair; opt-in
+    TF_SPLIT9,     // the same with 9 products
+    TF_PRESPLIT,   // split (6 products) with the weights pre-split at load time (ConvArgs::wsp; trunk only)
+    TF_F16,        // fp16 operands (adaf_conv2d_bn_act_f16 only)
+    TF_LAT,        // small-batch form on v_mfma_f32_16x16x4_f32 (conv_lat.hip, which also holds its eligibility)
+};
+struct TileRow {
+    int id;            // adaf_conv_params.tile / adaf_resnet50_set_tiles
+    int bm, bn;        // block tile
+    int wgm, wgn;      // wave grid
+    TileFamily fam;
+    int fallback;      // the id that takes a shape this row's kernel cannot (0: none, the conv is refused)
+    int presplit;      // the pre-split row the automatic split choice moves to when the weights are pre-split (0: none)
+    float eff;         // rows the cost model chooses among: relative MFMA efficiency of the main loop, refined from profiles/ measurements
+};
+constexpr int kTileAutoSplit = 40;      // not a tile: the automatic choice among the split tiles
+// Everything above 4 is reachable only through an explicit override (tools/conv_probe.py, tests) or the rules of resolve_f32_tile.
+constexpr TileRow kTileTable[] = {
+    {1, 128, 128, 2, 2, TF_REG, 0, 0, 1.00f},
+    {2, 128, 64, 2, 2, TF_REG, 0, 0, 1.02f},
+    {3, 64, 64, 2, 2, TF_REG, 0, 0, 0.98f},
+    {4, 64, 128, 2, 2, TF_REG, 0, 0, 0.99f},
+    {5, 256, 128, 4, 2, TF_REG, 0, 0, 0.f},            // 8 waves, 1 block/CU
+    {21, 128, 128, 2, 2, TF_DMA_TOP, 1, 0, 0.f},
+    {22, 128, 64, 2, 2, TF_DMA_TOP, 2, 0, 0.f},
+    {23, 64, 64, 2, 2, TF_DMA_TOP, 3, 0, 0.f},
+    {24, 64, 128, 2, 2, TF_DMA_TOP, 4, 0, 0.f},
+    {25, 256, 128, 4, 2, TF_DMA_TOP, 5, 0, 0.f},       // 8 waves of 64x64
+    {26, 256, 128, 2, 2, TF_DMA_TOP, 1, 0, 0.f},       // 4 waves of 128x64
+    {31, 128, 128, 2, 2, TF_DMA_MID, 1, 0, 0.f},
+    {32, 128, 64, 2, 2, TF_DMA_MID, 2, 0, 0.f},
+    {33, 64, 64, 2, 2, TF_DMA_MID, 3, 0, 0.f},
+    {34, 64, 128, 2, 2, TF_DMA_MID, 4, 0, 0.f},
+    {38, 128, 32, 4, 1, TF_DMA_MID, 1, 0, 0.f},        // narrow outputs (cout <= 32, MobileNetV2 project convs): four waves of 32x32
+    {39, 256, 32, 4, 1, TF_DMA_MID, 1, 0, 0.f},        // narrow outputs: four waves of 64x32
+    {41, 128, 128, 2, 2, TF_SPLIT6, 1, 65, 0.f},
+    {42, 128, 64, 2, 2, TF_SPLIT6, 2, 62, 0.f},
+    {43, 64, 64, 2, 2, TF_SPLIT6, 3, 63, 0.f},
+    {44, 64, 128, 2, 2, TF_SPLIT6, 4, 64, 0.f},
+    {45, 256, 128, 4, 2, TF_SPLIT6, 5, 0, 0.f},        // 8 waves of 64x64
+    {46, 256, 128, 2, 2, TF_SPLIT6, 1, 0, 0.f},        // 4 waves of 128x64
+    {51, 128, 128, 2, 2, TF_SPLIT9, 1, 0, 0.f},
+    {52, 128, 64, 2, 2, TF_SPLIT9, 2, 0, 0.f},
+    {53, 64, 64, 2, 2, TF_SPLIT9, 3, 0, 0.f},
+    {54, 64, 128, 2, 2, TF_SPLIT9, 4, 0, 0.f},
+    {61, 128, 128, 2, 2, TF_PRESPLIT, 41, 0, 0.f},
+    {62, 128, 64, 2, 2, TF_PRESPLIT, 42, 0, 0.f},
+    {63, 64, 64, 2, 2, TF_PRESPLIT, 43, 0, 0.f},
+    {64, 64, 128, 2, 2, TF_PRESPLIT, 44, 0, 0.f},
+    {65, 128, 128, 4, 1, TF_PRESPLIT, 41, 0, 0.f},     // waves of 32x128: fewest activation splits per product
+    {66, 256, 128, 8, 1, TF_PRESPLIT, 41, 0, 0.f},     // 8 waves of 32x128: 30 % less L2->LDS traffic per product
+    {67, 256, 128, 4, 2, TF_PRESPLIT, 41, 0, 0.f},     // 8 waves of 64x64
+    {71, 128, 128, 2, 2, TF_BAR23, 1, 0, 0.f},
+    {72, 128, 64, 2, 2, TF_BAR23, 2, 0, 0.f},
+    {73, 64, 64, 2, 2, TF_BAR23, 3, 0, 0.f},
+    {74, 64, 128, 2, 2, TF_BAR23, 4, 0, 0.f},
+    {81, 128, 128, 2, 2, TF_F16, 0, 0, 0.f},
+    {82, 128, 64, 2, 2, TF_F16, 0, 0, 0.f},
+    {83, 64, 64, 2, 2, TF_F16, 0, 0, 0.f},
+    {84, 64, 128, 2, 2, TF_F16, 0, 0, 0.f},
+    {88, 128, 32, 4, 1, TF_F16, 0, 0, 0.f},
+    {95, 32, 32, 2, 2, TF_LAT, 0, 0, 0.f},             // four 16x16 wave tiles
+#ifdef ADAF_EXP_TILES      // 256 x 256 block tiles, 8 waves of 128x64: experiments only (tools/exp/build_exp_tiles.sh), not in the product library
+    {27, 256, 256, 2, 4, TF_DMA_TOP, 1, 0, 0.f},
+    {37, 256, 256, 2, 4, TF_DMA_MID, 1, 0, 0.f},
+    {47, 256, 256, 2, 4, TF_SPLIT6, 1, 0, 0.f},
+#endif
+};
+constexpr int kNumTiles = (int)(sizeof(kTileTable) / sizeof(kTileTable[0]));
+constexpr int kTileOut16 = 2;           // the register-staged tile that also exists with an fp16 store (fp32 operands)
+constexpr int kTileF16Lo = 81, kTileF16Hi = 88;          // the id range of the fp16-operand tiles (adaf_conv2d_bn_act_f16 refuses any other)
+constexpr int kTilePoolF32 = 32, kTilePoolF16 = 82;     // the tiles that also exist with the pooled epilogue (128 x 64: whole images per 128 rows)
 
-// (the lean K loop / epilogue forms were an option, "conv_lean", while they were measured against the forms they replace -- tools/lean_ab.py, rounds 3-5;
-//  the general forms remain as the fallback for operands beyond the scalar-base DMA's 4 GB reach and for edge tiles)
-static constexpr int conv_lean_enabled() { return 1; }
-
-template <int BM, int BN, int WGM, int WGN, int BK, int FLAGS>
-void launch_cfg(ConvArgs a, bool dense, hipStream_t s) {
-    if (a.vec_epi && conv_lean_enabled() == 1) a.vec_epi = 2;     // interior tiles take the lean epilogue
-    a.tiles_n = (a.N + BN - 1) / BN;
-    a.nblocks = ((a.M + BM - 1) / BM) * a.tiles_n;
-    if (dense)
-        hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, WGM, WGN, BK, true, FLAGS>), dim3(a.nblocks), dim3(64 * WGM * WGN), 0, s, a);
-    else
-        hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, WGM, WGN, BK, false, FLAGS>), dim3(a.nblocks), dim3(64 * WGM * WGN), 0, s, a);
+constexpr int tile_index(int id) {      // position in kTileTable, -1: no such tile
+    for (int i = 0; i < kNumTiles; ++i)
+        if (kTileTable[i].id == id) return i;
+    return -1;
 }
-
-// fp16-operand launches (tile ids 81..84, 88): `a` arrives in ELEMENT units; the loader counts 32-bit words
-template <int BM, int BN, int WGM, int WGN, int DT>
-void launch_glds16(ConvArgs a, bool dense, hipStream_t s) {
-    a.tiles_n = (a.N + BN - 1) / BN;
-    a.nblocks = ((a.M + BM - 1) / BM) * a.tiles_n;
-    a.K /= 2; a.cin /= 2; a.ldx /= 2; a.tsm_fold /= 2;
-    const bool special = a.tsm_T > 0 || (a.K & 31);
-    if (dense && special)
-        hipLaunchKernelGGL((conv_gemm_glds_kernel<BM, BN, WGM, WGN, true, 1, true, 0, false, DT>), dim3(a.nblocks), dim3(64 * WGM * WGN), 0, s, a);
-    else if (dense)
-        hipLaunchKernelGGL((conv_gemm_glds_kernel<BM, BN, WGM, WGN, true, 1, false, 0, false, DT>), dim3(a.nblocks), dim3(64 * WGM * WGN), 0, s, a);
-    else
-        hipLaunchKernelGGL((conv_gemm_glds_kernel<BM, BN, WGM, WGN, false, 1, false, 0, false, DT>), dim3(a.nblocks), dim3(64 * WGM * WGN), 0, s, a);
+constexpr int family_tile(TileFamily fam, int bm, int bn) {     // the family's (first) tile with this block shape, 0: none
+    for (int i = 0; i < kNumTiles; ++i)
+        if (kTileTable[i].fam == fam && kTileTable[i].bm == bm && kTileTable[i].bn == bn) return kTileTable[i].id;
+    return 0;
 }
+constexpr int family_tile_like(TileFamily fam, int id) { return family_tile(fam, kTileTable[tile_index(id)].bm, kTileTable[tile_index(id)].bn); }
+// what a family means for conv_gemm_glds_kernel's PIPE / EMU arguments (0 where the kernel has none)
+constexpr int family_pipe(TileFamily f) { return f == TF_BAR23 ? 2 : f == TF_REG || f == TF_DMA_TOP || f == TF_LAT ? 0 : 1; }
+constexpr int family_split(TileFamily f) { return f == TF_SPLIT6 || f == TF_PRESPLIT ? 6 : f == TF_SPLIT9 ? 9 : 0; }
+// which rows have which special form (read by the planner at run time and by the launcher at compile time)
+constexpr bool has_pos_major_form(const TileRow& r) { return r.fam == TF_DMA_MID || r.fam == TF_PRESPLIT; }
+// (of the pre-split tiles only the 128 x 128 tile of four 32 x 128 waves, the one the split plan uses, has the lean K loop: the planes addressed
+//  from a scalar base, no pointer arithmetic on the vector ALU the split itself needs -- CG_ABL 4: the DMA issue was 8 % of the split convs' time)
+constexpr bool has_lean_form(const TileRow& r) {
+    return r.fam == TF_DMA_MID || (r.fam == TF_PRESPLIT && r.bm == 128 && r.bn == 128 && r.wgm == 4 && r.wgn == 1);
+}
+// (64x64 tiles keep the builtin form of a plain 1x1: measured equal at K = 1024 and 7 % slower at K = 2048, cout 512 -- stage 4's conv1)
+constexpr bool lean_dense_pays(const TileRow& r) { return has_lean_form(r) && r.bm * r.bn > 64 * 64; }
+constexpr bool has_lean_shift_form(const TileRow& r) { return r.fam == TF_DMA_MID && r.bm * r.bn > 64 * 64; }
 
-template <int BM, int BN, int WGM, int WGN>
-void launch_glds16_dt(const ConvArgs& a, bool dense, hipStream_t s) {
-    // operands fp16; output fp16 or fp32; residual (if any) fp16
-    if (a.out16) launch_glds16<BM, BN, WGM, WGN, 4 | 2 | 1>(a, dense, s);
-    else launch_glds16<BM, BN, WGM, WGN, 4 | 2>(a, dense, s);
+// DT argument of conv_gemm_glds_kernel / ET of conv_gemm_kernel: which operands are fp16
+enum { DT_OUT16 = 1, DT_RES16 = 2, DT_IN16 = 4 };
+enum PoolKind { POOL_F32, POOL_F16, POOL_F16_ROUNDED };
+
+// The decision for one conv: a tile and the kernel form, by name, plus the launch-time fields of ConvArgs that follow from them.
+struct ConvPlan {
+    int tile = -1;              // resolved tile id; < 0: no kernel takes this conv
+    int row = -1;               // its row in kTileTable (block shape, wave grid, family = pipe variant / split kind / pre-split weights)
+    bool dense = false;         // DENSE: operand rows are contiguous K-vectors (a 1x1 stride-1 conv, or a strided 1x1 as a row gather)
+    bool gather = false;        //   ... the strided 1x1 case
+    bool special = false;       // SPECIAL: temporal shift in the operand load, or a partial last K slice
+    bool lean = false;          // LEAN: straight-line K loop on scalar-base DMA
+    bool pos_major = false;     // PM: position-major tiles with padding-tap skipping
+    bool pool = false;          // POOL: global average pool in the epilogue
+    int dt = 0;                 // DT_* bits
+    ConvArgs a;                 // the conv as it is launched: tiles_n, nblocks, pm_images, pm_groups, vec_epi as planned; K, cin, ldx and
+                                // tsm_fold in 32-bit words (halved for fp16 operands)
+    explicit ConvPlan(const ConvArgs& conv) : a(conv) {}
+};
+
+bool conv_is_dense(const ConvArgs& a) { return a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0; }
+int conv_images(const ConvArgs& a) { return a.OH * a.OW > 0 ? a.M / (a.OH * a.OW) : 0; }
+
+// The scalar-base DMA of the lean forms addresses an operand with 32-bit byte offsets: is its last element within reach (4 GB)?
+bool dma_reach(size_t elems, size_t elem_bytes = 4) { return elems * elem_bytes < 0xffffff00ull; }
+bool operands_in_dma_reach(const ConvArgs& a) {
+    return dma_reach((size_t)a.M * a.ldx) && dma_reach((size_t)a.N * a.K) &&
+           (conv_is_dense(a) || dma_reach((size_t)a.H * a.W * a.ldx * (size_t)conv_images(a)));
+}
+// A strided 1x1 conv without padding (ResNet's downsample branch) is the dense GEMM with a row gather: lean forms only.
+bool strided_1x1_as_gather(const ConvArgs& a) {
+    return !conv_is_dense(a) && a.KH == 1 && a.KW == 1 && a.pad == 0 && a.stride > 1 && a.tsm_T == 0 && (a.K & 31) == 0;
 }
 
 // Share of the filter taps that touch the image, averaged over the output pixels (1 = no padding work to skip).  The
 // tap mask of a pixel is the product of a row mask and a column mask, so the count factorises.
-static double conv_tap_fill(const ConvArgs& a) {
+double conv_tap_fill(const ConvArgs& a) {
     auto axis = [&](int out, int in, int k) {
         long long c = 0;
         for (int o = 0; o < out; ++o)
@@ -1736,100 +1826,230 @@ static double conv_tap_fill(const ConvArgs& a) {
     };
     return (double)(axis(a.OH, a.H, a.KH) * axis(a.OW, a.W, a.KW)) / ((double)a.OH * a.OW * a.KH * a.KW);
 }
+// Position-major tiles with padding-tap skipping: a k x k conv, enough images sharing a pixel position to fill the tile rows, and at least
+// 4 % of the products padding.  On the split-bf16 pipe (pre-split rows; round 5) a skipped tap is whole MFMA steps of exact zeros, so the
+// result is bit-identical to the row-major split tile; pm_allow == 2 (all taps walked, an experiment) exists on the fp32 pipe only.
+bool pos_major_gate(const ConvArgs& a, const TileRow& r) {
+    const int ohw = a.OH * a.OW, images = conv_images(a);
+    return has_pos_major_form(r) && (r.fam == TF_PRESPLIT ? a.pm_allow == 1 : a.pm_allow != 0) && !conv_is_dense(a) && a.KH * a.KW > 1 &&
+           a.KH * a.KW <= 32 && images * ohw == a.M && images >= r.bm && ohw <= 4096 && conv_tap_fill(a) < 0.96;
+}
+// A conv1 with the fused temporal shift on the lean K loop (round 6): whole 32-channel slices on either side of the fold boundaries, every
+// row's frame neighbours inside the tensor (2 GB: the buffer form's offsets stay below the out-of-range marker)
+bool lean_shift_gate(const ConvArgs& a, const TileRow& r) {
+    return has_lean_shift_form(r) && conv_is_dense(a) && a.tsm_T > 0 && (a.K & 31) == 0 && (a.tsm_fold & 31) == 0 && a.stride == 1 &&
+           operands_in_dma_reach(a) && adaf_options().tsm_lean && (size_t)a.M * a.ldx * 4 < 0x7fff0000ull;
+}
 
-// position-major tiles are used when less than this share of the filter taps touches the image
-static constexpr double conv_pm_fill_threshold() { return 0.96; }
+// Does the DMA kernel take the shape (fp32 operands)?
+bool adaf_conv_glds_ok(const ConvArgs& a) {
+    if (conv_is_dense(a)) return a.K % 4 == 0;      // partial last slice is zero-filled
+    return a.K % 32 == 0 && a.cin % 32 == 0 && a.KH * a.KW <= 32;
+}
 
-template <int BM, int BN, int WGM, int WGN, int PIPE, int EMU = 0, bool BSP = false>
-void launch_glds(ConvArgs a, bool dense, hipStream_t s) {
-    if (a.vec_epi && conv_lean_enabled() == 1) a.vec_epi = 2;     // interior tiles take the lean epilogue
-    a.tiles_n = (a.N + BN - 1) / BN;
-    a.nblocks = ((a.M + BM - 1) / BM) * a.tiles_n;
-    // the lean K loop addresses rows with 32-bit byte offsets from a scalar base
-    const bool lean = conv_lean_enabled() && (size_t)a.M * a.ldx * 4 < 0xffffff00ull && (size_t)a.N * a.K * 4 < 0xffffff00ull &&
-                      (dense || (size_t)a.H * a.W * a.ldx * (size_t)(a.OH * a.OW > 0 ? a.M / (a.OH * a.OW) : 0) * 4 < 0xffffff00ull);
-    // split tiles (the 128 x 128 tile of four 32 x 128 waves, the one the split plan uses): the lean K loop with the pre-split planes
-    // addressed from a scalar base -- no pointer arithmetic on the vector ALU the split itself needs (CG_ABL 4: the DMA issue was 8 % of the
-    // split convs' time)
-    constexpr bool kLeanSplit = PIPE == 1 && EMU == 6 && BSP && BM == 128 && BN == 128 && WGM == 4 && WGN == 1;
-    const bool lean_split = kLeanSplit && lean && a.wsp && adaf_options().split_lean && (size_t)3 * a.N * a.K * 2 < 0xffffff00ull;
-    if constexpr (PIPE == 1 && EMU == 0 && !BSP) {
-        // position-major tiles with padding-tap skipping: when enough images share a pixel position to fill the tile
-        // rows and at least 4 % of the products are padding
-        const int ohw = a.OH * a.OW;
-        const int images = ohw > 0 ? a.M / ohw : 0;
-        if (!dense && a.pm_allow && a.KH * a.KW > 1 && a.KH * a.KW <= 32 && images * ohw == a.M && images >= BM && ohw <= 4096 &&
-            conv_tap_fill(a) < conv_pm_fill_threshold()) {
-            a.pm_images = images;
-            a.pm_groups = (images + BM - 1) / BM;
-            a.nblocks = ohw * a.pm_groups * a.tiles_n;
-            if (lean && a.pm_allow != 2)
-                hipLaunchKernelGGL((conv_gemm_glds_kernel<BM, BN, WGM, WGN, false, 1, false, 0, false, 0, true, true>), dim3(a.nblocks),
-                                   dim3(64 * WGM * WGN), 0, s, a);
-            else
-                hipLaunchKernelGGL((conv_gemm_glds_kernel<BM, BN, WGM, WGN, false, 1, false, 0, false, 0, true>), dim3(a.nblocks),
-                                   dim3(64 * WGM * WGN), 0, s, a);
-            return;
+// fp16 operands: word-granular eligibility of the DMA kernel
+bool conv_glds16_ok(const ConvArgs& a) {
+    if ((a.K & 1) || (a.cin & 1) || (a.ldx & 1)) return false;
+    if (conv_is_dense(a)) return (a.K / 2) % 4 == 0;
+    return (a.K / 2) % 32 == 0 && (a.cin / 2) % 32 == 0 && a.KH * a.KW <= 32;
+}
+
+// 32-wide column tiles when 64-wide ones would spend >= 20 % of the MFMA columns on padding (cout = 16, 24, 32, 96, 160: MobileNetV2's
+// project convs)
+bool narrow_output(const ConvArgs& a) { return (((a.N + 63) / 64) * 64 - a.N) * 5 >= a.N; }
+long long row_tiles(const ConvArgs& a, int bm) { return (a.M + bm - 1) / bm; }
+
+// The fp32 tile a conv takes: `tile` as asked for (0 = automatic, kTileAutoSplit), moved along the rows' fallback ids until one takes the shape.
+int resolve_f32_tile(const ConvArgs& a, int tile, int cus) {
+    const bool dma_ok = adaf_conv_glds_ok(a);
+    const bool presplit_ok = a.wsp != nullptr && (a.K & 31) == 0 && dma_ok;
+    if (tile == kTileAutoSplit) {   // split tiles, automatic: the bigger the wave tile the fewer split instructions per product
+        tile = 0;
+        if (dma_ok) {
+            if (a.N <= 64) tile = family_tile(TF_SPLIT6, 128, 64);
+            else if (row_tiles(a, 128) * ((a.N + 127) / 128) * 2 >= cus) tile = family_tile(TF_SPLIT6, 128, 128);
+            else tile = family_tile_like(TF_SPLIT6, adaf_pick_conv_tile(a.M, a.N, a.K, cus));   // tiny problems: fill the CUs first
+            if (presplit_ok) tile = kTileTable[tile_index(tile)].presplit;
         }
     }
-    if constexpr (PIPE == 1 && EMU == 6 && BSP) {
-        // the same position-major tiles on the split-bf16 pipe (round 5): a skipped tap is whole MFMA steps of exact zeros, so the result
-        // is bit-identical to the row-major split tile; the activation split (VALU) of the skipped slices disappears with their MFMAs
-        const int ohw = a.OH * a.OW;
-        const int images = ohw > 0 ? a.M / ohw : 0;
-        if (!dense && a.pm_allow == 1 && a.wsp && a.KH * a.KW > 1 && a.KH * a.KW <= 32 && images * ohw == a.M && images >= BM && ohw <= 4096 &&
-            (a.cin & 31) == 0 && conv_tap_fill(a) < conv_pm_fill_threshold()) {
-            a.pm_images = images;
-            a.pm_groups = (images + BM - 1) / BM;
-            a.nblocks = ohw * a.pm_groups * a.tiles_n;
-            if constexpr (kLeanSplit)
-                if (lean_split && a.pm_allow != 2) {
-                    hipLaunchKernelGGL((conv_gemm_glds_kernel<BM, BN, WGM, WGN, false, 1, false, 6, true, 0, true, true>), dim3(a.nblocks),
-                                       dim3(64 * WGM * WGN), 0, s, a);
-                    return;
-                }
-            hipLaunchKernelGGL((conv_gemm_glds_kernel<BM, BN, WGM, WGN, false, 1, false, 6, true, 0, true>), dim3(a.nblocks), dim3(64 * WGM * WGN), 0, s, a);
-            return;
+    if (tile <= 0) {
+        tile = adaf_pick_conv_tile(a.M, a.N, a.K, cus);
+        if (dma_ok) {
+            tile = family_tile_like(TF_DMA_MID, tile);
+            // narrow outputs: 128 x 32 tiles when there are enough row tiles to fill the device; with fewer rows but a long reduction
+            // (MobileNetV2's 960 -> 160 project convs on 7x7 maps: 25 k rows) waves of 64 x 32 under 256-row tiles -- 65 instead of 83 us
+            // per 512 frames (tools/tail_gemm_tiles.py)
+            if (narrow_output(a) && row_tiles(a, 128) >= cus) tile = family_tile(TF_DMA_MID, 128, 32);
+            else if (narrow_output(a) && a.K >= 512 && row_tiles(a, 256) * ((a.N + 31) / 32) >= cus) tile = family_tile(TF_DMA_MID, 256, 32);
         }
     }
+    for (int i = tile_index(tile); i >= 0; i = tile_index(tile)) {
+        const TileRow& r = kTileTable[i];
+        if (r.fam == TF_REG || (r.fam == TF_PRESPLIT ? presplit_ok : dma_ok && r.fam != TF_F16 && r.fam != TF_LAT)) return tile;
+        tile = r.fallback;      // (the fp16 and latency rows have none: they are not reached through here)
+    }
+    return -1;
+}
+
+void plan_row_major(ConvPlan& p, const ConvArgs& a, int tile, int bm_rows) {
+    p.row = tile_index(p.tile = tile);
+    p.a.tiles_n = (a.N + kTileTable[p.row].bn - 1) / kTileTable[p.row].bn;
+    p.a.nblocks = ((a.M + bm_rows - 1) / bm_rows) * p.a.tiles_n;
+}
+
+// The plan of one conv.  Pure: no HIP call, no launch; reads adaf_options().
+ConvPlan plan_conv(const ConvArgs& a, int tile, int cus) {
+    ConvPlan p(a);
+    const bool dense = conv_is_dense(a);
+    if (a.in16) {    // operands fp16; output fp16 or fp32; residual (if any) fp16.  `a` arrives in ELEMENT units; the loader counts 32-bit words
+        if (!conv_glds16_ok(a) || (a.res && !a.res16)) return p;
+        if (tile < kTileF16Lo || tile > kTileF16Hi) {      // not an id adaf_conv2d_bn_act_f16 passes on: the automatic choice
+            tile = family_tile_like(TF_F16, adaf_pick_conv_tile(a.M, a.N, a.K, cus));
+            if (narrow_output(a) && row_tiles(a, 128) >= cus) tile = family_tile(TF_F16, 128, 32);
+        }
+        if (tile_index(tile) < 0) return p;
+        plan_row_major(p, a, tile, kTileTable[tile_index(tile)].bm);
+        p.a.K /= 2; p.a.cin /= 2; p.a.ldx /= 2; p.a.tsm_fold /= 2;
+        p.dt = DT_IN16 | DT_RES16 | (a.out16 ? DT_OUT16 : 0);
+        p.dense = dense;
+        p.special = dense && (a.tsm_T > 0 || (p.a.K & 31));
+        return p;
+    }
+    if (a.out16) {   // fp32 operands, fp16 store (the 3x3 stem of the half-precision MobileNetV2): register-staged 128x64 tile
+        if (a.res) return p;
+        plan_row_major(p, a, kTileOut16, kTileTable[tile_index(kTileOut16)].bm);
+        p.dt = DT_OUT16;
+        p.dense = dense;
+        return p;
+    }
+    const int asked = tile_index(tile);
+    if (asked >= 0 && kTileTable[asked].fam == TF_LAT) {     // the small-batch form (bit-identical); conv_lat.hip may still decline the shape
+        p.row = tile_index(p.tile = tile);
+        return p;
+    }
+    tile = resolve_f32_tile(a, tile, cus);
+    if (tile < 0) return p;
+    const TileRow& r = kTileTable[tile_index(tile)];
+    plan_row_major(p, a, tile, r.bm);
+    if (a.vec_epi) p.a.vec_epi = 2;      // interior tiles take the lean epilogue
+    p.dense = dense;
+    if (r.fam == TF_REG) return p;
     const bool special = a.tsm_T > 0 || (a.K & 31);
-    if constexpr (kLeanSplit) {
-        // the split tile's dense form (and ResNet's strided 1x1 downsample convs as a row gather) with the lean K loop
-        const bool strided1x1 = !dense && a.KH == 1 && a.KW == 1 && a.pad == 0 && a.stride > 1 && a.tsm_T == 0 && (a.K & 31) == 0 &&
-                                (size_t)a.H * a.W * a.ldx * (size_t)(a.OH * a.OW > 0 ? a.M / (a.OH * a.OW) : 0) * 4 < 0xffffff00ull;
-        if ((dense || strided1x1) && !special && lean_split) {
-            hipLaunchKernelGGL((conv_gemm_glds_kernel<BM, BN, WGM, WGN, true, 1, false, 6, true, 0, false, true>), dim3(a.nblocks),
-                               dim3(64 * WGM * WGN), 0, s, a);
-            return;
-        }
+    p.special = dense && special;
+    // the lean K loop addresses rows with 32-bit byte offsets from a scalar base; on the pre-split tile the three bf16 planes too
+    const bool lean = has_lean_form(r) && operands_in_dma_reach(a) &&
+                      (r.fam != TF_PRESPLIT || (adaf_options().split_lean && dma_reach((size_t)3 * a.N * a.K, 2)));
+    if (pos_major_gate(a, r)) {
+        p.pos_major = true;
+        p.lean = lean && a.pm_allow != 2;
+        p.a.pm_images = conv_images(a);
+        p.a.pm_groups = (p.a.pm_images + r.bm - 1) / r.bm;
+        p.a.nblocks = a.OH * a.OW * p.a.pm_groups * p.a.tiles_n;
+    } else if ((dense || strided_1x1_as_gather(a)) && !special && lean && lean_dense_pays(r)) {
+        p.gather = !dense;
+        p.dense = p.lean = true;
+    } else if (lean_shift_gate(a, r)) {
+        p.lean = true;
     }
-    if constexpr (PIPE == 1 && EMU == 0 && !BSP) {
-        // (64x64 tiles keep the builtin form: measured equal at K = 1024 and 7 % slower at K = 2048, cout 512 -- stage 4's conv1)
-        // a strided 1x1 conv without padding (ResNet's downsample branch) is the same GEMM with a row gather: lean form only
-        const bool strided1x1 = !dense && a.KH == 1 && a.KW == 1 && a.pad == 0 && a.stride > 1 && a.tsm_T == 0 && (a.K & 31) == 0 &&
-                                (size_t)a.H * a.W * a.ldx * (size_t)(a.OH * a.OW > 0 ? a.M / (a.OH * a.OW) : 0) * 4 < 0xffffff00ull;
-        if ((dense || strided1x1) && !special && lean && conv_lean_enabled() == 1 && BM * BN > 64 * 64) {
-            hipLaunchKernelGGL((conv_gemm_glds_kernel<BM, BN, WGM, WGN, true, 1, false, 0, false, 0, false, true>), dim3(a.nblocks),
-                               dim3(64 * WGM * WGN), 0, s, a);
-            return;
+    return p;
+}
+
+// The three pooled launches share one eligibility: a 1x1 / stride 1 conv whose images of `hw` pixels fill a 128-row tile to >= 90 % (hw = 9
+// at 96^2 patches: 14 images = 126 rows; 16 at 128^2; 25 at 144^2), 16-byte epilogue, whole K slices.
+ConvPlan plan_conv_pool(const ConvArgs& a, int hw, const float* pool_out, int pool_ld, PoolKind kind) {
+    ConvPlan p(a);
+    const bool f16 = kind != POOL_F32;
+    const bool relu_like = a.act == ADAF_ACT_NONE || a.act == ADAF_ACT_RELU || a.act == ADAF_ACT_RELU6;
+    if (!adaf_options().conv_pool) return p;      // 0 = conv + separate avgpool_kernel (A/B)
+    if ((a.in16 != 0) != f16 || a.out16 || a.split_n || a.tsm_T > 0 || a.wsp || !conv_is_dense(a) || (a.N & 3) || !a.vec_epi) return p;
+    if (hw <= 0 || hw > 128 || a.M % hw || (128 / hw) * hw * 10 < 128 * 9 || (pool_ld & 3) || (reinterpret_cast<size_t>(pool_out) & 15)) return p;
+    if (kind == POOL_F32 && (a.res16 || (a.K & 31) || !relu_like || !operands_in_dma_reach(a))) return p;
+    if (f16 && (!conv_glds16_ok(a) || (a.K & 63))) return p;
+    if (kind == POOL_F16 && a.res) return p;      // (EfficientNet's head: swish / sigmoid allowed, no identity)
+    if (kind == POOL_F16_ROUNDED && ((a.res && !a.res16) || (a.ldr & 3) || !relu_like)) return p;
+    plan_row_major(p, a, f16 ? kTilePoolF16 : kTilePoolF32, (128 / hw) * hw);
+    p.dense = p.pool = true;
+    p.lean = !f16;
+    p.a.vec_epi = f16 ? a.vec_epi : 2;
+    p.dt = kind == POOL_F16 ? DT_IN16 : kind == POOL_F16_ROUNDED ? DT_IN16 | DT_RES16 : 0;
+    if (f16) { p.a.K /= 2; p.a.cin /= 2; p.a.ldx /= 2; }
+    return p;
+}
+
+// The one place where the kernels' positional template arguments are written: row I of kTileTable in the form the plan names.  It
+// instantiates, per row, exactly the forms has_*_form() allow; every macro call launches and returns.  (A lean dense kernel exists for every
+// TF_DMA_MID row although the planner asks for it only where lean_dense_pays(): the library's set of kernels is kept as it was.)
+template <int I>
+int launch_row(const ConvPlan& p, const ConvArgs& a, hipStream_t s) {
+    constexpr TileRow R = kTileTable[I];
+    const dim3 grid(a.nblocks), block(64 * R.wgm * R.wgn);
+    (void)grid; (void)block;
+#define CONV_REG(...) do { hipLaunchKernelGGL((conv_gemm_kernel<R.bm, R.bn, R.wgm, R.wgn, __VA_ARGS__>), grid, block, 0, s, a); return p.tile; } while (0)
+#define CONV_GLDS(...) do { hipLaunchKernelGGL((conv_gemm_glds_kernel<R.bm, R.bn, R.wgm, R.wgn, __VA_ARGS__>), grid, block, 0, s, a); return p.tile; } while (0)
+    if constexpr (R.fam == TF_LAT) {
+        return adaf_launch_conv_lat(a, s) ? p.tile : -1;
+    } else if constexpr (R.fam == TF_REG) {
+        //                             BK  DENSE  FLAGS ET
+        if constexpr (R.id == kTileOut16) {
+            if (p.dt == DT_OUT16 && p.dense) CONV_REG(32, true, 0, DT_OUT16);
+            if (p.dt == DT_OUT16) CONV_REG(32, false, 0, DT_OUT16);
         }
-    }
-    if constexpr (PIPE == 1 && EMU == 0 && !BSP && BM * BN > 64 * 64) {
-        // a conv1 with the fused temporal shift on the lean K loop (round 6): whole 32-channel slices on either side of the fold boundaries, every
-        // row's frame neighbours inside the tensor (2 GB: the buffer form's offsets stay below the out-of-range marker)
-        if (dense && a.tsm_T > 0 && (a.K & 31) == 0 && (a.tsm_fold & 31) == 0 && a.stride == 1 && lean && adaf_options().tsm_lean &&
-            (size_t)a.M * a.ldx * 4 < 0x7fff0000ull) {
-            hipLaunchKernelGGL((conv_gemm_glds_kernel<BM, BN, WGM, WGN, true, 1, true, 0, false, 0, false, true>), dim3(a.nblocks),
-                               dim3(64 * WGM * WGN), 0, s, a);
-            return;
+        if (p.dense) CONV_REG(32, true, 0);
+        CONV_REG(32, false, 0);
+    } else if constexpr (R.fam == TF_F16) {
+        constexpr int DT = DT_IN16 | DT_RES16;
+        //                                            DENSE  PIPE SPECIAL EMU BSP    DT            PM     LEAN   POOL
+        if constexpr (R.id == kTilePoolF16) {
+            if (p.pool && (p.dt & DT_RES16)) CONV_GLDS(true, 1, false, 0, false, DT, false, false, true);      // fp16-rounded values averaged
+            if (p.pool) CONV_GLDS(true, 1, false, 0, false, DT_IN16, false, false, true);
         }
+        if (p.special && (p.dt & DT_OUT16)) CONV_GLDS(true, 1, true, 0, false, DT | DT_OUT16);
+        if (p.dense && (p.dt & DT_OUT16)) CONV_GLDS(true, 1, false, 0, false, DT | DT_OUT16);
+        if (p.dt & DT_OUT16) CONV_GLDS(false, 1, false, 0, false, DT | DT_OUT16);
+        if (p.special) CONV_GLDS(true, 1, true, 0, false, DT);
+        if (p.dense) CONV_GLDS(true, 1, false, 0, false, DT);
+        CONV_GLDS(false, 1, false, 0, false, DT);
+    } else {
+        constexpr int PIPE = family_pipe(R.fam), EMU = family_split(R.fam);
+        constexpr bool BSP = R.fam == TF_PRESPLIT;
+        //                                                       DENSE  PIPE  SPECIAL EMU  BSP  DT PM     LEAN  POOL
+        if constexpr (R.id == kTilePoolF32)
+            if (p.pool) CONV_GLDS(true, PIPE, false, EMU, BSP, 0, false, true, true);
+        if constexpr (has_pos_major_form(R)) {
+            if constexpr (has_lean_form(R))
+                if (p.pos_major && p.lean) CONV_GLDS(false, PIPE, false, EMU, BSP, 0, true, true);
+            if (p.pos_major) CONV_GLDS(false, PIPE, false, EMU, BSP, 0, true);
+        }
+        if constexpr (has_lean_form(R))         // a plain 1x1, or a strided one as a row gather
+            if (p.lean && !p.special) CONV_GLDS(true, PIPE, false, EMU, BSP, 0, false, true);
+        if constexpr (has_lean_shift_form(R))   // conv1 with the fused temporal shift
+            if (p.lean && p.special) CONV_GLDS(true, PIPE, true, EMU, BSP, 0, false, true);
+        if (p.special) CONV_GLDS(true, PIPE, true, EMU, BSP);
+        if (p.dense) CONV_GLDS(true, PIPE, false, EMU, BSP);
+        CONV_GLDS(false, PIPE, false, EMU, BSP);
     }
-    if (dense && special)
-        hipLaunchKernelGGL((conv_gemm_glds_kernel<BM, BN, WGM, WGN, true, PIPE, true, EMU, BSP>), dim3(a.nblocks), dim3(64 * WGM * WGN), 0, s, a);
-    else if (dense)
-        hipLaunchKernelGGL((conv_gemm_glds_kernel<BM, BN, WGM, WGN, true, PIPE, false, EMU, BSP>), dim3(a.nblocks), dim3(64 * WGM * WGN), 0, s, a);
-    else
-        hipLaunchKernelGGL((conv_gemm_glds_kernel<BM, BN, WGM, WGN, false, PIPE, false, EMU, BSP>), dim3(a.nblocks), dim3(64 * WGM * WGN), 0, s, a);
+#undef CONV_REG
+#undef CONV_GLDS
+}
+
+template <int... I>
+int launch_rows(const ConvPlan& p, const ConvArgs& a, hipStream_t s, std::integer_sequence<int, I...>) {
+    int rc = -1;
+    (void)((p.row == I && ((rc = launch_row<I>(p, a, s)), true)) || ...);
+    return rc;
+}
+
+// Launches a plan on the kernel it names.  Returns the tile id or < 0.
+int launch_plan(const ConvPlan& p, hipStream_t s) {
+    return p.tile < 0 ? -1 : launch_rows(p, p.a, s, std::make_integer_sequence<int, kNumTiles>());
+}
+
+int launch_conv_pool(const ConvArgs& a, int hw, float* pool_out, int pool_ld, PoolKind kind, hipStream_t s) {
+    ConvPlan p = plan_conv_pool(a, hw, pool_out, pool_ld, kind);
+    if (p.tile < 0) return 0;
+    p.a.pool_hw = hw; p.a.pool_rows = (128 / hw) * hw; p.a.pool_out = pool_out; p.a.pool_ld = pool_ld;
+    launch_plan(p, s);
+    return 1;
 }
 
 }  // namespace
@@ -1838,215 +2058,65 @@ int adaf_pick_conv_tile(int M, int N, int K, int cus) {
     (void)K;
     int best = 1;
     double best_t = 1e300;
-    for (int t = 1; t <= ADAF_CONV_TILES; ++t) {
-        const long long blocks = (long long)((M + kTiles[t].bm - 1) / kTiles[t].bm) * ((N + kTiles[t].bn - 1) / kTiles[t].bn);
+    for (const TileRow& r : kTileTable) {
+        if (r.eff <= 0.f) continue;
+        const long long blocks = (long long)((M + r.bm - 1) / r.bm) * ((N + r.bn - 1) / r.bn);
         const long long rounds = (blocks + cus - 1) / cus;
-        const double cost = (double)rounds * kTiles[t].bm * kTiles[t].bn / kTiles[t].eff;
-        if (cost < best_t * 0.999) { best_t = cost; best = t; }
+        const double cost = (double)rounds * r.bm * r.bn / r.eff;
+        if (cost < best_t * 0.999) { best_t = cost; best = r.id; }
     }
-    return best;   // 1..4; the launcher upgrades it to the direct-to-LDS form (id + 20) when the shape allows
+    return best;   // a register-staged id; the planner moves it to the family it wants (family_tile_like)
 }
 
-bool adaf_conv_glds_ok(const ConvArgs& a) {
-    const bool dense = a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0;
-    if (dense) return a.K % 4 == 0;      // partial last slice is zero-filled
-    if (a.K % 32 || a.cin % 32 || a.KH * a.KW > 32) return false;
-    return true;
-}
+bool adaf_conv_tile_exists(int tile) { return tile == kTileAutoSplit || tile_index(tile) >= 0; }
 
-bool adaf_conv_tile_exists(int tile) {
-    switch (tile) {
-        case 1: case 2: case 3: case 4: case 5:
-        case 21: case 22: case 23: case 24: case 25: case 26:
-        case 31: case 32: case 33: case 34: case 38: case 39:
-        case 40: case 41: case 42: case 43: case 44: case 45: case 46:
-#ifdef ADAF_EXP_TILES      // 256 x 256 block tiles: experiments only (tools/exp/build_exp_tiles.sh), not in the product library
-        case 27: case 37: case 47:
-#endif
-        case 51: case 52: case 53: case 54:
-        case 61: case 62: case 63: case 64: case 65: case 66: case 67:
-        case 71: case 72: case 73: case 74:
-        case 81: case 82: case 83: case 84: case 88:      // fp16 operands (adaf_conv2d_bn_act_f16 only)
-        case 95:                                          // small-batch form on v_mfma_f32_16x16x4_f32 (conv_lat.hip)
-            return true;
-        default:
-            return false;
-    }
-}
+int adaf_launch_conv_gemm(const ConvArgs& a, int tile, int cus, hipStream_t s) { return launch_plan(plan_conv(a, tile, cus), s); }
 
-// fp16 operands (tile ids 81..84, 88): word-granular eligibility of the DMA kernel
-static bool conv_glds16_ok(const ConvArgs& a) {
-    if ((a.K & 1) || (a.cin & 1) || (a.ldx & 1)) return false;
-    const bool dense = a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0;
-    if (dense) return (a.K / 2) % 4 == 0;
-    return (a.K / 2) % 32 == 0 && (a.cin / 2) % 32 == 0 && a.KH * a.KW <= 32;
-}
-
-int adaf_launch_conv_gemm(const ConvArgs& a, int tile, int cus, hipStream_t s) {
-    if (a.in16) {
-        if (!conv_glds16_ok(a) || (a.res && !a.res16)) return -1;
-        const bool dense16 = a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0;
-        if (tile < 81 || tile > 88) {
-            tile = adaf_pick_conv_tile(a.M, a.N, a.K, cus) + 80;
-            const int pad64 = ((a.N + 63) / 64) * 64;
-            if ((pad64 - a.N) * 5 >= a.N && (long long)((a.M + 127) / 128) >= cus) tile = 88;
-        }
-        switch (tile) {
-            case 81: launch_glds16_dt<128, 128, 2, 2>(a, dense16, s); break;
-            case 82: launch_glds16_dt<128, 64, 2, 2>(a, dense16, s); break;
-            case 83: launch_glds16_dt<64, 64, 2, 2>(a, dense16, s); break;
-            case 84: launch_glds16_dt<64, 128, 2, 2>(a, dense16, s); break;
-            case 88: launch_glds16_dt<128, 32, 4, 1>(a, dense16, s); break;
-            default: return -1;
-        }
-        return tile;
-    }
-    if (a.out16) {   // fp32 operands, fp16 store (the 3x3 stem of the half-precision MobileNetV2): register-staged 128x64 tile
-        if (a.res) return -1;
-        ConvArgs b = a;
-        b.tiles_n = (b.N + 63) / 64;
-        b.nblocks = ((b.M + 127) / 128) * b.tiles_n;
-        const bool dense = a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0;
-        if (dense) hipLaunchKernelGGL((conv_gemm_kernel<128, 64, 2, 2, 32, true, 0, 1>), dim3(b.nblocks), dim3(256), 0, s, b);
-        else hipLaunchKernelGGL((conv_gemm_kernel<128, 64, 2, 2, 32, false, 0, 1>), dim3(b.nblocks), dim3(256), 0, s, b);
-        return 2;
-    }
-    if (tile == 95) return adaf_launch_conv_lat(a, s) ? 95 : -1;     // the small-batch form (conv_lat.hip; bit-identical)
-    const bool bsp_ok = a.wsp != nullptr && (a.K & 31) == 0 && adaf_conv_glds_ok(a);
-    if (tile == 40) {   // split tiles, automatic: the bigger the wave tile the fewer split instructions per product
-        tile = 0;
-        if (adaf_conv_glds_ok(a)) {
-            const long long blocks = (long long)((a.M + 127) / 128) * ((a.N + 127) / 128);
-            if (a.N <= 64) tile = 42;
-            else if (blocks * 2 >= cus) tile = 41;
-            else tile = adaf_pick_conv_tile(a.M, a.N, a.K, cus) + 40;   // tiny problems: fill the CUs first
-            if (bsp_ok) tile = tile == 41 ? 65 : tile + 20;   // weights pre-split: waves of 32x128 split the fewest activations per product
-        }
-    }
-    if (tile > 60 && tile < 70 && !bsp_ok) tile = tile >= 65 ? 41 : tile - 20;
-    if (tile <= 0) {
-        tile = adaf_pick_conv_tile(a.M, a.N, a.K, cus);
-        if (adaf_conv_glds_ok(a)) {
-            tile += 30;   // direct-to-LDS, DMA issued between MFMA groups
-            // 32-wide column tiles when 64-wide ones would spend >= 20 % of the MFMA columns on padding (cout = 16, 24, 32,
-            // 96, 160: MobileNetV2's project convs) and there are enough row tiles to fill the device
-            const int pad64 = ((a.N + 63) / 64) * 64;
-            if ((pad64 - a.N) * 5 >= a.N && (long long)((a.M + 127) / 128) >= cus) tile = 38;
-            // the same padding with fewer rows but a long reduction (MobileNetV2's 960 -> 160 project convs on 7x7 maps: 25 k rows):
-            // waves of 64 x 32 under 256-row tiles -- 65 instead of 83 us per 512 frames (tools/tail_gemm_tiles.py)
-            else if ((pad64 - a.N) * 5 >= a.N && a.K >= 512 && (long long)((a.M + 255) / 256) * ((a.N + 31) / 32) >= cus) tile = 39;
-        }
-    }
-    const bool dense = a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0;
-    if (tile > 70 && !adaf_conv_glds_ok(a)) tile -= 70;
-    if (tile > 40 && !adaf_conv_glds_ok(a)) tile = tile % 10 <= 5 ? tile % 10 : 1;   // split tiles exist only in the DMA form
-    if (tile > 30 && !adaf_conv_glds_ok(a)) tile -= 10;
-    if (tile > 20 && !adaf_conv_glds_ok(a)) tile = tile - 20 <= 5 ? tile - 20 : 1;   // shape not eligible for the DMA kernel
-    switch (tile) {
-        case 1: launch_cfg<128, 128, 2, 2, 32, 0>(a, dense, s); break;
-        case 2: launch_cfg<128, 64, 2, 2, 32, 0>(a, dense, s); break;
-        case 3: launch_cfg<64, 64, 2, 2, 32, 0>(a, dense, s); break;
-        case 4: launch_cfg<64, 128, 2, 2, 32, 0>(a, dense, s); break;
-        case 5: launch_cfg<256, 128, 4, 2, 32, 0>(a, dense, s); break;   // 8 waves, 1 block/CU
-        case 21: launch_glds<128, 128, 2, 2, false>(a, dense, s); break;
-        case 22: launch_glds<128, 64, 2, 2, false>(a, dense, s); break;
-        case 23: launch_glds<64, 64, 2, 2, false>(a, dense, s); break;
-        case 24: launch_glds<64, 128, 2, 2, false>(a, dense, s); break;
-        case 25: launch_glds<256, 128, 4, 2, false>(a, dense, s); break;        // 8 waves of 64x64
-        case 26: launch_glds<256, 128, 2, 2, false>(a, dense, s); break;        // 4 waves of 128x64
-#ifdef ADAF_EXP_TILES
-        case 27: launch_glds<256, 256, 2, 4, false>(a, dense, s); break;        // 8 waves of 128x64
-#endif
-        case 31: launch_glds<128, 128, 2, 2, true>(a, dense, s); break;   // 3x = 2x with the DMA issued between MFMA groups
-        case 32: launch_glds<128, 64, 2, 2, true>(a, dense, s); break;
-        case 33: launch_glds<64, 64, 2, 2, true>(a, dense, s); break;
-        case 34: launch_glds<64, 128, 2, 2, true>(a, dense, s); break;
-#ifdef ADAF_EXP_TILES
-        case 37: launch_glds<256, 256, 2, 4, true>(a, dense, s); break;
-#endif
-        case 38: launch_glds<128, 32, 4, 1, true>(a, dense, s); break;    // narrow outputs (cout <= 32): four waves of 32x32
-        case 39: launch_glds<256, 32, 4, 1, true>(a, dense, s); break;    // narrow outputs: four waves of 64x32
-        // 7x: fp32 pipe with the barrier between steps 2 and 3 of a slice (next slice's first fragments prefetched)
-        case 71: launch_glds<128, 128, 2, 2, 2>(a, dense, s); break;
-        case 72: launch_glds<128, 64, 2, 2, 2>(a, dense, s); break;
-        case 73: launch_glds<64, 64, 2, 2, 2>(a, dense, s); break;
-        case 74: launch_glds<64, 128, 2, 2, 2>(a, dense, s); break;
-        // 4x / 5x: fp32 operands split into bf16 parts on the bf16 matrix pipe (6 / 9 products per element pair); opt-in
-        case 41: launch_glds<128, 128, 2, 2, true, 6>(a, dense, s); break;
-        case 42: launch_glds<128, 64, 2, 2, true, 6>(a, dense, s); break;
-        case 43: launch_glds<64, 64, 2, 2, true, 6>(a, dense, s); break;
-        case 44: launch_glds<64, 128, 2, 2, true, 6>(a, dense, s); break;
-        case 45: launch_glds<256, 128, 4, 2, true, 6>(a, dense, s); break;        // 8 waves of 64x64
-        case 46: launch_glds<256, 128, 2, 2, true, 6>(a, dense, s); break;        // 4 waves of 128x64
-#ifdef ADAF_EXP_TILES
-        case 47: launch_glds<256, 256, 2, 4, true, 6>(a, dense, s); break;        // 8 waves of 128x64
-#endif
-        // 6x: split tiles with the weights pre-split at load time (ConvArgs::wsp)
-        case 61: launch_glds<128, 128, 2, 2, true, 6, true>(a, dense, s); break;
-        case 62: launch_glds<128, 64, 2, 2, true, 6, true>(a, dense, s); break;
-        case 63: launch_glds<64, 64, 2, 2, true, 6, true>(a, dense, s); break;
-        case 64: launch_glds<64, 128, 2, 2, true, 6, true>(a, dense, s); break;
-        case 65: launch_glds<128, 128, 4, 1, true, 6, true>(a, dense, s); break;   // waves of 32x128: fewest activation splits per product
-        case 66: launch_glds<256, 128, 8, 1, true, 6, true>(a, dense, s); break;   // 8 waves of 32x128: 30 % less L2->LDS traffic per product
-        case 67: launch_glds<256, 128, 4, 2, true, 6, true>(a, dense, s); break;   // 8 waves of 64x64
-        case 51: launch_glds<128, 128, 2, 2, true, 9>(a, dense, s); break;
-        case 52: launch_glds<128, 64, 2, 2, true, 9>(a, dense, s); break;
-        case 53: launch_glds<64, 64, 2, 2, true, 9>(a, dense, s); break;
-        case 54: launch_glds<64, 128, 2, 2, true, 9>(a, dense, s); break;
-        default: return -1;
-    }
-    return tile;
-}
-
-// The trunk's last conv3 with the global average pool in its epilogue (conv_epilogue_pool): 1x1 / stride 1 fp32, images of `hw`
-// pixels that fill a 128-row tile to >= 90 % (hw = 9 at 96^2 patches: 14 images = 126 rows; 16 at 128^2; 25 at 144^2).
+// The trunk's last conv3 with the global average pool in its epilogue (conv_epilogue_pool): 1x1 / stride 1 fp32.  1 = launched, 0 = not eligible.
 int adaf_launch_conv_pool(ConvArgs a, int hw, float* pool_out, int pool_ld, hipStream_t s) {
-    const int on = adaf_options().conv_pool;      // 0 = conv + separate avgpool_kernel (A/B)
-    if (!on || !conv_lean_enabled() || conv_lean_enabled() != 1) return 0;
-    if (a.in16 || a.out16 || a.res16 || a.split_n || a.tsm_T > 0 || a.wsp) return 0;
-    if (a.KH != 1 || a.KW != 1 || a.stride != 1 || a.pad != 0 || (a.K & 31) || (a.N & 3) || !a.vec_epi) return 0;
-    if (hw <= 0 || hw > 128 || a.M % hw || (128 / hw) * hw * 10 < 128 * 9 || (pool_ld & 3) || (reinterpret_cast<size_t>(pool_out) & 15)) return 0;
-    if (a.act != ADAF_ACT_NONE && a.act != ADAF_ACT_RELU && a.act != ADAF_ACT_RELU6) return 0;
-    if ((size_t)a.M * a.ldx * 4 >= 0xffffff00ull || (size_t)a.N * a.K * 4 >= 0xffffff00ull) return 0;
-    a.pool_hw = hw; a.pool_rows = (128 / hw) * hw; a.pool_out = pool_out; a.pool_ld = pool_ld;
-    a.vec_epi = 2;
-    a.tiles_n = (a.N + 63) / 64;
-    a.nblocks = ((a.M + a.pool_rows - 1) / a.pool_rows) * a.tiles_n;
-    hipLaunchKernelGGL((conv_gemm_glds_kernel<128, 64, 2, 2, true, 1, false, 0, false, 0, false, true, true>), dim3(a.nblocks), dim3(256), 0, s, a);
-    return 1;
+    return launch_conv_pool(a, hw, pool_out, pool_ld, POOL_F32, s);
 }
 
 // The same for fp16 operands and fp32 features (EfficientNet's head conv 1x1 + BN + swish + global average pool, effnet.hip): the 128 x 64
-// tile of launch_glds16 -- the tile the unfused head conv runs on, same MFMA instruction and k order -- with whole images per tile and
-// conv_epilogue_pool<SIG>.  `a` arrives in ELEMENT units like adaf_launch_conv_gemm's fp16 launches.  1 = launched, 0 = not eligible.
+// fp16 tile -- the tile the unfused head conv runs on, same MFMA instruction and k order -- with whole images per tile and
+// conv_epilogue_pool<SIG>.  `a` arrives in ELEMENT units like adaf_launch_conv_gemm's fp16 launches.
 int adaf_launch_conv_pool16(ConvArgs a, int hw, float* pool_out, int pool_ld, hipStream_t s) {
-    if (!adaf_options().conv_pool) return 0;
-    if (!a.in16 || a.out16 || a.res || a.split_n || a.tsm_T > 0 || a.wsp || !conv_glds16_ok(a)) return 0;
-    if (a.KH != 1 || a.KW != 1 || a.stride != 1 || a.pad != 0 || (a.K & 63) || (a.N & 3) || !a.vec_epi) return 0;
-    if (hw <= 0 || hw > 128 || a.M % hw || (128 / hw) * hw * 10 < 128 * 9 || (pool_ld & 3) || (reinterpret_cast<size_t>(pool_out) & 15)) return 0;
-    a.pool_hw = hw; a.pool_rows = (128 / hw) * hw; a.pool_out = pool_out; a.pool_ld = pool_ld;
-    a.tiles_n = (a.N + 63) / 64;
-    a.nblocks = ((a.M + a.pool_rows - 1) / a.pool_rows) * a.tiles_n;
-    a.K /= 2; a.cin /= 2; a.ldx /= 2;
-    hipLaunchKernelGGL((conv_gemm_glds_kernel<128, 64, 2, 2, true, 1, false, 0, false, 4, false, false, true>), dim3(a.nblocks), dim3(256), 0, s, a);
-    return 1;
+    return launch_conv_pool(a, hw, pool_out, pool_ld, POOL_F16, s);
 }
 
 // The fp16 ResNet trunk's last conv3 (ADAF_MATH_F16): 1x1 fp16 operands, fp16 identity, ReLU, global average pool of the fp16-ROUNDED
 // activated values (conv_epilogue_pool RND).  Every fp16 tile shape walks k in the same order per output, so this 128 x 64 tile gives the
-// bits of whichever tile the unfused conv takes; with the rounding and the pixel-order sum the features are those of conv + pool.  1 = launched.
+// bits of whichever tile the unfused conv takes; with the rounding and the pixel-order sum the features are those of conv + pool.
 int adaf_launch_conv_pool16_rounded(ConvArgs a, int hw, float* pool_out, int pool_ld, hipStream_t s) {
-    if (!adaf_options().conv_pool) return 0;
-    if (!a.in16 || a.out16 || (a.res && !a.res16) || a.split_n || a.tsm_T > 0 || a.wsp || !conv_glds16_ok(a)) return 0;
-    if (a.KH != 1 || a.KW != 1 || a.stride != 1 || a.pad != 0 || (a.K & 63) || (a.N & 3) || (a.ldr & 3) || !a.vec_epi) return 0;
-    if (a.act != ADAF_ACT_NONE && a.act != ADAF_ACT_RELU && a.act != ADAF_ACT_RELU6) return 0;
-    if (hw <= 0 || hw > 128 || a.M % hw || (128 / hw) * hw * 10 < 128 * 9 || (pool_ld & 3) || (reinterpret_cast<size_t>(pool_out) & 15)) return 0;
-    a.pool_hw = hw; a.pool_rows = (128 / hw) * hw; a.pool_out = pool_out; a.pool_ld = pool_ld;
-    a.tiles_n = (a.N + 63) / 64;
-    a.nblocks = ((a.M + a.pool_rows - 1) / a.pool_rows) * a.tiles_n;
-    a.K /= 2; a.cin /= 2; a.ldx /= 2;
-    hipLaunchKernelGGL((conv_gemm_glds_kernel<128, 64, 2, 2, true, 1, false, 0, false, 6, false, false, true>), dim3(a.nblocks), dim3(256), 0, s, a);
-    return 1;
+    return launch_conv_pool(a, hw, pool_out, pool_ld, POOL_F16_ROUNDED, s);
+}
+
+// Debug hook (not in include/adafocus.h): the plan of a conv, without a device.  `flags` carries what the params do not: ADAF_PLAN_* bits
+// below, pm_allow in bits 4-5, the pooled epilogue's pixels per image in bits 8 and up (0 = the plain conv).  Fills up to `n` ints of `out` in
+// the order of kPlanFields (tests/test_conv_plan_host.py, tools/conv_launch_digest.py name them) and returns 0, or the code with which the
+// C ABI's own validation (adaf_make_conv_args, adaf_set_conv_dtypes) refuses the conv before it plans.
+extern "C" int adaf_conv_plan_debug(const adaf_conv_params* p, int flags, int cus, int* out, int n) {
+    enum { IN16 = 1, OUT16 = 2, RES16 = 4, PRESPLIT = 8, VEC_EPI = 64 };
+    alignas(16) static const float operand[4] = {0.f, 0.f, 0.f, 0.f};      // stands for every operand: the planner looks at no operand's contents
+    alignas(16) static float result[4];
+    if (!out || cus <= 0) return ADAF_E_BADARG;
+    adaf_handle host;       // no device behind it: the validation reads its defaults and leaves its message there
+    ConvArgs a;
+    int rc = adaf_make_conv_args(&host, p, operand, operand, nullptr, nullptr, (flags & RES16) ? operand : nullptr, result, &a);
+    if (!rc && (flags & (IN16 | OUT16 | RES16))) rc = adaf_set_conv_dtypes(&host, (flags & IN16) != 0, (flags & OUT16) != 0, &a);
+    if (rc) return rc;
+    if (flags & PRESPLIT) a.wsp = reinterpret_cast<const unsigned short*>(operand);
+    a.pm_allow = (flags >> 4) & 3;
+    a.vec_epi = a.vec_epi && (flags & VEC_EPI);
+    const int hw = flags >> 8;
+    const ConvPlan c = hw > 0 ? plan_conv_pool(a, hw, operand, p->cout, !a.in16 ? POOL_F32 : a.res16 ? POOL_F16_ROUNDED : POOL_F16)
+                              : plan_conv(a, p->tile, cus);
+    const TileRow r = c.row >= 0 ? kTileTable[c.row] : TileRow{0, 0, 0, 0, 0, TF_REG, 0, 0, 0.f};
+    const int kPlanFields[] = {c.tile, r.bm, r.bn, r.wgm, r.wgn, (int)r.fam, r.fallback, family_pipe(r.fam), family_split(r.fam),
+                               r.fam == TF_PRESPLIT, c.dt, c.dense, c.gather, c.special, c.lean, c.pos_major, c.pool, c.a.tiles_n, c.a.nblocks,
+                               c.a.pm_images, c.a.pm_groups, c.a.vec_epi, c.a.K, c.a.cin, c.a.ldx, c.a.tsm_fold};
+    for (int i = 0; i < n && i < (int)(sizeof(kPlanFields) / sizeof(int)); ++i) out[i] = kPlanFields[i];
+    return ADAF_OK;
 }
 
 void adaf_launch_conv_naive(const ConvArgs& a, hipStream_t s) {
@@ -2063,7 +2133,7 @@ static bool fused_tail_pm(const ConvArgs& c2, int n3, int ldr, int* images_out, 
     *images_out = images;
     *groups_out = groups;
     // (with a group stride below 128 the idle rows count as padding too: up to 8 %)
-    return c2.pm_allow == 1 && conv_lean_enabled() != 0 && images * ohw == c2.M && images >= 128 && ohw <= 4096 &&
+    return c2.pm_allow == 1 && images * ohw == c2.M && images >= 128 && ohw <= 4096 &&
            (long long)groups * 128 * 100 <= (long long)images * (gstride == 128 ? 106 : 108) && (size_t)ohw * 8 * (size_t)(n3 > ldr ? n3 : ldr) * 4 < 0xffffff00ull;
 }
 
@@ -2090,7 +2160,7 @@ int adaf_launch_fused_tail(const ConvArgs& c2, const float* w3, const float* s3,
     fa.c2 = c2;
     fa.c2.tiles_n = 1;
     fa.c2.nblocks = (c2.M + 127) / 128;
-    fa.c2.vec_epi = conv_lean_enabled() == 1 ? 2 : 1;       // the next block's conv1 tile goes out through the lean epilogue
+    fa.c2.vec_epi = 2;       // the next block's conv1 tile goes out through the lean epilogue
     fa.w3 = w3; fa.s3 = s3; fa.b3 = b3; fa.res = res; fa.out = out; fa.n3 = n3; fa.ldr = ldr;
     fa.w1n = w1n; fa.s1n = s1n; fa.b1n = b1n; fa.out1 = out1; fa.act1n = ADAF_ACT_RELU;
     const int ohw = c2.OH * c2.OW;
