@@ -551,6 +551,7 @@ int adaf_gru_seq_forward_f32(adaf_handle* h, const float* x, int ldx, int batch,
     if (feat % 4 || hidden % 4 || ldx % 4) return adaf_fail(h, ADAF_E_LAYOUT, "gru_seq: feat, hidden, ldx must be multiples of 4");
     if (h0 && !adaf_aligned16(h0)) return adaf_fail(h, ADAF_E_LAYOUT, "gru_seq: h0 must be 16-byte aligned");
     if (ws_bytes < adaf_gru_cls_workspace_bytes(batch, steps, hidden)) return adaf_fail(h, ADAF_E_NOMEM, "gru_seq: workspace too small");
+    if (!adaf_aligned16(ws)) return adaf_fail(h, ADAF_E_LAYOUT, "gru_seq: the workspace must be 16-byte aligned");
     float* gi = static_cast<float*>(ws);
     float* gh = gi + (size_t)batch * steps * 3 * hidden;
     int rc = gru_scan(h, x, ldx, batch, steps, feat, hidden, w_ih, w_hh, b_ih, b_hh, h0, gi, gh, hs, nullptr, nullptr, 0, nullptr,
@@ -572,6 +573,7 @@ int adaf_gru_cls_forward_f32(adaf_handle* h, const float* x, int ldx, int batch,
     if (ldx == 0) ldx = feat;
     if (feat % 4 || hidden % 4 || ldx % 4) return adaf_fail(h, ADAF_E_LAYOUT, "gru_cls: feat, hidden, ldx must be multiples of 4");
     if (ws_bytes < adaf_gru_cls_workspace_bytes(batch, steps, hidden)) return adaf_fail(h, ADAF_E_NOMEM, "gru_cls: workspace too small");
+    if (!adaf_aligned16(ws)) return adaf_fail(h, ADAF_E_LAYOUT, "gru_cls: the workspace must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     float* gi = static_cast<float*>(ws);
     float* gh = gi + (size_t)batch * steps * 3 * hidden;
@@ -602,6 +604,7 @@ int adaf_gru_cls_train_forward_f32(adaf_handle* h, const float* x, int ldx, int 
     if (ldx == 0) ldx = feat;
     if (feat % 4 || hidden % 16 || ldx % 4) return adaf_fail(h, ADAF_E_LAYOUT, "gru_cls_train: feat %% 4, hidden %% 16, ldx %% 4 must be 0");
     if (ws_bytes < adaf_gru_cls_train_workspace_bytes(batch, steps, hidden)) return adaf_fail(h, ADAF_E_NOMEM, "gru_cls_train: workspace too small");
+    if (!adaf_aligned16(ws)) return adaf_fail(h, ADAF_E_LAYOUT, "gru_cls_train: the workspace must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     float* gh = static_cast<float*>(ws);
     float* hd = gh + (size_t)batch * 3 * hidden;
@@ -640,6 +643,7 @@ int adaf_gru_cls_backward_f32(adaf_handle* h, const float* x, int ldx, int batch
     if (ldx == 0) ldx = feat;
     if (feat % 4 || hidden % 16 || ldx % 4 || ldx < feat) return adaf_fail(h, ADAF_E_LAYOUT, "gru_cls_backward: feat %% 4, hidden %% 16, ldx %% 4 must be 0");
     if (ws_bytes < adaf_gru_cls_backward_workspace_bytes(batch, steps, hidden, classes)) return adaf_fail(h, ADAF_E_NOMEM, "gru_cls_backward: workspace too small");
+    if (!adaf_aligned16(ws)) return adaf_fail(h, ADAF_E_LAYOUT, "gru_cls_backward: the workspace must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     const int rows = batch * steps, h3 = 3 * hidden;
     float* hd = static_cast<float*>(ws);
@@ -697,6 +701,7 @@ int adaf_fc_meanpool_forward_f32(adaf_handle* h, const float* feat, int batch, i
         return adaf_fail(h, ADAF_E_BADARG, "fc_meanpool: non-positive extent");
     if (feat_dim % 4) return adaf_fail(h, ADAF_E_LAYOUT, "fc_meanpool: feat_dim %% 4");
     if (ws_bytes < (size_t)batch * steps * classes * sizeof(float)) return adaf_fail(h, ADAF_E_NOMEM, "fc_meanpool: workspace too small");
+    if (!adaf_aligned16(ws)) return adaf_fail(h, ADAF_E_LAYOUT, "fc_meanpool: the workspace must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     float* logit = static_cast<float*>(ws);
     int rc = linear_launch(h, feat, batch * steps, feat_dim, feat_dim, classes, fc_w, fc_b, logit, 0, st);

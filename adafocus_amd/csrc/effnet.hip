@@ -2244,6 +2244,7 @@ int adaf_effnet_forward(adaf_effnet* net, const float* frames_nhwc4, int n, int 
     if (pad_size <= 0) pad_size = size;
     if (featvec && ldvec < net->feat) return efail(h, ADAF_E_LAYOUT, "effnet: ldvec >= %d required", net->feat);
     if (upto_block >= 0 && !block_out) return efail(h, ADAF_E_BADARG, "effnet: upto_block needs block_out");
+    if (!adaf_aligned16(ws)) return efail(h, ADAF_E_LAYOUT, "effnet: the workspace must be 16-byte aligned");
     if (ws_bytes < adaf_effnet_workspace_bytes(net, n, size, pad_size)) return efail(h, ADAF_E_NOMEM, "effnet: workspace too small");
     hipStream_t st = (hipStream_t)stream;
     const bool f16 = net->dtype == ADAF_DTYPE_F16;
@@ -2391,6 +2392,7 @@ int adaf_pack_dw_weight_kxk_f32(adaf_handle* h, const float* w_c1kk, int channel
 }
 
 size_t adaf_dwconv_same_workspace_bytes(int n, int hh, int ww, int c, int k, int stride, int dtype) {
+    if (n <= 0 || hh <= 0 || ww <= 0 || c <= 0 || stride <= 0) return 0;
     const int oh = ceil_div(hh, stride), ow = ceil_div(ww, stride);
     const int tiles = adaf_effnet_dw_tiles(c, oh, ow, k, stride, dtype);
     // (at least one partial per (image, channel): the tiny-map kernel writes n * c sums whatever the tile planner says -- ADVICE r3)
@@ -2411,6 +2413,7 @@ int adaf_dwconv_same_bn_act(adaf_handle* h, const void* x, int dtype, int n, int
     const int oh = ceil_div(hh, stride), ow = ceil_div(ww, stride);
     float* part = nullptr;
     if (pool_mean) {
+        if (ws && !adaf_aligned16(ws)) return efail(h, ADAF_E_LAYOUT, "dwconv_same: the workspace must be 16-byte aligned");
         if (!ws || ws_bytes < adaf_dwconv_same_workspace_bytes(n, hh, ww, c, k, stride, dtype)) return efail(h, ADAF_E_NOMEM, "dwconv_same: workspace");
         part = static_cast<float*>(ws);
     }

@@ -241,6 +241,7 @@ int adaf_mobilenetv2_forward(adaf_mobilenetv2* net, const float* frames_nhwc4, i
     if (n <= 0 || size < 32) return mfail(h, ADAF_E_BADARG, "mobilenetv2: need n > 0 and size >= 32");
     if (tsm_segments > 0 && (n % tsm_segments || tsm_div <= 0)) return mfail(h, ADAF_E_BADARG, "mobilenetv2: n %% tsm_segments != 0");
     if (featvec && (ldvec < 1280 || ldvec % 4)) return mfail(h, ADAF_E_LAYOUT, "mobilenetv2: ldvec >= 1280 and %% 4 == 0 required");
+    if (!adaf_aligned16(ws)) return mfail(h, ADAF_E_LAYOUT, "mobilenetv2: the workspace must be 16-byte aligned");
     if (ws_bytes < adaf_mobilenetv2_workspace_bytes(net, n, size, tsm_segments)) return mfail(h, ADAF_E_NOMEM, "mobilenetv2: workspace too small");
     hipStream_t st = (hipStream_t)stream;
     size_t io, ex, dws;

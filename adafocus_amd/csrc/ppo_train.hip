@@ -395,6 +395,7 @@ int adaf_ppo_head_f32(adaf_handle* h, const float* head, int head_batch_major, i
     if (loss_mode && grad_mode) return adaf_fail(h, ADAF_E_BADARG, "ppo_head: either the PPO loss or upstream gradients");
     if (grad_mode && !dhead_out) return adaf_fail(h, ADAF_E_BADARG, "ppo_head: upstream gradients without dhead_out");
     if (loss_mode && ws_bytes < adaf_ppo_head_workspace_bytes(steps, batch)) return adaf_fail(h, ADAF_E_NOMEM, "ppo_head: workspace too small");
+    if (loss_mode && !adaf_aligned16(ws)) return adaf_fail(h, ADAF_E_LAYOUT, "ppo_head: the workspace must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     HeadArgs a;
     a.head = head; a.action = reinterpret_cast<const long long*>(actions); a.old_logprob = old_logprobs; a.returns = returns;

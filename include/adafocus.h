@@ -18,7 +18,18 @@
  *   - all functions return ADAF_OK (0) or a negative ADAF_E_* code; the message is available
  *     from adaf_last_error(); a handle is not thread-safe (one per device per process, like the
  *     reference's one Python thread per rank);
- *   - activations are fp32 NHWC ("pixel-major"): element (n,y,x,c) at ((n*H+y)*W+x)*ld + c.
+ *   - activations are fp32 NHWC ("pixel-major"): element (n,y,x,c) at ((n*H+y)*W+x)*ld + c;
+ *   - workspaces (`ws`, `ws_bytes`): caller-owned scratch memory.  EXACTLY the bytes the entry point's *_workspace_bytes query returns
+ *     suffice (no slack is assumed behind them, nothing in front of `ws` is touched); fewer bytes are refused with ADAF_E_NOMEM before
+ *     anything is launched.  `ws` must be 16-byte aligned in every entry point that takes one: anything less is ADAF_E_LAYOUT.  The three
+ *     networks, adaf_dwconv_same_bn_act and the two PPO gradients need it (16-byte loads and stores on slabs carved at multiples of 16
+ *     bytes); for the GRU calls, adaf_fc_meanpool_forward_f32 and adaf_ppo_head_f32 it is one uniform rule, not an established need of
+ *     their kernels (the second half of adaf_ppo_head_f32's 2 * T * B floats starts wherever T * B puts it).  The contents are UNDEFINED on entry and on exit: a call is designed to write
+ *     every word before it reads it (synchronisation words included: the persistent GRU scans clear their own barrier words), leaves
+ *     nothing there for a later call, and the caller may hand the same workspace to any other entry point next (stream order permitting).
+ *     tests/test_workspace_contract_gpu.py checks this for the words that feed the arithmetic (NaN, zero and stale prefills give the
+ *     same bits); a barrier word left uncleared is a race, which no prefill exposes reliably (LABNOTES 3.12).  A query returns 0 for a
+ *     non-positive extent, and the call with such an extent is refused with ADAF_E_BADARG.
  */
 #ifndef ADAFOCUS_H
 #define ADAFOCUS_H
@@ -404,7 +415,7 @@ int adaf_mobilenetv2_set_fusion(adaf_mobilenetv2* net, int on);
  *                             hand) + BN affine + activation; x, out [n,h,w,c] / [n,ceil(h/s),ceil(w/s),c] NHWC,
  *                             w_kkc [k*k][c] (adaf_pack_dw_weight_kxk_f32 from PyTorch's [c,1,k,k]); optionally the
  *                             squeeze pool_mean [n,c] = mean over the output pixels (fp32, summed in a fixed order;
- *                             needs ws of adaf_dwconv_same_workspace_bytes)
+ *                             needs ws of adaf_dwconv_same_workspace_bytes: 0 for a non-positive extent; 16-byte aligned)
  *   adaf_se_gate_f32          gate[n,c] = sigmoid(W_e swish(W_r pool_mean[n] + b_r) + b_e); W_r [squeezed,c], W_e [c,squeezed]
  *                             (_se_reduce / _se_expand weights in PyTorch layout)
  *   adaf_conv1x1_gated_bn     out[m,co] = (sum_k x[m,k] gate[m / hw, k] w[co,k]) * scale[co] + bias[co] (+ residual[m,co]):
@@ -578,7 +589,7 @@ int adaf_ppo_encoder_backward_f32(adaf_handle* h, const float* states, const flo
 /* ---- a8: linear classifier + temporal mean ---------------------------------------------
  * nn.Linear + ConsensusModule('avg') (+ glancer mean logits) -- STH/models/gfv_net.py:164-174,
  * STH/ops/basic_ops.py:17-26.  feat [B*T, F]; global_logit [B, Tg, C] or NULL; out [B, C];
- * ws holds B*T*C floats. */
+ * ws holds B*T*C floats (16-byte aligned; there is no query: ws_bytes >= B*T*C*4, less is ADAF_E_NOMEM). */
 int adaf_fc_meanpool_forward_f32(adaf_handle* h, const float* feat, int batch, int steps, int feat_dim, int classes,
                                  const float* fc_w, const float* fc_b, const float* global_logit, int global_steps,
                                  float* out, void* ws, size_t ws_bytes, void* stream);

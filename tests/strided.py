@@ -12,6 +12,8 @@ _G = load_tool("guard_bands")
 CANARY_F32, CANARY_F16 = _G.CANARY_F32, _G.CANARY_F16
 guarded, lead_for, fill, payload = _G.guarded, _G.lead_for, _G.fill, _G.payload
 find_guard_damage, assert_guards_intact, conv_call = _G.find_guard_damage, _G.assert_guards_intact, _G.conv_call
+guarded_workspace, workspace_damage, assert_workspace_intact = _G.guarded_workspace, _G.workspace_damage, _G.assert_workspace_intact
+is_all_canary, WS_GUARD_MIN = _G.is_all_canary, _G.WS_GUARD_MIN
 
 F16_STORE_REL = 2e-3         # one fp16 rounding of the stored value (tests/test_hip_parity_r2.py uses conv_f16_bound below)
 

@@ -151,3 +151,77 @@ def test_shared_bounds_are_the_existing_ones():
     ref = torch.tensor([0.5, -3.0])
     assert S.conv_f16_bound(torch.float32, ref) == 2e-4 and S.conv_f16_bound(torch.float16, ref) == 2e-3 * 3.0
     assert S.conv_f16_bound(torch.float16, ref * 0.1) == 2e-3
+
+
+# ---- guarded workspaces -------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("nbytes,offset", [(4, 0), (1000, 0), (1001, 0), (1003, 16), (4096, 4), (3 << 20, 64), ((3 << 20) + 2, 0)])
+def test_guarded_workspace_geometry(nbytes, offset):
+    buf, ws = S.guarded_workspace(nbytes, "cpu", offset_bytes=offset)
+    words = (nbytes + 3) // 4
+    guard = max(nbytes, 1 << 20)
+    assert S.WS_GUARD_MIN == 1 << 20
+    assert buf.dim() == 1 and buf.dtype == torch.float32 and ws.shape == (1, words) and ws.stride(1) == 1
+    assert ws.data_ptr() % 256 == offset                          # 256-byte aligned plus the offset
+    lead = ws.storage_offset() - buf.storage_offset()
+    assert 4 * lead >= guard and 4 * (buf.numel() - lead - words) >= guard         # both guards hold max(nbytes, 1 MiB) bytes
+    assert ws.data_ptr() == buf.data_ptr() + 4 * lead
+    assert S.is_all_canary(buf) and torch.isnan(ws).all()
+    S.assert_guards_intact(buf, ws)
+    S.assert_workspace_intact(buf, ws, nbytes=nbytes)
+    ws.fill_(2.0)                                                 # the whole payload may change, its last partial word included
+    S.assert_guards_intact(buf, ws)
+    assert S.workspace_damage(buf, ws, nbytes) is None and not S.is_all_canary(ws)
+
+
+def test_guarded_workspace_fills():
+    _, ws = S.guarded_workspace(40, "cpu", fill="zero")
+    assert torch.equal(ws, torch.zeros(1, 10))
+    stale = torch.arange(10, dtype=torch.float32) + 0.5
+    buf, ws = S.guarded_workspace(40, "cpu", fill=stale, offset_bytes=8)
+    assert torch.equal(ws.reshape(-1), stale)
+    S.assert_guards_intact(buf, ws)
+    stale_bits = torch.full((10,), S.CANARY_F32, dtype=torch.int64).to(torch.int32).view(torch.float32)      # bytes, not values: a NaN payload survives
+    _, ws = S.guarded_workspace(40, "cpu", fill=stale_bits)
+    assert S.is_all_canary(ws)
+    for bad in (dict(fill=torch.zeros(9)), dict(fill="ones"), dict(offset_bytes=2), dict(offset_bytes=-4)):
+        with pytest.raises(ValueError):
+            S.guarded_workspace(40, "cpu", **bad)
+    with pytest.raises(ValueError):
+        S.guarded_workspace(0, "cpu")
+
+
+@pytest.mark.parametrize("nbytes,offset", [(1000, 0), (1001, 0), (1002, 4), (8192, 16)])
+def test_guarded_workspace_damage_one_word_before_and_after(nbytes, offset):
+    words = (nbytes + 3) // 4
+    # one word in front of the start
+    buf, ws = S.guarded_workspace(nbytes, "cpu", fill="zero", offset_bytes=offset)
+    lead = ws.storage_offset()
+    buf[lead - 1] = 1.0
+    assert S.find_guard_damage(buf, ws) == (lead - 1, -1, words - 1, "lead")
+    assert "4 bytes in front of the workspace's start" in S.workspace_damage(buf, ws, nbytes)
+    with pytest.raises(AssertionError) as e:
+        S.assert_guards_intact(buf, ws, "ws")
+    assert "4 bytes in front of the payload's start" in str(e.value) and "lead" in str(e.value)
+    with pytest.raises(AssertionError) as e:
+        S.assert_workspace_intact(buf, ws, "gru ws", nbytes)
+    assert str(e.value).startswith("gru ws: ") and "4 bytes in front" in str(e.value)
+    # the first word behind the end: 0 bytes past the whole-word payload, (4 * words - nbytes) bytes past the byte count
+    buf, ws = S.guarded_workspace(nbytes, "cpu", fill="zero", offset_bytes=offset)
+    lead = ws.storage_offset()
+    buf[lead + words] = 1.0
+    assert S.find_guard_damage(buf, ws) == (lead + words, 1, 0, "trail")
+    assert "%d bytes past the workspace's end of %d bytes" % (4 * words - nbytes, nbytes) in S.workspace_damage(buf, ws, nbytes)
+    with pytest.raises(AssertionError) as e:
+        S.assert_guards_intact(buf, ws, "ws")
+    assert "0 bytes past the payload's end" in str(e.value) and "trail" in str(e.value)
+    # ... and far behind it: the last word of the allocation
+    buf, ws = S.guarded_workspace(nbytes, "cpu", offset_bytes=offset)
+    lead = ws.storage_offset()
+    buf[-1] = 0.0
+    far = 4 * (buf.numel() - 1 - lead) - nbytes
+    assert far >= (1 << 20) - 4 and "%d bytes past the workspace's end" % far in S.workspace_damage(buf, ws, nbytes)
+    # the first and the last payload word are not damage
+    buf, ws = S.guarded_workspace(nbytes, "cpu", offset_bytes=offset)
+    ws[0, 0], ws[0, -1] = 1.0, 2.0
+    S.assert_guards_intact(buf, ws)
+    assert S.workspace_damage(buf, ws, nbytes) is None

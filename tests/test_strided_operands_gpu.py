@@ -410,11 +410,17 @@ def test_bad_strides_are_refused_before_any_launch(dev):
             g.cls(g.x, ldx)
         with pytest.raises(AdafError):
             g.train(g.x, ldx)
+    torch.cuda.synchronize()
+    assert len(g._guarded) == 6 and all(S.is_all_canary(buf) for buf, _, _ in g._guarded)      # a refused call writes no workspace word
+    g._guarded = []
     fw = g.train(g.x, 8)
+    g.check_workspaces()
     with pytest.raises(AdafError):
         g.backward(g.x, 10, fw)
     with pytest.raises(AdafError):
         g.backward(g.x, 4, fw)                   # ldx < feat
+    torch.cuda.synchronize()
+    assert len(g._guarded) == 2 and all(S.is_all_canary(buf) for buf, _, _ in g._guarded)
 
 
 # ------------------------------------------------------------------------------------------------------------------ avgpool, copy2d
@@ -470,12 +476,22 @@ class _GruCase:
         self.x = self.x_cpu.to(dev)
         self.dlogits_cpu = rnd((batch * steps, classes), seed + 7, 0.1)
         self.dlogits = self.dlogits_cpu.to(dev)
+        self._guarded = []      # (buf, ws, nbytes) of every workspace handed out since the last check
 
     def _out(self, rows_shape, cols):
         return _empty(rows_shape, cols, 0, 0, self.dev)
 
     def _ws(self, nbytes):
-        return torch.empty(max(nbytes // 4, 1), device=self.dev, dtype=torch.float32), nbytes
+        """Exactly the queried bytes behind guard bands (tests/strided.py guarded_workspace); check_workspaces() looks at every one handed out."""
+        buf, ws = S.guarded_workspace(nbytes, self.dev)
+        self._guarded.append((buf, ws, nbytes))
+        return ws, nbytes
+
+    def check_workspaces(self):
+        torch.cuda.synchronize()
+        for buf, ws, nbytes in self._guarded:
+            S.assert_workspace_intact(buf, ws, "gru workspace of %d bytes" % nbytes, nbytes)
+        self._guarded = []
 
     def seq(self, x, ldx):
         p, (ws, nb) = self.p, self._ws(self.lib.adaf_gru_cls_workspace_bytes(self.b, self.t, self.hid))
@@ -572,6 +588,7 @@ def test_gru_entry_points_read_x_through_ldx(dev, ops):
         ops.set_gru_persistent(True, dev)
     assert torch.equal(xb.view(torch.int32), before)
     assert ops.gru_scan_timeouts(dev) == 0
+    g.check_workspaces()
 
 
 # ------------------------------------------------------------------------------------------------------------------ whole networks

@@ -77,23 +77,91 @@ def find_guard_damage(buf, view):
     rows, cols, ld, lead = _geometry(buf, view)
     bits = buf.view(_INT_OF[buf.dtype])
     canary = torch.tensor(_CANARY[buf.dtype], dtype=torch.int64).to(bits.dtype).item()
-    rel = torch.arange(bits.numel(), device=bits.device) - lead
-    in_payload = (rel >= 0) & (rel < rows * ld) & (rel.remainder(ld) < cols)
-    bad = (bits != canary) & ~in_payload
-    if not bool(bad.any()):
-        return None
-    off = int(torch.nonzero(bad)[0].item())
-    r, c = divmod(off - lead, ld)
-    region = "lead" if off < lead else "trail" if off >= lead + rows * ld else "gap"
-    return off, r, c, region
+    end = lead + rows * ld
+    # segment by segment (lead, the rows with their gaps, trail): no index tensor as long as the allocation (a workspace may hold 100 MB)
+    for lo, hi in ((0, lead), (lead, min(end, bits.numel())), (end, bits.numel())):
+        if hi <= lo or (lo == lead and ld == cols):
+            continue
+        bad = bits[lo:hi] != canary
+        if lo == lead:
+            bad &= (torch.arange(hi - lo, device=bits.device).remainder(ld) >= cols)
+        if bool(bad.any()):
+            off = lo + int(torch.nonzero(bad)[0].item())
+            r, c = divmod(off - lead, ld)
+            region = "lead" if off < lead else "trail" if off >= end else "gap"
+            return off, r, c, region
+    return None
 
 
 def assert_guards_intact(buf, view, what="buffer"):
     hit = find_guard_damage(buf, view)
     if hit is not None:
         rows, cols, ld, lead = _geometry(buf, view)
-        raise AssertionError("%s: guard damaged at flat offset %d = (row %d, column %d) in the %s (rows %d, cols %d, ld %d, lead %d)"
-                             % ((what,) + hit + (rows, cols, ld, lead)))
+        es, end = buf.element_size(), lead + (rows - 1) * ld + cols
+        where = ("%d bytes in front of the payload's start" % ((lead - hit[0]) * es) if hit[3] == "lead" else
+                 "%d bytes past the payload's end" % ((hit[0] - end) * es) if hit[3] == "trail" else "between two rows")
+        raise AssertionError("%s: guard damaged at flat offset %d = (row %d, column %d) in the %s, %s (rows %d, cols %d, ld %d, lead %d)"
+                             % ((what,) + hit + (where, rows, cols, ld, lead)))
+
+
+# ---- caller-owned workspaces ----------------------------------------------------------------------------------------------------------
+WS_GUARD_MIN = 1 << 20       # bytes of canary on either side of a workspace, at least
+
+
+def guarded_workspace(nbytes, device="cpu", fill="nan", offset_bytes=0):
+    """(buf, ws) for a workspace of exactly `nbytes` bytes (what a *_workspace_bytes query returned): ONE flat fp32 allocation, `ws` the
+    (1, ceil(nbytes / 4))-word payload as a one-row view that starts 256-byte aligned plus `offset_bytes` (a multiple of 4), with
+    max(nbytes, 1 MiB) bytes of canary in front of and behind it -- an overrun shorter than the workspace itself lands in memory the
+    caller owns.  `fill`: "nan" (the canary: a word that is read before it is written poisons the result), "zero", or a tensor whose
+    bytes are copied in (what an earlier call left in its workspace).  Check with find_guard_damage / assert_guards_intact /
+    workspace_damage."""
+    nbytes, offset_bytes = int(nbytes), int(offset_bytes)
+    if nbytes <= 0 or offset_bytes < 0 or offset_bytes % 4:
+        raise ValueError("guarded_workspace: nbytes > 0 and a non-negative offset_bytes that is a multiple of 4 required")
+    words = (nbytes + 3) // 4
+    guard = max(nbytes, WS_GUARD_MIN) // 4
+    # room to move the payload's start onto a 256-byte boundary whatever the allocation's own alignment
+    # (filled where it lives: a 100 MB workspace is not staged on the host; CANARY_F32 fits a signed 32-bit word)
+    bits = torch.full((guard + 64 + offset_bytes // 4 + words + guard,), CANARY_F32, dtype=torch.int32, device=device)
+    buf = bits.view(torch.float32)
+    lead = guard + (-(buf.data_ptr() + 4 * guard) % 256) // 4 + offset_bytes // 4
+    ws = buf.as_strided((1, words), (words, 1), lead)
+    if isinstance(fill, torch.Tensor):
+        src = fill.detach().contiguous().reshape(-1).view(torch.int32)
+        if src.numel() != words:
+            raise ValueError("guarded_workspace: the fill holds %d words, the workspace %d" % (src.numel(), words))
+        ws.view(torch.int32).copy_(src.reshape(1, words))
+    elif fill == "zero":
+        ws.zero_()
+    elif fill != "nan":
+        raise ValueError("guarded_workspace: fill is 'nan', 'zero' or a tensor")
+    return buf, ws
+
+
+def workspace_damage(buf, ws, nbytes=None):
+    """None, or a sentence that names the first damaged guard word by its byte offset in front of the workspace's start or past its end
+    (the end is `nbytes`, else the payload's whole words)."""
+    hit = find_guard_damage(buf, ws)
+    if hit is None:
+        return None
+    off, _, _, region = hit
+    lead = ws.storage_offset() - buf.storage_offset()
+    end = 4 * ws.shape[-1] if nbytes is None else int(nbytes)
+    if region == "lead":
+        return "guard word damaged %d bytes in front of the workspace's start (flat offset %d)" % (4 * (lead - off), off)
+    return "guard word damaged %d bytes past the workspace's end of %d bytes (flat offset %d)" % (4 * (off - lead) - end, end, off)
+
+
+def assert_workspace_intact(buf, ws, what="workspace", nbytes=None):
+    msg = workspace_damage(buf, ws, nbytes)
+    if msg is not None:
+        raise AssertionError("%s: %s" % (what, msg))
+
+
+def is_all_canary(t):
+    """Every fp32 word of `t` still holds the canary bits (nothing wrote it)."""
+    c = t.contiguous().view(torch.int32)
+    return bool((c == torch.tensor(CANARY_F32, dtype=torch.int64).to(torch.int32).item()).all())
 
 
 # ---- the C ABI with real strides -----------------------------------------------------------------------------------------------------
