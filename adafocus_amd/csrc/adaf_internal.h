@@ -83,6 +83,47 @@ struct AdafAuxPool {
     }
 };
 
+// Runs the frame chunks [f0, f0 + nc) of a batch of n through run_chunk(f0, nc, slot, stream) -> ADAF_* code, two at a time where
+// pairing is on and the batch has more than one chunk: chunk 2i on the caller's stream `st` in workspace slot 0, chunk 2i + 1 on the
+// pool's helper stream in slot 1 (forked from and joined to `st` by events); an odd last chunk alone on `st`.  Returns the first error.
+template <typename RunChunk>
+int adaf_run_chunk_pairs(AdafAuxPool& pool, hipStream_t st, int n, int chunk, bool pair, RunChunk run_chunk) {
+    AdafAuxPool::Aux* ax = (pair && n > chunk) ? pool.get(st) : nullptr;      // (no helper to be had: one chunk after the other)
+    for (int f0 = 0; f0 < n; f0 += chunk) {
+        const int nc = (n - f0) < chunk ? (n - f0) : chunk;
+        int rc;
+        if (ax && f0 + chunk < n) {
+            const int f1 = f0 + chunk;
+            const int nc1 = (n - f1) < chunk ? (n - f1) : chunk;
+            (void)hipEventRecord(ax->ev_fork, st);
+            (void)hipStreamWaitEvent(ax->stream, ax->ev_fork, 0);
+            rc = run_chunk(f0, nc, 0, st);
+            if (!rc) rc = run_chunk(f1, nc1, 1, ax->stream);
+            // ALWAYS join, also when a launch failed after the fork: whatever the helper stream still has queued writes the
+            // caller's workspace / outputs, and the caller may reuse them as soon as this call returns
+            (void)hipEventRecord(ax->ev_join, ax->stream);
+            (void)hipStreamWaitEvent(st, ax->ev_join, 0);
+            if (rc) return rc;
+            f0 = f1;
+        } else if ((rc = run_chunk(f0, nc, 0, st))) return rc;
+    }
+    return ADAF_OK;
+}
+
+// A workspace layout is written ONCE, as a function that walks this cursor over (base, offset): take<T>(count) hands out the next
+// region of `count` elements of T -- its bytes rounded up to `align` -- and advances.  With a null base it only measures: the
+// *_workspace_bytes query runs the layout function on nullptr and returns `off`, the call runs the same function on `ws`.
+struct AdafCarver {
+    char* base;
+    size_t off = 0;
+    explicit AdafCarver(void* ws) : base(static_cast<char*>(ws)) {}
+    template <typename T> T* take(size_t count, size_t align = sizeof(T)) {
+        T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+        off += (count * sizeof(T) + align - 1) / align * align;
+        return p;
+    }
+};
+
 // Process-wide tuning / A-B switches of the library (adaf_set_global_option / adaf_get_global_option in include/adafocus.h; defaults = the plan
 // every number in DESIGN.md is measured with).  They replace the environment variables of earlier rounds: tests flip them in-process.
 struct AdafOptions {
@@ -154,6 +195,11 @@ struct ConvArgs {
 int adaf_fail(adaf_handle* h, int code, const char* fmt, ...);       // stores the formatted message in the handle, returns `code`
 int adaf_hip_fail(adaf_handle* h, hipError_t e, const char* what);   // ADAF_E_LAUNCH with the runtime's error string
 bool adaf_aligned16(const void* p);
+// The workspace check of every entry point that takes one: ADAF_E_NOMEM when ws_bytes < need, ADAF_E_LAYOUT when `ws` is not 16-byte
+// aligned.  Which of the two a pointer that is BOTH short and misaligned gets differs between entry points and is part of their
+// behaviour, so the caller names the order.
+enum AdafWsOrder { ADAF_WS_SIZE_FIRST, ADAF_WS_ALIGN_FIRST };
+int adaf_check_ws(adaf_handle* h, const char* who, const void* ws, size_t ws_bytes, size_t need, AdafWsOrder order);
 int adaf_conv_out(int in, int k, int stride, int pad);
 // Validates a conv description and flattens it; returns ADAF_OK or an error code.
 int adaf_make_conv_args(adaf_handle* h, const adaf_conv_params* p, const float* x, const float* w, const float* scale,

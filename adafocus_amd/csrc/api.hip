@@ -22,6 +22,11 @@ int adaf_hip_fail(adaf_handle* h, hipError_t e, const char* what) {
 }
 
 bool adaf_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+int adaf_check_ws(adaf_handle* h, const char* who, const void* ws, size_t ws_bytes, size_t need, AdafWsOrder order) {
+    const bool small = ws_bytes < need, skew = !adaf_aligned16(ws);
+    if (small && (order == ADAF_WS_SIZE_FIRST || !skew)) return adaf_fail(h, ADAF_E_NOMEM, "%s: workspace %zu < %zu bytes", who, ws_bytes, need);
+    return skew ? adaf_fail(h, ADAF_E_LAYOUT, "%s: the workspace must be 16-byte aligned", who) : ADAF_OK;
+}
 int adaf_conv_out(int in, int k, int stride, int pad) { return (in + 2 * pad - k) / stride + 1; }
 
 // Validates a conv description and flattens it; returns ADAF_OK or an error code.
@@ -460,10 +465,17 @@ int adaf_copy2d_f32(adaf_handle* h, const float* src, int lds, float* dst, int l
 // ======================================================================================
 // GRU classifier / linear + temporal mean
 // ======================================================================================
+struct GruClsWs { float *gi, *gh, *hs; };      // gi [B*T, 3H], gh [B, 3H], hidden states [B, T, H] (adaf_gru_seq_forward_f32 has its own)
+static size_t gru_cls_layout(void* ws, int batch, int steps, int hidden, GruClsWs* r) {
+    AdafCarver c(ws);
+    r->gi = c.take<float>((size_t)batch * steps * 3 * hidden);
+    r->gh = c.take<float>((size_t)batch * 3 * hidden);
+    r->hs = c.take<float>((size_t)batch * steps * hidden);
+    return c.off;
+}
 size_t adaf_gru_cls_workspace_bytes(int batch, int steps, int hidden) {
-    if (batch <= 0 || steps <= 0 || hidden <= 0) return 0;
-    // gi [B*T, 3H] + gh [B, 3H] + hidden states [B, T, H]
-    return ((size_t)batch * steps * 3 * hidden + (size_t)batch * 3 * hidden + (size_t)batch * steps * hidden) * sizeof(float);
+    GruClsWs r;
+    return (batch <= 0 || steps <= 0 || hidden <= 0) ? 0 : gru_cls_layout(nullptr, batch, steps, hidden, &r);
 }
 
 static int linear_launch(adaf_handle* h, const float* x, int rows, int ldx, int in, int out_dim, const float* w,
@@ -550,12 +562,11 @@ int adaf_gru_seq_forward_f32(adaf_handle* h, const float* x, int ldx, int batch,
     if (ldx == 0) ldx = feat;
     if (feat % 4 || hidden % 4 || ldx % 4) return adaf_fail(h, ADAF_E_LAYOUT, "gru_seq: feat, hidden, ldx must be multiples of 4");
     if (h0 && !adaf_aligned16(h0)) return adaf_fail(h, ADAF_E_LAYOUT, "gru_seq: h0 must be 16-byte aligned");
-    if (ws_bytes < adaf_gru_cls_workspace_bytes(batch, steps, hidden)) return adaf_fail(h, ADAF_E_NOMEM, "gru_seq: workspace too small");
-    if (!adaf_aligned16(ws)) return adaf_fail(h, ADAF_E_LAYOUT, "gru_seq: the workspace must be 16-byte aligned");
-    float* gi = static_cast<float*>(ws);
-    float* gh = gi + (size_t)batch * steps * 3 * hidden;
-    int rc = gru_scan(h, x, ldx, batch, steps, feat, hidden, w_ih, w_hh, b_ih, b_hh, h0, gi, gh, hs, nullptr, nullptr, 0, nullptr,
-                      nullptr, (hipStream_t)stream);
+    GruClsWs r;
+    int rc = adaf_check_ws(h, "gru_seq", ws, ws_bytes, gru_cls_layout(ws, batch, steps, hidden, &r), ADAF_WS_SIZE_FIRST);
+    if (rc) return rc;
+    rc = gru_scan(h, x, ldx, batch, steps, feat, hidden, w_ih, w_hh, b_ih, b_hh, h0, r.gi, r.gh, hs, nullptr, nullptr, 0, nullptr,
+                  nullptr, (hipStream_t)stream);
     if (rc) return rc;
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? ADAF_OK : adaf_hip_fail(h, e, "gru_seq forward");
@@ -572,24 +583,27 @@ int adaf_gru_cls_forward_f32(adaf_handle* h, const float* x, int ldx, int batch,
     if (batch < 0 || steps <= 0 || feat <= 0 || hidden <= 0 || classes <= 0) return adaf_fail(h, ADAF_E_BADARG, "gru_cls: non-positive extent");
     if (ldx == 0) ldx = feat;
     if (feat % 4 || hidden % 4 || ldx % 4) return adaf_fail(h, ADAF_E_LAYOUT, "gru_cls: feat, hidden, ldx must be multiples of 4");
-    if (ws_bytes < adaf_gru_cls_workspace_bytes(batch, steps, hidden)) return adaf_fail(h, ADAF_E_NOMEM, "gru_cls: workspace too small");
-    if (!adaf_aligned16(ws)) return adaf_fail(h, ADAF_E_LAYOUT, "gru_cls: the workspace must be 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    float* gi = static_cast<float*>(ws);
-    float* gh = gi + (size_t)batch * steps * 3 * hidden;
-    float* hs = gh + (size_t)batch * 3 * hidden;  // [B, T, H]
-    int rc = gru_scan(h, x, ldx, batch, steps, feat, hidden, w_ih, w_hh, b_ih, b_hh, nullptr, gi, gh, hs, fc_w, fc_b, classes,
-                      logits_all, last, st);
+    GruClsWs r;
+    int rc = adaf_check_ws(h, "gru_cls", ws, ws_bytes, gru_cls_layout(ws, batch, steps, hidden, &r), ADAF_WS_SIZE_FIRST);
+    if (rc) return rc;
+    rc = gru_scan(h, x, ldx, batch, steps, feat, hidden, w_ih, w_hh, b_ih, b_hh, nullptr, r.gi, r.gh, r.hs, fc_w, fc_b, classes,
+                  logits_all, last, (hipStream_t)stream);
     if (rc) return rc;
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? ADAF_OK : adaf_hip_fail(h, e, "gru_cls forward");
 }
 
 // ---- stage-3 training of the GRU classifier (gru_bptt.hip) -------------------------------------------------------------------------
+struct GruTrainWs { float *gh, *hd; };     // gh [B, 3H] (the forward scan's per-step product / barrier words), the dropped-out states [B*T, H]
+static size_t gru_train_layout(void* ws, int batch, int steps, int hidden, GruTrainWs* r) {
+    AdafCarver c(ws);
+    r->gh = c.take<float>((size_t)batch * 3 * hidden);
+    r->hd = c.take<float>((size_t)batch * steps * hidden);
+    return c.off;
+}
 size_t adaf_gru_cls_train_workspace_bytes(int batch, int steps, int hidden) {
-    if (batch <= 0 || steps <= 0 || hidden <= 0) return 0;
-    // gh [B, 3H] (the forward scan's per-step product / barrier words) + the dropped-out states [B*T, H]
-    return ((size_t)batch * 3 * hidden + (size_t)batch * steps * hidden) * sizeof(float);
+    GruTrainWs r;
+    return (batch <= 0 || steps <= 0 || hidden <= 0) ? 0 : gru_train_layout(nullptr, batch, steps, hidden, &r);
 }
 
 int adaf_gru_cls_train_forward_f32(adaf_handle* h, const float* x, int ldx, int batch, int steps, int feat, int hidden, int classes,
@@ -603,14 +617,14 @@ int adaf_gru_cls_train_forward_f32(adaf_handle* h, const float* x, int ldx, int 
     if (batch < 0 || steps <= 0 || feat <= 0 || hidden <= 0 || classes <= 0) return adaf_fail(h, ADAF_E_BADARG, "gru_cls_train: non-positive extent");
     if (ldx == 0) ldx = feat;
     if (feat % 4 || hidden % 16 || ldx % 4) return adaf_fail(h, ADAF_E_LAYOUT, "gru_cls_train: feat %% 4, hidden %% 16, ldx %% 4 must be 0");
-    if (ws_bytes < adaf_gru_cls_train_workspace_bytes(batch, steps, hidden)) return adaf_fail(h, ADAF_E_NOMEM, "gru_cls_train: workspace too small");
-    if (!adaf_aligned16(ws)) return adaf_fail(h, ADAF_E_LAYOUT, "gru_cls_train: the workspace must be 16-byte aligned");
+    GruTrainWs r;
+    int rc = adaf_check_ws(h, "gru_cls_train", ws, ws_bytes, gru_train_layout(ws, batch, steps, hidden, &r), ADAF_WS_SIZE_FIRST);
+    if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
-    float* gh = static_cast<float*>(ws);
-    float* hd = gh + (size_t)batch * 3 * hidden;
+    float* const hd = r.hd;
     const int rows = batch * steps;
-    int rc = gru_scan(h, x, ldx, batch, steps, feat, hidden, w_ih, w_hh, b_ih, b_hh, nullptr, gi_out, gh, hs_out, nullptr, nullptr, 0, nullptr,
-                      nullptr, st);
+    rc = gru_scan(h, x, ldx, batch, steps, feat, hidden, w_ih, w_hh, b_ih, b_hh, nullptr, gi_out, r.gh, hs_out, nullptr, nullptr, 0, nullptr,
+                  nullptr, st);
     if (rc) return rc;
     const float* fc_in = hs_out;
     if (mask) {
@@ -623,13 +637,25 @@ int adaf_gru_cls_train_forward_f32(adaf_handle* h, const float* x, int ldx, int 
     return e == hipSuccess ? ADAF_OK : adaf_hip_fail(h, e, "gru_cls_train forward");
 }
 
+// dropped-out / shifted states + dY [B*T, H] each, gh + dgi + dgh [B*T, 3H] each, carry [B, H], column-sum partials (of 3H or `classes`
+// columns, whichever is more), the steps + 1 barrier words of the persistent scan in whole 256-byte lines
+struct GruBackwardWs { float *hd, *dy, *gh, *dgi, *dgh, *carry, *part; unsigned* bar; };
+static size_t gru_backward_layout(void* ws, int batch, int steps, int hidden, int classes, GruBackwardWs* r) {
+    const size_t rows = (size_t)batch * steps, h3 = 3 * (size_t)hidden, narrow = rows * hidden, wide = rows * h3;
+    AdafCarver c(ws);
+    r->hd = c.take<float>(narrow);
+    r->dy = c.take<float>(narrow);
+    r->gh = c.take<float>(wide);
+    r->dgi = c.take<float>(wide);
+    r->dgh = c.take<float>(wide);
+    r->carry = c.take<float>((size_t)batch * hidden);
+    r->part = c.take<float>(adaf_colsum_partial_floats(3 * hidden > classes ? 3 * hidden : classes));
+    r->bar = c.take<unsigned>((size_t)steps + 1, 256);
+    return c.off;
+}
 size_t adaf_gru_cls_backward_workspace_bytes(int batch, int steps, int hidden, int classes) {
-    if (batch <= 0 || steps <= 0 || hidden <= 0 || classes <= 0) return 0;
-    const size_t bt = (size_t)batch * steps, h3 = 3 * (size_t)hidden;
-    const size_t cols = h3 > (size_t)classes ? h3 : (size_t)classes;
-    // dropped-out / shifted states + dY [B*T, H] each, gh + dgi + dgh [B*T, 3H] each, carry [B, H], column-sum partials, barrier words
-    const size_t floats = 2 * bt * hidden + 3 * bt * h3 + (size_t)batch * hidden + adaf_colsum_partial_floats((int)cols);
-    return (floats + ((size_t)steps + 64) / 64 * 64) * sizeof(float);
+    GruBackwardWs r;
+    return (batch <= 0 || steps <= 0 || hidden <= 0 || classes <= 0) ? 0 : gru_backward_layout(nullptr, batch, steps, hidden, classes, &r);
 }
 
 int adaf_gru_cls_backward_f32(adaf_handle* h, const float* x, int ldx, int batch, int steps, int feat, int hidden, int classes,
@@ -642,26 +668,20 @@ int adaf_gru_cls_backward_f32(adaf_handle* h, const float* x, int ldx, int batch
     if (batch <= 0 || steps <= 0 || feat <= 0 || hidden <= 0 || classes <= 0) return adaf_fail(h, ADAF_E_BADARG, "gru_cls_backward: non-positive extent");
     if (ldx == 0) ldx = feat;
     if (feat % 4 || hidden % 16 || ldx % 4 || ldx < feat) return adaf_fail(h, ADAF_E_LAYOUT, "gru_cls_backward: feat %% 4, hidden %% 16, ldx %% 4 must be 0");
-    if (ws_bytes < adaf_gru_cls_backward_workspace_bytes(batch, steps, hidden, classes)) return adaf_fail(h, ADAF_E_NOMEM, "gru_cls_backward: workspace too small");
-    if (!adaf_aligned16(ws)) return adaf_fail(h, ADAF_E_LAYOUT, "gru_cls_backward: the workspace must be 16-byte aligned");
+    GruBackwardWs r;
+    int rc = adaf_check_ws(h, "gru_cls_backward", ws, ws_bytes, gru_backward_layout(ws, batch, steps, hidden, classes, &r), ADAF_WS_SIZE_FIRST);
+    if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int rows = batch * steps, h3 = 3 * hidden;
-    float* hd = static_cast<float*>(ws);
-    float* dy = hd + (size_t)rows * hidden;
-    float* gh = dy + (size_t)rows * hidden;
-    float* dgi = gh + (size_t)rows * h3;
-    float* dgh = dgi + (size_t)rows * h3;
-    float* carry = dgh + (size_t)rows * h3;
-    float* part = carry + (size_t)batch * hidden;
-    unsigned* bar = reinterpret_cast<unsigned*>(part + adaf_colsum_partial_floats(h3 > classes ? h3 : classes));
+    float *const hd = r.hd, *const dy = r.dy, *const gh = r.gh, *const dgi = r.dgi, *const dgh = r.dgh, *const carry = r.carry, *const part = r.part;
+    unsigned* const bar = r.bar;
     // FC + dropout: dW_fc = dlogits^T (hs * mask), db_fc = column sums, dY = (dlogits W_fc) * mask
     adaf_launch_rows_scale(hs, mask, hd, rows, hidden, steps, false, st);
     adaf_launch_gemm_strided(dlogits, 1, classes, hd, hidden, 1, dw_fc, hidden, nullptr, 0, classes, hidden, rows, st);
     adaf_launch_colsum(dlogits, rows, classes, classes, part, db_fc, st);
     adaf_launch_gemm_strided(dlogits, classes, 1, fc_w, hidden, 1, dy, hidden, mask, hidden, rows, hidden, classes, st);
     // gh = W_hh h_t + b_hh of every step in one engine GEMM (row (b, t) is step t+1's hidden projection)
-    int rc = linear_launch(h, hs, rows, hidden, hidden, h3, w_hh, b_hh, gh, 0, st);
-    if (rc) return rc;
+    if ((rc = linear_launch(h, hs, rows, hidden, hidden, h3, w_hh, b_hh, gh, 0, st))) return rc;
     // the T-sequential part: persistent under the forward scan's rules (not under capture unless "gru_graph_persistent"), and it takes
     // EVERY scan slot -- its 104 KB of LDS leave room for one block per CU, so no forward scan of this handle may run beside it
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
@@ -700,11 +720,12 @@ int adaf_fc_meanpool_forward_f32(adaf_handle* h, const float* feat, int batch, i
     if (batch < 0 || steps <= 0 || feat_dim <= 0 || classes <= 0 || (global_logit && global_steps <= 0))
         return adaf_fail(h, ADAF_E_BADARG, "fc_meanpool: non-positive extent");
     if (feat_dim % 4) return adaf_fail(h, ADAF_E_LAYOUT, "fc_meanpool: feat_dim %% 4");
-    if (ws_bytes < (size_t)batch * steps * classes * sizeof(float)) return adaf_fail(h, ADAF_E_NOMEM, "fc_meanpool: workspace too small");
-    if (!adaf_aligned16(ws)) return adaf_fail(h, ADAF_E_LAYOUT, "fc_meanpool: the workspace must be 16-byte aligned");
+    AdafCarver c(ws);
+    float* logit = c.take<float>((size_t)batch * steps * classes);      // the whole layout: the per-step logits [B*T, C]
+    int rc = adaf_check_ws(h, "fc_meanpool", ws, ws_bytes, c.off, ADAF_WS_SIZE_FIRST);
+    if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
-    float* logit = static_cast<float*>(ws);
-    int rc = linear_launch(h, feat, batch * steps, feat_dim, feat_dim, classes, fc_w, fc_b, logit, 0, st);
+    rc = linear_launch(h, feat, batch * steps, feat_dim, feat_dim, classes, fc_w, fc_b, logit, 0, st);
     if (rc) return rc;
     adaf_launch_segment_mean(logit, batch, steps, classes, global_logit, global_steps, out, st);
     hipError_t e = hipGetLastError();

@@ -2023,6 +2023,31 @@ int chunk_frames(int n) {
     return n < c ? n : c;
 }
 
+// The workspace, stated once: per chunk A and B (block in / out ping-pong), E (expanded), D (depthwise out) in the storage type, the
+// squeeze partials and the gates in fp32, each in whole 256-byte lines; a batch of more than one chunk has two chunks in flight and
+// a second set behind the first.  With ws == nullptr it only measures (the query).
+struct EfSlabs { char *A, *B, *E, *D; float *part, *gate; };
+struct EfWorkspace { int chunk; size_t bytes; EfSlabs slot[2]; };
+EfWorkspace workspace_layout(const adaf_effnet* net, int n, int size, int pad_size, void* ws) {
+    size_t io, ex, dw, pc, gc;
+    slab_sizes(net, size, pad_size, net->dtype, &io, &ex, &dw, &pc, &gc);
+    const size_t es = net->dtype == ADAF_DTYPE_F16 ? 2 : 4;
+    EfWorkspace w = {};
+    w.chunk = chunk_frames(n);
+    const int slots = n > w.chunk ? 2 : 1;       // two chunks in flight (whether or not the pairing is switched on)
+    AdafCarver c(ws);
+    for (int i = 0; i < slots; ++i) {
+        w.slot[i].A = c.take<char>((size_t)w.chunk * io * es, 256);
+        w.slot[i].B = c.take<char>((size_t)w.chunk * io * es, 256);
+        w.slot[i].E = c.take<char>((size_t)w.chunk * ex * es, 256);
+        w.slot[i].D = c.take<char>((size_t)w.chunk * dw * es, 256);
+        w.slot[i].part = c.take<float>((size_t)w.chunk * pc, 256);
+        w.slot[i].gate = c.take<float>((size_t)w.chunk * gc, 256);
+    }
+    w.bytes = c.off;
+    return w;
+}
+
 int run_dense(adaf_effnet* net, const EfConv& L, const void* in, bool in16, int n, int hh, int ww, int oh, int ow, int pad, int act,
               void* out, bool out16, hipStream_t st) {
     ConvArgs a;
@@ -2223,15 +2248,7 @@ int adaf_effnet_finalize(adaf_effnet* net, void* stream) {
 }
 
 size_t adaf_effnet_workspace_bytes(const adaf_effnet* net, int n, int size, int pad_size) {
-    if (!net || n <= 0 || size < 32) return 0;
-    size_t io, ex, dw, pc, gc;
-    slab_sizes(net, size, pad_size > 0 ? pad_size : size, net->dtype, &io, &ex, &dw, &pc, &gc);
-    const size_t es = net->dtype == ADAF_DTYPE_F16 ? 2 : 4;
-    const int chunk = chunk_frames(n);
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t per_chunk = al((size_t)chunk * io * es) * 2 + al((size_t)chunk * ex * es) + al((size_t)chunk * dw * es) + al((size_t)chunk * pc * 4) +
-                             al((size_t)chunk * gc * 4);
-    return per_chunk * (n > chunk ? 2 : 1);      // two chunks in flight (whether or not the pairing is switched on)
+    return (!net || n <= 0 || size < 32) ? 0 : workspace_layout(net, n, size, pad_size > 0 ? pad_size : size, nullptr).bytes;
 }
 
 int adaf_effnet_forward(adaf_effnet* net, const float* frames_nhwc4, int n, int size, int pad_size, int upto_block, void* block_out,
@@ -2244,25 +2261,16 @@ int adaf_effnet_forward(adaf_effnet* net, const float* frames_nhwc4, int n, int 
     if (pad_size <= 0) pad_size = size;
     if (featvec && ldvec < net->feat) return efail(h, ADAF_E_LAYOUT, "effnet: ldvec >= %d required", net->feat);
     if (upto_block >= 0 && !block_out) return efail(h, ADAF_E_BADARG, "effnet: upto_block needs block_out");
-    if (!adaf_aligned16(ws)) return efail(h, ADAF_E_LAYOUT, "effnet: the workspace must be 16-byte aligned");
-    if (ws_bytes < adaf_effnet_workspace_bytes(net, n, size, pad_size)) return efail(h, ADAF_E_NOMEM, "effnet: workspace too small");
-    hipStream_t st = (hipStream_t)stream;
+    const EfWorkspace W = workspace_layout(net, n, size, pad_size, ws);
+    int rc = adaf_check_ws(h, "effnet", ws, ws_bytes, W.bytes, ADAF_WS_ALIGN_FIRST);
+    if (rc) return rc;
     const bool f16 = net->dtype == ADAF_DTYPE_F16;
     const size_t es = f16 ? 2 : 4;
-    size_t io, ex, dws, pc, gc;
-    slab_sizes(net, size, pad_size, net->dtype, &io, &ex, &dws, &pc, &gc);
-    const int chunk = chunk_frames(n);
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t per_chunk = al((size_t)chunk * io * es) * 2 + al((size_t)chunk * ex * es) + al((size_t)chunk * dws * es) + al((size_t)chunk * pc * 4) +
-                             al((size_t)chunk * gc * 4);
-    // one chunk of patches through the whole network on stream `st` with its own part of the workspace
-    auto run_chunk = [&](int f0, int nc, char* base, hipStream_t st) -> int {
-        char* bufA = base;
-        char* bufB = bufA + al((size_t)chunk * io * es);
-        char* bufE = bufB + al((size_t)chunk * io * es);
-        char* bufD = bufE + al((size_t)chunk * ex * es);
-        float* part = reinterpret_cast<float*>(bufD + al((size_t)chunk * dws * es));
-        float* gate = reinterpret_cast<float*>(reinterpret_cast<char*>(part) + al((size_t)chunk * pc * 4));
+    // one chunk of patches through the whole network on stream `st` with its own slot of the workspace
+    auto run_chunk = [&](int f0, int nc, int slot, hipStream_t st) -> int {
+        const EfSlabs& slabs = W.slot[slot];
+        char *const bufA = slabs.A, *const bufB = slabs.B, *const bufE = slabs.E, *const bufD = slabs.D;
+        float *const part = slabs.part, *const gate = slabs.gate;
         int rc, tot;
         const int pb0 = same_pad(pad_size, 3, 2, &tot);
         int hw = conv_out_len(size, 3, 2, tot), ps = ceil_div(pad_size, 2);
@@ -2359,27 +2367,8 @@ int adaf_effnet_forward(adaf_effnet* net, const float* frames_nhwc4, int n, int 
         }
         return ADAF_OK;
     };
-    AdafAuxPool::Aux* ax = ((adaf_options().effnet_plan & ADAF_EF_PLAN_PAIR_CHUNKS) != 0 && n > chunk) ? net->aux.get(st) : nullptr;
-    const bool pair = ax != nullptr;
-    char* base0 = static_cast<char*>(ws);
-    for (int f0 = 0; f0 < n; f0 += chunk) {
-        const int nc = (n - f0) < chunk ? (n - f0) : chunk;
-        int rc;
-        if (pair && f0 + chunk < n) {
-            const int f1 = f0 + chunk;
-            const int nc1 = (n - f1) < chunk ? (n - f1) : chunk;
-            (void)hipEventRecord(ax->ev_fork, st);
-            (void)hipStreamWaitEvent(ax->stream, ax->ev_fork, 0);
-            rc = run_chunk(f0, nc, base0, st);
-            if (!rc) rc = run_chunk(f1, nc1, base0 + per_chunk, ax->stream);
-            // ALWAYS join, also when a launch failed after the fork: whatever the helper stream still has queued writes the caller's
-            // workspace / outputs, and the caller may reuse them as soon as this call returns
-            (void)hipEventRecord(ax->ev_join, ax->stream);
-            (void)hipStreamWaitEvent(st, ax->ev_join, 0);
-            if (rc) return rc;
-            f0 = f1;
-        } else if ((rc = run_chunk(f0, nc, base0, st))) return rc;
-    }
+    const bool pair = (adaf_options().effnet_plan & ADAF_EF_PLAN_PAIR_CHUNKS) != 0;
+    if ((rc = adaf_run_chunk_pairs(net->aux, (hipStream_t)stream, n, W.chunk, pair, run_chunk))) return rc;
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? ADAF_OK : efail(h, ADAF_E_LAUNCH, "effnet forward: %s", hipGetErrorString(e));
 }
@@ -2391,12 +2380,18 @@ int adaf_pack_dw_weight_kxk_f32(adaf_handle* h, const float* w_c1kk, int channel
     return ADAF_OK;
 }
 
-size_t adaf_dwconv_same_workspace_bytes(int n, int hh, int ww, int c, int k, int stride, int dtype) {
-    if (n <= 0 || hh <= 0 || ww <= 0 || c <= 0 || stride <= 0) return 0;
+// the pooled partials of adaf_dwconv_same_bn_act: one sum per (image, tile, channel)
+static size_t dwconv_same_layout(void* ws, int n, int hh, int ww, int c, int k, int stride, int dtype, float** part) {
     const int oh = ceil_div(hh, stride), ow = ceil_div(ww, stride);
     const int tiles = adaf_effnet_dw_tiles(c, oh, ow, k, stride, dtype);
+    AdafCarver cv(ws);
     // (at least one partial per (image, channel): the tiny-map kernel writes n * c sums whatever the tile planner says -- ADVICE r3)
-    return (size_t)n * (tiles > 0 ? tiles : 1) * c * 4;
+    *part = cv.take<float>((size_t)n * (tiles > 0 ? tiles : 1) * c);
+    return cv.off;
+}
+size_t adaf_dwconv_same_workspace_bytes(int n, int hh, int ww, int c, int k, int stride, int dtype) {
+    float* part;
+    return (n <= 0 || hh <= 0 || ww <= 0 || c <= 0 || stride <= 0) ? 0 : dwconv_same_layout(nullptr, n, hh, ww, c, k, stride, dtype, &part);
 }
 
 int adaf_dwconv_same_bn_act(adaf_handle* h, const void* x, int dtype, int n, int hh, int ww, int c, int k, int stride, const float* w_kkc,
@@ -2412,10 +2407,10 @@ int adaf_dwconv_same_bn_act(adaf_handle* h, const void* x, int dtype, int n, int
     const int pt = same_pad(hh, k, stride, &ty), pl = same_pad(ww, k, stride, &tx);
     const int oh = ceil_div(hh, stride), ow = ceil_div(ww, stride);
     float* part = nullptr;
-    if (pool_mean) {
-        if (ws && !adaf_aligned16(ws)) return efail(h, ADAF_E_LAYOUT, "dwconv_same: the workspace must be 16-byte aligned");
-        if (!ws || ws_bytes < adaf_dwconv_same_workspace_bytes(n, hh, ww, c, k, stride, dtype)) return efail(h, ADAF_E_NOMEM, "dwconv_same: workspace");
-        part = static_cast<float*>(ws);
+    if (pool_mean) {        // (only the pooled means have a workspace)
+        if (!ws) return efail(h, ADAF_E_NOMEM, "dwconv_same: workspace");
+        const int rc = adaf_check_ws(h, "dwconv_same", ws, ws_bytes, dwconv_same_layout(ws, n, hh, ww, c, k, stride, dtype, &part), ADAF_WS_ALIGN_FIRST);
+        if (rc) return rc;
     }
     const int tiles = adaf_launch_dw_same(x, dtype, n, hh, ww, c, k, stride, pt, pl, oh, ow, w_kkc, scale, bias, act, out, part, (hipStream_t)stream);
     if (tiles <= 0) return efail(h, ADAF_E_LAYOUT, "dwconv_same: shape not supported");

@@ -131,6 +131,27 @@ int chunk_frames(int n, int tsm_segments) {
     return c;
 }
 
+// The workspace, stated once: per chunk A and B (block in / out ping-pong), E (expanded), D (depthwise out), packed; a batch of more than
+// one chunk has two chunks in flight and a second set behind the first.  With ws == nullptr it only measures (the query).
+struct MbSlabs { float *A, *B, *E, *D; };
+struct MbWorkspace { int chunk; size_t bytes; MbSlabs slot[2]; };
+MbWorkspace workspace_layout(const adaf_mobilenetv2* net, int n, int size, int tsm_segments, void* ws) {
+    size_t io, ex, dw;
+    slab_sizes(net, size, &io, &ex, &dw);
+    MbWorkspace w = {};
+    w.chunk = chunk_frames(n, tsm_segments);
+    const int slots = n > w.chunk ? 2 : 1;       // two chunks in flight (whether or not the pairing is switched on)
+    AdafCarver c(ws);
+    for (int i = 0; i < slots; ++i) {
+        w.slot[i].A = c.take<float>((size_t)w.chunk * io);
+        w.slot[i].B = c.take<float>((size_t)w.chunk * io);
+        w.slot[i].E = c.take<float>((size_t)w.chunk * ex);
+        w.slot[i].D = c.take<float>((size_t)w.chunk * dw);
+    }
+    w.bytes = c.off;
+    return w;
+}
+
 int run_conv(adaf_mobilenetv2* net, const MbConv& L, const float* in, int n, int hh, int ww, int act, const float* res,
              float* out, int tsm_T, int tsm_div, hipStream_t st) {
     ConvArgs a;
@@ -224,11 +245,7 @@ int adaf_mobilenetv2_finalize(adaf_mobilenetv2* net, void* stream) {
 }
 
 size_t adaf_mobilenetv2_workspace_bytes(const adaf_mobilenetv2* net, int n, int size, int tsm_segments) {
-    if (!net || n <= 0 || size <= 0) return 0;
-    size_t io, ex, dw;
-    slab_sizes(net, size, &io, &ex, &dw);
-    const int chunk = chunk_frames(n, tsm_segments);
-    return (size_t)chunk * (2 * io + ex + dw) * sizeof(float) * (n > chunk ? 2 : 1);     // two chunks in flight
+    return (!net || n <= 0 || size <= 0) ? 0 : workspace_layout(net, n, size, tsm_segments, nullptr).bytes;
 }
 
 int adaf_mobilenetv2_forward(adaf_mobilenetv2* net, const float* frames_nhwc4, int n, int size, int tsm_segments,
@@ -241,19 +258,13 @@ int adaf_mobilenetv2_forward(adaf_mobilenetv2* net, const float* frames_nhwc4, i
     if (n <= 0 || size < 32) return mfail(h, ADAF_E_BADARG, "mobilenetv2: need n > 0 and size >= 32");
     if (tsm_segments > 0 && (n % tsm_segments || tsm_div <= 0)) return mfail(h, ADAF_E_BADARG, "mobilenetv2: n %% tsm_segments != 0");
     if (featvec && (ldvec < 1280 || ldvec % 4)) return mfail(h, ADAF_E_LAYOUT, "mobilenetv2: ldvec >= 1280 and %% 4 == 0 required");
-    if (!adaf_aligned16(ws)) return mfail(h, ADAF_E_LAYOUT, "mobilenetv2: the workspace must be 16-byte aligned");
-    if (ws_bytes < adaf_mobilenetv2_workspace_bytes(net, n, size, tsm_segments)) return mfail(h, ADAF_E_NOMEM, "mobilenetv2: workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    size_t io, ex, dws;
-    slab_sizes(net, size, &io, &ex, &dws);
-    const int chunk = chunk_frames(n, tsm_segments);
-    float* bufA = static_cast<float*>(ws);
-    float* bufB = bufA + (size_t)chunk * io;
-    float* bufE = bufB + (size_t)chunk * io;
-    float* bufD = bufE + (size_t)chunk * ex;
+    const MbWorkspace W = workspace_layout(net, n, size, tsm_segments, ws);
+    int rc = adaf_check_ws(h, "mobilenetv2", ws, ws_bytes, W.bytes, ADAF_WS_ALIGN_FIRST);
+    if (rc) return rc;
 
-    // one chunk of frames through the whole network on stream `st` with its own quarter of the workspace
-    auto run_chunk = [&](int f0, int nc, float* bufA, float* bufB, float* bufE, float* bufD, hipStream_t st) -> int {
+    // one chunk of frames through the whole network on stream `st` with its own slot of the workspace
+    auto run_chunk = [&](int f0, int nc, int slot, hipStream_t st) -> int {
+        float *const bufA = W.slot[slot].A, *const bufB = W.slot[slot].B, *const bufE = W.slot[slot].E, *const bufD = W.slot[slot].D;
         int hw = cdiv_out(size, 3, 2, 1);
         int rc;
         float* cur = bufA;
@@ -346,30 +357,7 @@ int adaf_mobilenetv2_forward(adaf_mobilenetv2* net, const float* frames_nhwc4, i
         if (featvec) adaf_launch_avgpool(fm, nc, hw * hw, 1280, featvec + (size_t)f0 * ldvec, ldvec, st);
         return ADAF_OK;
     };
-    const size_t per_chunk = (size_t)chunk * (2 * io + ex + dws);
-    AdafAuxPool::Aux* ax = (net->pair && n > chunk) ? net->aux.get(st) : nullptr;
-    const bool pair = ax != nullptr;
-    float* base2 = static_cast<float*>(ws) + per_chunk;
-    for (int f0 = 0; f0 < n; f0 += chunk) {
-        const int nc = (n - f0) < chunk ? (n - f0) : chunk;
-        int rc;
-        if (pair && f0 + chunk < n) {
-            const int f1 = f0 + chunk;
-            const int nc1 = (n - f1) < chunk ? (n - f1) : chunk;
-            (void)hipEventRecord(ax->ev_fork, st);
-            (void)hipStreamWaitEvent(ax->stream, ax->ev_fork, 0);
-            rc = run_chunk(f0, nc, bufA, bufB, bufE, bufD, st);
-            if (!rc)
-                rc = run_chunk(f1, nc1, base2, base2 + (size_t)chunk * io, base2 + (size_t)chunk * 2 * io,
-                               base2 + (size_t)chunk * (2 * io + ex), ax->stream);
-            // ALWAYS join, also when a launch failed after the fork: whatever the helper stream still has queued writes the
-            // caller's workspace / outputs, and the caller may reuse them as soon as this call returns
-            (void)hipEventRecord(ax->ev_join, ax->stream);
-            (void)hipStreamWaitEvent(st, ax->ev_join, 0);
-            if (rc) return rc;
-            f0 = f1;
-        } else if ((rc = run_chunk(f0, nc, bufA, bufB, bufE, bufD, st))) return rc;
-    }
+    if ((rc = adaf_run_chunk_pairs(net->aux, (hipStream_t)stream, n, W.chunk, net->pair, run_chunk))) return rc;
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? ADAF_OK : mfail(h, ADAF_E_LAUNCH, "mobilenetv2 forward: %s", hipGetErrorString(e));
 }

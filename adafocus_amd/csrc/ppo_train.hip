@@ -345,9 +345,30 @@ int launch_wenc_grad(adaf_handle* h, const float* states, const float* de1, cons
 size_t wenc_sk_floats(int npix, int cin, int cmid) {
     return (cmid == 32 && cin % 128 == 0) ? (size_t)sk_slices(npix, cin, kSkCus) * 32 * cin : 0;
 }
-size_t wenc_ws_floats(int npix, int cin, int cmid) {      // either form of adaf_ppo_wenc_grad_f32: the partials, or the masked gradient
+
+// ---- workspace layouts: each written once, measured by the query (null base) and carved by the call -----------------------------------
+size_t ppo_head_layout(void* ws, int steps, int batch, float** terms) {
+    AdafCarver c(ws);
+    *terms = c.take<float>(2 * (size_t)steps * batch);      // the two per-row loss terms
+    return c.off;
+}
+size_t wenc_layout(void* ws, int npix, int cin, int cmid, float** buf) {      // either form of adaf_ppo_wenc_grad_f32: the partials, or the masked gradient
     const size_t sk = wenc_sk_floats(npix, cin, cmid), chain = (size_t)npix * cmid;
-    return sk > chain ? sk : chain;
+    AdafCarver c(ws);
+    *buf = c.take<float>(sk > chain ? sk : chain);
+    return c.off;
+}
+// dE [rows, hidden], dE1 [rows, hw * cmid], the pixel-major dW_lin [hidden, hw * cmid], column-sum partials, the split-K slice partials
+struct EncBackwardWs { float *de, *de1, *dwl, *part, *wws; };
+size_t enc_backward_layout(void* ws, int steps, int batch, int map_pixels, int channels, int conv_out, int hidden, EncBackwardWs* r) {
+    const size_t rows = (size_t)steps * batch, mid = (size_t)map_pixels * conv_out;
+    AdafCarver c(ws);
+    r->de = c.take<float>(rows * hidden);
+    r->de1 = c.take<float>(rows * mid);
+    r->dwl = c.take<float>((size_t)hidden * mid);
+    r->part = c.take<float>(adaf_colsum_partial_floats(hidden));
+    r->wws = c.take<float>(wenc_sk_floats((int)(rows * map_pixels), channels, conv_out));
+    return c.off;
 }
 
 }  // namespace
@@ -378,8 +399,8 @@ int adaf_ppo_returns_f32(adaf_handle* h, const float* rewards, int steps, int ba
 }
 
 size_t adaf_ppo_head_workspace_bytes(int steps, int batch) {
-    if (steps <= 0 || batch <= 0) return 0;
-    return 2 * (size_t)steps * batch * sizeof(float);      // the two per-row loss terms
+    float* terms;
+    return (steps <= 0 || batch <= 0) ? 0 : ppo_head_layout(nullptr, steps, batch, &terms);
 }
 
 int adaf_ppo_head_f32(adaf_handle* h, const float* head, int head_batch_major, int steps, int batch, int n_actions, const int64_t* actions,
@@ -394,13 +415,14 @@ int adaf_ppo_head_f32(adaf_handle* h, const float* head, int head_batch_major, i
     if (loss_mode && (!old_logprobs || !returns || !loss_out || !ws)) return adaf_fail(h, ADAF_E_BADARG, "ppo_head: the loss needs old_logprobs, returns, loss_out and a workspace");
     if (loss_mode && grad_mode) return adaf_fail(h, ADAF_E_BADARG, "ppo_head: either the PPO loss or upstream gradients");
     if (grad_mode && !dhead_out) return adaf_fail(h, ADAF_E_BADARG, "ppo_head: upstream gradients without dhead_out");
-    if (loss_mode && ws_bytes < adaf_ppo_head_workspace_bytes(steps, batch)) return adaf_fail(h, ADAF_E_NOMEM, "ppo_head: workspace too small");
-    if (loss_mode && !adaf_aligned16(ws)) return adaf_fail(h, ADAF_E_LAYOUT, "ppo_head: the workspace must be 16-byte aligned");
+    float* terms = static_cast<float*>(ws);       // (only the loss has a workspace; the kernel reads the argument in loss mode alone)
+    int rc;
+    if (loss_mode && (rc = adaf_check_ws(h, "ppo_head", ws, ws_bytes, ppo_head_layout(ws, steps, batch, &terms), ADAF_WS_SIZE_FIRST))) return rc;
     hipStream_t st = (hipStream_t)stream;
     HeadArgs a;
     a.head = head; a.action = reinterpret_cast<const long long*>(actions); a.old_logprob = old_logprobs; a.returns = returns;
     a.g_logprob = g_logprob; a.g_value = g_value; a.g_entropy = g_entropy;
-    a.logprob = logprobs_out; a.value = values_out; a.entropy = entropy_out; a.terms = static_cast<float*>(ws); a.dhead = dhead_out;
+    a.logprob = logprobs_out; a.value = values_out; a.entropy = entropy_out; a.terms = terms; a.dhead = dhead_out;
     a.T = steps; a.B = batch; a.A = n_actions; a.head_bt = head_batch_major ? 1 : 0; a.mode = loss_mode ? 1 : (grad_mode ? 2 : 0);
     a.eps_clip = eps_clip;
     const int n = steps * batch;
@@ -421,8 +443,8 @@ int adaf_ppo_rows_transpose_f32(adaf_handle* h, const float* in, int ni, int nj,
 }
 
 size_t adaf_ppo_wenc_grad_workspace_bytes(int pixels, int channels, int conv_out) {
-    if (pixels <= 0 || channels <= 0 || conv_out <= 0) return 0;
-    return wenc_ws_floats(pixels, channels, conv_out) * sizeof(float);
+    float* buf;
+    return (pixels <= 0 || channels <= 0 || conv_out <= 0) ? 0 : wenc_layout(nullptr, pixels, channels, conv_out, &buf);
 }
 
 int adaf_ppo_wenc_grad_f32(adaf_handle* h, const float* states, const float* de1, const float* e1, int pixels, int channels, int conv_out,
@@ -430,21 +452,19 @@ int adaf_ppo_wenc_grad_f32(adaf_handle* h, const float* states, const float* de1
     if (!h) return ADAF_E_BADARG;
     if (!states || !de1 || !e1 || !dw_out || !ws) return adaf_fail(h, ADAF_E_BADARG, "ppo_wenc_grad: null pointer");
     if (pixels <= 0 || channels <= 0 || conv_out <= 0) return adaf_fail(h, ADAF_E_BADARG, "ppo_wenc_grad: non-positive extent");
-    if (!adaf_aligned16(states) || !adaf_aligned16(ws) || !adaf_aligned16(dw_out)) return adaf_fail(h, ADAF_E_LAYOUT, "ppo_wenc_grad: 16-byte alignment");
-    if (ws_bytes < adaf_ppo_wenc_grad_workspace_bytes(pixels, channels, conv_out)) return adaf_fail(h, ADAF_E_NOMEM, "ppo_wenc_grad: workspace too small");
-    int rc = launch_wenc_grad(h, states, de1, e1, pixels, channels, conv_out, split_k, dw_out, static_cast<float*>(ws), (hipStream_t)stream);
+    if (!adaf_aligned16(states) || !adaf_aligned16(dw_out)) return adaf_fail(h, ADAF_E_LAYOUT, "ppo_wenc_grad: 16-byte alignment");
+    float* buf;
+    int rc = adaf_check_ws(h, "ppo_wenc_grad", ws, ws_bytes, wenc_layout(ws, pixels, channels, conv_out, &buf), ADAF_WS_ALIGN_FIRST);
     if (rc) return rc;
+    if ((rc = launch_wenc_grad(h, states, de1, e1, pixels, channels, conv_out, split_k, dw_out, buf, (hipStream_t)stream))) return rc;
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? ADAF_OK : adaf_hip_fail(h, e, "ppo_wenc_grad launch");
 }
 
 size_t adaf_ppo_encoder_backward_workspace_bytes(int steps, int batch, int map_pixels, int channels, int conv_out, int hidden) {
+    EncBackwardWs r;
     if (steps <= 0 || batch <= 0 || map_pixels <= 0 || channels <= 0 || conv_out <= 0 || hidden <= 0) return 0;
-    const size_t rows = (size_t)steps * batch, mid = (size_t)map_pixels * conv_out;
-    // dE [rows, hidden] + dE1 [rows, hw * cmid] + the pixel-major dW_lin [hidden, hw * cmid] + column-sum partials + the split-K slice partials
-    const size_t floats = rows * hidden + rows * mid + (size_t)hidden * mid + adaf_colsum_partial_floats(hidden) +
-                          wenc_sk_floats((int)(rows * map_pixels), channels, conv_out);
-    return floats * sizeof(float);
+    return enc_backward_layout(nullptr, steps, batch, map_pixels, channels, conv_out, hidden, &r);
 }
 
 int adaf_ppo_encoder_backward_f32(adaf_handle* h, const float* states, const float* e1, const float* e_bt, const float* dx_bt, int steps,
@@ -456,16 +476,14 @@ int adaf_ppo_encoder_backward_f32(adaf_handle* h, const float* states, const flo
     if (steps <= 0 || batch <= 0 || map_pixels <= 0 || channels <= 0 || conv_out <= 0 || hidden <= 0)
         return adaf_fail(h, ADAF_E_BADARG, "ppo_encoder_backward: non-positive extent");
     if (conv_out != 32 || channels % 128) return adaf_fail(h, ADAF_E_LAYOUT, "ppo_encoder_backward: 32 conv outputs and channels %% 128 == 0 expected");
-    if (!adaf_aligned16(states) || !adaf_aligned16(ws)) return adaf_fail(h, ADAF_E_LAYOUT, "ppo_encoder_backward: 16-byte alignment");
-    if (ws_bytes < adaf_ppo_encoder_backward_workspace_bytes(steps, batch, map_pixels, channels, conv_out, hidden))
-        return adaf_fail(h, ADAF_E_NOMEM, "ppo_encoder_backward: workspace too small");
+    if (!adaf_aligned16(states)) return adaf_fail(h, ADAF_E_LAYOUT, "ppo_encoder_backward: 16-byte alignment");
+    EncBackwardWs r;
+    int rc = adaf_check_ws(h, "ppo_encoder_backward", ws, ws_bytes, enc_backward_layout(ws, steps, batch, map_pixels, channels, conv_out, hidden, &r),
+                           ADAF_WS_ALIGN_FIRST);
+    if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int rows = steps * batch, mid = map_pixels * conv_out;
-    float* de = static_cast<float*>(ws);
-    float* de1 = de + (size_t)rows * hidden;
-    float* dwl = de1 + (size_t)rows * mid;
-    float* part = dwl + (size_t)hidden * mid;
-    float* wws = part + adaf_colsum_partial_floats(hidden);
+    float *const de = r.de, *const de1 = r.de1, *const dwl = r.dwl, *const part = r.part, *const wws = r.wws;
     // dE[t * B + b] = dx[b * T + t] * (E[b * T + t] > 0): the GRU's (B, T) rows back to the states' (T, B) order, ReLU mask on the way
     {
         const size_t n = (size_t)rows * hidden;
@@ -479,8 +497,7 @@ int adaf_ppo_encoder_backward_f32(adaf_handle* h, const float* states, const flo
     }
     adaf_launch_colsum(de, rows, hidden, hidden, part, db_lin, st);
     adaf_launch_gemm_strided(de, hidden, 1, w_lin_pm, mid, 1, de1, mid, nullptr, 0, rows, mid, hidden, st);
-    int rc = launch_wenc_grad(h, states, de1, e1, rows * map_pixels, channels, conv_out, 1, dw_enc, wws, st);
-    if (rc) return rc;
+    if ((rc = launch_wenc_grad(h, states, de1, e1, rows * map_pixels, channels, conv_out, 1, dw_enc, wws, st))) return rc;
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? ADAF_OK : adaf_hip_fail(h, e, "ppo_encoder_backward launch");
 }

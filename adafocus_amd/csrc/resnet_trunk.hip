@@ -115,6 +115,18 @@ adaf_conv_params layer_params(const ConvLayer& L, int n, int hh, int ww, int act
     return p;
 }
 
+// The workspace, stated once: five slabs (block input, block output, two bottleneck temporaries, downsample branch), each as
+// large as the biggest activation: the stem output or the first stage's 256-channel map; a sixth for the
+// shifted block input when the temporal shift wraps whole blocks (adaf_resnet50_set_shift_place).  ws == nullptr: only measures
+// (adaf_resnet50_workspace_bytes, which may be asked without a net: five slabs).
+size_t trunk_layout(const adaf_resnet50* net, int n, int patch, void* ws, float* buf[6]) {
+    const int s1 = adaf_conv_out(patch, 7, 2, 3), s2 = adaf_conv_out(s1, 3, 2, 1);
+    const size_t a = (size_t)s1 * s1 * 64, b = (size_t)s2 * s2 * 256;
+    AdafCarver c(ws);
+    for (int i = 0; i < 6; ++i) buf[i] = (i < 5 || (net && net->tsm_block)) ? c.take<float>((a > b ? a : b) * n) : nullptr;
+    return c.off;
+}
+
 inline const float* as_f32(const void* p) { return static_cast<const float*>(p); }   // fp16 buffers travel as float* through ConvArgs
 
 // Walks the trunk in the arithmetic net->math names; `rec` (optional) gets one hipEvent before each launch plus one at the end.
@@ -130,8 +142,9 @@ int run_trunk(adaf_resnet50* net, const float* x4, int n, int P, int tsm_T, int 
     if (ldfeat < 2048 || ldfeat % 4 || !adaf_aligned16(feat) || !adaf_aligned16(x4) || !adaf_aligned16(ws))
         return adaf_fail(h, ADAF_E_LAYOUT, "resnet50: ldfeat >= 2048, %% 4 == 0 and 16-byte aligned buffers required");
     if (tsm_T > 0 && n % tsm_T) return adaf_fail(h, ADAF_E_BADARG, "resnet50: n=%d not a multiple of tsm_segments=%d", n, tsm_T);
-    const size_t need = adaf_resnet50_workspace_bytes(net, n, P);
-    if (ws_bytes < need) return adaf_fail(h, ADAF_E_NOMEM, "resnet50: workspace %zu < %zu bytes", ws_bytes, need);
+    float* buf[6];
+    // (a misaligned workspace was refused above, in front of the shift check: the order of the codes is part of the entry point's behaviour)
+    if (int rc = adaf_check_ws(h, "resnet50", ws, ws_bytes, trunk_layout(net, n, P, ws, buf), ADAF_WS_ALIGN_FIRST)) return rc;
 
     // Small problems (BASELINE config 1: B*T = 16 patches -> 576 / 144 output pixels in stages 3 / 4): a conv whose GEMM has at most
     // `lat_rows` rows is as long as ONE accumulator chain on the engine, and runs on the latency form instead (conv_lat.hip:
@@ -150,10 +163,6 @@ int run_trunk(adaf_resnet50* net, const float* x4, int n, int P, int tsm_T, int 
     const bool stage1_f32 = net->math == ADAF_MATH_F32 || (net->math == ADAF_MATH_F32_SPLIT_BF16 && adaf_options().split_stage1_f32);
     const bool tsm_block = net->tsm_block && tsm_T > 0;
     const int tsm_c1 = tsm_block ? 0 : tsm_T;     // the temporal shift conv1's operand load carries
-    const int nslab = net->tsm_block ? 6 : 5;
-    const size_t slab = need / (nslab * sizeof(float));  // largest activation, floats
-    float* buf[6];
-    for (int i = 0; i < nslab; ++i) buf[i] = static_cast<float*>(ws) + i * slab;
 
     // The fp16 trunk (ADAF_MATH_F16, include/adafocus.h: numerics contract).  Same slabs as the fp32 plan (an fp16 map takes half of one), same
     // block walk: stem + max-pool with an fp16 store, then every conv on the fp16-operand tiles (conv_gemm.hip, tile ids 81..84 / 88: fp16
@@ -533,13 +542,8 @@ int adaf_resnet50_finalize(adaf_resnet50* net, void* stream) {
 }
 
 size_t adaf_resnet50_workspace_bytes(const adaf_resnet50* net, int n, int patch) {
-    if (n <= 0 || patch <= 0) return 0;
-    // five slabs (block input, block output, two bottleneck temporaries, downsample branch), each as
-    // large as the biggest activation: the stem output or the first stage's 256-channel map; a sixth for the
-    // shifted block input when the temporal shift wraps whole blocks (adaf_resnet50_set_shift_place)
-    const int s1 = adaf_conv_out(patch, 7, 2, 3), s2 = adaf_conv_out(s1, 3, 2, 1);
-    const size_t a = (size_t)s1 * s1 * 64, b = (size_t)s2 * s2 * 256;
-    return (size_t)((net && net->tsm_block) ? 6 : 5) * n * (a > b ? a : b) * sizeof(float);
+    float* buf[6];
+    return (n <= 0 || patch <= 0) ? 0 : trunk_layout(net, n, patch, nullptr, buf);
 }
 
 int adaf_resnet50_forward(adaf_resnet50* net, const float* patches_nhwc4, int n, int patch, int tsm_segments,

@@ -119,7 +119,7 @@ def guarded_workspace(nbytes, device="cpu", fill="nan", offset_bytes=0):
     if nbytes <= 0 or offset_bytes < 0 or offset_bytes % 4:
         raise ValueError("guarded_workspace: nbytes > 0 and a non-negative offset_bytes that is a multiple of 4 required")
     words = (nbytes + 3) // 4
-    guard = max(nbytes, WS_GUARD_MIN) // 4
+    guard = (max(nbytes, WS_GUARD_MIN) + 3) // 4      # whole words: a size that is no multiple of 4 still gets its full guard
     # room to move the payload's start onto a 256-byte boundary whatever the allocation's own alignment
     # (filled where it lives: a 100 MB workspace is not staged on the host; CANARY_F32 fits a signed 32-bit word)
     bits = torch.full((guard + 64 + offset_bytes // 4 + words + guard,), CANARY_F32, dtype=torch.int32, device=device)
