@@ -191,7 +191,7 @@ struct ConvArgs {
     float* pool_out;
 };
 
-// api.hip: helpers of the C-ABI layer's host code (api.hip, resnet_trunk.hip)
+// api.hip: helpers of the C-ABI layer's host code (every entry point's error and workspace checks)
 int adaf_fail(adaf_handle* h, int code, const char* fmt, ...);       // stores the formatted message in the handle, returns `code`
 int adaf_hip_fail(adaf_handle* h, hipError_t e, const char* what);   // ADAF_E_LAUNCH with the runtime's error string
 bool adaf_aligned16(const void* p);
@@ -360,7 +360,8 @@ void adaf_launch_gru_gates(const float* gi, int ldgi_t, const float* gh, const f
 void adaf_launch_segment_mean(const float* logit, int B, int T, int C, const float* glog, int Tg, float* out,
                               hipStream_t s);
 void adaf_launch_copy2d(const float* src, int lds, float* dst, int ldd, int rows, int cols, hipStream_t s);
-void adaf_launch_pack_dw_weight(const float* w, int c, float* o, hipStream_t s);
+void adaf_launch_pack_dw_kxk(const float* w, int c, int k, float* o, hipStream_t s);     // depthwise filter [c][k*k] -> [k*k][c]
+void adaf_launch_pack_dw_weight(const float* w, int c, float* o, hipStream_t s);            // the same at k = 3
 void adaf_launch_dwconv3x3(const float* x, int n, int h, int w, int c, int stride, const float* wt, const float* scale,
                            const float* bias, int act, float* o, hipStream_t s);
 void adaf_launch_grid_actions(const float* logits, int rows, int a, const float* table, long long* idx, float* act,

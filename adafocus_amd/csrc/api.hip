@@ -6,7 +6,7 @@
 
 #include "adaf_internal.h"
 
-// ---- helpers shared with resnet_trunk.hip (declared in adaf_internal.h) ----------------
+// ---- helpers shared with the other host files (declared in adaf_internal.h) -----------
 int adaf_fail(adaf_handle* h, int code, const char* fmt, ...) {
     char buf[512];
     va_list ap;

@@ -15,17 +15,15 @@
 //   squeeze -> FC -> swish -> FC -> sigmoid   se_gate_kernel, one block per image (wave-shuffle dot products)
 //   project 1x1 + BN (+ identity)     gated_project_kernel: the SE gate multiplies the A operand on its way from HBM to LDS
 //                                     (sigmoid(s) * x, then the conv -- the reference's order), MFMA, BN + identity epilogue
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <cmath>
-#include <map>
 #include <string>
 #include <type_traits>
 #include <vector>
 
-#include "adaf_internal.h"
+#include "adaf_net.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -1463,13 +1461,6 @@ __global__ void pack_stem_bank_kernel(const float* __restrict__ w, int c0, float
     o[idx] = (col < c0 && k < 27) ? w[(size_t)col * 36 + tap * 4 + ch] : 0.f;
 }
 
-// [C,1,K,K] (PyTorch depthwise) -> [K*K][C]
-__global__ void pack_dw_kxk_kernel(const float* __restrict__ w, int c, int kk, float* __restrict__ o) {
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= kk * c) return;
-    const int ch = idx % c, tap = idx / c;
-    o[idx] = w[(size_t)ch * kk + tap];
-}
 // [R][C] -> [C][R]
 __global__ void transpose_kernel(const float* __restrict__ w, int rows, int cols, float* __restrict__ o) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1844,23 +1835,10 @@ bool adaf_launch_ef_stem(const float* x4, int dtype, int n, int size, int oh, in
     return true;
 }
 
-void adaf_launch_pack_dw_kxk(const float* w, int c, int k, float* o, hipStream_t s) {
-    hipLaunchKernelGGL(pack_dw_kxk_kernel, dim3((unsigned)((k * k * c + 255) / 256)), dim3(256), 0, s, w, c, k * k, o);
-}
-
 // ======================================================================================================================
 // The network object
 // ======================================================================================================================
-struct EfConv {
-    std::string name;     // "stem", "b3.expand", "b3.dw", "b3.project", "head"
-    int cin, cout, k, stride;
-    bool dw;
-    int cin_pad;
-    float* w = nullptr;   // dense: [cout][k][k][cin_pad] fp32; depthwise: [k*k][c]
-    void* w16 = nullptr;  // dense 1x1 filters in fp16 (ADAF_DTYPE_F16)
-    float* scale = nullptr;
-    float* bias = nullptr;
-};
+using EfConv = AdafNetConv;     // "stem", "b3.expand", "b3.dw", "b3.project", "head"; w16: the dense 1x1 filters in fp16 (ADAF_DTYPE_F16)
 struct EfBlock {
     int k, stride, expand_ratio, cin, cout, hid, sq;
     int expand, dwc, project;       // indices into convs (expand = -1 when the ratio is 1)
@@ -1868,15 +1846,16 @@ struct EfBlock {
     float* se_br = nullptr;         // [sq]
     float* se_wet = nullptr;        // [sq][hid] (transposed _se_expand.weight)
     float* se_be = nullptr;         // [hid]
-    void* wef = nullptr;            // fp16 storage: expand / project filters in MFMA B-fragment order for the whole-block kernel
-    void* wpf = nullptr;            //  (mbconv_whole.hip)
+    unsigned short* wef = nullptr;  // fp16 storage: expand / project filters in MFMA B-fragment order for the whole-block kernel
+    unsigned short* wpf = nullptr;  //  (mbconv_whole.hip)
     float* wdl = nullptr;           //  ... and the depthwise taps + folded BN as one row per channel
 };
 
 struct adaf_effnet {
     adaf_handle* h = nullptr;
     float width = 1.f, depth = 1.f;
-    std::map<std::string, std::pair<const float*, size_t>> params;
+    AdafParamTable params;  // what set_param registered since the last finalize
+    AdafWeightArena arena;  // every derived weight buffer: packed filters, folded BN, SE matrices, B fragments
     std::vector<EfConv> convs;
     std::vector<EfBlock> blocks;
     int stem = 0, head = 0, feat = 1280;
@@ -1890,39 +1869,9 @@ struct adaf_effnet {
     // and joined to the caller's stream by events, one helper per caller stream -- as adaf_mobilenetv2 does): the launches of the 9 x 9 and
     // 5 x 5 stages, the SE gates and every launch's ramp and tail leave room that a neighbour fills.
     AdafAuxPool aux;        // (adaf_internal.h: LRU over caller streams, mutex-guarded)
-    // Every derived weight buffer (packed filters, folded BN, SE matrices, B fragments) is carved out of a few large slabs: a
-    // launch of the whole-block kernel reads ~14 of them, and as separate small hipMalloc()s each sat in pages of its own.
-    std::vector<void*> slabs;
-    char* slab_cur = nullptr;
-    size_t slab_left = 0;
-    void* carve(size_t bytes) {
-        bytes = (bytes + 255) & ~(size_t)255;
-        if (bytes > slab_left) {
-            const size_t sz = bytes > ((size_t)32 << 20) ? bytes : ((size_t)32 << 20);
-            void* p = nullptr;
-            if (hipMalloc(&p, sz) != hipSuccess) return nullptr;
-            slabs.push_back(p);
-            slab_cur = static_cast<char*>(p);
-            slab_left = sz;
-        }
-        void* r = slab_cur;
-        slab_cur += bytes;
-        slab_left -= bytes;
-        return r;
-    }
 };
 
 namespace {
-
-int efail(adaf_handle* h, int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    if (h) h->err = buf;
-    return code;
-}
 
 // efficientnet_pytorch utils.py round_filters / round_repeats (depth_divisor 8)
 int round_filters(int filters, float width) {
@@ -1943,7 +1892,7 @@ void build(adaf_effnet* net) {
     net->blocks.clear();
     const int c0 = round_filters(32, net->width);
     net->stem = 0;
-    net->convs.push_back({"stem", 3, c0, 3, 2, false, 4});
+    net->convs.push_back(adaf_net_conv("stem", 3, c0, 3, 2, false, 4));
     int last = c0;
     for (auto& s : kBase) {
         const int i0 = round_filters(s[4], net->width), o = round_filters(s[5], net->width), rep = round_repeats(s[0], net->depth);
@@ -1958,21 +1907,21 @@ void build(adaf_effnet* net) {
             if (s[3] != 1) {
                 snprintf(nm, sizeof(nm), "b%d.expand", bi);
                 b.expand = (int)net->convs.size();
-                net->convs.push_back({nm, b.cin, b.hid, 1, 1, false, b.cin});
+                net->convs.push_back(adaf_net_conv(nm, b.cin, b.hid, 1, 1, false, b.cin));
             }
             snprintf(nm, sizeof(nm), "b%d.dw", bi);
             b.dwc = (int)net->convs.size();
-            net->convs.push_back({nm, b.hid, b.hid, b.k, b.stride, true, b.hid});
+            net->convs.push_back(adaf_net_conv(nm, b.hid, b.hid, b.k, b.stride, true, b.hid));
             snprintf(nm, sizeof(nm), "b%d.project", bi);
             b.project = (int)net->convs.size();
-            net->convs.push_back({nm, b.hid, b.cout, 1, 1, false, b.hid});
+            net->convs.push_back(adaf_net_conv(nm, b.hid, b.cout, 1, 1, false, b.hid));
             net->blocks.push_back(b);
             last = o;
         }
     }
     net->feat = round_filters(1280, net->width);
     net->head = (int)net->convs.size();
-    net->convs.push_back({"head", last, net->feat, 1, 1, false, last});
+    net->convs.push_back(adaf_net_conv("head", last, net->feat, 1, 1, false, last));
 }
 
 inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
@@ -2050,16 +1999,8 @@ EfWorkspace workspace_layout(const adaf_effnet* net, int n, int size, int pad_si
 
 int run_dense(adaf_effnet* net, const EfConv& L, const void* in, bool in16, int n, int hh, int ww, int oh, int ow, int pad, int act,
               void* out, bool out16, hipStream_t st) {
-    ConvArgs a;
-    memset(&a, 0, sizeof(a));
-    a.x = static_cast<const float*>(in); a.w = in16 ? static_cast<const float*>(L.w16) : L.w;
-    a.scale = L.scale; a.bias = L.bias; a.res = nullptr; a.out = static_cast<float*>(out);
-    a.M = n * oh * ow; a.N = L.cout; a.K = L.k * L.k * L.cin_pad;
-    a.cin = L.cin_pad; a.H = hh; a.W = ww; a.OH = oh; a.OW = ow; a.KH = a.KW = L.k; a.stride = L.stride; a.pad = pad;
-    a.ldx = L.cin_pad; a.ldo = L.cout; a.ldr = L.cout; a.act = act;
-    a.zeros = net->h->zeros;
-    a.vec_epi = (L.cout % 4 == 0) ? 1 : 0;
-    a.in16 = in16; a.out16 = out16; a.res16 = 0;
+    ConvArgs a = adaf_net_conv_args(L, in16 ? static_cast<const void*>(L.w16) : L.w, in, n, hh, ww, oh, ow, pad, act, nullptr, out, net->h->zeros);
+    a.in16 = in16; a.out16 = out16;
     return adaf_launch_conv_gemm(a, 0, net->h->cus, st) > 0 ? ADAF_OK : ADAF_E_LAUNCH;
 }
 
@@ -2070,7 +2011,7 @@ extern "C" {
 int adaf_effnet_create(adaf_handle* h, float width_coefficient, float depth_coefficient, adaf_effnet** out) {
     if (!h || !out) return ADAF_E_BADARG;
     if (!(width_coefficient >= 0.5f && width_coefficient <= 4.f && depth_coefficient >= 0.5f && depth_coefficient <= 8.f))
-        return efail(h, ADAF_E_BADARG, "effnet: width / depth coefficients out of range");
+        return adaf_fail(h, ADAF_E_BADARG, "effnet: width / depth coefficients out of range");
     adaf_effnet* net = new adaf_effnet();
     net->h = h;
     net->width = width_coefficient;
@@ -2082,7 +2023,7 @@ int adaf_effnet_create(adaf_handle* h, float width_coefficient, float depth_coef
 
 int adaf_effnet_destroy(adaf_effnet* net) {
     if (!net) return ADAF_OK;
-    for (void* p : net->slabs) (void)hipFree(p);
+    net->arena.release();
     net->aux.destroy();
     delete net;
     return ADAF_OK;
@@ -2154,7 +2095,7 @@ int adaf_effnet_fused_expand_blocks(const adaf_effnet* net, int size, int pad_si
 
 int adaf_effnet_set_dtype(adaf_effnet* net, int dtype) {
     if (!net) return ADAF_E_BADARG;
-    if (dtype != ADAF_DTYPE_F32 && dtype != ADAF_DTYPE_F16) return efail(net->h, ADAF_E_BADARG, "effnet: unknown dtype %d", dtype);
+    if (dtype != ADAF_DTYPE_F32 && dtype != ADAF_DTYPE_F16) return adaf_fail(net->h, ADAF_E_BADARG, "effnet: unknown dtype %d", dtype);
     if (dtype != net->dtype) net->finalized = false;
     net->dtype = dtype;
     return ADAF_OK;
@@ -2162,50 +2103,29 @@ int adaf_effnet_set_dtype(adaf_effnet* net, int dtype) {
 
 int adaf_effnet_set_param(adaf_effnet* net, const char* name, const float* dev_ptr, size_t numel) {
     if (!net || !name || !dev_ptr) return ADAF_E_BADARG;
-    net->params[name] = std::make_pair(dev_ptr, numel);
+    net->params.set(name, dev_ptr, numel);
     net->finalized = false;
     return ADAF_OK;
 }
 
-int adaf_effnet_finalize(adaf_effnet* net, void* stream) {
-    if (!net) return ADAF_E_BADARG;
+static int finalize_registered(adaf_effnet* net, void* stream) {
     adaf_handle* h = net->h;
     hipStream_t st = (hipStream_t)stream;
-    auto get = [&](const std::string& key, size_t numel, const float** p) -> int {
-        auto it = net->params.find(key);
-        if (it == net->params.end()) return efail(h, ADAF_E_STATE, "effnet: missing parameter '%s'", key.c_str());
-        if (it->second.second != numel)
-            return efail(h, ADAF_E_BADARG, "effnet: '%s' has %zu elements, expected %zu", key.c_str(), it->second.second, numel);
-        *p = it->second.first;
-        return ADAF_OK;
-    };
-    auto alloc = [&](float** p, size_t count) -> int {
-        if (!*p && !(*p = static_cast<float*>(net->carve(count * sizeof(float))))) return efail(h, ADAF_E_NOMEM, "effnet: hipMalloc");
-        return ADAF_OK;
-    };
+    AdafWeightArena& arena = net->arena;
+    auto get = [&](const std::string& key, size_t numel, const float** p) { return net->params.get(h, "effnet", key, numel, p); };
+    const auto nomem = [&] { return adaf_fail(h, ADAF_E_NOMEM, "effnet: hipMalloc packed weights"); };
     for (auto& L : net->convs) {
-        const float *w, *g, *b, *m, *v;
-        int rc;
-        const size_t wn_in = L.dw ? (size_t)L.cout * L.k * L.k : (size_t)L.cout * L.cin * L.k * L.k;
-        if ((rc = get(L.name + ".weight", wn_in, &w))) return rc;
-        if ((rc = get(L.name + ".bn.weight", L.cout, &g))) return rc;
-        if ((rc = get(L.name + ".bn.bias", L.cout, &b))) return rc;
-        if ((rc = get(L.name + ".bn.running_mean", L.cout, &m))) return rc;
-        if ((rc = get(L.name + ".bn.running_var", L.cout, &v))) return rc;
-        const size_t wn = L.dw ? (size_t)L.k * L.k * L.cout : (size_t)L.cout * L.k * L.k * L.cin_pad;
-        if ((rc = alloc(&L.w, wn)) || (rc = alloc(&L.scale, L.cout)) || (rc = alloc(&L.bias, L.cout))) return rc;
-        if (L.dw) adaf_launch_pack_dw_kxk(w, L.cout, L.k, L.w, st);
-        else adaf_launch_pack_weight(w, L.cout, L.cin, L.k, L.k, L.cin_pad, L.w, st);
+        const float* w;
+        if (int rc = adaf_pack_conv_bn(h, "effnet", net->params, arena, L, 1e-3f, st, &w)) return rc;     // utils.py: batch_norm_epsilon = 1e-3
         if (!L.dw && L.k == 1 && net->dtype == ADAF_DTYPE_F16) {
-            if (!L.w16 && !(L.w16 = net->carve(wn * sizeof(unsigned short)))) return efail(h, ADAF_E_NOMEM, "effnet: hipMalloc");
+            if (!arena.take(&L.w16, L.packed_floats())) return nomem();
             adaf_launch_pack_weight_f16(w, L.cout, L.cin, 1, 1, L.cin_pad, L.w16, st);
         }
-        adaf_launch_fold_bn(g, b, m, v, 1e-3f, L.cout, L.scale, L.bias, st);     // utils.py: batch_norm_epsilon = 1e-3
     }
     {
         const EfConv& S = net->convs[net->stem];
         if (S.cout <= 48 && S.k == 3 && S.cin_pad == 4) {
-            if (!net->stem_bank && !(net->stem_bank = static_cast<float*>(net->carve(64 * 24 * 4)))) return efail(h, ADAF_E_NOMEM, "effnet: hipMalloc");
+            if (!arena.take(&net->stem_bank, (size_t)64 * 24)) return nomem();
             adaf_launch_pack_stem_bank(S.w, S.cout, net->stem_bank, st);
         }
     }
@@ -2218,9 +2138,9 @@ int adaf_effnet_finalize(adaf_effnet* net, void* stream) {
         if ((rc = get(std::string(nm) + ".weight", (size_t)b.sq * b.hid, &wr)) || (rc = get(std::string(nm) + ".bias", b.sq, &br))) return rc;
         snprintf(nm, sizeof(nm), "b%zu.se_expand", bi);
         if ((rc = get(std::string(nm) + ".weight", (size_t)b.sq * b.hid, &we)) || (rc = get(std::string(nm) + ".bias", b.hid, &be))) return rc;
-        if ((rc = alloc(&b.se_wr, (size_t)b.sq * b.hid)) || (rc = alloc(&b.se_br, b.sq)) || (rc = alloc(&b.se_wet, (size_t)b.sq * b.hid)) ||
-            (rc = alloc(&b.se_be, b.hid)))
-            return rc;
+        if (!arena.take(&b.se_wr, (size_t)b.sq * b.hid) || !arena.take(&b.se_br, (size_t)b.sq) || !arena.take(&b.se_wet, (size_t)b.sq * b.hid) ||
+            !arena.take(&b.se_be, (size_t)b.hid))
+            return nomem();
         (void)hipMemcpyAsync(b.se_wr, wr, (size_t)b.sq * b.hid * 4, hipMemcpyDeviceToDevice, st);
         (void)hipMemcpyAsync(b.se_br, br, (size_t)b.sq * 4, hipMemcpyDeviceToDevice, st);
         (void)hipMemcpyAsync(b.se_be, be, (size_t)b.hid * 4, hipMemcpyDeviceToDevice, st);
@@ -2231,20 +2151,26 @@ int adaf_effnet_finalize(adaf_effnet* net, void* stream) {
             if ((rc = get(net->convs[b.expand].name + ".weight", (size_t)b.hid * b.cin, &wexp)) ||
                 (rc = get(net->convs[b.project].name + ".weight", (size_t)b.cout * b.hid, &wproj)))
                 return rc;
-            if (!b.wef && !(b.wef = net->carve(adaf_mbw_bfrag_halfs(b.hid, b.cin, true) * 2))) return efail(h, ADAF_E_NOMEM, "effnet: hipMalloc");
-            if (!b.wpf && !(b.wpf = net->carve(adaf_mbw_bfrag_halfs(b.cout, b.hid, false) * 2))) return efail(h, ADAF_E_NOMEM, "effnet: hipMalloc");
+            if (!arena.take(&b.wef, adaf_mbw_bfrag_halfs(b.hid, b.cin, true)) || !arena.take(&b.wpf, adaf_mbw_bfrag_halfs(b.cout, b.hid, false))) return nomem();
             adaf_launch_pack_bfrag_f16(wexp, b.hid, b.cin, true, b.wef, st);
             adaf_launch_pack_bfrag_f16(wproj, b.cout, b.hid, false, b.wpf, st);
-            if (!b.wdl && !(b.wdl = static_cast<float*>(net->carve((size_t)b.hid * adaf_mbw_tap_row(b.k) * 4)))) return efail(h, ADAF_E_NOMEM, "effnet: hipMalloc");
+            if (!arena.take(&b.wdl, (size_t)b.hid * adaf_mbw_tap_row(b.k))) return nomem();
             const EfConv& D = net->convs[b.dwc];
             adaf_launch_pack_dw_rows(D.w, D.scale, D.bias, b.hid, b.k, b.wdl, st);
         }
     }
     hipError_t e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return efail(h, ADAF_E_LAUNCH, "effnet finalize: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return adaf_hip_fail(h, e, "effnet finalize");
     net->aux.prepare(4);        // helper streams exist before the first forward (which may be captured into a HIP graph)
     net->finalized = true;
     return ADAF_OK;
+}
+
+int adaf_effnet_finalize(adaf_effnet* net, void* stream) {
+    if (!net) return ADAF_E_BADARG;
+    const int rc = finalize_registered(net, stream);
+    net->params.clear();       // a registration lives until here, whatever finalize returned (include/adafocus.h)
+    return rc;
 }
 
 size_t adaf_effnet_workspace_bytes(const adaf_effnet* net, int n, int size, int pad_size) {
@@ -2255,12 +2181,12 @@ int adaf_effnet_forward(adaf_effnet* net, const float* frames_nhwc4, int n, int 
                         float* featmap, float* featvec, int ldvec, void* ws, size_t ws_bytes, void* stream) {
     if (!net) return ADAF_E_BADARG;
     adaf_handle* h = net->h;
-    if (!net->finalized) return efail(h, ADAF_E_STATE, "effnet: finalize() has not been called");
-    if (!frames_nhwc4 || !ws) return efail(h, ADAF_E_BADARG, "effnet: null pointer");
-    if (n <= 0 || size < 32) return efail(h, ADAF_E_BADARG, "effnet: need n > 0 and size >= 32");
+    if (!net->finalized) return adaf_fail(h, ADAF_E_STATE, "effnet: finalize() has not been called");
+    if (!frames_nhwc4 || !ws) return adaf_fail(h, ADAF_E_BADARG, "effnet: null pointer");
+    if (n <= 0 || size < 32) return adaf_fail(h, ADAF_E_BADARG, "effnet: need n > 0 and size >= 32");
     if (pad_size <= 0) pad_size = size;
-    if (featvec && ldvec < net->feat) return efail(h, ADAF_E_LAYOUT, "effnet: ldvec >= %d required", net->feat);
-    if (upto_block >= 0 && !block_out) return efail(h, ADAF_E_BADARG, "effnet: upto_block needs block_out");
+    if (featvec && ldvec < net->feat) return adaf_fail(h, ADAF_E_LAYOUT, "effnet: ldvec >= %d required", net->feat);
+    if (upto_block >= 0 && !block_out) return adaf_fail(h, ADAF_E_BADARG, "effnet: upto_block needs block_out");
     const EfWorkspace W = workspace_layout(net, n, size, pad_size, ws);
     int rc = adaf_check_ws(h, "effnet", ws, ws_bytes, W.bytes, ADAF_WS_ALIGN_FIRST);
     if (rc) return rc;
@@ -2282,7 +2208,7 @@ int adaf_effnet_forward(adaf_effnet* net, const float* frames_nhwc4, int n, int 
         if (!(own_stem && adaf_launch_ef_stem(frames_nhwc4 + (size_t)f0 * size * size * 4, net->dtype, nc, size, hw, hw, pb0, S.w, net->stem_bank, S.scale, S.bias,
                                               S.cout, ADAF_ACT_SWISH, cur, st)) &&
             (rc = run_dense(net, S, frames_nhwc4 + (size_t)f0 * size * size * 4, false, nc, size, size, hw, hw, pb0, ADAF_ACT_SWISH, cur, f16, st)))
-            return efail(h, rc, "effnet: stem launch");
+            return adaf_fail(h, rc, "effnet: stem launch");
         size_t out_elems = (size_t)hw * hw * S.cout;
         for (size_t bi = 0; bi < net->blocks.size(); ++bi) {
             if (upto_block >= 0 && (int)bi >= upto_block) break;
@@ -2321,18 +2247,18 @@ int adaf_effnet_forward(adaf_effnet* net, const float* frames_nhwc4, int n, int 
                     if (!(own_expand && adaf_launch_ef_expand(cur, net->dtype, (long long)nc * hw * hw, b.cin, f16 ? E.w16 : static_cast<const void*>(E.w),
                                                               E.scale, E.bias, b.hid, ADAF_ACT_SWISH, bufE, net->h->cus, st)) &&
                         (rc = run_dense(net, E, cur, f16, nc, hw, hw, hw, hw, 0, ADAF_ACT_SWISH, bufE, f16, st)))
-                        return efail(h, rc, "effnet: expand launch (block %zu)", bi);
+                        return adaf_fail(h, rc, "effnet: expand launch (block %zu)", bi);
                     dw_in = bufE;
                 }
                 if (tiles <= 0)
                     tiles = adaf_launch_dw_same(dw_in, net->dtype, nc, hw, hw, b.hid, b.k, b.stride, pbd, pbd, ohw, ohw, D.w, D.scale,
                                                 D.bias, ADAF_ACT_SWISH, bufD, part, st);
             }
-            if (tiles <= 0) return efail(h, ADAF_E_LAUNCH, "effnet: depthwise launch (block %zu)", bi);
+            if (tiles <= 0) return adaf_fail(h, ADAF_E_LAUNCH, "effnet: depthwise launch (block %zu)", bi);
             adaf_launch_se_gate(part, tiles, ohw * ohw, nc, b.hid, b.se_wr, b.se_br, b.sq, b.se_wet, 1, b.hid, b.se_be, gate, st);
             if (adaf_launch_gated_project(bufD, net->dtype, nc * ohw * ohw, ohw * ohw, b.hid, gate, f16 ? P.w16 : static_cast<const void*>(P.w),
                                           b.cout, P.scale, P.bias, skip ? cur : nullptr, nxt, st) < 0)
-                return efail(h, ADAF_E_LAUNCH, "effnet: project launch (block %zu)", bi);
+                return adaf_fail(h, ADAF_E_LAUNCH, "effnet: project launch (block %zu)", bi);
             char* t = cur; cur = nxt; nxt = t;
             hw = ohw;
             ps = ceil_div(ps, b.stride);
@@ -2348,18 +2274,12 @@ int adaf_effnet_forward(adaf_effnet* net, const float* frames_nhwc4, int n, int 
         // adaf_launch_conv_pool16: no fp32 map -- 157 MB per 1024 patches of 144^2 -- and one launch; the bits of conv + avgpool_kernel)
         if (f16 && featvec && !featmap && (plan & ADAF_EF_PLAN_HEAD_POOL) && net->feat % 4 == 0 && ldvec % 4 == 0) {
             const EfConv& Hc = net->convs[net->head];
-            ConvArgs a;
-            memset(&a, 0, sizeof(a));
-            a.x = reinterpret_cast<const float*>(cur); a.w = reinterpret_cast<const float*>(Hc.w16);
-            a.scale = Hc.scale; a.bias = Hc.bias;
-            a.M = nc * hw * hw; a.N = Hc.cout; a.K = Hc.cin_pad;
-            a.cin = Hc.cin_pad; a.H = a.OH = hw; a.W = a.OW = hw; a.KH = a.KW = 1; a.stride = 1;
-            a.ldx = Hc.cin_pad; a.ldo = Hc.cout; a.ldr = Hc.cout; a.act = ADAF_ACT_SWISH;
-            a.zeros = net->h->zeros; a.vec_epi = 1; a.in16 = 1;
+            ConvArgs a = adaf_net_conv_args(Hc, Hc.w16, cur, nc, hw, hw, hw, hw, 0, ADAF_ACT_SWISH, nullptr, nullptr, net->h->zeros);
+            a.in16 = 1;
             if (adaf_launch_conv_pool16(a, hw * hw, featvec + (size_t)f0 * ldvec, ldvec, st)) return ADAF_OK;
         }
         if ((rc = run_dense(net, net->convs[net->head], cur, f16, nc, hw, hw, hw, hw, 0, ADAF_ACT_SWISH, fm, false, st)))
-            return efail(h, rc, "effnet: head launch");
+            return adaf_fail(h, rc, "effnet: head launch");
         if (featvec) {
             if (net->feat % 4 == 0 && ldvec % 4 == 0) adaf_launch_avgpool(fm, nc, hw * hw, net->feat, featvec + (size_t)f0 * ldvec, ldvec, st);
             else hipLaunchKernelGGL((avgpool_any_kernel<float>), dim3((unsigned)(((size_t)nc * net->feat + 255) / 256)), dim3(256), 0, st, fm, nc,
@@ -2370,12 +2290,12 @@ int adaf_effnet_forward(adaf_effnet* net, const float* frames_nhwc4, int n, int 
     const bool pair = (adaf_options().effnet_plan & ADAF_EF_PLAN_PAIR_CHUNKS) != 0;
     if ((rc = adaf_run_chunk_pairs(net->aux, (hipStream_t)stream, n, W.chunk, pair, run_chunk))) return rc;
     hipError_t e = hipGetLastError();
-    return e == hipSuccess ? ADAF_OK : efail(h, ADAF_E_LAUNCH, "effnet forward: %s", hipGetErrorString(e));
+    return e == hipSuccess ? ADAF_OK : adaf_hip_fail(h, e, "effnet forward");
 }
 
 // ---- stand-alone ops (tests, and building blocks for other MBConv networks) ---------------------------------------------
 int adaf_pack_dw_weight_kxk_f32(adaf_handle* h, const float* w_c1kk, int channels, int k, float* w_kkc, void* stream) {
-    if (!h || !w_c1kk || !w_kkc || channels <= 0 || k <= 0) return efail(h, ADAF_E_BADARG, "pack_dw_kxk: bad argument");
+    if (!h || !w_c1kk || !w_kkc || channels <= 0 || k <= 0) return adaf_fail(h, ADAF_E_BADARG, "pack_dw_kxk: bad argument");
     adaf_launch_pack_dw_kxk(w_c1kk, channels, k, w_kkc, (hipStream_t)stream);
     return ADAF_OK;
 }
@@ -2397,48 +2317,48 @@ size_t adaf_dwconv_same_workspace_bytes(int n, int hh, int ww, int c, int k, int
 int adaf_dwconv_same_bn_act(adaf_handle* h, const void* x, int dtype, int n, int hh, int ww, int c, int k, int stride, const float* w_kkc,
                             const float* scale, const float* bias, int act, void* out, float* pool_mean, void* ws, size_t ws_bytes,
                             void* stream) {
-    if (!h || !x || !w_kkc || !scale || !bias || !out) return efail(h, ADAF_E_BADARG, "dwconv_same: null pointer");
+    if (!h || !x || !w_kkc || !scale || !bias || !out) return adaf_fail(h, ADAF_E_BADARG, "dwconv_same: null pointer");
     if (n <= 0 || hh <= 0 || ww <= 0 || c <= 0 || (k != 3 && k != 5) || (stride != 1 && stride != 2))
-        return efail(h, ADAF_E_BADARG, "dwconv_same: k in {3, 5}, stride in {1, 2}");
-    if (dtype != ADAF_DTYPE_F32 && dtype != ADAF_DTYPE_F16) return efail(h, ADAF_E_BADARG, "dwconv_same: dtype");
-    if (c % (dtype == ADAF_DTYPE_F16 ? 8 : 4)) return efail(h, ADAF_E_LAYOUT, "dwconv_same: channels must fill 16-byte chunks");
-    if (act < ADAF_ACT_NONE || act > ADAF_ACT_SWISH) return efail(h, ADAF_E_BADARG, "dwconv_same: activation");
+        return adaf_fail(h, ADAF_E_BADARG, "dwconv_same: k in {3, 5}, stride in {1, 2}");
+    if (dtype != ADAF_DTYPE_F32 && dtype != ADAF_DTYPE_F16) return adaf_fail(h, ADAF_E_BADARG, "dwconv_same: dtype");
+    if (c % (dtype == ADAF_DTYPE_F16 ? 8 : 4)) return adaf_fail(h, ADAF_E_LAYOUT, "dwconv_same: channels must fill 16-byte chunks");
+    if (act < ADAF_ACT_NONE || act > ADAF_ACT_SWISH) return adaf_fail(h, ADAF_E_BADARG, "dwconv_same: activation");
     int ty, tx;
     const int pt = same_pad(hh, k, stride, &ty), pl = same_pad(ww, k, stride, &tx);
     const int oh = ceil_div(hh, stride), ow = ceil_div(ww, stride);
     float* part = nullptr;
     if (pool_mean) {        // (only the pooled means have a workspace)
-        if (!ws) return efail(h, ADAF_E_NOMEM, "dwconv_same: workspace");
+        if (!ws) return adaf_fail(h, ADAF_E_NOMEM, "dwconv_same: workspace");
         const int rc = adaf_check_ws(h, "dwconv_same", ws, ws_bytes, dwconv_same_layout(ws, n, hh, ww, c, k, stride, dtype, &part), ADAF_WS_ALIGN_FIRST);
         if (rc) return rc;
     }
     const int tiles = adaf_launch_dw_same(x, dtype, n, hh, ww, c, k, stride, pt, pl, oh, ow, w_kkc, scale, bias, act, out, part, (hipStream_t)stream);
-    if (tiles <= 0) return efail(h, ADAF_E_LAYOUT, "dwconv_same: shape not supported");
+    if (tiles <= 0) return adaf_fail(h, ADAF_E_LAYOUT, "dwconv_same: shape not supported");
     if (pool_mean) adaf_launch_pool_finish(part, n, tiles, c, oh * ow, pool_mean, (hipStream_t)stream);
     hipError_t e = hipGetLastError();
-    return e == hipSuccess ? ADAF_OK : efail(h, ADAF_E_LAUNCH, "dwconv_same: %s", hipGetErrorString(e));
+    return e == hipSuccess ? ADAF_OK : adaf_hip_fail(h, e, "dwconv_same");
 }
 
 int adaf_se_gate_f32(adaf_handle* h, const float* pool_mean, int n, int c, const float* w_reduce, const float* b_reduce, int squeezed,
                      const float* w_expand, const float* b_expand, float* gate, void* stream) {
-    if (!h || !pool_mean || !w_reduce || !b_reduce || !w_expand || !b_expand || !gate) return efail(h, ADAF_E_BADARG, "se_gate: null pointer");
-    if (n <= 0 || c <= 0 || c % 4 || squeezed <= 0 || (size_t)(c + squeezed) * 16 > 60 * 1024) return efail(h, ADAF_E_BADARG, "se_gate: extents (c %% 4 == 0)");
+    if (!h || !pool_mean || !w_reduce || !b_reduce || !w_expand || !b_expand || !gate) return adaf_fail(h, ADAF_E_BADARG, "se_gate: null pointer");
+    if (n <= 0 || c <= 0 || c % 4 || squeezed <= 0 || (size_t)(c + squeezed) * 16 > 60 * 1024) return adaf_fail(h, ADAF_E_BADARG, "se_gate: extents (c %% 4 == 0)");
     adaf_launch_se_gate(pool_mean, 1, 1, n, c, w_reduce, b_reduce, squeezed, w_expand, squeezed, 1, b_expand, gate, (hipStream_t)stream);
     hipError_t e = hipGetLastError();
-    return e == hipSuccess ? ADAF_OK : efail(h, ADAF_E_LAUNCH, "se_gate: %s", hipGetErrorString(e));
+    return e == hipSuccess ? ADAF_OK : adaf_hip_fail(h, e, "se_gate");
 }
 
 int adaf_conv1x1_gated_bn(adaf_handle* h, const void* x, int dtype, int n_images, int hw, int cin, const float* gate, const void* w,
                           int cout, const float* scale, const float* bias, const void* residual, void* out, void* stream) {
-    if (!h || !x || !w || !out) return efail(h, ADAF_E_BADARG, "conv1x1_gated: null pointer");
-    if (dtype != ADAF_DTYPE_F32 && dtype != ADAF_DTYPE_F16) return efail(h, ADAF_E_BADARG, "conv1x1_gated: dtype");
+    if (!h || !x || !w || !out) return adaf_fail(h, ADAF_E_BADARG, "conv1x1_gated: null pointer");
+    if (dtype != ADAF_DTYPE_F32 && dtype != ADAF_DTYPE_F16) return adaf_fail(h, ADAF_E_BADARG, "conv1x1_gated: dtype");
     if (n_images <= 0 || hw <= 0 || cin <= 0 || cout <= 0 || cin % (dtype == ADAF_DTYPE_F16 ? 8 : 4))
-        return efail(h, ADAF_E_LAYOUT, "conv1x1_gated: cin must fill 16-byte chunks");
-    if ((long long)n_images * hw > 0x7fffffffLL) return efail(h, ADAF_E_BADARG, "conv1x1_gated: too many rows");
+        return adaf_fail(h, ADAF_E_LAYOUT, "conv1x1_gated: cin must fill 16-byte chunks");
+    if ((long long)n_images * hw > 0x7fffffffLL) return adaf_fail(h, ADAF_E_BADARG, "conv1x1_gated: too many rows");
     if (adaf_launch_gated_project(x, dtype, n_images * hw, hw, cin, gate, w, cout, scale, bias, residual, out, (hipStream_t)stream) < 0)
-        return efail(h, ADAF_E_LAYOUT, "conv1x1_gated: shape not supported");
+        return adaf_fail(h, ADAF_E_LAYOUT, "conv1x1_gated: shape not supported");
     hipError_t e = hipGetLastError();
-    return e == hipSuccess ? ADAF_OK : efail(h, ADAF_E_LAUNCH, "conv1x1_gated: %s", hipGetErrorString(e));
+    return e == hipSuccess ? ADAF_OK : adaf_hip_fail(h, e, "conv1x1_gated");
 }
 
 }  // extern "C"

@@ -241,12 +241,12 @@ __global__ void segment_mean_kernel(const float* __restrict__ logit, int B, int 
     out[idx] = r;
 }
 
-// [C,1,3,3] (PyTorch depthwise) -> [3][3][C]
-__global__ void pack_dw_weight_kernel(const float* __restrict__ w, int c, float* __restrict__ o) {
+// [C,1,K,K] (PyTorch depthwise) -> [K*K][C]
+__global__ void pack_dw_kxk_kernel(const float* __restrict__ w, int c, int kk, float* __restrict__ o) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= 9 * c) return;
+    if (idx >= kk * c) return;
     const int ch = idx % c, tap = idx / c;
-    o[idx] = w[ch * 9 + tap];
+    o[idx] = w[(size_t)ch * kk + tap];
 }
 
 // Depthwise 3x3 (pad 1, stride 1|2) + BN affine + ReLU6|ReLU|none, NHWC, 4 channels x PX output pixels per thread.
@@ -434,9 +434,10 @@ void adaf_launch_segment_mean(const float* logit, int B, int T, int C, const flo
                        out);
 }
 
-void adaf_launch_pack_dw_weight(const float* w, int c, float* o, hipStream_t s) {
-    hipLaunchKernelGGL(pack_dw_weight_kernel, dim3(blocks_for(9LL * c)), dim3(256), 0, s, w, c, o);
+void adaf_launch_pack_dw_kxk(const float* w, int c, int k, float* o, hipStream_t s) {
+    hipLaunchKernelGGL(pack_dw_kxk_kernel, dim3(blocks_for((long long)k * k * c)), dim3(256), 0, s, w, c, k * k, o);
 }
+void adaf_launch_pack_dw_weight(const float* w, int c, float* o, hipStream_t s) { adaf_launch_pack_dw_kxk(w, c, 3, o, s); }
 
 void adaf_launch_dwconv3x3(const float* x, int n, int h, int w, int c, int stride, const float* wt, const float* scale,
                            const float* bias, int act, float* o, hipStream_t s) {

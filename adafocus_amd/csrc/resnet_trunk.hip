@@ -3,28 +3,21 @@
 // conv_lat.hip, stem.hip, misc_ops.hip and crop.hip.  No PyTorch types, no allocation in forward calls.
 #include <cstdio>
 #include <cstring>
-#include <map>
 #include <string>
 #include <vector>
 
-#include "adaf_internal.h"
+#include "adaf_net.h"
 
-struct ConvLayer {
-    std::string name;      // e.g. "layer1.0.conv1"
-    std::string bn;        // e.g. "layer1.0.bn1"
-    int cin, cout, k, stride, pad;
-    int cin_pad;
+struct ConvLayer : AdafNetConv {     // (w16: the packed bank rounded to fp16, nearest-even -- ADAF_MATH_F16 only; not for the stem)
+    int pad;
     bool tsm = false;      // a Bottleneck conv1 that the 'blockres' temporal shift wraps (make_temporal_shift's n_round rule)
-    float* w = nullptr;    // packed OHWI
-    unsigned short* wsp = nullptr;   // the same as three bf16 planes (ADAF_MATH_F32_SPLIT_BF16 only)
-    unsigned short* w16 = nullptr;   // the same rounded to fp16, nearest-even (ADAF_MATH_F16 only; not for the stem)
-    float* scale = nullptr;
-    float* bias = nullptr;
+    unsigned short* wsp = nullptr;   // the packed bank as three bf16 planes (ADAF_MATH_F32_SPLIT_BF16 only)
 };
 
 struct adaf_resnet50 {
     adaf_handle* h = nullptr;
-    std::map<std::string, std::pair<const float*, size_t>> params;
+    AdafParamTable params;         // what set_param registered since the last finalize
+    AdafWeightArena arena;         // every packed buffer below and in convs
     std::vector<ConvLayer> convs;  // [0] = stem, then per block conv1, conv2, conv3, (downsample)
     std::vector<int> tiles;        // per conv launch override
     int blocks[4] = {3, 4, 6, 3};  // Bottlenecks per stage: ResNet-50, -101 or -152 (inferred from the parameter names at finalize)
@@ -53,7 +46,10 @@ int total_blocks(const adaf_resnet50* net) { return net->blocks[0] + net->blocks
 
 void build_layers(adaf_resnet50* net) {
     net->convs.clear();
-    net->convs.push_back({"conv1", "bn1", 3, 64, 7, 2, 3, 4});
+    auto add = [&](const std::string& name, const std::string& bn, int cin, int cout, int k, int stride, int pad, int cin_pad, bool tsm = false) {
+        net->convs.push_back({{name, bn, cin, cout, k, stride, false, cin_pad}, pad, tsm});
+    };
+    add("conv1", "bn1", 3, 64, 7, 2, 3, 4);
     // make_temporal_shift, place 'blockres' (STH/ops/temporal_shift.py:122-136): a layer3 of 23 or more blocks gives n_round = 2,
     // and block i of every stage has its conv1 shifted iff i % n_round == 0
     const int n_round = net->blocks[2] >= 23 ? 2 : 1;
@@ -65,31 +61,14 @@ void build_layers(adaf_resnet50* net) {
             snprintf(pre, sizeof(pre), "layer%d.%d.", s + 1, b);
             const int stride = (b == 0 && s > 0) ? 2 : 1;
             const std::string p(pre);
-            net->convs.push_back({p + "conv1", p + "bn1", inplanes, planes, 1, 1, 0, inplanes, b % n_round == 0});
-            net->convs.push_back({p + "conv2", p + "bn2", planes, planes, 3, stride, 1, planes});
-            net->convs.push_back({p + "conv3", p + "bn3", planes, planes * 4, 1, 1, 0, planes});
-            if (b == 0) net->convs.push_back({p + "downsample.0", p + "downsample.1", inplanes, planes * 4, 1, stride, 0, inplanes});
+            add(p + "conv1", p + "bn1", inplanes, planes, 1, 1, 0, inplanes, b % n_round == 0);
+            add(p + "conv2", p + "bn2", planes, planes, 3, stride, 1, planes);
+            add(p + "conv3", p + "bn3", planes, planes * 4, 1, 1, 0, planes);
+            if (b == 0) add(p + "downsample.0", p + "downsample.1", inplanes, planes * 4, 1, stride, 0, inplanes);
             inplanes = planes * 4;
         }
     }
     net->tiles.assign(net->convs.size(), 0);
-}
-
-// Releases the device buffers of every conv of the plan (the plan itself is dropped or rebuilt by the caller).
-void free_layers(adaf_resnet50* net) {
-    for (auto& L : net->convs) {
-        if (L.w) (void)hipFree(L.w);
-        if (L.wsp) (void)hipFree(L.wsp);
-        if (L.w16) (void)hipFree(L.w16);
-        if (L.scale) (void)hipFree(L.scale);
-        if (L.bias) (void)hipFree(L.bias);
-    }
-}
-
-// A device buffer of `count` elements on first use (finalize and set_math may run again over the same plan); false = out of memory
-template <typename T>
-bool dev_alloc(T** p, size_t count) {
-    return *p || hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T)) == hipSuccess;
 }
 
 struct Launch {   // one enqueued kernel of the forward pass, for the profiler
@@ -411,19 +390,14 @@ int adaf_resnet50_create(adaf_handle* h, adaf_resnet50** out) {
 
 int adaf_resnet50_destroy(adaf_resnet50* net) {
     if (!net) return ADAF_OK;
-    if (net->stem_w) (void)hipFree(net->stem_w);
-    if (net->l10_w) (void)hipFree(net->l10_w);
-    if (net->l10_scale) (void)hipFree(net->l10_scale);
-    if (net->l10_bias) (void)hipFree(net->l10_bias);
-    if (net->l10_w16) (void)hipFree(net->l10_w16);
-    free_layers(net);
+    net->arena.release();
     delete net;
     return ADAF_OK;
 }
 
 int adaf_resnet50_set_param(adaf_resnet50* net, const char* name, const float* dev_ptr, size_t numel) {
     if (!net || !name || !dev_ptr) return ADAF_E_BADARG;
-    net->params[name] = std::make_pair(dev_ptr, numel);
+    net->params.set(name, dev_ptr, numel);
     net->finalized = false;
     return ADAF_OK;
 }
@@ -434,8 +408,8 @@ static int split_weights(adaf_resnet50* net, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     for (size_t i = 1; i < net->convs.size(); ++i) {
         ConvLayer& L = net->convs[i];
-        const size_t wn = (size_t)L.cout * L.k * L.k * L.cin_pad;
-        if (!dev_alloc(&L.wsp, 3 * wn))
+        const size_t wn = L.packed_floats();
+        if (!net->arena.take(&L.wsp, 3 * wn))
             return adaf_fail(h, ADAF_E_NOMEM, "resnet50: hipMalloc split weights");
         adaf_launch_split_weight(L.w, wn, L.wsp, st);
     }
@@ -451,15 +425,15 @@ static int f16_weights(adaf_resnet50* net, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     for (size_t i = 1; i < net->convs.size(); ++i) {
         ConvLayer& L = net->convs[i];
-        const size_t wn = (size_t)L.cout * L.k * L.k * L.cin_pad;
-        if (!dev_alloc(&L.w16, wn))
+        const size_t wn = L.packed_floats();
+        if (!net->arena.take(&L.w16, wn))
             return adaf_fail(h, ADAF_E_NOMEM, "resnet50: hipMalloc fp16 weights");
         adaf_launch_cast(L.w, (long long)wn, L.w16, 1, st);
     }
     if (net->l10_w) {
         const ConvLayer &C1 = net->convs[1], &DS = net->convs[4];
         const size_t wn = (size_t)C1.cout * C1.cin_pad + (size_t)DS.cout * DS.cin_pad;
-        if (!dev_alloc(&net->l10_w16, wn))
+        if (!net->arena.take(&net->l10_w16, wn))
             return adaf_fail(h, ADAF_E_NOMEM, "resnet50: hipMalloc merged fp16 filters");
         adaf_launch_cast(net->l10_w, (long long)wn, net->l10_w16, 1, st);
     }
@@ -468,18 +442,9 @@ static int f16_weights(adaf_resnet50* net, void* stream) {
     return ADAF_OK;
 }
 
-int adaf_resnet50_finalize(adaf_resnet50* net, void* stream) {
-    if (!net) return ADAF_E_BADARG;
+static int finalize_registered(adaf_resnet50* net, void* stream) {
     adaf_handle* h = net->h;
     hipStream_t st = (hipStream_t)stream;
-    auto get = [&](const std::string& key, size_t numel, const float** p) -> int {
-        auto it = net->params.find(key);
-        if (it == net->params.end()) return adaf_fail(h, ADAF_E_STATE, "resnet50: missing parameter '%s'", key.c_str());
-        if (it->second.second != numel)
-            return adaf_fail(h, ADAF_E_BADARG, "resnet50: '%s' has %zu elements, expected %zu", key.c_str(), it->second.second, numel);
-        *p = it->second.first;
-        return ADAF_OK;
-    };
     // the depth: the highest "layerS.B." block index registered per stage
     int found[4] = {0, 0, 0, 0};
     for (const auto& kv : net->params) {
@@ -487,33 +452,26 @@ int adaf_resnet50_finalize(adaf_resnet50* net, void* stream) {
         if (sscanf(kv.first.c_str(), "layer%d.%d.%n", &s, &b, &len) == 2 && len > 0 && s >= 1 && s <= 4 && b >= 0 && b + 1 > found[s - 1])
             found[s - 1] = b + 1;
     }
+    // (a registration that names no Bottleneck says nothing about the depth: the plan's own, and the packer names what is missing)
+    if (!(found[0] | found[1] | found[2] | found[3])) memcpy(found, net->blocks, sizeof(found));
     int depth = -1;
     for (int d = 0; d < 3; ++d)
         if (!memcmp(found, kDepths[d], sizeof(found))) depth = d;
     if (depth < 0)
         return adaf_fail(h, ADAF_E_BADARG, "resnet50: parameters name {%d, %d, %d, %d} Bottlenecks per stage; the trunk runs {3, 4, 6, 3} (ResNet-50), "
                     "{3, 4, 23, 3} (ResNet-101) or {3, 8, 36, 3} (ResNet-152)", found[0], found[1], found[2], found[3]);
-    if (memcmp(found, net->blocks, sizeof(found))) {   // another depth than the plan holds: drop its packed filters, rebuild the plan
-        free_layers(net);
+    if (memcmp(found, net->blocks, sizeof(found))) {   // another depth than the plan holds: drop every packed buffer, rebuild the plan
+        net->arena.release();
+        net->stem_w = net->l10_w = net->l10_scale = net->l10_bias = nullptr;
+        net->l10_w16 = nullptr;
         memcpy(net->blocks, found, sizeof(found));
         build_layers(net);
     }
     for (auto& L : net->convs) {
-        const float *w, *g, *b, *m, *v;
-        int rc;
-        if ((rc = get(L.name + ".weight", (size_t)L.cout * L.cin * L.k * L.k, &w))) return rc;
-        if ((rc = get(L.bn + ".weight", L.cout, &g))) return rc;
-        if ((rc = get(L.bn + ".bias", L.cout, &b))) return rc;
-        if ((rc = get(L.bn + ".running_mean", L.cout, &m))) return rc;
-        if ((rc = get(L.bn + ".running_var", L.cout, &v))) return rc;
-        const size_t wn = (size_t)L.cout * L.k * L.k * L.cin_pad;
-        if (!dev_alloc(&L.w, wn)) return adaf_fail(h, ADAF_E_NOMEM, "resnet50: hipMalloc weights");
-        if (!dev_alloc(&L.scale, L.cout)) return adaf_fail(h, ADAF_E_NOMEM, "resnet50: hipMalloc scale");
-        if (!dev_alloc(&L.bias, L.cout)) return adaf_fail(h, ADAF_E_NOMEM, "resnet50: hipMalloc bias");
-        adaf_launch_pack_weight(w, L.cout, L.cin, L.k, L.k, L.cin_pad, L.w, st);
-        adaf_launch_fold_bn(g, b, m, v, 1e-5f, L.cout, L.scale, L.bias, st);
+        const float* w;
+        if (int rc = adaf_pack_conv_bn(h, "resnet50", net->params, net->arena, L, 1e-5f, st, &w)) return rc;
         if (&L == &net->convs[0]) {
-            if (!dev_alloc(&net->stem_w, adaf_stem_weight_floats()))
+            if (!net->arena.take(&net->stem_w, adaf_stem_weight_floats()))
                 return adaf_fail(h, ADAF_E_NOMEM, "resnet50: hipMalloc stem weights");
             adaf_launch_pack_stem_weight(w, net->stem_w, st);
         }
@@ -523,7 +481,7 @@ int adaf_resnet50_finalize(adaf_resnet50* net, void* stream) {
         if (C1.k == 1 && DS.k == 1 && C1.stride == 1 && DS.stride == 1 && C1.cin_pad == DS.cin_pad && C1.cout % 64 == 0) {
             const size_t n1 = (size_t)C1.cout * C1.cin_pad, n2 = (size_t)DS.cout * DS.cin_pad;
             const int cm = C1.cout + DS.cout;
-            if (!dev_alloc(&net->l10_w, n1 + n2) || !dev_alloc(&net->l10_scale, cm) || !dev_alloc(&net->l10_bias, cm))
+            if (!net->arena.take(&net->l10_w, n1 + n2) || !net->arena.take(&net->l10_scale, (size_t)cm) || !net->arena.take(&net->l10_bias, (size_t)cm))
                 return adaf_fail(h, ADAF_E_NOMEM, "resnet50: hipMalloc merged layer1.0 filters");
             (void)hipMemcpyAsync(net->l10_w, C1.w, n1 * sizeof(float), hipMemcpyDeviceToDevice, st);
             (void)hipMemcpyAsync(net->l10_w + n1, DS.w, n2 * sizeof(float), hipMemcpyDeviceToDevice, st);
@@ -539,6 +497,13 @@ int adaf_resnet50_finalize(adaf_resnet50* net, void* stream) {
     if (net->math == ADAF_MATH_F32_SPLIT_BF16) return split_weights(net, stream);
     if (net->math == ADAF_MATH_F16) return f16_weights(net, stream);
     return ADAF_OK;
+}
+
+int adaf_resnet50_finalize(adaf_resnet50* net, void* stream) {
+    if (!net) return ADAF_E_BADARG;
+    const int rc = finalize_registered(net, stream);
+    net->params.clear();       // a registration lives until here, whatever finalize returned (include/adafocus.h)
+    return rc;
 }
 
 size_t adaf_resnet50_workspace_bytes(const adaf_resnet50* net, int n, int patch) {

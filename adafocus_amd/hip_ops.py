@@ -424,42 +424,67 @@ class _StreamScratch:
         return len(self._ws)
 
 
-class ResNet50Trunk:
-    """adaf_resnet50: the whole local CNN (stem ... layer4, avgpool) as ~55 back-to-back launches on
-    one stream, weights packed / BN folded once.  Replaces ResNet.get_featmap(x, pooled=True)
-    (ACT/models/resnet.py:211-225) and TSN.forward(no_reshape=True) (STH/models/tsn.py:215-241)."""
+class _NetEngine:
+    """What the three network objects of the C ABI share: device / handle / library / per-stream scratch, the object's life and
+    load().  A subclass names its symbols' stem (adaf_<_ABI>_create / _destroy / _set_param / _finalize)."""
+    _ABI = None
 
-    def __init__(self, device):
+    def __init__(self, device, *create_args):
         self.device = torch.device(device)
         self._h = L.handle(self.device)
         self._lib = L.load_library()
         net = C.c_void_p()
-        L.check(self._lib.adaf_resnet50_create(self._h, C.byref(net)), self._h)
+        L.check(self._sym("create")(self._h, *create_args, C.byref(net)), self._h)
         self._net = net
         self._scratch = _StreamScratch(self.device)
-        self.n_launches = self._lib.adaf_resnet50_launch_count(net)
+
+    def _sym(self, what):
+        return getattr(self._lib, "adaf_%s_%s" % (self._ABI, what))
 
     def __del__(self):
         try:
             if getattr(self, "_net", None):
-                self._lib.adaf_resnet50_destroy(self._net)
+                self._sym("destroy")(self._net)
                 self._net = None
         except Exception:
             pass
 
+    def _wanted(self, name):
+        return True
+
     def load(self, params):
-        """params: mapping torchvision-style name -> tensor (on this device).  Non-trunk entries
-        (fc.*, num_batches_tracked) are ignored."""
+        """params: mapping parameter name -> fp32 tensor on this device.  The library reads them during finalize only (packed
+        copies; include/adafocus.h), so every load registers the full set and the tensors may go when it returns."""
         keep = []
         for name, t in params.items():
-            if name.startswith("fc.") or name.endswith("num_batches_tracked"):
+            if not self._wanted(name):
                 continue
             L.need_gpu_f32(t)
             t = t.detach().contiguous()
             keep.append(t)
-            L.check(self._lib.adaf_resnet50_set_param(self._net, name.encode(), L.ptr(t), t.numel()), self._h)
-        L.check(self._lib.adaf_resnet50_finalize(self._net, L.stream_ptr()), self._h)
+            L.check(self._sym("set_param")(self._net, name.encode(), L.ptr(t), t.numel()), self._h)
+        L.check(self._sym("finalize")(self._net, L.stream_ptr()), self._h)
         del keep
+
+
+class ResNet50Trunk(_NetEngine):
+    """adaf_resnet50: the whole local CNN (stem ... layer4, avgpool) as ~55 back-to-back launches on
+    one stream, weights packed / BN folded once.  Replaces ResNet.get_featmap(x, pooled=True)
+    (ACT/models/resnet.py:211-225) and TSN.forward(no_reshape=True) (STH/models/tsn.py:215-241)."""
+    _ABI = "resnet50"
+
+    def __init__(self, device):
+        super().__init__(device)
+        self.n_launches = self._lib.adaf_resnet50_launch_count(self._net)
+
+    def _wanted(self, name):
+        return not (name.startswith("fc.") or name.endswith("num_batches_tracked"))
+
+    def load(self, params):
+        """params: mapping torchvision-style name -> tensor (on this device).  Non-trunk entries
+        (fc.*, num_batches_tracked) are ignored.  The names give the depth (ResNet-50, -101 or -152)."""
+        super().load(params)
+        self.n_launches = self._lib.adaf_resnet50_launch_count(self._net)
 
     def _workspace(self, n, patch):
         """One scratch buffer per HIP stream: passes enqueued on different streams (pipelined batches)
@@ -649,36 +674,10 @@ def gru_seq_forward(x, w_ih, w_hh, b_ih, b_hh, h0=None):
     return hs
 
 
-class MobileNetV2Net:
-    """adaf_mobilenetv2: the glancer's feature extractor on the conv engine + depthwise kernel."""
-
-    def __init__(self, device):
-        self.device = torch.device(device)
-        self._h = L.handle(self.device)
-        self._lib = L.load_library()
-        net = C.c_void_p()
-        L.check(self._lib.adaf_mobilenetv2_create(self._h, C.byref(net)), self._h)
-        self._net = net
-        self._scratch = _StreamScratch(self.device)
-
-    def __del__(self):
-        try:
-            if getattr(self, "_net", None):
-                self._lib.adaf_mobilenetv2_destroy(self._net)
-                self._net = None
-        except Exception:
-            pass
-
-    def load(self, params):
-        """params: neutral name ('stem.weight', 'b3.dw.bn.running_var', ...) -> tensor on this device."""
-        keep = []
-        for name, t in params.items():
-            L.need_gpu_f32(t)
-            t = t.detach().contiguous()
-            keep.append(t)
-            L.check(self._lib.adaf_mobilenetv2_set_param(self._net, name.encode(), L.ptr(t), t.numel()), self._h)
-        L.check(self._lib.adaf_mobilenetv2_finalize(self._net, L.stream_ptr()), self._h)
-        del keep
+class MobileNetV2Net(_NetEngine):
+    """adaf_mobilenetv2: the glancer's feature extractor on the conv engine + depthwise kernel.
+    load(): neutral name ('stem.weight', 'b3.dw.bn.running_var', ...) -> tensor on this device."""
+    _ABI = "mobilenetv2"
 
     def set_fusion(self, on):
         """Expand 1x1 -> depthwise 3x3 in one kernel for the high-resolution blocks (default on)."""
@@ -943,28 +942,15 @@ def conv1x1_gated_bn(x, gate, w, scale=None, bias=None, residual=None):
     return out
 
 
-class EffNetNet:
+class EffNetNet(_NetEngine):
     """adaf_effnet: EfficientNet feature extractor (MBConv + squeeze-and-excite + swish; csrc/effnet.hip)."""
+    _ABI = "effnet"
 
     def __init__(self, device, width, depth):
-        self.device = torch.device(device)
-        self._h = L.handle(self.device)
-        self._lib = L.load_library()
-        net = C.c_void_p()
-        L.check(self._lib.adaf_effnet_create(self._h, C.c_float(width), C.c_float(depth), C.byref(net)), self._h)
-        self._net = net
-        self._scratch = _StreamScratch(self.device)
-        self.feature_dim = self._lib.adaf_effnet_feature_dim(net)
+        super().__init__(device, C.c_float(width), C.c_float(depth))
+        self.feature_dim = self._lib.adaf_effnet_feature_dim(self._net)
         self.dtype = DTYPE_F32
         self.pad_size = 0          # default image size the SAME padding is computed for (0 = the input's own); the owner sets it
-
-    def __del__(self):
-        try:
-            if getattr(self, "_net", None):
-                self._lib.adaf_effnet_destroy(self._net)
-                self._net = None
-        except Exception:
-            pass
 
     def blocks(self):
         out = []
@@ -990,16 +976,6 @@ class EffNetNet:
     def fused_expand_blocks(self, size, pad_size=None):
         """MBConv blocks of a forward at this input size whose expand conv runs inside the depthwise launch (fp16 storage; effnet.hip XN > 0)."""
         return int(self._lib.adaf_effnet_fused_expand_blocks(self._net, int(size), int(self.pad_size if pad_size is None else pad_size)))
-
-    def load(self, params):
-        keep = []
-        for name, t in params.items():
-            L.need_gpu_f32(t)
-            t = t.detach().contiguous()
-            keep.append(t)
-            L.check(self._lib.adaf_effnet_set_param(self._net, name.encode(), L.ptr(t), t.numel()), self._h)
-        L.check(self._lib.adaf_effnet_finalize(self._net, L.stream_ptr()), self._h)
-        del keep
 
     def out_size(self, size, pad_size=0):
         """Spatial size of the feature map for an input of `size` (SAME padding computed for pad_size or size)."""

@@ -12,7 +12,8 @@
  * Conventions
  *   - every pointer named in a compute call is a DEVICE pointer owned by the caller
  *     (PyTorch tensors' data_ptr()); the library allocates only its handle and the packed
- *     weight copies made by adaf_resnet50_finalize();
+ *     weight copies made by the finalize() of a network object (adaf_resnet50_finalize,
+ *     adaf_mobilenetv2_finalize, adaf_effnet_finalize; freed by its destroy());
  *   - `stream` is a hipStream_t passed as void* (NULL = the null stream); calls enqueue work
  *     and return, they never synchronise the device;
  *   - all functions return ADAF_OK (0) or a negative ADAF_E_* code; the message is available
@@ -255,13 +256,16 @@ int adaf_temporal_shift_f32(adaf_handle* h, const float* x, int nt, int c, int h
  */
 int adaf_resnet50_create(adaf_handle* h, adaf_resnet50** out);
 int adaf_resnet50_destroy(adaf_resnet50* net);
-/* Registers a device pointer to a parameter / buffer in PyTorch layout; the data is read by
- * adaf_resnet50_finalize() and not needed afterwards. */
+/* Registers a device pointer to a parameter / buffer in PyTorch layout.  LIFETIME (the same for the three network objects): a
+ * registration lives until the next finalize() of this object returns, with ADAF_OK or an error -- finalize reads the data, keeps
+ * packed copies only and forgets every registered pointer, so the data is not needed afterwards.  Every finalize therefore needs
+ * the complete set registered since the one before: without it, it is ADAF_E_STATE "missing parameter '<name>'". */
 int adaf_resnet50_set_param(adaf_resnet50* net, const char* name, const float* dev_ptr, size_t numel);
 /* Packs weights (OIHW -> OHWI, stem cin 3 -> 4), folds BN, on `stream`; synchronises that stream.  The depth is read from the
  * registered names: the highest "layerS.B." block index per stage.  {3,4,6,3}, {3,4,23,3} and {3,8,36,3} are accepted, anything else
  * is ADAF_E_BADARG (the message names the counts found).  A new depth rebuilds the launch plan: adaf_resnet50_launch_count and the
- * adaf_resnet50_set_tiles table follow it, and tile overrides reset to 0. */
+ * adaf_resnet50_set_tiles table follow it, and tile overrides reset to 0.  Only the names registered since the last finalize count
+ * (a ResNet-50 may follow a ResNet-101 on one object); a registration that names no block keeps the plan's depth. */
 int adaf_resnet50_finalize(adaf_resnet50* net, void* stream);
 size_t adaf_resnet50_workspace_bytes(const adaf_resnet50* net, int n, int patch);
 /* patches_nhwc4 [n, patch, patch, 4] (adaf_crop_gather_f32 with ADAF_LAYOUT_NHWC4);
@@ -383,6 +387,8 @@ int adaf_dwconv3x3_bn_act_f32(adaf_handle* h, const float* x, int n, int hh, int
 typedef struct adaf_mobilenetv2 adaf_mobilenetv2;
 int adaf_mobilenetv2_create(adaf_handle* h, adaf_mobilenetv2** out);
 int adaf_mobilenetv2_destroy(adaf_mobilenetv2* net);
+/* Neutral names ("stem.weight", "b3.dw.bn.running_var", ...); a registration lives until the next finalize returns
+ * (adaf_resnet50_set_param: LIFETIME). */
 int adaf_mobilenetv2_set_param(adaf_mobilenetv2* net, const char* name, const float* dev_ptr, size_t numel);
 int adaf_mobilenetv2_finalize(adaf_mobilenetv2* net, void* stream);
 size_t adaf_mobilenetv2_workspace_bytes(const adaf_mobilenetv2* net, int n, int size, int tsm_segments);
@@ -472,6 +478,8 @@ int adaf_effnet_fused_expand_blocks(const adaf_effnet* net, int size, int pad_si
 /* ADAF_EF_PLAN_HEAD_POOL (fp16 storage, `features` requested without `featmap`, head maps that fill a 128-row tile to >= 90 %: 3 x 3, 4 x 4,
  * 5 x 5): the head conv 1x1 + BN + swish does not write its fp32 map -- the global average pool runs in the conv launch's epilogue
  * (csrc/conv_gemm.hip adaf_launch_conv_pool16), adding a map's pixels in pixel order and dividing, as the pool launch does: the same bits. */
+/* A registration lives until the next finalize returns (adaf_resnet50_set_param: LIFETIME): adaf_effnet_set_dtype followed by
+ * finalize needs the full set registered again. */
 int adaf_effnet_set_param(adaf_effnet* net, const char* name, const float* dev_ptr, size_t numel);
 int adaf_effnet_finalize(adaf_effnet* net, void* stream);
 size_t adaf_effnet_workspace_bytes(const adaf_effnet* net, int n, int size, int pad_size);
