@@ -456,6 +456,26 @@ int adaf_effnet_feature_dim(const adaf_effnet* net);
 int adaf_effnet_block_count(const adaf_effnet* net);
 int adaf_effnet_block_info(const adaf_effnet* net, int block, int* info8);
 int adaf_effnet_set_dtype(adaf_effnet* net, int dtype);
+/* EfficientNet, fp16 storage: NUMERICS CONTRACT (ADAF_DTYPE_F16; every launch plan below computes exactly this -- the CPU model
+ * tests/effnet_contract.py restates it and cites the kernel lines, tests/test_effnet_contract_gpu.py holds every block of B3 to it).
+ * "Rounded" = fp32 -> fp16, round to nearest even, of the finished fp32 value (never a fused single rounding of a wider one).
+ *   filters    expand, project and head (1x1) filters are rounded once at finalize.  The stem filter, the depthwise taps, every folded
+ *              BN affine (scale = w / sqrt(var + 1e-3), bias = b - mean * scale) and the SE matrices and biases stay fp32.
+ *   stem       fp32 frames x fp32 taps, fp32 accumulate, fma(acc, scale, bias), swish; the stored map is rounded once.
+ *   expand     fp16 operands, fp32 accumulate, fma(acc, scale, bias), swish, rounded once -- also where the expanded map never reaches
+ *              HBM (expand inside the depthwise launch, whole-block kernels): the taps read the ROUNDED values.
+ *   depthwise  fp32 taps on the widened fp16 inputs in (ky, kx) order, fma(acc, scale, bias), swish; the stored map is rounded once.
+ *              The squeeze sums the UNROUNDED fp32 values; mean = sum * (1 / pixels).
+ *   SE gate    fp32 throughout: reduce FC + bias, swish, expand FC + bias, sigmoid.
+ *   gated A    the project conv's operand is fp16(float(D16) * gate): an fp32 product, rounded once.
+ *   project    fp16 operands, fp32 accumulate, fma(acc, scale, bias), + float(identity16) AFTER the affine, rounded once.
+ *   head       fp16 operands, fp32 accumulate, fma(acc, scale, bias), swish; the fp32 map is NOT rounded; featvec is the mean of the
+ *              fp32 map.
+ * Order-dependent, hence NOT part of the contract (they differ between plans and from any other implementation by fp32 rounding, which
+ * a later rounding point turns into isolated one-ulp flips of stored values): the k order of every 1x1 accumulation, the order of
+ * the squeeze's pixel sum (tile partials / raster order / per-lane), the SE dot products, the order of the head pool's pixel sum (that both head plans add in pixel order and divide is
+ * part of THEIR bit-identity claim, ADAF_EF_PLAN_HEAD_POOL below, not of the contract), and the last bit of the logistic function
+ * (exp2 and reciprocal units).  Plans that claim MORE than the contract -- the same bits -- say so where they are declared. */
 /* on (DEFAULT): fp16 storage only -- the stride-1 MBConv blocks whose map is at most 9 x 9 and the stride-2 block that takes a 9 x 9
  * map to 5 x 5 (blocks 9-17, 18 and 19-24 of B3 at 144^2: 16 blocks; block 25 (hid 2304 > 2048) keeps the four-launch plan;
  * patches) run as ONE launch per block: a workgroup owns whole images, the 6x-expanded map goes from the MFMA accumulators
