@@ -248,7 +248,7 @@ struct MbStemArgs {       // fused stem -> block 1 (t = 1: depthwise + project) 
     int tiles_x, tiles_y, total_tiles;
     const float* zeros;
 };
-void adaf_launch_mb_stem_b1(MbStemArgs a, int cus, hipStream_t s);
+void adaf_launch_mb_stem_b1(MbStemArgs a, hipStream_t s);
 bool adaf_mb_stem_b1_strip_ok(int S, int H1);                      // mbstrip.hip
 void adaf_launch_mb_stem_b1_strip(MbStemArgs a, hipStream_t s);
 bool adaf_mb_block_strip_ok(int cin, int hid, int cout, int stride, int h, int w);
@@ -265,7 +265,7 @@ void adaf_launch_mb_block(MbFuseArgs a, hipStream_t s);
 // the VALU: quad permutes for 1 and 2, then the half-row and row MIRRORS for 4 and 8 -- after the step before them the lanes of a group hold
 // identical bits, so taking the mirrored lane IS the xor exchange --, ds_swizzle for 16, v_permlane32_swap for 32.  (__shfl_xor compiles to
 // ds_bpermute_b32: six dependent LDS round trips per sum -- the squeeze FC of the EfficientNet kernels spent more time in them than in its
-// filter rows.)  All 64 lanes must be active.  The SE kernels of effnet.hip and mbconv_whole.hip share it: their gates agree bit for bit.
+// filter rows.)  All 64 lanes must be active.  The SE kernels of effnet_kernels.hip and mbconv_whole.hip share it: their gates agree bit for bit.
 __device__ __forceinline__ float adaf_wave_sum(float v) {
     auto dpp = [](float x, auto ctrl_tag) {
         return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), decltype(ctrl_tag)::value, 0xf, 0xf, false));
@@ -291,6 +291,30 @@ bool adaf_launch_mbconv_whole(const void* x, int n, int hw, int stride, int cin,
                               const float* be, const float* wdl, const float* se_wr, const float* se_br,
                               const float* se_wet, const float* se_be, const void* wpf, const float* sp, const float* bp, bool skip, void* out,
                               hipStream_t s);
+
+// effnet_kernels.hip: the launches of an EfficientNet MBConv block and of its stem (fp32 or fp16 storage; effnet_net.hip walks them)
+int adaf_effnet_dw_tiles(int c, int oh, int ow, int k, int stride, int dtype);      // squeeze partial-sum tiles per image of adaf_launch_dw_same (> 0) or < 0
+int adaf_effnet_dw_tiles_fused(int c, int oh, int ow, int k, int stride);           // the same of adaf_launch_dw_expand; < 0: not a shape of its kernel
+// both return the partial-sum tiles per image (> 0), or < 0 when the shape is not the kernel's; pool_part: [n][tiles][c] floats or nullptr
+int adaf_launch_dw_expand(const void* x, int n, int hh, int ww, int cin, const void* xw, const float* xscale, const float* xbias, int c, int k,
+                          int stride, int pad_t, int pad_l, int oh, int ow, const float* wt, const float* scale, const float* bias, int act,
+                          void* out, float* pool_part, hipStream_t s);
+int adaf_launch_dw_same(const void* x, int dtype, int n, int hh, int ww, int c, int k, int stride, int pad_t, int pad_l, int oh,
+                        int ow, const float* wt, const float* scale, const float* bias, int act, void* out, float* pool_part,
+                        hipStream_t s);
+bool adaf_launch_ef_expand(const void* x, int dtype, long long m, int k, const void* w, const float* scale, const float* bias, int n, int act,
+                           void* out, int cus, hipStream_t s);                      // false = not eligible (the conv engine takes it)
+void adaf_launch_pool_finish(const float* part, int n, int tiles, int c, int hw, float* mean, hipStream_t s);
+void adaf_launch_se_gate(const float* part, int tiles, int hw, int n, int c, const float* wr, const float* br, int sq,
+                         const float* we, int we_ldc, int we_ldj, const float* be, float* gate, hipStream_t s);
+int adaf_launch_gated_project(const void* x, int dtype, int m, int hw, int k, const float* gate, const void* w, int n,
+                              const float* scale, const float* bias, const void* res, void* out, int cus, hipStream_t s,
+                              int act = ADAF_ACT_NONE);                             // the column tile it chose (> 0) or < 0
+void adaf_launch_pack_stem_bank(const float* w, int c0, float* o, hipStream_t s);
+bool adaf_launch_ef_stem(const float* x4, int dtype, int n, int size, int oh, int ow, int pad, const float* w, const float* bank, const float* scale,
+                         const float* bias, int c0, int act, void* out, hipStream_t s);
+void adaf_launch_transpose(const float* w, int rows, int cols, float* o, hipStream_t s);     // [rows][cols] -> [cols][rows]
+void adaf_launch_avgpool_any(const float* x, int n, int hw, int c, float* o, int ldo, hipStream_t s);   // adaf_launch_avgpool without its c % 4 == 0
 
 // gru_scan.hip
 int adaf_gru_scan_blocks_per_cu();

@@ -2077,7 +2077,7 @@ int adaf_launch_conv_pool(ConvArgs a, int hw, float* pool_out, int pool_ld, hipS
     return launch_conv_pool(a, hw, pool_out, pool_ld, POOL_F32, s);
 }
 
-// The same for fp16 operands and fp32 features (EfficientNet's head conv 1x1 + BN + swish + global average pool, effnet.hip): the 128 x 64
+// The same for fp16 operands and fp32 features (EfficientNet's head conv 1x1 + BN + swish + global average pool, effnet_kernels.hip): the 128 x 64
 // fp16 tile -- the tile the unfused head conv runs on, same MFMA instruction and k order -- with whole images per tile and
 // conv_epilogue_pool<SIG>.  `a` arrives in ELEMENT units like adaf_launch_conv_gemm's fp16 launches.
 int adaf_launch_conv_pool16(ConvArgs a, int hw, float* pool_out, int pool_ld, hipStream_t s) {

@@ -1,18 +1,13 @@
-// Fused expand (1x1 conv + BN + ReLU6) -> depthwise 3x3 (+ BN + ReLU6) of a MobileNetV2 inverted-residual
-// block (ACT/models/mobilenet.py:42-68; STH/models/mobilenetv2.py): the 6x-expanded feature map never goes
-// to HBM.  For the glancer's high-resolution blocks (b2..b7, 112^2..28^2 maps) that tensor is the largest
-// transfer of the whole network (4.8 MB per 224^2 frame for b2 alone, written once and read once).
-//
-// One block = one spatial tile of one frame:
-//   stride 1: 8x8 outputs <- 10x10 input halo;  stride 2: 3x8 outputs <- 7x17 input halo  (<= 128 halo pixels)
-//   1. the halo pixels' Cin input channels go to LDS once;
-//   2. per chunk of 32 hidden channels:  E[halo][32] = X[halo][Cin] * We[32][Cin]^T on the fp32 matrix pipe
-//      (one 32x32 tile per wave, same k order as the conv engine -> bit-identical to the unfused expand),
-//      BN + ReLU6, halo pixels outside the image forced to 0 (the depthwise conv pads the EXPANDED map),
-//      E to LDS;  then the 3x3 depthwise taps on the VALU straight from LDS (same tap order as
-//      dwconv3x3_kernel), BN + ReLU6, 16-byte stores.
-// The halo is recomputed by neighbouring tiles (1.56x / 1.24x of the expand FLOPs, which are ~1/10 of the
-// block's traffic-equivalent cost at these channel counts).
+// Fused kernels of MobileNetV2's high-resolution inverted-residual blocks (ACT/models/mobilenet.py:42-68; STH/models/mobilenetv2.py),
+// all with WAVE-PRIVATE tiles: a wave owns a small output tile and runs its whole chain -- MFMA expand / stem GEMM, BN + ReLU6, the
+// intermediate in its own few KB of LDS, the 3x3 depthwise taps on the VALU, (project GEMM,) 16-byte stores -- with no block-level
+// barrier anywhere; the other waves of the CU fill the gaps of its dependent chain.  The 6x-expanded maps never go to HBM:
+// for the glancer's blocks b2..b7 (112^2..28^2 maps) they are the largest transfers of the network (4.8 MB per 224^2 frame for b2 alone).
+//   mb_expand_dw_w_kernel<S, CIN>   expand 1x1 -> depthwise 3x3, 6x6 (stride 1) / 3x4 (stride 2) outputs per wave, cin = 16 / 24 / 32
+//   mb_stem_b1_w_kernel             stem 3x3/2 -> block 1 (depthwise 3x3 -> project 32 -> 16), 4x8 outputs per wave
+//   mb_block_w_kernel<CIN>          a whole stride-1 block (expand -> depthwise -> project + identity), 4x8 outputs per wave
+// The halo of a tile is recomputed by its neighbours.  Every kernel forms the products of an output in the order of the unfused
+// launches (conv engine + dwconv3x3_kernel): bit-identical to them.  (The strip-walking forms of the same blocks are in mbstrip.hip.)
 #include <cstdlib>
 #include "adaf_internal.h"
 
@@ -22,135 +17,13 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 namespace {
 
-template <int S>
-__global__ __launch_bounds__(256) void mb_expand_dw_kernel(const MbFuseArgs a) {
-    constexpr int TH = S == 1 ? 8 : 3, TW = 8;
-    constexpr int IH = (TH - 1) * S + 3, IW = (TW - 1) * S + 3;
-    constexpr int HP = IH * IW;     // 100 / 119 halo pixels
-    constexpr int MP = 128;         // padded to four 32-row bands, one per wave
-    constexpr int EP = 36;          // E row pitch in floats
-    static_assert(HP <= MP, "halo must fit four bands");
-    extern __shared__ __attribute__((aligned(16))) float smem[];   // X[MP][cin+4] | We chunk [32][cin+4] | E[MP][EP]
-    float* Xs = smem;
-    float* Ws = smem + MP * (a.cin + 4);
-    float* Es = Ws + 32 * (a.cin + 4);
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int bid = blockIdx.x;
-    const int tx = bid % a.tiles_x;
-    bid /= a.tiles_x;
-    const int ty = bid % a.tiles_y;
-    const int img = bid / a.tiles_y;
-    const int oy0 = ty * TH, ox0 = tx * TW;
-    const int iy0 = oy0 * S - 1, ix0 = ox0 * S - 1;
-    const int cq = a.cin >> 2;      // 16-byte chunks per pixel
-    const int xp = a.cin + 4;       // LDS pitch of X and We rows: conflict-free b128 fragment reads for cin = 16, 24, 32
-    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-
-    for (int idx = tid; idx < MP * cq; idx += 256) {
-        const int p = idx / cq, c = idx - p * cq;
-        const int iy = iy0 + p / IW, ix = ix0 + p % IW;
-        const bool ok = p < HP && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
-        const f32x4 v = *reinterpret_cast<const f32x4*>(ok ? a.x + (((size_t)img * a.H + iy) * a.W + ix) * a.cin + 4 * c : a.zeros);
-        *reinterpret_cast<f32x4*>(&Xs[p * xp + 4 * c]) = v;
-    }
-    // which of this lane's 16 accumulator rows are halo pixels inside the image
-    unsigned emask = 0;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int p = 32 * wave + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        const int iy = iy0 + p / IW, ix = ix0 + p % IW;
-        if (p < HP && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W) emask |= 1u << r;
-    }
-    const int c4 = tid & 7, pg = tid >> 3;
-    const int fr = (32 * wave + (lane & 31)) * xp + 4 * (lane >> 5);
-    const int fw = (lane & 31) * xp + 4 * (lane >> 5);
-
-    // expand weights of a chunk: 32 rows x cq chunks <= 256 -> at most one 16-byte piece per thread
-    const int wr = tid / cq, wc = tid - wr * cq;
-    const bool wmine = tid < 32 * cq;
-    auto wload = [&](int ch0) -> f32x4 {
-        return (wmine && ch0 + wr < a.hid) ? *reinterpret_cast<const f32x4*>(a.we + (size_t)(ch0 + wr) * a.cin + 4 * wc) : zero4;
-    };
-    if (wmine) *reinterpret_cast<f32x4*>(&Ws[wr * xp + 4 * wc]) = wload(0);
-
-    for (int ch0 = 0; ch0 < a.hid; ch0 += 32) {
-        // everything this chunk and the next need from global memory is requested before the first barrier, so its
-        // latency runs under the expand GEMM instead of in front of the depthwise phase / the next chunk
-        const f32x4 wnext = wload(ch0 + 32);
-        const int ch = ch0 + 4 * c4;
-        const int chs = ch < a.hid ? ch : 0;
-        f32x4 k[9];
-#pragma unroll
-        for (int t = 0; t < 9; ++t) k[t] = *reinterpret_cast<const f32x4*>(a.wd + (size_t)t * a.hid + chs);
-        const f32x4 dsc = *reinterpret_cast<const f32x4*>(a.sd + chs);
-        const f32x4 dbi = *reinterpret_cast<const f32x4*>(a.bd + chs);
-        const int nch = ch0 + (lane & 31);
-        const bool nv = nch < a.hid;
-        const float esc = nv ? a.se[nch] : 0.f, ebi = nv ? a.be[nch] : 0.f;
-        __syncthreads();
-        f32x16 acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-        for (int kk = 0; kk < a.cin / 8; ++kk) {
-            const f32x4 af = *reinterpret_cast<const f32x4*>(&Xs[fr + 8 * kk]);
-            const f32x4 bf = *reinterpret_cast<const f32x4*>(&Ws[fw + 8 * kk]);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af.x, bf.x, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af.y, bf.y, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af.z, bf.z, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af.w, bf.w, acc, 0, 0, 0);
-        }
-        {
-            const float sc = esc, bi = ebi;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int p = 32 * wave + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                const float e = fminf(fmaxf(fmaf(acc[r], sc, bi) + 0.f, 0.f), 6.f);
-                Es[p * EP + (lane & 31)] = ((emask >> r) & 1u) ? e : 0.f;
-            }
-        }
-        __syncthreads();
-        if (wmine) *reinterpret_cast<f32x4*>(&Ws[wr * xp + 4 * wc]) = wnext;   // every wave is past its reads of this chunk's weights
-        if (ch < a.hid) {
-            const f32x4 sc = dsc, bi = dbi;
-#pragma unroll
-            for (int o = pg; o < TH * TW; o += 32) {
-                const int oy = o / TW, ox = o - oy * TW;
-                const int gy = oy0 + oy, gx = ox0 + ox;
-                f32x4 s = zero4;
-#pragma unroll
-                for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-                    for (int kx = 0; kx < 3; ++kx) {
-                        const f32x4 v = *reinterpret_cast<const f32x4*>(&Es[((oy * S + ky) * IW + ox * S + kx) * EP + 4 * c4]);
-                        const f32x4 w = k[ky * 3 + kx];
-                        s.x = fmaf(v.x, w.x, s.x);
-                        s.y = fmaf(v.y, w.y, s.y);
-                        s.z = fmaf(v.z, w.z, s.z);
-                        s.w = fmaf(v.w, w.w, s.w);
-                    }
-                if (gy < a.OH && gx < a.OW) {
-                    f32x4 r;
-                    r.x = fminf(fmaxf(fmaf(s.x, sc.x, bi.x), 0.f), 6.f);
-                    r.y = fminf(fmaxf(fmaf(s.y, sc.y, bi.y), 0.f), 6.f);
-                    r.z = fminf(fmaxf(fmaf(s.z, sc.z, bi.z), 0.f), 6.f);
-                    r.w = fminf(fmaxf(fmaf(s.w, sc.w, bi.w), 0.f), 6.f);
-                    *reinterpret_cast<f32x4*>(a.out + (((size_t)img * a.OH + gy) * a.OW + gx) * a.hid + ch) = r;
-                }
-            }
-        }
-        // no barrier here: the next chunk's barrier (after its weight load) orders these reads of E before the next writes
-    }
-}
-
 // ---------------------------------------------------------------------------------------------------------
-// The same fused block with WAVE-PRIVATE tiles: every wave owns a small output tile (6x6 at stride 1, 3x4 at stride 2: a halo of
-// 64 / 63 pixels = two MFMA row bands) and runs expand -> BN/ReLU6 -> E in its own 9 KB of LDS -> depthwise taps -> stores on
-// its own, with no block-level barrier anywhere.  The kernel above is bound by the latency of its barrier-separated phase
-// chain; here the chain is private to a wave and the other waves of the CU fill its gaps.  The halo pixels'
+// Expand (1x1 conv + BN + ReLU6) -> depthwise 3x3 (+ BN + ReLU6): every wave owns a small output tile (6x6 at stride 1, 3x4 at
+// stride 2: a halo of 64 / 63 pixels = two MFMA row bands) and runs expand -> BN/ReLU6 -> E in its own 9 KB of LDS -> depthwise taps
+// -> stores on its own.  Halo pixels outside the image are forced to 0 (the depthwise conv pads the EXPANDED map).  The halo pixels'
 // input channels are loaded straight into MFMA A fragments (no X image in LDS), the expand filter rows into B fragments.
-// Costs: 1.8x (stride 1) / 1.3x (stride 2) of the expand products are halo recomputation.  Same products in the same order
-// per output as the kernels above: bit-identical.
+// Costs: 1.8x (stride 1) / 1.3x (stride 2) of the expand products are halo recomputation.  Same k order as the conv engine, same
+// tap order as dwconv3x3_kernel: bit-identical to the unfused launches.
 template <int S, int CIN>
 __global__ __launch_bounds__(256, 3) void mb_expand_dw_w_kernel(const MbFuseArgs a) {
     constexpr int OTH = S == 1 ? 6 : 3, OTW = S == 1 ? 6 : 4;
@@ -314,157 +187,14 @@ __global__ __launch_bounds__(256, 3) void mb_expand_dw_w_kernel(const MbFuseArgs
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// Stem (3x3 stride-2 conv 3->32 + BN + ReLU6) -> block 1 (depthwise 3x3 + BN + ReLU6 -> project 1x1 32->16 + BN)
-// in one persistent kernel: reads the 224^2 pixel-major frame, writes the 112^2 x 16 map; the two 112^2 x 32
-// intermediates (1.6 MB per frame each, the 2nd and 3rd largest tensors of the network) stay in LDS.
-//   tile = 8x8 outputs <- 10x10 stem outputs (halo) <- 21x21 input pixels
-//   stem GEMM: the k index of the packed filter is (tap, channel-of-4), so a lane's 16-byte A fragment IS one input
-//   pixel of the tile in LDS -- no im2col; K = 36 -> five groups of 8 (the 10th "tap" reads a zero vector), the
-//   same group order as the conv engine's two k slices, so the result is bit-identical to the unfused stem.
-// (Requesting the next tile's pixels during the current tile's compute was tried and was slower: 14.6 vs 13.9 ms
-//  per 1024 frames for the whole glancer; three co-resident blocks already cover the load.)
-template <int DUMMY>
-__global__ __launch_bounds__(256) void mb_stem_b1_kernel(const MbStemArgs a) {
-    constexpr int TW = 8, IW = 10, HP = 100, MP = 128, EP = 36;
-    constexpr int XW = 21, XPIX = 21 * 21;
-    __shared__ __attribute__((aligned(16))) float Xs[(XPIX + 1) * 4];   // + one zero pixel
-    __shared__ __attribute__((aligned(16))) float Wst[32 * 44];
-    __shared__ __attribute__((aligned(16))) float Es[MP * EP];
-    __shared__ __attribute__((aligned(16))) float Ds[64 * EP];
-    __shared__ __attribute__((aligned(16))) float Wps[32 * EP];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5;
-    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-
-    for (int idx = tid; idx < 32 * 10; idx += 256) {
-        const int nr = idx / 10, c = idx - nr * 10;
-        *reinterpret_cast<f32x4*>(&Wst[nr * 44 + 4 * c]) = c < 9 ? *reinterpret_cast<const f32x4*>(a.ws + nr * 36 + 4 * c) : zero4;
-    }
-    for (int idx = tid; idx < 32 * 8; idx += 256) {
-        const int nr = idx >> 3, c = idx & 7;
-        *reinterpret_cast<f32x4*>(&Wps[nr * EP + 4 * c]) = nr < 16 ? *reinterpret_cast<const f32x4*>(a.wp + nr * 32 + 4 * c) : zero4;
-    }
-    if (tid < 4) Xs[XPIX * 4 + tid] = 0.f;
-    const int c4 = tid & 7, pg = tid >> 3;
-    f32x4 k[9];
-#pragma unroll
-    for (int t = 0; t < 9; ++t) k[t] = *reinterpret_cast<const f32x4*>(a.wd + t * 32 + 4 * c4);
-    const f32x4 dsc = *reinterpret_cast<const f32x4*>(a.sd + 4 * c4);
-    const f32x4 dbi = *reinterpret_cast<const f32x4*>(a.bd + 4 * c4);
-    const int nl = lane & 31;
-    const float ssc = a.ss[nl], sbi = a.bs[nl];
-    const float psc = nl < 16 ? a.sp[nl] : 0.f, pbi = nl < 16 ? a.bp[nl] : 0.f;
-    // A-fragment offsets of this lane's halo pixel: tap t = 2*kk + half -> input pixel (2*hy + kh, 2*hx + kw) of the tile
-    const int p = 32 * wave + nl;
-    const int pl = p < HP ? p : 0;
-    const int base = ((2 * (pl / IW)) * XW + 2 * (pl % IW)) * 4;
-    int aoff[5];
-#pragma unroll
-    for (int kk = 0; kk < 5; ++kk) {
-        const int t = 2 * kk + half;
-        aoff[kk] = t < 9 ? base + ((t / 3) * XW + t % 3) * 4 : XPIX * 4;
-    }
-    const int woff = nl * 44 + 4 * half;
-
-    for (int tile = blockIdx.x; tile < a.total_tiles; tile += gridDim.x) {
-        int q = tile;
-        const int tx = q % a.tiles_x;
-        q /= a.tiles_x;
-        const int ty = q % a.tiles_y;
-        const int img = q / a.tiles_y;
-        const int oy0 = ty * 8, ox0 = tx * 8;
-        const int hy0 = oy0 - 1, hx0 = ox0 - 1;
-        const int iy0 = 2 * hy0 - 1, ix0 = 2 * hx0 - 1;
-        __syncthreads();   // the previous tile's readers are done with Xs / Es / Ds
-        for (int idx = tid; idx < XPIX; idx += 256) {
-            const int r = idx / XW, c = idx - r * XW;
-            const int iy = iy0 + r, ix = ix0 + c;
-            const bool ok = (unsigned)iy < (unsigned)a.S && (unsigned)ix < (unsigned)a.S;
-            *reinterpret_cast<f32x4*>(&Xs[idx * 4]) =
-                *reinterpret_cast<const f32x4*>(ok ? a.x + (((size_t)img * a.S + iy) * a.S + ix) * 4 : a.zeros);
-        }
-        unsigned emask = 0;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int pp = 32 * wave + (r & 3) + 8 * (r >> 2) + 4 * half;
-            const int hy = hy0 + pp / IW, hx = hx0 + pp % IW;
-            if (pp < HP && (unsigned)hy < (unsigned)a.H1 && (unsigned)hx < (unsigned)a.H1) emask |= 1u << r;
-        }
-        __syncthreads();
-        f32x16 acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-        for (int kk = 0; kk < 5; ++kk) {
-            const f32x4 af = *reinterpret_cast<const f32x4*>(&Xs[aoff[kk]]);
-            const f32x4 bf = *reinterpret_cast<const f32x4*>(&Wst[woff + 8 * kk]);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af.x, bf.x, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af.y, bf.y, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af.z, bf.z, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af.w, bf.w, acc, 0, 0, 0);
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int pp = 32 * wave + (r & 3) + 8 * (r >> 2) + 4 * half;
-            const float e = fminf(fmaxf(fmaf(acc[r], ssc, sbi) + 0.f, 0.f), 6.f);
-            Es[pp * EP + nl] = ((emask >> r) & 1u) ? e : 0.f;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int o = pg; o < 64; o += 32) {
-            const int oy = o / TW, ox = o - oy * TW;
-            f32x4 s = zero4;
-#pragma unroll
-            for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-                for (int kx = 0; kx < 3; ++kx) {
-                    const f32x4 v = *reinterpret_cast<const f32x4*>(&Es[((oy + ky) * IW + ox + kx) * EP + 4 * c4]);
-                    const f32x4 w = k[ky * 3 + kx];
-                    s.x = fmaf(v.x, w.x, s.x);
-                    s.y = fmaf(v.y, w.y, s.y);
-                    s.z = fmaf(v.z, w.z, s.z);
-                    s.w = fmaf(v.w, w.w, s.w);
-                }
-            f32x4 r;
-            r.x = fminf(fmaxf(fmaf(s.x, dsc.x, dbi.x), 0.f), 6.f);
-            r.y = fminf(fmaxf(fmaf(s.y, dsc.y, dbi.y), 0.f), 6.f);
-            r.z = fminf(fmaxf(fmaf(s.z, dsc.z, dbi.z), 0.f), 6.f);
-            r.w = fminf(fmaxf(fmaf(s.w, dsc.w, dbi.w), 0.f), 6.f);
-            *reinterpret_cast<f32x4*>(&Ds[o * EP + 4 * c4]) = r;
-        }
-        __syncthreads();
-        if (wave < 2) {   // project: 64 pixels x 16 channels, K = 32
-            f32x16 pa;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) pa[r] = 0.f;
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) {
-                const f32x4 af = *reinterpret_cast<const f32x4*>(&Ds[(32 * wave + nl) * EP + 8 * kk + 4 * half]);
-                const f32x4 bf = *reinterpret_cast<const f32x4*>(&Wps[nl * EP + 8 * kk + 4 * half]);
-                pa = __builtin_amdgcn_mfma_f32_32x32x2f32(af.x, bf.x, pa, 0, 0, 0);
-                pa = __builtin_amdgcn_mfma_f32_32x32x2f32(af.y, bf.y, pa, 0, 0, 0);
-                pa = __builtin_amdgcn_mfma_f32_32x32x2f32(af.z, bf.z, pa, 0, 0, 0);
-                pa = __builtin_amdgcn_mfma_f32_32x32x2f32(af.w, bf.w, pa, 0, 0, 0);
-            }
-            if (nl < 16) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int o = 32 * wave + (r & 3) + 8 * (r >> 2) + 4 * half;
-                    const int gy = oy0 + o / TW, gx = ox0 + o % TW;
-                    if (gy < a.H1 && gx < a.H1)
-                        a.out[(((size_t)img * a.H1 + gy) * a.H1 + gx) * 16 + nl] = fmaf(pa[r], psc, pbi) + 0.f;
-                }
-            }
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// Stem -> block 1 with WAVE-PRIVATE tiles (the restructuring that paid for the expand -> depthwise blocks above): a wave owns
+// Stem (3x3 stride-2 conv 3->32 + BN + ReLU6) -> block 1 (depthwise 3x3 + BN + ReLU6 -> project 1x1 32->16 + BN): reads the 224^2
+// pixel-major frame, writes the 112^2 x 16 map; the two 112^2 x 32 intermediates (1.6 MB per frame each) stay in LDS.  A wave owns
 // 4 x 8 block-1 outputs <- 6 x 10 stem outputs (60 halo pixels = two MFMA row bands) <- 13 x 21 input pixels, and runs
 // window -> stem GEMM -> BN/ReLU6 -> E -> depthwise taps -> D (the project conv's A operand, exactly one row band) -> project
 // GEMM -> BN -> 16-byte stores on its own: no block-level barrier.  All filters live in registers (stem and project B
-// fragments) or LDS (taps).  112 = 28 x 4 = 14 x 8: the tiles cover the map exactly.  Same products in the same order as
-// mb_stem_b1_kernel and the unfused launches: bit-identical.
+// fragments) or LDS (taps).  112 = 28 x 4 = 14 x 8: the tiles cover the map exactly.  The k index of the packed stem filter is
+// (tap, channel-of-4), so a lane's 16-byte A fragment IS one input pixel of the window -- no im2col; K = 36 in the group order of the
+// conv engine's k slices.  Same products in the same order as the unfused launches: bit-identical.
 __global__ __launch_bounds__(256, 4) void mb_stem_b1_w_kernel(const MbStemArgs a) {
     constexpr int OTH = 4, OTW = 8;
     constexpr int HH = OTH + 2, HW = OTW + 2, HP = HH * HW;          // stem-output halo 6 x 10
@@ -849,7 +579,9 @@ __global__ __launch_bounds__(256, 3) void mb_block_w_kernel(const MbFuseArgs a) 
 
 }  // namespace
 
-bool adaf_mb_expand_dw_ok(int cin, int hid, int hw) { return cin % 8 == 0 && cin <= 32 && hid % 4 == 0 && hw >= 28; }
+// exactly the shapes adaf_launch_mb_expand_dw has a kernel for (MobileNetV2's b2..b7: cin 16 / 24 / 32, hid = 6 cin; the taps of up to
+// 192 hidden channels are LDS-resident)
+bool adaf_mb_expand_dw_ok(int cin, int hid, int hw) { return (cin == 16 || cin == 24 || cin == 32) && hid % 4 == 0 && hid <= 192 && hw >= 28; }
 
 template <int S, int CIN>
 static void launch_expand_dw_w(MbFuseArgs a, hipStream_t s) {
@@ -860,32 +592,20 @@ static void launch_expand_dw_w(MbFuseArgs a, hipStream_t s) {
     hipLaunchKernelGGL((mb_expand_dw_w_kernel<S, CIN>), dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, s, a);
 }
 
-// (the wave-private kernels were an option, "mb_wave", while they were measured against the block-cooperative ones, rounds 2-5; the latter remain
-//  as the fallback for hidden widths beyond the LDS-resident tap table)
-static constexpr bool mb_wave_enabled() { return true; }
-
+// (the caller has asked adaf_mb_expand_dw_ok; stride 1 | 2)
 void adaf_launch_mb_expand_dw(MbFuseArgs a, int stride, hipStream_t s) {
-    if (mb_wave_enabled() && a.hid <= 192) {
-        if (stride == 1 && a.cin == 16) return launch_expand_dw_w<1, 16>(a, s);
-        if (stride == 2 && a.cin == 16) return launch_expand_dw_w<2, 16>(a, s);
-        if (stride == 1 && a.cin == 24) return launch_expand_dw_w<1, 24>(a, s);
-        if (stride == 2 && a.cin == 24) return launch_expand_dw_w<2, 24>(a, s);
-        if (stride == 1 && a.cin == 32) return launch_expand_dw_w<1, 32>(a, s);
-        if (stride == 2 && a.cin == 32) return launch_expand_dw_w<2, 32>(a, s);
-    }
-    const int th = stride == 1 ? 8 : 3, tw = 8;
-    a.tiles_x = (a.OW + tw - 1) / tw;
-    a.tiles_y = (a.OH + th - 1) / th;
-    const unsigned blocks = (unsigned)a.n * a.tiles_x * a.tiles_y;
-    const size_t smem = sizeof(float) * ((size_t)160 * (a.cin + 4) + 128 * 36);
-    if (stride == 1) hipLaunchKernelGGL((mb_expand_dw_kernel<1>), dim3(blocks), dim3(256), smem, s, a);
-    else hipLaunchKernelGGL((mb_expand_dw_kernel<2>), dim3(blocks), dim3(256), smem, s, a);
+    if (stride == 1 && a.cin == 16) return launch_expand_dw_w<1, 16>(a, s);
+    if (stride == 2 && a.cin == 16) return launch_expand_dw_w<2, 16>(a, s);
+    if (stride == 1 && a.cin == 24) return launch_expand_dw_w<1, 24>(a, s);
+    if (stride == 2 && a.cin == 24) return launch_expand_dw_w<2, 24>(a, s);
+    if (stride == 1 && a.cin == 32) return launch_expand_dw_w<1, 32>(a, s);
+    if (stride == 2 && a.cin == 32) return launch_expand_dw_w<2, 32>(a, s);
 }
 
 // whole-block kernel: stride-1 blocks with up to 32 output channels (b3, b5, b6 of MobileNetV2 1.0)
 bool adaf_mb_block_ok(int cin, int hid, int cout, int stride, int hw) {
-    if (mb_wave_enabled() && stride == 2) return adaf_mb_block_strip_ok(cin, hid, cout, stride, hw, hw);     // (stride 2: the strip form only)
-    return mb_wave_enabled() && stride == 1 && (cin == 16 || cin == 24 || cin == 32) && hid % 4 == 0 && hid <= 192 && cout % 4 == 0 &&
+    if (stride == 2) return adaf_mb_block_strip_ok(cin, hid, cout, stride, hw, hw);     // (stride 2: the strip form only)
+    return stride == 1 && (cin == 16 || cin == 24 || cin == 32) && hid % 4 == 0 && hid <= 192 && cout % 4 == 0 &&
            cout <= 32 && hw >= 28;
 }
 
@@ -900,18 +620,10 @@ void adaf_launch_mb_block(MbFuseArgs a, hipStream_t s) {
     else hipLaunchKernelGGL((mb_block_w_kernel<32>), grid, block, 0, s, a);
 }
 
-void adaf_launch_mb_stem_b1(MbStemArgs a, int cus, hipStream_t s) {
-    if (mb_wave_enabled() && adaf_mb_stem_b1_strip_ok(a.S, a.H1)) return adaf_launch_mb_stem_b1_strip(a, s);
-    if (mb_wave_enabled()) {
-        a.tiles_x = (a.H1 + 7) / 8;
-        a.tiles_y = (a.H1 + 3) / 4;
-        a.total_tiles = a.n * a.tiles_x * a.tiles_y;
-        hipLaunchKernelGGL(mb_stem_b1_w_kernel, dim3((unsigned)((a.total_tiles + 3) / 4)), dim3(256), 0, s, a);
-        return;
-    }
+void adaf_launch_mb_stem_b1(MbStemArgs a, hipStream_t s) {
+    if (adaf_mb_stem_b1_strip_ok(a.S, a.H1)) return adaf_launch_mb_stem_b1_strip(a, s);
     a.tiles_x = (a.H1 + 7) / 8;
-    a.tiles_y = a.tiles_x;
+    a.tiles_y = (a.H1 + 3) / 4;
     a.total_tiles = a.n * a.tiles_x * a.tiles_y;
-    const int blocks = a.total_tiles < cus * 3 ? a.total_tiles : cus * 3;
-    hipLaunchKernelGGL((mb_stem_b1_kernel<0>), dim3(blocks), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(mb_stem_b1_w_kernel, dim3((unsigned)((a.total_tiles + 3) / 4)), dim3(256), 0, s, a);
 }

@@ -5,9 +5,9 @@
 // (it does not even exist in LDS: it goes from the MFMA accumulators straight into the depthwise taps), the depthwise output
 // lives in LDS only, the squeeze is an in-block reduction and the two SE matrix products run inside the block -- four launches
 // and three HBM round trips of the widest tensors of the block become one launch that reads the block input and writes the block
-// output.  PARITY UNPINNED like the rest of config 5 (the reference holds no EfficientNet: effnet.hip's header); the algorithm is
+// output.  PARITY UNPINNED like the rest of config 5 (the reference holds no EfficientNet: effnet_kernels.hip's header); the algorithm is
 // model.py MBConvBlock.forward of `efficientnet_pytorch` as restated by oracle/ref_effnet.py:mbconv, and every value is produced by
-// the arithmetic of the four-launch plan of effnet.hip (same MFMA instruction and k order, same BN / swish expressions, the same
+// the arithmetic of the four-launch plan of effnet_kernels.hip (same MFMA instruction and k order, same BN / swish expressions, the same
 // fp16 roundings of the expanded map, the depthwise output and the gated operand); only the order of the squeeze's fp32 sum differs.
 //
 // Phases of a workgroup (8 waves, G images; NB = G x ceil(HW^2 / 32) row bands of 32 pixels):
@@ -684,7 +684,7 @@ bool plan_mbw(int hw, int stride, int cin, int hid, int cout, int sq, int gmax, 
 template <int HW, int K, int G, int S = 1>
 void launch_mbw_one(const MbwArgs& a, size_t lds, hipStream_t s) {
     // dynamic LDS above 64 KB has to be asked for -- per DEVICE (function attributes are per device and a process may hold handles on
-    // several), so on every launch like the other launchers of effnet.hip; it is a host-side table update, not a device call
+    // several), so on every launch like the other launchers of effnet_kernels.hip; it is a host-side table update, not a device call
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mbconv_whole_kernel<HW, K, G, S>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax);
     hipLaunchKernelGGL((mbconv_whole_kernel<HW, K, G, S>), dim3((unsigned)((a.n + G - 1) / G)), dim3(kMbwThreads), lds, s, a);
 }

@@ -228,7 +228,7 @@ int adaf_mobilenetv2_forward(adaf_mobilenetv2* net, const float* frames_nhwc4, i
             sa.x = frames_nhwc4 + (size_t)f0 * size * size * 4; sa.n = nc; sa.S = size; sa.H1 = hw;
             sa.ws = S.w; sa.ss = S.scale; sa.bs = S.bias; sa.wd = D.w; sa.sd = D.scale; sa.bd = D.bias;
             sa.wp = P.w; sa.sp = P.scale; sa.bp = P.bias; sa.out = bufA; sa.zeros = net->h->zeros;
-            adaf_launch_mb_stem_b1(sa, net->h->cus, st);
+            adaf_launch_mb_stem_b1(sa, st);
             first_block = 1;
         } else if ((rc = run_conv(net, net->convs[net->stem], frames_nhwc4 + (size_t)f0 * size * size * 4, nc, size, size,
                                   ADAF_ACT_RELU6, nullptr, bufA, 0, 0, st)))

@@ -6,7 +6,7 @@ installed here: **parity unpinned** -- what is mirrored is the package's publish
 `extract_features`, `forward`, the `_conv_stem` / `_blocks.N._depthwise_conv` / `_se_reduce` ... key names) so a checkpoint
 saved from it loads with strict=True, and its published algorithm (oracle/ref_effnet.py restates it on the CPU).
 
-The nn.Modules below only hold parameters; every forward runs on `adaf_effnet` (csrc/effnet.hip).
+The nn.Modules below only hold parameters; every forward runs on `adaf_effnet` (csrc/effnet_net.hip, csrc/effnet_kernels.hip).
 """
 import math
 
@@ -68,7 +68,7 @@ class MBConvBlock(nn.Module):
         self._bn2 = _bn(cout)
 
     def forward(self, inputs, drop_connect_rate=None):
-        raise NotImplementedError("adafocus_amd runs the whole network through EfficientNet.extract_features (csrc/effnet.hip)")
+        raise NotImplementedError("adafocus_amd runs the whole network through EfficientNet.extract_features (csrc/effnet_net.hip, csrc/effnet_kernels.hip)")
 
 
 class EfficientNet(nn.Module):

@@ -943,7 +943,7 @@ def conv1x1_gated_bn(x, gate, w, scale=None, bias=None, residual=None):
 
 
 class EffNetNet(_NetEngine):
-    """adaf_effnet: EfficientNet feature extractor (MBConv + squeeze-and-excite + swish; csrc/effnet.hip)."""
+    """adaf_effnet: EfficientNet feature extractor (MBConv + squeeze-and-excite + swish; csrc/effnet_net.hip)."""
     _ABI = "effnet"
 
     def __init__(self, device, width, depth):
@@ -974,7 +974,7 @@ class EffNetNet(_NetEngine):
         return int(self._lib.adaf_effnet_whole_blocks(self._net, int(size), int(self.pad_size if pad_size is None else pad_size)))
 
     def fused_expand_blocks(self, size, pad_size=None):
-        """MBConv blocks of a forward at this input size whose expand conv runs inside the depthwise launch (fp16 storage; effnet.hip XN > 0)."""
+        """MBConv blocks of a forward at this input size whose expand conv runs inside the depthwise launch (fp16 storage; effnet_kernels.hip XN > 0)."""
         return int(self._lib.adaf_effnet_fused_expand_blocks(self._net, int(size), int(self.pad_size if pad_size is None else pad_size)))
 
     def out_size(self, size, pad_size=0):

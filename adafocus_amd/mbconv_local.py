@@ -5,7 +5,7 @@ leftovers (STH/ops/models_ada.py:6,69-75 needs the un-vendored `efficientnet_pyt
 lists B3 with feature dimension 1536, 1.80 GFLOPs / 12 M parameters) -- SURVEY.md section 8(c): **parity unpinned**.
 
 ``EfficientNetLocalCNN`` (args.local_arch = "efficientnet-b3"): the network config 5 names -- MBConv with squeeze-and-excite,
-swish, 3x3 / 5x5 depthwise, B3 widths / depths, BN eps 1e-3 -- adafocus_amd/efficientnet.py on csrc/effnet.hip +
+swish, 3x3 / 5x5 depthwise, B3 widths / depths, BN eps 1e-3 -- adafocus_amd/efficientnet.py on csrc/effnet_net.hip, csrc/effnet_kernels.hip +
 csrc/mbconv_whole.hip, checked against oracle/ref_effnet.py (the published algorithm of `efficientnet_pytorch`).  It runs with
 activations and 1x1 filters stored as fp16 (fp32 accumulate) or fp32 and is reported by bench.py under `also`, never as `value`.
 (Round 2's MobileNetV2-topology stand-in, local_arch = "mbconv_f16", is gone: round 3 built the real network.)

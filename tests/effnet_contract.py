@@ -10,29 +10,29 @@ tells five wrong placements of a rounding, a padding or the identity apart -- or
 
 Rounding points, each read off the kernels (csrc = adafocus_amd/csrc):
 
-  filters    The 1x1 filters (expand, project, head) are rounded to fp16 at finalize: effnet.hip:2120-2123
+  filters    The 1x1 filters (expand, project, head) are rounded to fp16 at finalize: effnet_net.hip:302-305
              (adaf_launch_pack_weight_f16 for every conv with k == 1 that is not depthwise) and, for the whole-block kernel,
-             effnet.hip:2155-2156 (adaf_launch_pack_bfrag_f16, mbconv_whole.hip:637-639: the same rounding of the same fp32
+             effnet_net.hip:337-338 (adaf_launch_pack_bfrag_f16, mbconv_whole.hip:637-639: the same rounding of the same fp32
              values into fragment order).  Depthwise taps, every folded BN affine, the SE matrices and biases stay fp32
-             (effnet.hip:2141-2147, 2157-2159).  The STEM filter stays fp32 as well: k == 3, so effnet.hip:2120 skips it, and the stem
-             kernels multiply fp32 frames by fp32 taps on the fp32 matrix pipe (effnet.hip:1396-1409).
-  stem       fp32 products, BN affine as one fma, swish, ONE rounding at the store: effnet.hip:1419 / 1441 (Chunk<T>::pack).
+             (effnet_net.hip:323-329, 339-341).  The STEM filter stays fp32 as well: k == 3, so effnet_net.hip:302 skips it, and the stem
+             kernels multiply fp32 frames by fp32 taps on the fp32 matrix pipe (effnet_kernels.hip:1396-1409).
+  stem       fp32 products, BN affine as one fma, swish, ONE rounding at the store: effnet_kernels.hip:1419 / 1441 (Chunk<T>::pack).
   expand     fp16 operands, fp32 accumulate, fma(acc, scale, bias), swish, one rounding -- in every plan: the conv engine's epilogue
              (conv_gemm.hip:243-249), the strip kernel of the narrow blocks, the expand inside the depthwise launch
-             (effnet.hip:293-299) and the whole-block kernel (mbconv_whole.hip:265-268: the accumulators are rounded before the taps
+             (effnet_kernels.hip:293-299) and the whole-block kernel (mbconv_whole.hip:265-268: the accumulators are rounded before the taps
              read them).
   depthwise  fp32 taps on the (exactly widened) fp16 inputs in (ky, kx) order, fma(acc, scale, bias), swish; the STORED map is
-             rounded once (effnet.hip:438-441, 547-552; mbconv_whole.hip:320-324, 355-359).  The squeeze sums the UNROUNDED fp32
-             values in every plan: effnet.hip:439 (`psum += v` before pack), effnet.hip:551, mbconv_whole.hip:321 / 356; the mean is
-             sum * (1 / hw) (effnet.hip:876, mbconv_whole.hip:405-414).
-  SE gate    fp32 throughout: effnet.hip:879-929, mbconv_whole.hip:419-494.
-  gated A    fp16(float(D16) * gate): effnet.hip:1023-1030 (gated_project_kernel's staging), the narrow-project strips
-             (effnet.hip:708-709) and mbconv_whole.hip:540-546.
-  project    fp16 operands, fp32 accumulate, fma(acc, scale, bias) + float(identity16), one rounding: effnet.hip:1107-1118 / 1132-1134,
+             rounded once (effnet_kernels.hip:438-441, 547-552; mbconv_whole.hip:320-324, 355-359).  The squeeze sums the UNROUNDED fp32
+             values in every plan: effnet_kernels.hip:439 (`psum += v` before pack), effnet_kernels.hip:551, mbconv_whole.hip:321 / 356; the mean is
+             sum * (1 / hw) (effnet_kernels.hip:876, mbconv_whole.hip:405-414).
+  SE gate    fp32 throughout: effnet_kernels.hip:879-929, mbconv_whole.hip:419-494.
+  gated A    fp16(float(D16) * gate): effnet_kernels.hip:1023-1030 (gated_project_kernel's staging), the narrow-project strips
+             (effnet_kernels.hip:708-709) and mbconv_whole.hip:540-546.
+  project    fp16 operands, fp32 accumulate, fma(acc, scale, bias) + float(identity16), one rounding: effnet_kernels.hip:1107-1118 / 1132-1134,
              mbconv_whole.hip:628.  The identity is added AFTER the affine.
   head       fp16 operands (the stored block output, the fp16 head filter), fp32 accumulate, affine, swish; the fp32 map is NOT
-             rounded (effnet.hip:2281: run_dense with an fp32 output) and the pooled vector is the mean of the fp32 map in pixel
-             order (effnet.hip:2284; the pool-in-epilogue form conv_gemm.hip:301, 350 without RND: the same bits).
+             rounded (effnet_net.hip:460: run_dense with an fp32 output) and the pooled vector is the mean of the fp32 map in pixel
+             order (effnet_net.hip:463; the pool-in-epilogue form conv_gemm.hip:301, 350 without RND: the same bits).
 
 Not part of the contract (order-dependent fp32 sums, which differ between plans and between this model and the kernels): the k order
 of the 1x1 convs' accumulation, the order of the squeeze's pixel sum, the SE dot products, the head pool; and the logistic function

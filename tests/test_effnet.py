@@ -1,4 +1,4 @@
-"""GPU tests of the EfficientNet path (BASELINE config 5's local CNN; csrc/effnet.hip) through the C ABI.
+"""GPU tests of the EfficientNet path (BASELINE config 5's local CNN; csrc/effnet_net.hip, csrc/effnet_kernels.hip) through the C ABI.
 
 PARITY UNPINNED: the reference has no EfficientNet on a live path, so the checker is
 oracle/ref_effnet.py -- the published algorithm of the package the reference names -- and plain torch ops for the building

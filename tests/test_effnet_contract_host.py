@@ -23,7 +23,7 @@ moves an operand of the 6x-expanded 36 x 36 map across a rounding boundary under
                                          directly: test_effnet_contract_gpu.py::test_dwconv_f16_elementwise holds the returned fp32 squeeze
                                          mean to the fp64 mean of the unrounded values at fp32 spread (the mean of the rounded map is 1e-4
                                          away, 500 bounds).  The whole-block kernel returns no mean: its squeeze is tied by reading the code
-                                         only (mbconv_whole.hip:321, 356 sum the fp32 value, as effnet.hip:439, 551 do).
+                                         only (mbconv_whole.hip:321, 356 sum the fp32 value, as effnet_kernels.hip:439, 551 do).
   (b) gated operand not rounded          0.2 - 0.4 of ALL outputs flip, again by one ulp (max e 1.0 on most blocks, 1.2 - 2.0 on eleven);
                                          above the bound only on blocks 0 and 2 of 100^2 and block 0 of 144^2, by half an ulp or less,
                                          which another host's fp32 sums can undo.  NOT RELIABLY SEEN by a maximum: an operand kept in fp32

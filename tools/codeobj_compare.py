@@ -39,7 +39,7 @@ def kernels(lib_path):
                     cur, h = m.group(1), hashlib.sha256()
                     if cur in meta:
                         out[cur] = (meta[cur], h)
-                elif cur in meta and line.strip():
+                elif cur in meta and line.strip() not in ("", "..."):      # ("...": zero padding up to the next symbol's alignment)
                     # "\ts_load_dwordx2 s[0:1], ...   // 000000001900: C0060002 00000000"  ->  text + encoding, no address
                     ins, _, enc = line.partition("//")
                     h.update((ins.strip() + " | " + enc.split(":", 1)[-1].split("<")[0].strip() + "\n").encode())

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """One sha256 per tiny-map depthwise case (output map; the squeeze sums are reported rounded: their summation order differs
 between the two kernels).  tests/test_effnet.py calls digests() with the library option "effnet_plan" at its default (one thread
-per image x 4 channels, padding taps skipped: csrc/effnet.hip dw_small_kernel) and with ADAF_EF_PLAN_TINY_DW cleared
+per image x 4 channels, padding taps skipped: csrc/effnet_kernels.hip dw_small_kernel) and with ADAF_EF_PLAN_TINY_DW cleared
 (dw_same_kernel) and expects the same digests.  Run as a script it prints both arms."""
 import hashlib
 import os

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Phase timeline of the depthwise launches of EfficientNet-B3 (csrc/effnet.hip dw_same_kernel built with -DEF_TRACE by
+"""Phase timeline of the depthwise launches of EfficientNet-B3 (csrc/effnet_kernels.hip dw_same_kernel built with -DEF_TRACE by
 tools/exp/build_mbw_trace.sh): s_memtime stamps of every wave at the phase boundaries, averaged over the workgroups of the launch of block K.
 usage: python tools/dw_trace.py [block=2] [N=1024] [P=144]"""
 import ctypes as C

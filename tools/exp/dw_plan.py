@@ -1,4 +1,4 @@
-"""Python restatement of plan_dw (csrc/effnet.hip) to look at the tile plans; usage: python tools/exp/dw_plan.py"""
+"""Python restatement of plan_dw (csrc/effnet_kernels.hip) to look at the tile plans; usage: python tools/exp/dw_plan.py"""
 def plan(C, OH, OW, K, S, esize=2, xp=False, budget=None, stage_cost=None):
     budget = budget or 48 * 1024
     stage_cost = stage_cost or (96.0 if xp else 6.0)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Phase timeline of the EfficientNet stem kernel (csrc/effnet.hip ef_stem_kernel, trace build of tools/exp/build_mbw_trace.sh).
+"""Phase timeline of the EfficientNet stem kernel (csrc/effnet_kernels.hip ef_stem_kernel, trace build of tools/exp/build_mbw_trace.sh).
 usage: python tools/stem_trace.py [N=1024] [P=144]"""
 import ctypes as C
 import os
