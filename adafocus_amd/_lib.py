@@ -39,6 +39,7 @@ SYMBOLS = (
     "adaf_gru_cls_train_workspace_bytes", "adaf_gru_cls_train_forward_f32", "adaf_gru_cls_backward_workspace_bytes", "adaf_gru_cls_backward_f32",
     "adaf_ppo_sample_f32", "adaf_ppo_returns_f32", "adaf_ppo_head_workspace_bytes", "adaf_ppo_head_f32", "adaf_ppo_rows_transpose_f32",
     "adaf_ppo_wenc_grad_workspace_bytes", "adaf_ppo_wenc_grad_f32", "adaf_ppo_encoder_backward_workspace_bytes", "adaf_ppo_encoder_backward_f32",
+    "adaf_ppo_sample_actions_f32", "adaf_ppo_rewards_f32",
 )
 
 
@@ -125,6 +126,8 @@ def load_library():
     lib.adaf_gru_cls_backward_workspace_bytes.argtypes = [ip, ip, ip, ip]
     lib.adaf_gru_cls_backward_f32.argtypes = [vp, vp, ip, ip, ip, ip, ip, ip] + [vp] * 16 + [C.c_size_t, vp]
     lib.adaf_ppo_sample_f32.argtypes = [vp, vp, ip, ip, ip, vp, vp, vp, vp, vp]
+    lib.adaf_ppo_sample_actions_f32.argtypes = [vp, vp, ip, ip, ip, ip, vp, vp, vp, vp, vp, vp]
+    lib.adaf_ppo_rewards_f32.argtypes = [vp, vp, vp, vp, ip, ip, ip, ip, vp, vp, vp, vp]
     lib.adaf_ppo_returns_f32.argtypes = [vp, vp, ip, ip, fp, vp, vp]
     lib.adaf_ppo_head_workspace_bytes.restype = C.c_size_t
     lib.adaf_ppo_head_workspace_bytes.argtypes = [ip, ip]

@@ -1,6 +1,10 @@
 // Stage-2 training (ACT/models/ppo.py:84-92,98-122,147-178): what PPO needs around the GRU + Linear forward / backward of gru_bptt.hip.
 //
 //   ppo_sample_kernel        Categorical(softmax(logits)).sample() from caller-drawn uniforms, its log-probability, the probabilities
+//   ppo_sample_actions_kernel  the same sampling for a whole roll-out in one launch: logits in the GRU scan's (B, T) row order, actions and
+//                            log-probabilities in the memory's (T, B) order, crop coordinates table[action] in the trunk's (B, T) order
+//   ppo_rewards_kernel       confidence = softmax probability of the target class per (clip, step), one wave per clip, and the reward of
+//                            main_dist.py:574-581 from it; ppo_ce_last_kernel the mean cross-entropy of the last step
 //   ppo_returns_kernel       R_t = r_t + gamma R_{t+1}, then (R - mean) / (std + 1e-5) over all T*B entries (unbiased std), one block
 //   ppo_head_kernel          per row of the stacked head output [actor logits | critic value]: log-softmax, log-probability of the stored
 //                            action, entropy, value, the clipped-surrogate loss terms AND d loss.mean() / d head in the same pass
@@ -19,28 +23,120 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 namespace {
 
 // ---- sampling ---------------------------------------------------------------------------------------------------------------------------
-// One thread per row (rows = clips of one roll-out step, A <= a few dozen): max, sum of exponentials and the running sum all in index order.
+// One thread per row (A <= a few dozen): max, sum of exponentials and the running sum all in index order.
 // The sampled index is the first a whose running sum exceeds u * total; the last index if rounding leaves none.
-__global__ void ppo_sample_kernel(const float* logits, int ld, int rows, int A, const float* u, long long* action, float* logprob,
-                                  float* probs) {
-    const int r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= rows) return;
-    const float* l = logits + (size_t)r * ld;
+__device__ __forceinline__ void ppo_sample_row(const float* l, int A, float u, float* probs, int* pick_out, float* logprob_out) {
     float mx = l[0];
     for (int a = 1; a < A; ++a) mx = fmaxf(mx, l[a]);
     float total = 0.f;
     for (int a = 0; a < A; ++a) total += expf(l[a] - mx);
-    const float thr = u[r] * total;
+    const float thr = u * total;
     float run = 0.f;
     int pick = A - 1;
     for (int a = 0; a < A; ++a) {
         const float e = expf(l[a] - mx);
         run += e;
-        if (probs) probs[(size_t)r * A + a] = e / total;
+        if (probs) probs[a] = e / total;
         if (run > thr && pick == A - 1) pick = a;
     }
+    *pick_out = pick;
+    *logprob_out = (l[pick] - mx) - logf(total);
+}
+
+// rows = clips of one roll-out step
+__global__ void ppo_sample_kernel(const float* logits, int ld, int rows, int A, const float* u, long long* action, float* logprob,
+                                  float* probs) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= rows) return;
+    int pick;
+    float lp;
+    ppo_sample_row(logits + (size_t)r * ld, A, u[r], probs ? probs + (size_t)r * A : nullptr, &pick, &lp);
     action[r] = pick;
-    logprob[r] = (l[pick] - mx) - logf(total);
+    logprob[r] = lp;
+}
+
+// The whole roll-out: thread i = t * B + b reads logits row b * T + t (the GRU scan's order) and uniform i, writes action / logprob i (the
+// memory's order) and the crop coordinates table[action] into row b * T + t (the order the trunk's frame-gathering launch reads)
+__global__ void ppo_sample_actions_kernel(const float* logits, int ld, int T, int B, int A, const float* u, const float* table,
+                                          long long* action, float* logprob, float* coords) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= T * B) return;
+    const int t = i / B, b = i - t * B;
+    const size_t row = (size_t)b * T + t;
+    int pick;
+    float lp;
+    ppo_sample_row(logits + row * ld, A, u[i], nullptr, &pick, &lp);
+    action[i] = pick;
+    logprob[i] = lp;
+    if (coords) {
+        coords[2 * row] = table[2 * pick];
+        coords[2 * row + 1] = table[2 * pick + 1];
+    }
+}
+
+// ---- rewards ----------------------------------------------------------------------------------------------------------------------------
+// max and sum of exp(l - max) of one row of C logits by one wave; every lane gets both.  The sum: lane i adds its columns i, i + 64, ... in
+// index order, then six butterfly levels (lane i takes lane i ^ 32's partial, then ^ 16, 8, 4, 2, 1): a fixed tree, the same in every lane
+__device__ __forceinline__ void wave_softmax_stats(const float* l, int C, int lane, float* mx_out, float* total_out) {
+    float mx = -INFINITY;
+    for (int c = lane; c < C; c += 64) mx = fmaxf(mx, l[c]);
+    for (int s = 32; s > 0; s >>= 1) mx = fmaxf(mx, __shfl_xor(mx, s, 64));
+    float part = 0.f;
+    for (int c = lane; c < C; c += 64) part += expf(l[c] - mx);
+    for (int s = 32; s > 0; s >>= 1) part = part + __shfl_xor(part, s, 64);
+    *mx_out = mx;
+    *total_out = part;
+}
+
+// grid B, 64 threads: wave b walks its clip's T steps (rows b * T + t).  kind 0: conf_t - conf_{t-1} (conf_{-1} = 0), 1: conf_t,
+// 2: conf_t - the baseline's conf_t.  A target outside [0, C) reads nothing and gives NaN
+__global__ __launch_bounds__(64) void ppo_rewards_kernel(const float* logits, const float* base, const long long* target, int T, int B, int C,
+                                                         int kind, float* rewards, float* conf_out) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const long long tg = target[b];
+    const bool ok = tg >= 0 && tg < C;
+    float prev = 0.f;
+    for (int t = 0; t < T; ++t) {
+        const size_t row = (size_t)b * T + t;
+        float mx, total;
+        wave_softmax_stats(logits + row * C, C, lane, &mx, &total);
+        const float conf = ok ? expf(logits[row * C + tg] - mx) / total : NAN;
+        float r = conf;
+        if (kind == 0) {
+            r = conf - prev;
+            prev = conf;
+        } else if (kind == 2) {
+            wave_softmax_stats(base + row * C, C, lane, &mx, &total);
+            r = conf - (ok ? expf(base[row * C + tg] - mx) / total : NAN);
+        }
+        if (lane == 0) {
+            rewards[(size_t)t * B + b] = r;
+            if (conf_out) conf_out[(size_t)t * B + b] = conf;
+        }
+    }
+}
+
+// mean over clips of the cross-entropy of step T - 1: one block of four waves; wave w takes clips w, w + 4, ... of a chunk of 256 clips,
+// thread 0 adds the chunk's values in clip order
+__global__ __launch_bounds__(256) void ppo_ce_last_kernel(const float* logits, const long long* target, int T, int B, int C, float* out) {
+    __shared__ float ce[256];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    float sum = 0.f;
+    for (int b0 = 0; b0 < B; b0 += 256) {
+        const int nb = min(256, B - b0);
+        for (int k = wave; k < nb; k += 4) {
+            const long long tg = target[b0 + k];
+            const float* l = logits + ((size_t)(b0 + k) * T + (T - 1)) * C;
+            float mx, total;
+            wave_softmax_stats(l, C, lane, &mx, &total);
+            if (lane == 0) ce[k] = (tg >= 0 && tg < C) ? logf(total) - (l[tg] - mx) : NAN;
+        }
+        __syncthreads();
+        if (tid == 0)
+            for (int k = 0; k < nb; ++k) sum += ce[k];
+        __syncthreads();
+    }
+    if (tid == 0) *out = sum / (float)B;
 }
 
 // ---- returns ----------------------------------------------------------------------------------------------------------------------------
@@ -387,6 +483,36 @@ int adaf_ppo_sample_f32(adaf_handle* h, const float* logits, int ld, int rows, i
                        reinterpret_cast<long long*>(action_out), logprob_out, probs_out);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? ADAF_OK : adaf_hip_fail(h, e, "ppo_sample launch");
+}
+
+int adaf_ppo_sample_actions_f32(adaf_handle* h, const float* logits, int ld, int steps, int batch, int n_actions, const float* uniforms,
+                                const float* table_yx, int64_t* action_out, float* logprob_out, float* coords_out, void* stream) {
+    if (!h) return ADAF_E_BADARG;
+    if (!logits || !uniforms || !action_out || !logprob_out) return adaf_fail(h, ADAF_E_BADARG, "ppo_sample_actions: null pointer");
+    if (steps <= 0 || batch <= 0 || n_actions <= 0) return adaf_fail(h, ADAF_E_BADARG, "ppo_sample_actions: non-positive extent");
+    if (!coords_out != !table_yx) return adaf_fail(h, ADAF_E_BADARG, "ppo_sample_actions: coords_out and table_yx go together");
+    if (ld == 0) ld = n_actions;
+    if (ld < n_actions) return adaf_fail(h, ADAF_E_BADARG, "ppo_sample_actions: ld < n_actions");
+    const int n = steps * batch;
+    hipLaunchKernelGGL(ppo_sample_actions_kernel, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream, logits, ld, steps, batch, n_actions,
+                       uniforms, table_yx, reinterpret_cast<long long*>(action_out), logprob_out, coords_out);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? ADAF_OK : adaf_hip_fail(h, e, "ppo_sample_actions launch");
+}
+
+int adaf_ppo_rewards_f32(adaf_handle* h, const float* logits, const float* base_logits, const int64_t* target, int steps, int batch,
+                         int classes, int kind, float* rewards_out, float* conf_out, float* ce_last_out, void* stream) {
+    if (!h) return ADAF_E_BADARG;
+    if (!logits || !target || !rewards_out) return adaf_fail(h, ADAF_E_BADARG, "ppo_rewards: null pointer");
+    if (steps <= 0 || batch <= 0 || classes <= 0) return adaf_fail(h, ADAF_E_BADARG, "ppo_rewards: non-positive extent");
+    if (kind < ADAF_REWARD_PREV || kind > ADAF_REWARD_RANDOM) return adaf_fail(h, ADAF_E_BADARG, "ppo_rewards: kind must be 0 (prev), 1 (conf) or 2 (random)");
+    if (kind == ADAF_REWARD_RANDOM && !base_logits) return adaf_fail(h, ADAF_E_BADARG, "ppo_rewards: the random reward needs base_logits");
+    hipStream_t st = (hipStream_t)stream;
+    const long long* tg = reinterpret_cast<const long long*>(target);
+    hipLaunchKernelGGL(ppo_rewards_kernel, dim3(batch), dim3(64), 0, st, logits, base_logits, tg, steps, batch, classes, kind, rewards_out, conf_out);
+    if (ce_last_out) hipLaunchKernelGGL(ppo_ce_last_kernel, dim3(1), dim3(256), 0, st, logits, tg, steps, batch, classes, ce_last_out);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? ADAF_OK : adaf_hip_fail(h, e, "ppo_rewards launch");
 }
 
 int adaf_ppo_returns_f32(adaf_handle* h, const float* rewards, int steps, int batch, float gamma, float* returns_out, void* stream) {

@@ -18,7 +18,7 @@ which reproduces the reference logits.  Stage-3 training (``tr
 train_stage 3: only ``classifier.*`` learns) runs the frozen part on the same HIP path and the classifier with a HIP backward
 (csrc/gru_bptt.hip).  Stage-2 training (``policy_train_mode()``: only ``focuser.policy.policy`` learns) runs the roll-out through
 ``one_step_act(training=True)`` and the PPO update through ``Focuser.update()`` with a HIP backward (csrc/ppo_train.hip; the loop body is
-``adafocus_amd.train.train_stage2_batch``).  The other training branches (stages 0 and 1) are out of scope and raise.  ``GFV.one_step_act(training=False)`` -- the body of the
+``adafocus_amd.train.train_stage2_batch``; ``rollout_act`` is the T steps as one batched pass, the body of ``train_stage2_batch_fused``).  The other training branches (stages 0 and 1) are out of scope and raise.  ``GFV.one_step_act(training=False)`` -- the body of the
 stage-2 VALIDATION loop (ACT/main_dist.py:346-362), reward baseline included -- keeps the reference's
 per-step structure on the same HIP ops (round 6, pinned by G15).
 """
@@ -308,6 +308,55 @@ class GFV(nn.Module):
             return logits, last_out, patch_size_list, baseline_logits
         return logits, last_out, patch_size_list, action_list, baseline_logits
 
+    @torch.no_grad()
+    def rollout_act(self, frames, global_feat_map, global_feat, uniforms=None):
+        """The T calls of `one_step_act(training=True)` of one stage-2 batch as one batched pass (the policy's input never contains local
+        features, so every action is sampled before any patch is cropped).  frames (B, T, 3, H, W), global_feat_map / global_feat as
+        `glance` returns them, uniforms (T, B) or None (torch.rand(B) per step, in step order).  Policy over all steps
+        (`ActorCritic.act_rollout_nhwc`: focuser.memory gets what the loop appends), ONE trunk pass over the B*T sampled crops, for
+        reward = 'random' a second one over the random crops (origins drawn per step in step order from numpy's global generator, as the
+        loop draws them), the classifier scan (`classifier.hx` is left as the loop leaves it) and the baseline branch.
+        Returns (logits (T, B, C), baseline logits (T, B, C)), bit for bit the loop's."""
+        b, t = frames.shape[0], frames.shape[1]
+        logits, base_logits = self._rollout_rows(frames, global_feat_map, global_feat, uniforms)
+        c = logits.shape[1]
+        return logits.view(b, t, c).transpose(0, 1).contiguous(), base_logits.view(b, t, c).transpose(0, 1).contiguous()
+
+    @torch.no_grad()
+    def _rollout_rows(self, frames, global_feat_map, global_feat, uniforms=None):
+        """rollout_act in the classifier's own row order: (logits (B*T, C), baseline logits (B*T, C)), rows b * T + t."""
+        if self.focuser.policy is None:
+            raise NotImplementedError("one_step_act(training=True) is the stage-2 (PPO) roll-out: this is a random-patch model, it has no "
+                                      "policy to roll out (use training=False)")
+        if not self.focuser.policy.policy_old.training:
+            raise NotImplementedError("one_step_act(training=True) is the stage-2 (PPO) roll-out: call model.policy_train_mode() first "
+                                      "(focuser.policy.policy_old is in eval mode)")
+        if self.rew not in ("random", "padding", "prev", "conf"):
+            raise NotImplementedError("reward %r" % (self.rew,))
+        b, t = frames.shape[0], frames.shape[1]
+        dev = frames.device
+        flat = frames.reshape(b * t, *frames.shape[2:])
+        # (B, T, C, h, w), the permuted view of the pixel-major map -> the map itself, (B*T, h, w, C): free for the HIP glancer's output
+        fmap = global_feat_map.permute(0, 1, 3, 4, 2).reshape(b * t, *global_feat_map.shape[3:], global_feat_map.shape[2])
+        focuser = self.focuser
+        if self.rew == "random":
+            # the random crops' origins first: host work and one copy, drawn step by step as the loop draws them (rows b * T + t)
+            hh, ww = frames.shape[3], frames.shape[4]
+            per_step = np.stack([random_crop_actions(b, hh, ww, focuser.patch_sampler.size) for _ in range(t)], 1)
+            base_coords = torch.from_numpy(per_step.reshape(b * t, 2)).to(dev)
+        _, coords = focuser.policy.policy_old.act_rollout_nhwc(fmap, b, t, focuser.memory, focuser.action_table(dev), uniforms)
+        gvec = global_feat if self.with_glancer else None
+        feature = self.hot_path_features(flat, gvec, coords, b, t)
+        if self.rew == "random":
+            base = self.hot_path_features(flat, gvec, base_coords, b, t)
+        else:
+            base = torch.zeros_like(feature)
+            if gvec is not None:
+                base[:, :, :gvec.shape[2]] = gvec
+        cls = self.classifier
+        logits, _, cls.hx, hs = cls._steps_from(feature, None, want_hs=True)
+        return logits, cls.branch_forward(base, hs)
+
     def train_mode(self, args):
         """gfv_net.py:62-81 for train_stage == 3 (call after model.train(), as ACT/main_dist.py does): the glancer, the focuser and
         both policies go to eval mode; only the classifier trains (dropout on, HIP backward).  Stages 0 and 1 (the backbones' training) are
@@ -495,6 +544,19 @@ class Focuser(nn.Module):
         return self.net.feature_dim
 
 
+def random_crop_actions(n, hh, ww, size):
+    """PatchSampler.random_actions on the host: the draws for n frames of hh x ww, in its order, as a float32 (n, 2) array."""
+    act = np.zeros((n, 2), dtype=np.float64)
+    if hh != size:
+        if hh != ww:
+            raise ValueError("random crops: square frames expected (the gather scales both axes by H - P, utils.py:40-42)")
+        for i in range(n):
+            act[i, 0] = np.random.randint(0, hh - size)
+            act[i, 1] = np.random.randint(0, ww - size)
+        act = (act + 0.5) / (hh - size)
+    return act.astype(np.float32)
+
+
 class PatchSampler(nn.Module):
     def __init__(self, size=96, random=True):
         super().__init__()
@@ -511,16 +573,7 @@ class PatchSampler(nn.Module):
         """One crop origin per image drawn exactly like utils.py:24-35 (`np.random.randint(0, H - P)` for y, then for x, image by image; no draw
         at H == P), returned as gather actions (origin + 0.5) / (H - P): floor(a * (H - P)) (utils.py:42) lands on the drawn integer whatever
         the rounding.  A seeded numpy generator therefore reproduces the reference's crops."""
-        n, hh, ww = imgs.shape[0], imgs.shape[2], imgs.shape[3]
-        act = np.zeros((n, 2), dtype=np.float64)
-        if hh != self.size:
-            if hh != ww:
-                raise ValueError("random crops: square frames expected (the gather scales both axes by H - P, utils.py:40-42)")
-            for i in range(n):
-                act[i, 0] = np.random.randint(0, hh - self.size)
-                act[i, 1] = np.random.randint(0, ww - self.size)
-            act = (act + 0.5) / (hh - self.size)
-        return torch.from_numpy(act.astype(np.float32)).to(imgs.device)
+        return torch.from_numpy(random_crop_actions(imgs.shape[0], imgs.shape[2], imgs.shape[3], self.size)).to(imgs.device)
 
     def random_sample(self, imgs):
         """gfv_net.py:376-381: a crop at a random position per image."""
@@ -579,9 +632,9 @@ class RecurrentClassifier(nn.Module):
         return hip_ops.gru_cls_forward(feature, g.weight_ih_l0.detach(), g.weight_hh_l0.detach(), g.bias_ih_l0.detach(),
                                        g.bias_hh_l0.detach(), self.fc.weight.detach(), self.fc.bias.detach())
 
-    def _steps_from(self, feature, hx):
+    def _steps_from(self, feature, hx, want_hs=False):
         """GRU over feature (B,t,F) from the hidden state hx ((1,B,H) or None = zeros) + FC on every step: (logits (B*t,C), last (B,C),
-        final hidden (1,B,H))."""
+        final hidden (1,B,H)[, every step's hidden state (B,t,H) when want_hs])."""
         if self.training:
             raise RuntimeError("RecurrentClassifier: eval mode only (dropout must be the identity)")
         g = self.gru
@@ -589,7 +642,29 @@ class RecurrentClassifier(nn.Module):
         hs = hip_ops.gru_seq_forward(feature, g.weight_ih_l0.detach(), g.weight_hh_l0.detach(), g.bias_ih_l0.detach(), g.bias_hh_l0.detach(),
                                      h0=None if hx is None else hx[0])
         logits = hip_ops.linear(hs.reshape(b * t, -1), self.fc.weight.detach(), self.fc.bias.detach())
-        return logits, logits.view(b, t, -1)[:, -1, :].reshape(b, -1), hs[:, -1].unsqueeze(0).contiguous()
+        out = (logits, logits.view(b, t, -1)[:, -1, :].reshape(b, -1), hs[:, -1].unsqueeze(0).contiguous())
+        return out + (hs,) if want_hs else out
+
+    def branch_forward(self, x_base, hs):
+        """The reward baseline of every step at once: for each (b, t) ONE GRU step on x_base[b, t] from the main scan's h_{t-1} (hs (B,T,H)
+        = the hidden states `_steps_from` ran through; zeros at t = 0), then the FC; nothing is stored.  `test_single_forward` called before
+        every `single_forward` of a step loop, as scans of one step over the B*T rows.  Returns logits (B*T, C), rows b * T + t.
+        The scan's two forms sum W_hh h in different orders: the persistent kernel serves up to 256 rows, the launch-per-step
+        form the rest, so a step's bits depend on which form its batch takes.  The rows therefore go in chunks of at most 256 when a step of
+        batch B takes the persistent form (B <= 256), in one call otherwise: every row gets the form the step loop's step gets."""
+        if self.training:
+            raise RuntimeError("RecurrentClassifier: eval mode only (dropout must be the identity)")
+        g = self.gru
+        b, t, _ = x_base.shape
+        rows = b * t
+        h0 = torch.zeros_like(hs)
+        h0[:, 1:] = hs[:, :-1]
+        h0, x = h0.view(rows, -1), x_base.reshape(rows, 1, -1)
+        chunk = 256 if b <= 256 else rows
+        w = [p.detach() for p in (g.weight_ih_l0, g.weight_hh_l0, g.bias_ih_l0, g.bias_hh_l0)]
+        outs = [hip_ops.gru_seq_forward(x[i:i + chunk], *w, h0=h0[i:i + chunk]).view(-1, self.hidden_dim) for i in range(0, rows, chunk)]
+        out = outs[0] if len(outs) == 1 else torch.cat(outs, 0)
+        return hip_ops.linear(out, self.fc.weight.detach(), self.fc.bias.detach())
 
     def _state(self, reset, b):
         if reset:

@@ -253,6 +253,64 @@ def ppo_sample(logits, uniforms, want_probs=False):
     return (action, logprob, probs) if want_probs else (action, logprob)
 
 
+def ppo_sample_actions(logits, uniforms, table=None):
+    """The sampling of a whole roll-out in one launch: logits (B*T, A) with rows b*T+t (a row stride >= A is taken as it is), uniforms (T, B)
+    in [0, 1), table (A, 2) or None -> (actions int64 (T, B), logprobs (T, B)[, coords (B*T, 2) = table[action], rows b*T+t]).  Per row the
+    arithmetic is ppo_sample's: the same bits as T calls of it."""
+    L.need_gpu_f32(logits, uniforms, table)
+    if logits.dim() != 2 or uniforms.dim() != 2:
+        raise ValueError("ppo_sample_actions: logits (B*T, A) and uniforms (T, B) expected")
+    if logits.stride(1) != 1 or logits.stride(0) < logits.shape[1]:
+        logits = logits.contiguous()
+    uniforms = uniforms.contiguous()
+    rows, a = logits.shape
+    t, b = uniforms.shape
+    if rows != t * b:
+        raise ValueError("ppo_sample_actions: one uniform per row expected")
+    if table is not None and tuple(table.shape) != (a, 2):
+        raise ValueError("ppo_sample_actions: table (A, 2) expected")
+    action = torch.empty((t, b), device=logits.device, dtype=torch.int64)
+    logprob = torch.empty((t, b), device=logits.device, dtype=torch.float32)
+    coords = torch.empty((rows, 2), device=logits.device, dtype=torch.float32) if table is not None else None
+    h = _h(logits)
+    L.check(L.load_library().adaf_ppo_sample_actions_f32(h, L.ptr(logits), logits.stride(0), t, b, a, L.ptr(uniforms),
+                                                         L.ptr(None if table is None else table.contiguous()), L.ptr(action), L.ptr(logprob),
+                                                         L.ptr(coords), L.stream_ptr()), h)
+    return (action, logprob) if table is None else (action, logprob, coords)
+
+
+REWARD_KINDS = {"prev": 0, "conf": 1, "random": 2}
+
+
+def ppo_rewards(logits, base_logits, target, steps, kind, want_conf=False, want_ce_last=False):
+    """The rewards of a whole roll-out (ACT/main_dist.py:511-516, 574-581): logits (B*T, C) with rows b*T+t, base_logits the same shape (the
+    baseline's; None unless kind is 'random'), target (B,) int64, kind 'prev' | 'conf' | 'random' (or its number) ->
+    rewards (T, B)[, confidences (T, B)][, the mean cross-entropy of the last step (1,)]."""
+    L.need_gpu_f32(logits, base_logits)
+    if target.dtype != torch.int64 or not target.is_cuda:
+        raise ValueError("ppo_rewards: int64 GPU target (B,) expected")
+    logits, target = logits.contiguous(), target.contiguous()
+    t, b = int(steps), target.numel()
+    if logits.dim() != 2 or logits.shape[0] != t * b:
+        raise ValueError("ppo_rewards: logits (B*T, C) expected")
+    if base_logits is not None:
+        if base_logits.shape != logits.shape:
+            raise ValueError("ppo_rewards: base_logits of the logits' shape expected")
+        base_logits = base_logits.contiguous()
+    kind = REWARD_KINDS.get(kind, kind)
+    if not isinstance(kind, int):
+        raise NotImplementedError("reward %r" % (kind,))
+    dev, fp = logits.device, torch.float32
+    rewards = torch.empty((t, b), device=dev, dtype=fp)
+    conf = torch.empty((t, b), device=dev, dtype=fp) if want_conf else None
+    ce = torch.empty((1,), device=dev, dtype=fp) if want_ce_last else None
+    h = _h(logits)
+    L.check(L.load_library().adaf_ppo_rewards_f32(h, L.ptr(logits), L.ptr(base_logits), L.ptr(target), t, b, logits.shape[1], kind,
+                                                  L.ptr(rewards), L.ptr(conf), L.ptr(ce), L.stream_ptr()), h)
+    out = (rewards,) + ((conf,) if want_conf else ()) + ((ce,) if want_ce_last else ())
+    return out if len(out) > 1 else rewards
+
+
 def ppo_returns(rewards, gamma):
     """rewards (T, B) -> discounted returns, normalised over all T*B entries (ACT/models/ppo.py:148-157)."""
     L.need_gpu_f32(rewards)

@@ -9,6 +9,9 @@ activations, HIP backward for every policy parameter) and ``PPO.update`` runs re
 Adam step}.  The GRU with both heads is the stage-3 GRU + Linear pair with the actor and critic weights stacked into one (A + 1)-row
 Linear.  The Linear state encoder (``policy_conv=False``) has no backward here: its ``evaluate`` / ``update`` raise.
 
+``ActorCritic.act_rollout_nhwc`` is the sampling roll-out of all T steps at once (the policy's input never contains local features): it
+leaves the memory as T calls of ``act(training=True)`` leave it and returns the crop coordinates in the trunk's row order.
+
 ``ActorCritic.act_sequence_nhwc`` is the offline-inference form on the HIP engine: in eval mode the
 policy input is only the glancer feature map and its own hidden state (ppo.py:67-96), so all T
 actions are computed before any patch is cropped -- 1x1 conv + Linear over all B*T frames at once,
@@ -169,6 +172,37 @@ class ActorCritic(nn.Module):
         logits = hip_ops.linear(hs.view(b * t, -1), act.weight.detach(), act.bias.detach())
         idx, actions = hip_ops.grid_actions(logits, table)
         return idx.view(b, t), actions
+
+    @torch.no_grad()
+    def act_rollout_nhwc(self, featmap_nhwc, b, t, memory, table, uniforms=None):
+        """The sampling roll-out of stage-2 training in one pass: T calls of ``act(training=True)`` (the first with restart_batch) on the
+        steps of featmap (B*T, h, w, C) pixel-major, frames b * T + t.  Encoder over all B*T frames, one GRU scan, one actor GEMM, one
+        sampling launch; `memory` is left exactly as the T calls leave it (states: the (B, C, h, w) views of the map; actions, logprobs:
+        T tensors (B,); hidden: the zero state and T entries (1, B, H)).  uniforms (T, B) in [0, 1); None draws torch.rand(B) on the device
+        T times in step order, the loop's draw sequence.  Returns (actions (T, B) int64, coords (B*T, 2) fp32 = table[action], rows
+        b * T + t: what the frame-gathering trunk pass reads)."""
+        dev = featmap_nhwc.device
+        g, act = self.gru, self.actor[0]
+        if self.policy_conv:
+            e = self._encode(featmap_nhwc)
+        else:   # the Linear encoder flattens the reference's (C, h, w) order
+            e = self._encode(featmap_nhwc.permute(0, 3, 1, 2))
+        hs = hip_ops.gru_seq_forward(e.view(b, t, -1), g.weight_ih_l0.detach(), g.weight_hh_l0.detach(),
+                                     g.bias_ih_l0.detach(), g.bias_hh_l0.detach())
+        logits = hip_ops.linear(hs.view(b * t, -1), act.weight.detach(), act.bias.detach())
+        if uniforms is None:
+            uniforms = torch.stack([torch.rand(b, device=dev, dtype=torch.float32) for _ in range(t)], 0)
+        actions, logprobs, coords = hip_ops.ppo_sample_actions(logits, uniforms, table)
+        steps = featmap_nhwc.unflatten(0, (b, t))
+        hs_tb = hs.transpose(0, 1).contiguous()
+        del memory.hidden[:]
+        memory.hidden.append(torch.zeros(1, b, self.hidden_state_dim, device=dev))
+        for s in range(t):
+            memory.states.append(steps[:, s].permute(0, 3, 1, 2))
+            memory.actions.append(actions[s])
+            memory.logprobs.append(logprobs[s])
+            memory.hidden.append(hs_tb[s:s + 1])
+        return actions, coords
 
 
 _FWD_TENSORS = ("states", "e1", "e_bt", "gi", "hs", "head", "head_w", "w_ih", "w_hh", "b_hh", "w_lin")

@@ -4,13 +4,18 @@
     for images, target in loader:
         preds, loss = train_stage2_batch(model, images.cuda(), target[:, 0].cuda(), args)
 
+``train_stage2_batch_fused`` is the same body with the roll-out as one batched pass (``GFV.rollout_act``: all T actions sampled first, one
+trunk pass over the B*T crops) and the rewards from one kernel; same contract, same predictions.
+
 Both CNNs and the classifier stay frozen and run on the HIP path; only ``focuser.policy.policy`` learns (``PPO.update``: HIP forward and
 backward, PyTorch's Adam step).
 """
 import torch
 import torch.nn.functional as F
 
-__all__ = ["get_reward", "train_stage2_batch"]
+from . import hip_ops
+
+__all__ = ["get_reward", "train_stage2_batch", "train_stage2_batch_fused"]
 
 
 def get_reward(args, confidence, confidence_last, baseline):
@@ -51,3 +56,24 @@ def train_stage2_batch(model, images, target, args):
         model.focuser.memory.rewards.append(reward)
     model.focuser.update()
     return torch.stack(local_results), loss
+
+
+def train_stage2_batch_fused(model, images, target, args, uniforms=None):
+    """train_stage2_batch with the T roll-out steps as one batched pass: glance, `model.rollout_act` (policy over all steps, one trunk pass
+    over the B*T sampled crops, classifier scan and baseline branch), the rewards of all steps from `hip_ops.ppo_rewards` into
+    model.focuser.memory.rewards as T (1, B) entries, then model.focuser.update().  uniforms (T, B) steers the sampling (None: torch.rand
+    per step).  Same contract and return value: (predictions of every step stacked (T, B, C), the last step's cross-entropy)."""
+    if args.reward not in hip_ops.REWARD_KINDS:
+        raise NotImplementedError("reward %r" % (args.reward,))
+    b = target.shape[0]
+    t = args.num_segments
+    input_prime = model.glancer_input(images)
+    frames = images.view(b, t, 3, model.input_size, model.input_size)
+    with torch.no_grad():
+        global_feat_map, global_feat = model.glance(input_prime)
+        logits, baseline = model._rollout_rows(frames, global_feat_map, global_feat, uniforms)        # rows b * T + t
+        rewards, loss = hip_ops.ppo_rewards(logits, baseline, target, t, args.reward, want_ce_last=True)
+        preds = logits.view(b, t, -1).transpose(0, 1).contiguous()
+    model.focuser.memory.rewards.extend(rewards[s:s + 1] for s in range(t))
+    model.focuser.update()
+    return preds, loss[0]

@@ -574,6 +574,20 @@ int adaf_gru_cls_backward_f32(adaf_handle* h, const float* x, int ldx, int batch
  * adaf_ppo_sample_f32: Categorical(softmax(logits)).sample() (ppo.py:84-92) from caller-drawn uniforms u [rows] in [0, 1).
  *   logits [rows, A] with row stride ld (0 = A).  action_out [rows] int64 = the first a whose running sum of exp(l - max), in index
  *   order, exceeds u * total (the last index if rounding leaves none); logprob_out [rows]; probs_out [rows, A] or NULL.
+ * adaf_ppo_sample_actions_f32: the sampling of a whole roll-out in one launch.  logits [B*T, A] with rows b * T + t (the order the GRU scan
+ *   and the actor GEMM produce) and row stride ld (0 = A), uniforms [T, B], table_yx [A, 2].  action_out [T, B] int64 and logprob_out
+ *   [T, B] (the order Memory and PPO.update use); coords_out [B*T, 2] = table_yx[action] with rows b * T + t (the order the trunk's
+ *   frame-gathering first launch reads).  Per row the arithmetic is adaf_ppo_sample_f32's (one device function): the same bits as T calls
+ *   of it.  coords_out and table_yx may both be NULL (indices only); one without the other is ADAF_E_BADARG.
+ * adaf_ppo_rewards_f32: the rewards of a whole roll-out (ACT/main_dist.py:511-516, 574-581).  logits [B*T, C] contiguous with rows
+ *   b * T + t, base_logits the same shape (the reward baseline's; may be NULL unless kind is ADAF_REWARD_RANDOM), target [B] int64.
+ *   The confidence of (b, t) is the softmax probability of class target[b]: exp(l[target] - max) / sum, one wave per row; the sum of
+ *   exp(l - max) is taken as lane-strided partials in index order (lane i adds columns i, i + 64, ...), then a fixed butterfly tree over
+ *   the 64 lanes (partner lane i ^ 32, then ^ 16, 8, 4, 2, 1).  rewards_out [T, B]: ADAF_REWARD_PREV conf_t - conf_{t-1} with
+ *   conf_{-1} = 0 (step 0 is the confidence itself, bit for bit), ADAF_REWARD_CONF conf_t, ADAF_REWARD_RANDOM conf_t - the baseline's
+ *   conf_t.  conf_out [T, B] (may be NULL): the confidences.  ce_last_out [1] (may be NULL): the mean over clips of the cross-entropy of
+ *   step T - 1, log(sum) - (l[target] - max) per clip, added over clips in index order.  A target outside [0, C) reads nothing out of
+ *   range: that clip's rewards and confidences are NaN (and so is ce_last_out); other clips are untouched.  No workspace.
  * adaf_ppo_returns_f32: rewards [T, B] -> R_t = r_t + gamma R_{t+1}, then (R - mean) / (std + 1e-5) over all T*B entries with the
  *   unbiased standard deviation (ppo.py:148-157), sums in a fixed order.  returns_out [T, B].
  * adaf_ppo_head_f32: per row of the stacked head output head [T*B, A + 1] (row b * T + t when head_batch_major, else t * B + b; columns
@@ -599,6 +613,11 @@ int adaf_gru_cls_backward_f32(adaf_handle* h, const float* x, int ldx, int batch
  * The workspace queries are plain arithmetic (no device needed) and return 0 for a non-positive extent. */
 int adaf_ppo_sample_f32(adaf_handle* h, const float* logits, int ld, int rows, int n_actions, const float* uniforms, int64_t* action_out,
                         float* logprob_out, float* probs_out, void* stream);
+enum { ADAF_REWARD_PREV = 0, ADAF_REWARD_CONF = 1, ADAF_REWARD_RANDOM = 2 };
+int adaf_ppo_sample_actions_f32(adaf_handle* h, const float* logits, int ld, int steps, int batch, int n_actions, const float* uniforms,
+                                const float* table_yx, int64_t* action_out, float* logprob_out, float* coords_out, void* stream);
+int adaf_ppo_rewards_f32(adaf_handle* h, const float* logits, const float* base_logits, const int64_t* target, int steps, int batch,
+                         int classes, int kind, float* rewards_out, float* conf_out, float* ce_last_out, void* stream);
 int adaf_ppo_returns_f32(adaf_handle* h, const float* rewards, int steps, int batch, float gamma, float* returns_out, void* stream);
 size_t adaf_ppo_head_workspace_bytes(int steps, int batch);
 int adaf_ppo_head_f32(adaf_handle* h, const float* head, int head_batch_major, int steps, int batch, int n_actions, const int64_t* actions,

@@ -19,10 +19,17 @@
   full_batch_ms         train_stage2_batch end to end
 Times are HIP-event means over --steps calls after --warmup calls unless said otherwise; one process, one device.
 
+`--rollout` is a mode of its own (profiles/stage2_rollout_probe.json): for reward = 'random' and 'prev', `train_stage2_batch` (the step
+loop) and `train_stage2_batch_fused` (all T steps in one batched pass) ALTERNATING within a round, --rounds rounds of --steps calls each
+after a warm-up; the mean over rounds with the smallest and largest round beside it, the ratio of the means, and the fused body's parts
+on their own (glance, policy roll-out, trunk pass over the sampled crops, the random crops' pass, classifier scan + baseline branch,
+rewards, update).  It ASSERTS that the fused body is at least 1.5x faster than the step loop for both reward kinds (after writing --out).
+
 Every GPU step runs under a time limit of its own and the steps are chained, so that a failure ends the run:
 
     timeout -k 10 300 rocprofv3 --kernel-trace -d TRACE -- python tools/stage2_train_probe.py --splitk-only && \
     timeout -k 10 420 python tools/stage2_train_probe.py --trace TRACE --out profiles/stage2_train_probe.json
+    timeout -k 10 300 python tools/stage2_train_probe.py --rollout --out profiles/stage2_rollout_probe.json
 
 Nothing is caught inside: an error in any part, the PyTorch context included, ends the process with a non-zero status.
 """
@@ -36,11 +43,12 @@ import os
 import sys
 import types
 
+import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from adafocus_amd import hip_ops, synth, train  # noqa: E402
-from adafocus_amd.gfv_net import GFV  # noqa: E402
+from adafocus_amd.gfv_net import GFV, random_crop_actions  # noqa: E402
 from adafocus_amd.ppo import Memory  # noqa: E402
 from tests.helpers import manifest  # noqa: E402
 
@@ -119,8 +127,90 @@ def torch_update(ppo, pol, opt, states_nchw, actions, old, returns):
     opt.step()
 
 
+ROLLOUT_GATE = 1.5
+
+
+def rollout_mode(a, dev):
+    """The step loop against the fused body, alternating; see the module docstring."""
+    res = {"probe": "stage2_rollout", "B": B, "T": T, "P": P, "A": A, "C": C, "H": H, "device": torch.cuda.get_device_name(0),
+           "rounds": a.rounds, "calls_per_round": a.steps, "gate": ROLLOUT_GATE}
+    images = torch.from_numpy(synth.synth_frames(B, T, 224, seed=5)).to(dev)
+    target = torch.randint(0, 200, (B,), device=dev)
+    for reward in ("random", "prev"):
+        args = types.SimpleNamespace(num_segments=T, num_classes=200, reward=reward, dataset="actnet", input_size=224, batch_size=B,
+                                     patch_size=P, with_glancer=True, feature_map_channels=C, glance_size=224, action_dim=A,
+                                     hidden_state_dim=H, policy_conv=True, gpu=0, continuous=False, gamma=0.7, policy_lr=0.0003,
+                                     random_patch=False, dropout=0.5, consensus="gru", hidden_dim=1024, train_stage=2)
+        model = GFV(args)
+        model.load_state_dict({k: torch.from_numpy(v) for k, v in synth.synth_state_dict(manifest()["ACT"], 1007).items()}, strict=True)
+        model = model.to(dev)
+        model.policy_train_mode()
+
+        def loop():
+            return train.train_stage2_batch(model, images, target, args)
+
+        def fused():
+            return train.train_stage2_batch_fused(model, images, target, args)
+        timed(loop, 1, 2)
+        timed(fused, 1, 2)
+        ours, theirs = [], []
+        for _ in range(a.rounds):
+            theirs.append(timed(loop, a.steps, 0))
+            ours.append(timed(fused, a.steps, 0))
+        r = {"step_loop_ms": round(statistics.mean(theirs), 4), "step_loop_ms_min_max": [round(min(theirs), 4), round(max(theirs), 4)],
+             "fused_ms": round(statistics.mean(ours), 4), "fused_ms_min_max": [round(min(ours), 4), round(max(ours), 4)]}
+        r["speedup"] = round(statistics.mean(theirs) / statistics.mean(ours), 3)
+        # the fused body's parts, each on its own (the sum leaves out what overlaps and the host work between the parts)
+        foc, cls, mem = model.focuser, model.classifier, model.focuser.memory
+        flat = images.view(B * T, 3, 224, 224)
+        table = foc.action_table(dev)
+        with torch.no_grad():
+            r["glance_ms"] = round(timed(lambda: model.glance(images), a.steps, a.warmup), 4)
+            fmap, fvec = model.glance(images)
+            nhwc = fmap.permute(0, 1, 3, 4, 2).reshape(B * T, HW, HW, C)
+
+            def policy():
+                mem.clear_memory()
+                return foc.policy.policy_old.act_rollout_nhwc(nhwc, B, T, mem, table)
+            r["policy_rollout_ms"] = round(timed(policy, a.steps, a.warmup), 4)
+            _, coords = policy()
+            r["trunk_pass_ms"] = round(timed(lambda: model.hot_path_features(flat, fvec, coords, B, T), a.steps, a.warmup), 4)
+            feature = model.hot_path_features(flat, fvec, coords, B, T)
+
+            def random_crops():
+                return torch.from_numpy(np.stack([random_crop_actions(B, 224, 224, P) for _ in range(T)], 1).reshape(B * T, 2)).to(dev)
+            r["random_crop_draw_ms"] = round(timed(random_crops, a.steps, a.warmup), 4)
+
+            def classifier():
+                logits, _, _, hs = cls._steps_from(feature, None, want_hs=True)
+                return logits, cls.branch_forward(feature, hs)
+            r["classifier_ms"] = round(timed(classifier, a.steps, a.warmup), 4)
+            logits, base = classifier()
+            r["rewards_ms"] = round(timed(lambda: hip_ops.ppo_rewards(logits, base, target, T, reward, want_ce_last=True), a.steps, a.warmup), 4)
+            rewards = hip_ops.ppo_rewards(logits, base, target, T, reward)
+        mem.rewards.extend(rewards[s:s + 1] for s in range(T))
+        stored = Memory()
+        for name in ("states", "actions", "logprobs", "rewards"):
+            getattr(stored, name).extend(getattr(mem, name))
+        r["ppo_update_ms"] = round(timed(lambda: foc.policy.update(stored), a.steps, a.warmup), 4)
+        mem.clear_memory()
+        assert hip_ops.gru_scan_timeouts() == 0
+        res[reward] = r
+        del model, stored, fmap, fvec, nhwc, feature, logits, base
+        torch.cuda.empty_cache()
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+    for reward in ("random", "prev"):
+        assert res[reward]["speedup"] >= ROLLOUT_GATE, "fused body %.2fx the step loop for reward %r: below %.1fx" % (
+            res[reward]["speedup"], reward, ROLLOUT_GATE)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--rollout", action="store_true")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--rounds", type=int, default=5)
@@ -131,6 +221,9 @@ def main():
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
+    if a.rollout:
+        rollout_mode(a, dev)
+        return
     if a.splitk_only:
         sets = splitk_inputs(dev)
         splitk_calls(sets, 20)
