@@ -40,6 +40,8 @@ SYMBOLS = (
     "adaf_ppo_sample_f32", "adaf_ppo_returns_f32", "adaf_ppo_head_workspace_bytes", "adaf_ppo_head_f32", "adaf_ppo_rows_transpose_f32",
     "adaf_ppo_wenc_grad_workspace_bytes", "adaf_ppo_wenc_grad_f32", "adaf_ppo_encoder_backward_workspace_bytes", "adaf_ppo_encoder_backward_f32",
     "adaf_ppo_sample_actions_f32", "adaf_ppo_rewards_f32",
+    "adaf_ppo_gauss_sample_f32", "adaf_ppo_gauss_head_f32", "adaf_bn_train_workspace_bytes", "adaf_bn_train_forward_f32", "adaf_bn_train_backward_f32",
+    "adaf_ppo_encoder_bn_backward_workspace_bytes", "adaf_ppo_encoder_bn_backward_f32",
 )
 
 
@@ -139,6 +141,15 @@ def load_library():
     lib.adaf_ppo_encoder_backward_workspace_bytes.restype = C.c_size_t
     lib.adaf_ppo_encoder_backward_workspace_bytes.argtypes = [ip, ip, ip, ip, ip, ip]
     lib.adaf_ppo_encoder_backward_f32.argtypes = [vp, vp, vp, vp, vp, ip, ip, ip, ip, ip, ip, vp, vp, vp, vp, vp, C.c_size_t, vp]
+    lib.adaf_ppo_gauss_sample_f32.argtypes = [vp, vp, vp, ip, fp, vp, vp, vp]
+    lib.adaf_ppo_gauss_head_f32.argtypes = [vp, vp, ip, ip, ip, vp, fp, vp, vp, fp] + [vp] * 8 + [C.c_size_t, vp]
+    lib.adaf_bn_train_workspace_bytes.restype = C.c_size_t
+    lib.adaf_bn_train_workspace_bytes.argtypes = [ip, ip]
+    lib.adaf_bn_train_forward_f32.argtypes = [vp, vp, ip, ip, vp, vp, fp, fp, vp, vp, ip, vp, vp, vp, vp, C.c_size_t, vp]
+    lib.adaf_bn_train_backward_f32.argtypes = [vp, vp, vp, vp, ip, ip] + [vp] * 7 + [C.c_size_t, vp]
+    lib.adaf_ppo_encoder_bn_backward_workspace_bytes.restype = C.c_size_t
+    lib.adaf_ppo_encoder_bn_backward_workspace_bytes.argtypes = [ip] * 7
+    lib.adaf_ppo_encoder_bn_backward_f32.argtypes = [vp] * 5 + [ip] * 6 + [vp] * 17 + [C.c_size_t, vp]
     lib.adaf_crop_gather_nhwc4_f32.argtypes = [vp, vp, ip, ip, ip, vp, ip, ip, ip, vp, vp, vp]
     lib.adaf_ingest_u8_f32.argtypes = [vp, vp, ip, ip, ip, ip, C.POINTER(C.c_float), C.POINTER(C.c_float), vp, vp]
     lib.adaf_crop_resize_f32.argtypes = [vp, vp, ip, ip, ip, ip, ip, vp, ip, ip, vp, ip, ip, vp, ip, vp, vp]

@@ -14,6 +14,17 @@
 //                            partial in MFMA accumulators; ppo_wenc_reduce_kernel adds the slices in slice order
 //   small layout kernels     (T, B) <-> (B, T) row permutation (with the ReLU mask), the Linear gradient's pixel-major -> nn.Linear permutation
 //
+// The continuous policy of the Something-Something tree (STH/models/ppo_continuous.py) adds
+//   ppo_gauss_sample_kernel  a = 1 - relu(1 - relu(mu + sigma z)) from caller-drawn normals, one rounding per operation, and the
+//                            log-probability of the clamped action under N(mu, sigma^2 I)
+//   ppo_gauss_head_kernel    ppo_head_kernel's sibling for the stacked head [mean logits (2) | value]: sigmoid, Gaussian log-probability,
+//                            the constant entropy, and the same loss tail (one device function, ppo_loss_tail)
+//   bn_* kernels             BatchNorm with batch statistics over the rows of a [rows, cols] matrix: two-pass column statistics (the mean,
+//                            then the squared deviations) as slice partials in row order + a fixed-order sum over the slices (in double), the running
+//                            statistics' update, normalise + affine (+ ReLU), and the backward (d gamma, d beta, dx)
+//   ppo_wenc_splitk_kernel   also with 64 conv outputs (two 32-row accumulator sets at 128 channels per block) and with a gradient
+//                            whose mask is already applied (no E1 operand)
+//
 // fp32 throughout, no atomics: the same inputs give the same bits.  Every kernel compiles to zero scratch.
 #include "adaf_internal.h"
 
@@ -194,7 +205,31 @@ struct HeadArgs {
     float* dhead;             // [T*B, A + 1] in the head's row order (may be null)
     int T, B, A, head_bt, mode;   // mode 0: statistics only, 1: PPO loss + its gradient, 2: gradient from g_*
     float eps_clip;
+    const float* action_yx;   // [T, B, 2] the stored continuous actions and the policy's standard deviation (ppo_gauss_head_kernel only)
+    float sigma;
 };
+
+// The tail both loss heads share, from a row's log-probability of its stored action, value and entropy: the two per-row loss terms
+// (-min(surr1, surr2) - 0.01 entropy, (value - return)^2) and d loss.mean() / d (logprob, value, entropy).
+// autograd through torch.min / torch.clamp: an unclamped ratio carries the whole advantage (half through each equal branch); a clamped
+// one carries it only when surr1 wins the min (half of it on an exact tie)
+struct PpoTail { float term_pg, term_v, g_lp, g_v, g_ent; };
+__device__ __forceinline__ PpoTail ppo_loss_tail(float lp_act, float old_lp, float R, float v, float ent, float eps_clip, int n) {
+    PpoTail o;
+    const float inv_n = 1.f / (float)n;
+    const float ratio = expf(lp_act - old_lp);
+    const float adv = R - v;
+    const float lo = 1.f - eps_clip, hi = 1.f + eps_clip;
+    const float surr1 = ratio * adv, surr2 = fminf(fmaxf(ratio, lo), hi) * adv;
+    o.term_pg = -fminf(surr1, surr2) - 0.01f * ent;
+    o.term_v = (v - R) * (v - R);
+    float g_ratio = adv;
+    if (ratio < lo || ratio > hi) g_ratio = surr1 < surr2 ? adv : (surr1 == surr2 ? 0.5f * adv : 0.f);
+    o.g_lp = -g_ratio * ratio * inv_n;
+    o.g_v = (v - R) * inv_n;            // 0.5 * MSE, a mean over all rows, broadcast into every row's loss
+    o.g_ent = -0.01f * inv_n;
+    return o;
+}
 
 __global__ void ppo_head_kernel(const HeadArgs h) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x, n = h.T * h.B;
@@ -220,20 +255,12 @@ __global__ void ppo_head_kernel(const HeadArgs h) {
     if (h.mode == 0) return;
     float g_lp, g_v, g_ent;
     if (h.mode == 1) {
-        const float inv_n = 1.f / (float)n;
-        const float ratio = expf(lp_act - h.old_logprob[i]);
-        const float R = h.returns[i], adv = R - v;
-        const float lo = 1.f - h.eps_clip, hi = 1.f + h.eps_clip;
-        const float surr1 = ratio * adv, surr2 = fminf(fmaxf(ratio, lo), hi) * adv;
-        h.terms[i] = -fminf(surr1, surr2) - 0.01f * ent;
-        h.terms[n + i] = (v - R) * (v - R);
-        // autograd through torch.min / torch.clamp: an unclamped ratio carries the whole advantage (half through each equal branch); a clamped
-        // one carries it only when surr1 wins the min (half of it on an exact tie)
-        float g_ratio = adv;
-        if (ratio < lo || ratio > hi) g_ratio = surr1 < surr2 ? adv : (surr1 == surr2 ? 0.5f * adv : 0.f);
-        g_lp = -g_ratio * ratio * inv_n;
-        g_v = (v - R) * inv_n;            // 0.5 * MSE, a mean over all rows, broadcast into every row's loss
-        g_ent = -0.01f * inv_n;
+        const PpoTail tl = ppo_loss_tail(lp_act, h.old_logprob[i], h.returns[i], v, ent, h.eps_clip, n);
+        h.terms[i] = tl.term_pg;
+        h.terms[n + i] = tl.term_v;
+        g_lp = tl.g_lp;
+        g_v = tl.g_v;
+        g_ent = tl.g_ent;
     } else {
         g_lp = h.g_logprob ? h.g_logprob[i] : 0.f;
         g_v = h.g_value ? h.g_value[i] : 0.f;
@@ -260,6 +287,179 @@ __global__ __launch_bounds__(256) void ppo_loss_sum_kernel(const float* terms, i
     const float a = block_sum_256(s, red), m = block_sum_256(q, red);
     if (threadIdx.x == 0) *loss = a / (float)n + 0.5f * (m / (float)n);
 }
+
+// ---- the Gaussian policy (continuous actions) -----------------------------------------------------------------------------------------------
+constexpr float kLog2Pi = 1.8378770664093453f;
+
+// log N(a; mu, sigma^2 I) of a two-dimensional action: -1/2 sum(((a - mu) / sigma)^2) - 2 log sigma - log 2 pi
+__device__ __forceinline__ float gauss_logprob(float a0, float a1, float mu0, float mu1, float sigma) {
+    const float z0 = (a0 - mu0) / sigma, z1 = (a1 - mu1) / sigma;
+    return -0.5f * (z0 * z0 + z1 * z1) - 2.f * logf(sigma) - kLog2Pi;
+}
+
+// One thread per row.  The action is ppo_continuous.py:98-101 on the sample mu + sigma z with one fp32 rounding per operation, in that
+// order, nothing contracted: an interior value carries the torch expression's last bit (and floor(a * (H - P)) follows it)
+__global__ void ppo_gauss_sample_kernel(const float* mean, const float* noise, int rows, float sigma, float* action, float* logprob) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= rows) return;
+    float a[2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const float raw = __fadd_rn(mean[2 * r + k], __fmul_rn(sigma, noise[2 * r + k]));
+        a[k] = __fsub_rn(1.f, fmaxf(__fsub_rn(1.f, fmaxf(raw, 0.f)), 0.f));
+        action[2 * r + k] = a[k];
+    }
+    logprob[r] = gauss_logprob(a[0], a[1], mean[2 * r], mean[2 * r + 1], sigma);
+}
+
+// ppo_head_kernel for head rows [mean logit y, mean logit x, value] and stored actions [T, B, 2]: mu = sigmoid(logit) (the engine's
+// 1 / (1 + exp(-v))), the entropy is the constant 1 + log 2 pi + 2 log sigma (no gradient),
+// d logprob / d logit_k = (a_k - mu_k) / sigma^2 * mu_k (1 - mu_k)
+__global__ void ppo_gauss_head_kernel(const HeadArgs h) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x, n = h.T * h.B;
+    if (i >= n) return;
+    const int t = i / h.B, b = i - t * h.B;
+    const size_t hrow = (size_t)(h.head_bt ? b * h.T + t : i) * 3;
+    const float* l = h.head + hrow;
+    const float a0 = h.action_yx[2 * (size_t)i], a1 = h.action_yx[2 * (size_t)i + 1];
+    const float mu0 = 1.f / (1.f + expf(-l[0])), mu1 = 1.f / (1.f + expf(-l[1]));
+    const float lp_act = gauss_logprob(a0, a1, mu0, mu1, h.sigma), v = l[2];
+    const float ent = 1.f + kLog2Pi + 2.f * logf(h.sigma);
+    if (h.logprob) h.logprob[i] = lp_act;
+    if (h.value) h.value[i] = v;
+    if (h.entropy) h.entropy[i] = ent;
+    if (h.mode == 0) return;
+    float g_lp, g_v;
+    if (h.mode == 1) {
+        const PpoTail tl = ppo_loss_tail(lp_act, h.old_logprob[i], h.returns[i], v, ent, h.eps_clip, n);
+        h.terms[i] = tl.term_pg;
+        h.terms[n + i] = tl.term_v;
+        g_lp = tl.g_lp;
+        g_v = tl.g_v;
+    } else {
+        g_lp = h.g_logprob ? h.g_logprob[i] : 0.f;
+        g_v = h.g_value ? h.g_value[i] : 0.f;
+    }
+    if (!h.dhead) return;
+    float* d = h.dhead + hrow;
+    const float inv_var = 1.f / (h.sigma * h.sigma);
+    d[0] = g_lp * ((a0 - mu0) * inv_var) * (mu0 * (1.f - mu0));
+    d[1] = g_lp * ((a1 - mu1) * inv_var) * (mu1 * (1.f - mu1));
+    d[2] = g_v;
+}
+
+// ---- BatchNorm with batch statistics over the rows of x [rows, cols] ---------------------------------------------------------------------
+// Column sums as kBnSlices partials, each over its rows in ascending order, then added in slice order (adaf_launch_colsum's scheme).  The
+// sums are carried in double and rounded once: torch's CPU BatchNorm, the yardstick of the tests, accumulates that way, and the kernels
+// are a few microseconds whatever the accumulator.
+constexpr int kBnSlices = 32;
+
+// grid (ceil(cols / 64), kBnSlices), 64 threads.  mean == nullptr: part[s, c] = sum x;  else: sum (x - mean[c])^2
+__global__ void bn_colstat_partial_kernel(const float* x, const float* mean, int rows, int cols, double* part) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x, s = blockIdx.y;
+    if (c >= cols) return;
+    const int per = (rows + kBnSlices - 1) / kBnSlices, r0 = s * per, r1 = min(rows, r0 + per);
+    double v = 0.0;
+    if (mean) {
+        const double m = mean[c];
+        for (int r = r0; r < r1; ++r) {
+            const double d = (double)x[(size_t)r * cols + c] - m;
+            v += d * d;
+        }
+    } else {
+        for (int r = r0; r < r1; ++r) v += (double)x[(size_t)r * cols + c];
+    }
+    part[(size_t)s * cols + c] = v;
+}
+
+// pass 0: mean[c];  pass 1: invstd[c] = 1 / sqrt(biased variance + eps) and the running statistics' update (momentum; unbiased variance)
+__global__ void bn_stats_final_kernel(const double* part, int rows, int cols, int pass, float eps, float momentum, float* mean, float* invstd,
+                                      float* running_mean, float* running_var) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= cols) return;
+    double v = 0.0;
+    for (int s = 0; s < kBnSlices; ++s) v += part[(size_t)s * cols + c];
+    if (pass == 0) {
+        mean[c] = (float)(v / (double)rows);
+        return;
+    }
+    invstd[c] = (float)(1.0 / sqrt(v / (double)rows + (double)eps));
+    const double m = momentum;
+    if (running_mean) running_mean[c] = (float)((1.0 - m) * (double)running_mean[c] + m * (double)mean[c]);
+    if (running_var) running_var[c] = (float)((1.0 - m) * (double)running_var[c] + m * (v / (double)(rows - 1)));
+}
+
+// y = (x - mean) * invstd * gamma + beta (then ReLU when relu)
+__global__ void bn_normalize_kernel(const float* x, const float* mean, const float* invstd, const float* gamma, const float* beta, size_t n,
+                                    int cols, int relu, float* y) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int c = (int)(i % cols);
+    const float v = (x[i] - mean[c]) * invstd[c] * gamma[c] + beta[c];
+    y[i] = relu ? fmaxf(v, 0.f) : v;
+}
+
+// part[s, c] = sum dy_m, part[kBnSlices + s, c] = sum dy_m * (x - mean) over the slice's rows; dy_m = dy where y > 0 (y == nullptr: dy as it is)
+__global__ void bn_bwd_partial_kernel(const float* x, const float* y, const float* dy, const float* mean, int rows, int cols, double* part) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x, s = blockIdx.y;
+    if (c >= cols) return;
+    const int per = (rows + kBnSlices - 1) / kBnSlices, r0 = s * per, r1 = min(rows, r0 + per);
+    const double m = mean[c];
+    double sb = 0.0, sg = 0.0;
+    for (int r = r0; r < r1; ++r) {
+        const size_t i = (size_t)r * cols + c;
+        const double g = (!y || y[i] > 0.f) ? dy[i] : 0.f;
+        sb += g;
+        sg += g * ((double)x[i] - m);
+    }
+    part[(size_t)s * cols + c] = sb;
+    part[(size_t)(kBnSlices + s) * cols + c] = sg;
+}
+
+// d beta = sum dy_m;  d gamma = sum dy_m * xhat = invstd * sum dy_m * (x - mean)
+__global__ void bn_bwd_final_kernel(const double* part, const float* invstd, int cols, float* dgamma, float* dbeta) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= cols) return;
+    double sb = 0.0, sg = 0.0;
+    for (int s = 0; s < kBnSlices; ++s) {
+        sb += part[(size_t)s * cols + c];
+        sg += part[(size_t)(kBnSlices + s) * cols + c];
+    }
+    dbeta[c] = (float)sb;
+    dgamma[c] = (float)(sg * (double)invstd[c]);
+}
+
+// dx = gamma * invstd / n * (n * dy_m - d beta - xhat * d gamma)
+__global__ void bn_bwd_dx_kernel(const float* x, const float* y, const float* dy, const float* gamma, const float* mean, const float* invstd,
+                                 const float* dgamma, const float* dbeta, size_t n, int rows, int cols, float* dx) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int c = (int)(i % cols);
+    const float g = (!y || y[i] > 0.f) ? dy[i] : 0.f;
+    const float xh = (x[i] - mean[c]) * invstd[c];
+    dx[i] = gamma[c] * invstd[c] / (float)rows * ((float)rows * g - dbeta[c] - xh * dgamma[c]);
+}
+
+void launch_bn_forward(const float* x, int rows, int cols, const float* gamma, const float* beta, float eps, float momentum, float* running_mean,
+                       float* running_var, int relu, float* y, float* mean, float* invstd, double* part, hipStream_t st) {
+    const dim3 gp((cols + 63) / 64, kBnSlices), gc((cols + 63) / 64);
+    const size_t n = (size_t)rows * cols;
+    hipLaunchKernelGGL(bn_colstat_partial_kernel, gp, dim3(64), 0, st, x, (const float*)nullptr, rows, cols, part);
+    hipLaunchKernelGGL(bn_stats_final_kernel, gc, dim3(64), 0, st, part, rows, cols, 0, eps, momentum, mean, invstd, running_mean, running_var);
+    hipLaunchKernelGGL(bn_colstat_partial_kernel, gp, dim3(64), 0, st, x, (const float*)mean, rows, cols, part);
+    hipLaunchKernelGGL(bn_stats_final_kernel, gc, dim3(64), 0, st, part, rows, cols, 1, eps, momentum, mean, invstd, running_mean, running_var);
+    hipLaunchKernelGGL(bn_normalize_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, x, mean, invstd, gamma, beta, n, cols, relu, y);
+}
+
+void launch_bn_backward(const float* x, const float* y, const float* dy, int rows, int cols, const float* gamma, const float* mean,
+                        const float* invstd, float* dx, float* dgamma, float* dbeta, double* part, hipStream_t st) {
+    const size_t n = (size_t)rows * cols;
+    hipLaunchKernelGGL(bn_bwd_partial_kernel, dim3((cols + 63) / 64, kBnSlices), dim3(64), 0, st, x, y, dy, mean, rows, cols, part);
+    hipLaunchKernelGGL(bn_bwd_final_kernel, dim3((cols + 63) / 64), dim3(64), 0, st, part, invstd, cols, dgamma, dbeta);
+    hipLaunchKernelGGL(bn_bwd_dx_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, x, y, dy, gamma, mean, invstd, dgamma, dbeta, n, rows,
+                       cols, dx);
+}
+size_t bn_partial_doubles(int cols) { return 2 * (size_t)kBnSlices * cols; }
 
 // ---- layout kernels ---------------------------------------------------------------------------------------------------------------------
 // out[(j * ni + i), :] = in[(i * nj + j), :] (* (gate[(i * nj + j), :] > 0) when gate != nullptr): (T, B) <-> (B, T) rows of `width` floats
@@ -299,18 +499,20 @@ __global__ void ppo_relu_mask_kernel(const float* x, const float* gate, float* o
 // has retired by then --, pinned by scheduling barriers.
 constexpr int kSkThreads = 512, kSkWaves = 8, kSkU = 4;      // kSkU pixel pairs per group
 
-template <int NQ>
+// MH sets of 32 conv outputs (1 or 2): with two, conv output 32 mh + m is row m of the accumulators of set mh, both sets fed by the same
+// state fragments.  GATED = false: the gradient has its mask applied already (after a BatchNorm backward) and no E1 is read.
+template <int NQ, int MH>
 struct SkStage {
     f32x4 b[kSkU][NQ];
-    float d[kSkU], e[kSkU];
+    float d[kSkU][MH], e[kSkU][MH];
     bool ok[kSkU];
 };
 
-template <int NQ>
+template <int NQ, int MH, bool GATED>
 __global__ __launch_bounds__(kSkThreads) void ppo_wenc_splitk_kernel(const float* __restrict__ S, const float* __restrict__ dE1,
                                                                       const float* __restrict__ E1, float* __restrict__ part, int npix,
                                                                       int cin, int pps) {
-    constexpr int NA = 4 * NQ;
+    constexpr int NA = 4 * NQ * MH, CM = 32 * MH;
     __shared__ float red[2][NA * 16 * 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, nl = lane & 31;
     const int c0 = blockIdx.x * 128 * NQ;
@@ -323,34 +525,42 @@ __global__ __launch_bounds__(kSkThreads) void ppo_wenc_splitk_kernel(const float
         for (int r = 0; r < 16; ++r) acc[q][r] = 0.f;
 
     // branch-free: a pixel past the slice reads the slice's last pixel (a cache hit) and takes a zero gradient
-    auto load = [&](int g, SkStage<NQ>& s) {
+    auto load = [&](int g, SkStage<NQ, MH>& s) {
 #pragma unroll
         for (int u = 0; u < kSkU; ++u) {
             const int pix = p0 + (g * kSkU + u) * 2 + half, pc = min(pix, p1 - 1);
             const float* sp = S + (size_t)pc * cin + c0 + 4 * nl;
 #pragma unroll
             for (int j = 0; j < NQ; ++j) s.b[u][j] = *reinterpret_cast<const f32x4*>(sp + 128 * j);
-            s.d[u] = dE1[(size_t)pc * 32 + nl];
-            s.e[u] = E1[(size_t)pc * 32 + nl];
+#pragma unroll
+            for (int mh = 0; mh < MH; ++mh) {
+                s.d[u][mh] = dE1[(size_t)pc * CM + 32 * mh + nl];
+                s.e[u][mh] = GATED ? E1[(size_t)pc * CM + 32 * mh + nl] : 1.f;
+            }
             s.ok[u] = pix < p1;
         }
     };
 
-    auto products = [&](const SkStage<NQ>& s) {
+    auto products = [&](const SkStage<NQ, MH>& s) {
 #pragma unroll
         for (int u = 0; u < kSkU; ++u) {
-            const float a = s.ok[u] && s.e[u] > 0.f ? s.d[u] : 0.f;     // the ReLU mask of the conv output, applied on the way in
 #pragma unroll
-            for (int j = 0; j < NQ; ++j)
+            for (int mh = 0; mh < MH; ++mh) {
+                const float a = s.ok[u] && s.e[u][mh] > 0.f ? s.d[u][mh] : 0.f;     // the ReLU mask of the conv output, applied on the way in
 #pragma unroll
-                for (int q = 0; q < 4; ++q)
-                    acc[4 * j + q] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, s.b[u][j][q], acc[4 * j + q], 0, 0, 0);
+                for (int j = 0; j < NQ; ++j)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const int k = 4 * (mh * NQ + j) + q;
+                        acc[k] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, s.b[u][j][q], acc[k], 0, 0, 0);
+                    }
+            }
         }
     };
     // per group: requests, products, then a VALU read (an add into `fence`) of the youngest MFMA result, pinned by scheduling barriers: the
     // next group's loads are requested only after every product that read the landing registers has retired.  The latency of a group's
     // loads is covered by the block's other seven waves
-    SkStage<NQ> st;
+    SkStage<NQ, MH> st;
     float fence = 0.f;
     for (int g = wave; g < ngroups; g += kSkWaves) {
         load(g, st);
@@ -386,15 +596,17 @@ __global__ __launch_bounds__(kSkThreads) void ppo_wenc_splitk_kernel(const float
         __syncthreads();
     }
     if (wave == 0) {
-        float* o = part + (size_t)blockIdx.y * 32 * cin + c0 + 4 * nl;
+        float* o = part + (size_t)blockIdx.y * CM * cin + c0 + 4 * nl;
 #pragma unroll
-        for (int j = 0; j < NQ; ++j)
+        for (int mh = 0; mh < MH; ++mh)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = (r & 3) + 8 * (r >> 2) + 4 * half;
-                const f32x4 v = {acc[4 * j][r], acc[4 * j + 1][r], acc[4 * j + 2][r], acc[4 * j + 3][r]};
-                *reinterpret_cast<f32x4*>(o + (size_t)m * cin + 128 * j) = v;
-            }
+            for (int j = 0; j < NQ; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int m = (r & 3) + 8 * (r >> 2) + 4 * half, k = 4 * (mh * NQ + j);
+                    const f32x4 v = {acc[k][r], acc[k + 1][r], acc[k + 2][r], acc[k + 3][r]};
+                    *reinterpret_cast<f32x4*>(o + (size_t)(32 * mh + m) * cin + 128 * j) = v;
+                }
     }
 }
 
@@ -407,39 +619,52 @@ __global__ void ppo_wenc_reduce_kernel(const float* part, int slices, int n, flo
     out[i] = v;
 }
 
-// pixel slices of the split-K launch: about one block per CU, at least 64 pixels per slice (plain arithmetic: the workspace query uses it)
-int sk_slices(int npix, int cin, int cus) {
-    const int chunks = cin % 256 == 0 ? cin / 256 : cin / 128;
+// pixel slices of the split-K launch: about one block per CU, at least 64 pixels per slice (plain arithmetic: the workspace query uses it).
+// A block takes 256 channels of 32 conv outputs where the channel count allows, else (and always with 64 outputs) 128
+int sk_slices(int npix, int cin, int cmid, int cus) {
+    const int chunks = (cmid == 32 && cin % 256 == 0) ? cin / 256 : cin / 128;
     int s = cus / (chunks > 0 ? chunks : 1);
     const int most = (npix + 63) / 64;
     if (s > most) s = most;
     return s < 1 ? 1 : s;
 }
 constexpr int kSkCus = 256;     // the workspace is sized for the MI355X's 256 CUs whatever the device reports (never fewer slices than used)
+bool sk_shape_ok(int cin, int cmid) { return (cmid == 32 || cmid == 64) && cin > 0 && cin % 128 == 0; }
 
+template <int NQ, int MH>
+void launch_sk(bool gated, dim3 grid, hipStream_t st, const float* states, const float* de1, const float* e1, float* ws, int npix, int cin, int pps) {
+    if (gated)
+        hipLaunchKernelGGL((ppo_wenc_splitk_kernel<NQ, MH, true>), grid, dim3(kSkThreads), 0, st, states, de1, e1, ws, npix, cin, pps);
+    else
+        hipLaunchKernelGGL((ppo_wenc_splitk_kernel<NQ, MH, false>), grid, dim3(kSkThreads), 0, st, states, de1, e1, ws, npix, cin, pps);
+}
+
+// e1 == nullptr: de1 has its mask applied already
 int launch_wenc_grad(adaf_handle* h, const float* states, const float* de1, const float* e1, int npix, int cin, int cmid, int split_k,
                      float* dw, float* ws, hipStream_t st) {
     if (split_k) {
-        if (cmid != 32 || cin % 128) return adaf_fail(h, ADAF_E_LAYOUT, "ppo_wenc_grad: the split-K form needs 32 conv outputs and channels %% 128 == 0");
+        if (!sk_shape_ok(cin, cmid)) return adaf_fail(h, ADAF_E_LAYOUT, "ppo_wenc_grad: the split-K form needs 32 or 64 conv outputs and channels %% 128 == 0");
         const int cus = h->cus < kSkCus ? h->cus : kSkCus;
-        const int slices = sk_slices(npix, cin, cus), pps = ((npix + slices - 1) / slices + 1) / 2 * 2;
+        const int slices = sk_slices(npix, cin, cmid, cus), pps = ((npix + slices - 1) / slices + 1) / 2 * 2;
         const int used = (npix + pps - 1) / pps;
-        if (cin % 256 == 0)
-            hipLaunchKernelGGL(ppo_wenc_splitk_kernel<2>, dim3(cin / 256, used), dim3(kSkThreads), 0, st, states, de1, e1, ws, npix, cin, pps);
+        if (cmid == 64)
+            launch_sk<1, 2>(e1 != nullptr, dim3(cin / 128, used), st, states, de1, e1, ws, npix, cin, pps);
+        else if (cin % 256 == 0)
+            launch_sk<2, 1>(e1 != nullptr, dim3(cin / 256, used), st, states, de1, e1, ws, npix, cin, pps);
         else
-            hipLaunchKernelGGL(ppo_wenc_splitk_kernel<1>, dim3(cin / 128, used), dim3(kSkThreads), 0, st, states, de1, e1, ws, npix, cin, pps);
-        hipLaunchKernelGGL(ppo_wenc_reduce_kernel, dim3((32 * cin + 255) / 256), dim3(256), 0, st, ws, used, 32 * cin, dw);
+            launch_sk<1, 1>(e1 != nullptr, dim3(cin / 128, used), st, states, de1, e1, ws, npix, cin, pps);
+        hipLaunchKernelGGL(ppo_wenc_reduce_kernel, dim3((cmid * cin + 255) / 256), dim3(256), 0, st, ws, used, cmid * cin, dw);
     } else {
         // the single-chain form: the masked gradient as a tensor, then dW[m, c] = sum_i masked[i, m] S[i, c] as one ascending chain per output
         const size_t n = (size_t)npix * cmid;
-        hipLaunchKernelGGL(ppo_relu_mask_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, de1, e1, ws, n);
-        adaf_launch_gemm_strided(ws, 1, cmid, states, cin, 1, dw, cin, nullptr, 0, cmid, cin, npix, st);
+        if (e1) hipLaunchKernelGGL(ppo_relu_mask_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, de1, e1, ws, n);
+        adaf_launch_gemm_strided(e1 ? ws : de1, 1, cmid, states, cin, 1, dw, cin, nullptr, 0, cmid, cin, npix, st);
     }
     return ADAF_OK;
 }
 
 size_t wenc_sk_floats(int npix, int cin, int cmid) {
-    return (cmid == 32 && cin % 128 == 0) ? (size_t)sk_slices(npix, cin, kSkCus) * 32 * cin : 0;
+    return sk_shape_ok(cin, cmid) ? (size_t)sk_slices(npix, cin, cmid, kSkCus) * cmid * cin : 0;
 }
 
 // ---- workspace layouts: each written once, measured by the query (null base) and carved by the call -----------------------------------
@@ -454,9 +679,10 @@ size_t wenc_layout(void* ws, int npix, int cin, int cmid, float** buf) {      //
     *buf = c.take<float>(sk > chain ? sk : chain);
     return c.off;
 }
-// dE [rows, hidden], dE1 [rows, hw * cmid], the pixel-major dW_lin [hidden, hw * cmid], column-sum partials, the split-K slice partials
-struct EncBackwardWs { float *de, *de1, *dwl, *part, *wws; };
-size_t enc_backward_layout(void* ws, int steps, int batch, int map_pixels, int channels, int conv_out, int hidden, EncBackwardWs* r) {
+// dE [rows, hidden], dE1 [rows, hw * cmid], the pixel-major dW_lin [hidden, hw * cmid], column-sum partials, the split-K slice partials;
+// with BatchNorm also the gradients in front of the two BatchNorms (dL [rows, hidden], dC [rows, hw * cmid]) and their column partials
+struct EncBackwardWs { float *de, *de1, *dwl, *part, *wws, *dl, *dc; double* bnp; };
+size_t enc_backward_layout(void* ws, int steps, int batch, int map_pixels, int channels, int conv_out, int hidden, bool bn, EncBackwardWs* r) {
     const size_t rows = (size_t)steps * batch, mid = (size_t)map_pixels * conv_out;
     AdafCarver c(ws);
     r->de = c.take<float>(rows * hidden);
@@ -464,7 +690,58 @@ size_t enc_backward_layout(void* ws, int steps, int batch, int map_pixels, int c
     r->dwl = c.take<float>((size_t)hidden * mid);
     r->part = c.take<float>(adaf_colsum_partial_floats(hidden));
     r->wws = c.take<float>(wenc_sk_floats((int)(rows * map_pixels), channels, conv_out));
+    r->dl = r->dc = nullptr;
+    r->bnp = nullptr;
+    if (bn) {
+        r->dl = c.take<float>(rows * hidden);
+        r->dc = c.take<float>(rows * mid);
+        r->bnp = c.take<double>(bn_partial_doubles(hidden > conv_out ? hidden : conv_out));
+    }
     return c.off;
+}
+size_t bn_layout(void* ws, int cols, double** part) {
+    AdafCarver c(ws);
+    *part = c.take<double>(bn_partial_doubles(cols));
+    return c.off;
+}
+
+// What the state encoder kept and what its backward fills.  The BatchNorm members are null without BatchNorm (then e1 / e_bt are the conv's
+// and the Linear's own outputs after ReLU)
+struct EncBackwardArgs {
+    const float *states, *e1, *e_bt, *dx_bt, *w_lin_pm;
+    const float *c1, *gamma1, *mean1, *invstd1;       // BN2d: the raw conv output [rows * hw, cmid] and the statistics it was normalised with
+    const float *l1, *gamma2, *mean2, *invstd2;       // BN1d: the raw Linear output [rows, hidden], rows t * B + b
+    float *dw_enc, *dw_lin, *db_lin, *dgamma1, *dbeta1, *dgamma2, *dbeta2;
+    int steps, batch, map_pixels, channels, conv_out, hidden;
+};
+
+int run_encoder_backward(adaf_handle* h, const EncBackwardArgs& a, const EncBackwardWs& r, hipStream_t st) {
+    const int rows = a.steps * a.batch, mid = a.map_pixels * a.conv_out, hidden = a.hidden;
+    const bool bn = a.c1 != nullptr;
+    // dE[t * B + b] = dx[b * T + t] * (E[b * T + t] > 0): the GRU's (B, T) rows back to the states' (T, B) order, ReLU mask on the way
+    {
+        const size_t n = (size_t)rows * hidden;
+        hipLaunchKernelGGL(ppo_rows_transpose_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a.dx_bt, a.e_bt, r.de, a.batch, a.steps, hidden);
+    }
+    const float* dl = r.de;      // the gradient of the Linear's own output
+    if (bn) {
+        launch_bn_backward(a.l1, nullptr, r.de, rows, hidden, a.gamma2, a.mean2, a.invstd2, r.dl, a.dgamma2, a.dbeta2, r.bnp, st);
+        dl = r.dl;
+    }
+    // Linear: dW_lin = dL^T E1 (pixel-major columns, then permuted), db_lin = column sums, dE1 = dL W_lin
+    adaf_launch_gemm_strided(dl, 1, hidden, a.e1, mid, 1, r.dwl, mid, nullptr, 0, hidden, mid, rows, st);
+    {
+        const size_t n = (size_t)hidden * mid;
+        hipLaunchKernelGGL(ppo_lin_grad_permute_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, r.dwl, a.dw_lin, hidden, a.map_pixels, a.conv_out);
+    }
+    adaf_launch_colsum(dl, rows, hidden, hidden, r.part, a.db_lin, st);
+    adaf_launch_gemm_strided(dl, hidden, 1, a.w_lin_pm, mid, 1, r.de1, mid, nullptr, 0, rows, mid, hidden, st);
+    const int npix = rows * a.map_pixels;
+    if (bn) {      // the ReLU mask goes into the BatchNorm backward; the conv's gradient arrives dense
+        launch_bn_backward(a.c1, a.e1, r.de1, npix, a.conv_out, a.gamma1, a.mean1, a.invstd1, r.dc, a.dgamma1, a.dbeta1, r.bnp, st);
+        return launch_wenc_grad(h, a.states, r.dc, nullptr, npix, a.channels, a.conv_out, 1, a.dw_enc, r.wws, st);
+    }
+    return launch_wenc_grad(h, a.states, r.de1, a.e1, npix, a.channels, a.conv_out, 1, a.dw_enc, r.wws, st);
 }
 
 }  // namespace
@@ -545,7 +822,7 @@ int adaf_ppo_head_f32(adaf_handle* h, const float* head, int head_batch_major, i
     int rc;
     if (loss_mode && (rc = adaf_check_ws(h, "ppo_head", ws, ws_bytes, ppo_head_layout(ws, steps, batch, &terms), ADAF_WS_SIZE_FIRST))) return rc;
     hipStream_t st = (hipStream_t)stream;
-    HeadArgs a;
+    HeadArgs a = {};
     a.head = head; a.action = reinterpret_cast<const long long*>(actions); a.old_logprob = old_logprobs; a.returns = returns;
     a.g_logprob = g_logprob; a.g_value = g_value; a.g_entropy = g_entropy;
     a.logprob = logprobs_out; a.value = values_out; a.entropy = entropy_out; a.terms = terms; a.dhead = dhead_out;
@@ -576,7 +853,7 @@ size_t adaf_ppo_wenc_grad_workspace_bytes(int pixels, int channels, int conv_out
 int adaf_ppo_wenc_grad_f32(adaf_handle* h, const float* states, const float* de1, const float* e1, int pixels, int channels, int conv_out,
                            int split_k, float* dw_out, void* ws, size_t ws_bytes, void* stream) {
     if (!h) return ADAF_E_BADARG;
-    if (!states || !de1 || !e1 || !dw_out || !ws) return adaf_fail(h, ADAF_E_BADARG, "ppo_wenc_grad: null pointer");
+    if (!states || !de1 || !dw_out || !ws) return adaf_fail(h, ADAF_E_BADARG, "ppo_wenc_grad: null pointer");
     if (pixels <= 0 || channels <= 0 || conv_out <= 0) return adaf_fail(h, ADAF_E_BADARG, "ppo_wenc_grad: non-positive extent");
     if (!adaf_aligned16(states) || !adaf_aligned16(dw_out)) return adaf_fail(h, ADAF_E_LAYOUT, "ppo_wenc_grad: 16-byte alignment");
     float* buf;
@@ -590,7 +867,7 @@ int adaf_ppo_wenc_grad_f32(adaf_handle* h, const float* states, const float* de1
 size_t adaf_ppo_encoder_backward_workspace_bytes(int steps, int batch, int map_pixels, int channels, int conv_out, int hidden) {
     EncBackwardWs r;
     if (steps <= 0 || batch <= 0 || map_pixels <= 0 || channels <= 0 || conv_out <= 0 || hidden <= 0) return 0;
-    return enc_backward_layout(nullptr, steps, batch, map_pixels, channels, conv_out, hidden, &r);
+    return enc_backward_layout(nullptr, steps, batch, map_pixels, channels, conv_out, hidden, false, &r);
 }
 
 int adaf_ppo_encoder_backward_f32(adaf_handle* h, const float* states, const float* e1, const float* e_bt, const float* dx_bt, int steps,
@@ -604,28 +881,128 @@ int adaf_ppo_encoder_backward_f32(adaf_handle* h, const float* states, const flo
     if (conv_out != 32 || channels % 128) return adaf_fail(h, ADAF_E_LAYOUT, "ppo_encoder_backward: 32 conv outputs and channels %% 128 == 0 expected");
     if (!adaf_aligned16(states)) return adaf_fail(h, ADAF_E_LAYOUT, "ppo_encoder_backward: 16-byte alignment");
     EncBackwardWs r;
-    int rc = adaf_check_ws(h, "ppo_encoder_backward", ws, ws_bytes, enc_backward_layout(ws, steps, batch, map_pixels, channels, conv_out, hidden, &r),
+    int rc = adaf_check_ws(h, "ppo_encoder_backward", ws, ws_bytes, enc_backward_layout(ws, steps, batch, map_pixels, channels, conv_out, hidden, false, &r),
                            ADAF_WS_ALIGN_FIRST);
     if (rc) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    const int rows = steps * batch, mid = map_pixels * conv_out;
-    float *const de = r.de, *const de1 = r.de1, *const dwl = r.dwl, *const part = r.part, *const wws = r.wws;
-    // dE[t * B + b] = dx[b * T + t] * (E[b * T + t] > 0): the GRU's (B, T) rows back to the states' (T, B) order, ReLU mask on the way
-    {
-        const size_t n = (size_t)rows * hidden;
-        hipLaunchKernelGGL(ppo_rows_transpose_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dx_bt, e_bt, de, batch, steps, hidden);
-    }
-    // Linear: dW_lin = dE^T E1 (pixel-major columns, then permuted), db_lin = column sums, dE1 = dE W_lin
-    adaf_launch_gemm_strided(de, 1, hidden, e1, mid, 1, dwl, mid, nullptr, 0, hidden, mid, rows, st);
-    {
-        const size_t n = (size_t)hidden * mid;
-        hipLaunchKernelGGL(ppo_lin_grad_permute_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dwl, dw_lin, hidden, map_pixels, conv_out);
-    }
-    adaf_launch_colsum(de, rows, hidden, hidden, part, db_lin, st);
-    adaf_launch_gemm_strided(de, hidden, 1, w_lin_pm, mid, 1, de1, mid, nullptr, 0, rows, mid, hidden, st);
-    if ((rc = launch_wenc_grad(h, states, de1, e1, rows * map_pixels, channels, conv_out, 1, dw_enc, wws, st))) return rc;
+    EncBackwardArgs a = {};
+    a.states = states; a.e1 = e1; a.e_bt = e_bt; a.dx_bt = dx_bt; a.w_lin_pm = w_lin_pm;
+    a.dw_enc = dw_enc; a.dw_lin = dw_lin; a.db_lin = db_lin;
+    a.steps = steps; a.batch = batch; a.map_pixels = map_pixels; a.channels = channels; a.conv_out = conv_out; a.hidden = hidden;
+    if ((rc = run_encoder_backward(h, a, r, (hipStream_t)stream))) return rc;
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? ADAF_OK : adaf_hip_fail(h, e, "ppo_encoder_backward launch");
+}
+
+// ---- the continuous policy ------------------------------------------------------------------------------------------------
+int adaf_ppo_gauss_sample_f32(adaf_handle* h, const float* mean, const float* noise, int rows, float sigma, float* action_out, float* logprob_out,
+                              void* stream) {
+    if (!h) return ADAF_E_BADARG;
+    if (!mean || !noise || !action_out || !logprob_out) return adaf_fail(h, ADAF_E_BADARG, "ppo_gauss_sample: null pointer");
+    if (rows <= 0 || !(sigma > 0.f)) return adaf_fail(h, ADAF_E_BADARG, "ppo_gauss_sample: non-positive extent or sigma");
+    hipLaunchKernelGGL(ppo_gauss_sample_kernel, dim3((rows + 63) / 64), dim3(64), 0, (hipStream_t)stream, mean, noise, rows, sigma, action_out, logprob_out);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? ADAF_OK : adaf_hip_fail(h, e, "ppo_gauss_sample launch");
+}
+
+int adaf_ppo_gauss_head_f32(adaf_handle* h, const float* head, int head_batch_major, int steps, int batch, const float* actions, float sigma,
+                            const float* old_logprobs, const float* returns, float eps_clip, const float* g_logprob, const float* g_value,
+                            float* logprobs_out, float* values_out, float* entropy_out, float* loss_out, float* dhead_out, void* ws,
+                            size_t ws_bytes, void* stream) {
+    if (!h) return ADAF_E_BADARG;
+    if (!head || !actions) return adaf_fail(h, ADAF_E_BADARG, "ppo_gauss_head: null pointer");
+    if (steps <= 0 || batch <= 0 || !(sigma > 0.f)) return adaf_fail(h, ADAF_E_BADARG, "ppo_gauss_head: non-positive extent or sigma");
+    const bool loss_mode = old_logprobs || returns || loss_out;
+    const bool grad_mode = g_logprob || g_value;
+    if (loss_mode && (!old_logprobs || !returns || !loss_out || !ws)) return adaf_fail(h, ADAF_E_BADARG, "ppo_gauss_head: the loss needs old_logprobs, returns, loss_out and a workspace");
+    if (loss_mode && grad_mode) return adaf_fail(h, ADAF_E_BADARG, "ppo_gauss_head: either the PPO loss or upstream gradients");
+    if (grad_mode && !dhead_out) return adaf_fail(h, ADAF_E_BADARG, "ppo_gauss_head: upstream gradients without dhead_out");
+    float* terms = static_cast<float*>(ws);
+    int rc;
+    if (loss_mode && (rc = adaf_check_ws(h, "ppo_gauss_head", ws, ws_bytes, ppo_head_layout(ws, steps, batch, &terms), ADAF_WS_SIZE_FIRST))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    HeadArgs a = {};
+    a.head = head; a.action_yx = actions; a.sigma = sigma; a.old_logprob = old_logprobs; a.returns = returns;
+    a.g_logprob = g_logprob; a.g_value = g_value;
+    a.logprob = logprobs_out; a.value = values_out; a.entropy = entropy_out; a.terms = terms; a.dhead = dhead_out;
+    a.T = steps; a.B = batch; a.A = 2; a.head_bt = head_batch_major ? 1 : 0; a.mode = loss_mode ? 1 : (grad_mode ? 2 : 0);
+    a.eps_clip = eps_clip;
+    const int n = steps * batch;
+    hipLaunchKernelGGL(ppo_gauss_head_kernel, dim3((n + 63) / 64), dim3(64), 0, st, a);
+    if (loss_mode) hipLaunchKernelGGL(ppo_loss_sum_kernel, dim3(1), dim3(256), 0, st, a.terms, n, loss_out);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? ADAF_OK : adaf_hip_fail(h, e, "ppo_gauss_head launch");
+}
+
+size_t adaf_bn_train_workspace_bytes(int rows, int cols) {
+    double* part;
+    return (rows <= 0 || cols <= 0) ? 0 : bn_layout(nullptr, cols, &part);
+}
+
+int adaf_bn_train_forward_f32(adaf_handle* h, const float* x, int rows, int cols, const float* gamma, const float* beta, float eps,
+                              float momentum, float* running_mean, float* running_var, int relu, float* y_out, float* mean_out,
+                              float* invstd_out, void* ws, size_t ws_bytes, void* stream) {
+    if (!h) return ADAF_E_BADARG;
+    if (!x || !gamma || !beta || !y_out || !mean_out || !invstd_out || !ws) return adaf_fail(h, ADAF_E_BADARG, "bn_train_forward: null pointer");
+    if (rows <= 0 || cols <= 0) return adaf_fail(h, ADAF_E_BADARG, "bn_train_forward: non-positive extent");
+    if (rows < 2) return adaf_fail(h, ADAF_E_BADARG, "bn_train_forward: more than one value per channel expected");
+    double* part;
+    int rc = adaf_check_ws(h, "bn_train_forward", ws, ws_bytes, bn_layout(ws, cols, &part), ADAF_WS_ALIGN_FIRST);
+    if (rc) return rc;
+    launch_bn_forward(x, rows, cols, gamma, beta, eps, momentum, running_mean, running_var, relu, y_out, mean_out, invstd_out, part, (hipStream_t)stream);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? ADAF_OK : adaf_hip_fail(h, e, "bn_train_forward launch");
+}
+
+int adaf_bn_train_backward_f32(adaf_handle* h, const float* x, const float* y, const float* dy, int rows, int cols, const float* gamma,
+                               const float* mean, const float* invstd, float* dx_out, float* dgamma_out, float* dbeta_out, void* ws,
+                               size_t ws_bytes, void* stream) {
+    if (!h) return ADAF_E_BADARG;
+    if (!x || !dy || !gamma || !mean || !invstd || !dx_out || !dgamma_out || !dbeta_out || !ws) return adaf_fail(h, ADAF_E_BADARG, "bn_train_backward: null pointer");
+    if (rows <= 0 || cols <= 0) return adaf_fail(h, ADAF_E_BADARG, "bn_train_backward: non-positive extent");
+    double* part;
+    int rc = adaf_check_ws(h, "bn_train_backward", ws, ws_bytes, bn_layout(ws, cols, &part), ADAF_WS_ALIGN_FIRST);
+    if (rc) return rc;
+    launch_bn_backward(x, y, dy, rows, cols, gamma, mean, invstd, dx_out, dgamma_out, dbeta_out, part, (hipStream_t)stream);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? ADAF_OK : adaf_hip_fail(h, e, "bn_train_backward launch");
+}
+
+size_t adaf_ppo_encoder_bn_backward_workspace_bytes(int steps, int batch, int map_pixels, int channels, int conv_out, int hidden, int with_bn) {
+    EncBackwardWs r;
+    if (steps <= 0 || batch <= 0 || map_pixels <= 0 || channels <= 0 || conv_out <= 0 || hidden <= 0) return 0;
+    return enc_backward_layout(nullptr, steps, batch, map_pixels, channels, conv_out, hidden, with_bn != 0, &r);
+}
+
+int adaf_ppo_encoder_bn_backward_f32(adaf_handle* h, const float* states, const float* e1, const float* e_bt, const float* dx_bt, int steps,
+                                     int batch, int map_pixels, int channels, int conv_out, int hidden, const float* w_lin_pm,
+                                     const float* c1, const float* gamma1, const float* mean1, const float* invstd1, const float* l1,
+                                     const float* gamma2, const float* mean2, const float* invstd2, float* dw_enc, float* dw_lin,
+                                     float* db_lin, float* dgamma1, float* dbeta1, float* dgamma2, float* dbeta2, void* ws, size_t ws_bytes,
+                                     void* stream) {
+    if (!h) return ADAF_E_BADARG;
+    if (!states || !e1 || !e_bt || !dx_bt || !w_lin_pm || !dw_enc || !dw_lin || !db_lin || !ws)
+        return adaf_fail(h, ADAF_E_BADARG, "ppo_encoder_bn_backward: null pointer");
+    const bool bn = c1 != nullptr;
+    const void* bnp[] = {c1, gamma1, mean1, invstd1, l1, gamma2, mean2, invstd2, dgamma1, dbeta1, dgamma2, dbeta2};
+    for (const void* q : bnp)
+        if (!q != !bn) return adaf_fail(h, ADAF_E_BADARG, "ppo_encoder_bn_backward: the BatchNorm operands go together (all or none)");
+    if (steps <= 0 || batch <= 0 || map_pixels <= 0 || channels <= 0 || conv_out <= 0 || hidden <= 0)
+        return adaf_fail(h, ADAF_E_BADARG, "ppo_encoder_bn_backward: non-positive extent");
+    if (!sk_shape_ok(channels, conv_out)) return adaf_fail(h, ADAF_E_LAYOUT, "ppo_encoder_bn_backward: 32 or 64 conv outputs and channels %% 128 == 0 expected");
+    if (hidden % 4 || (map_pixels * conv_out) % 4) return adaf_fail(h, ADAF_E_LAYOUT, "ppo_encoder_bn_backward: hidden and map_pixels * conv_out must be multiples of 4");
+    if (!adaf_aligned16(states)) return adaf_fail(h, ADAF_E_LAYOUT, "ppo_encoder_bn_backward: 16-byte alignment");
+    EncBackwardWs r;
+    int rc = adaf_check_ws(h, "ppo_encoder_bn_backward", ws, ws_bytes,
+                           enc_backward_layout(ws, steps, batch, map_pixels, channels, conv_out, hidden, bn, &r), ADAF_WS_ALIGN_FIRST);
+    if (rc) return rc;
+    EncBackwardArgs a = {};
+    a.states = states; a.e1 = e1; a.e_bt = e_bt; a.dx_bt = dx_bt; a.w_lin_pm = w_lin_pm;
+    a.c1 = c1; a.gamma1 = gamma1; a.mean1 = mean1; a.invstd1 = invstd1; a.l1 = l1; a.gamma2 = gamma2; a.mean2 = mean2; a.invstd2 = invstd2;
+    a.dw_enc = dw_enc; a.dw_lin = dw_lin; a.db_lin = db_lin; a.dgamma1 = dgamma1; a.dbeta1 = dbeta1; a.dgamma2 = dgamma2; a.dbeta2 = dbeta2;
+    a.steps = steps; a.batch = batch; a.map_pixels = map_pixels; a.channels = channels; a.conv_out = conv_out; a.hidden = hidden;
+    if ((rc = run_encoder_backward(h, a, r, (hipStream_t)stream))) return rc;
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? ADAF_OK : adaf_hip_fail(h, e, "ppo_encoder_bn_backward launch");
 }
 
 }  // extern "C"

@@ -7,6 +7,10 @@ local CNN (shift fused into conv1), and a linear classifier with temporal-mean c
 glancer's mean logits (:164-174).  Hot path here: ONE gather launch with ``frames_per_action = T``
 (NHWC4), ONE TSM trunk pass over B*T patches -- the reward-baseline branch (:153-160,176-186), when
 requested, rides in the SAME pass as a second half of the batch -- then ``adaf_fc_meanpool_forward_f32``.
+
+Stage-2 training (``policy_train_mode()``: only ``focuser.policy.policy`` learns) runs the roll-out through
+``action_stage2(training=True)`` with actions sampled from the continuous policy and the PPO update through ``Focuser.update()`` with a HIP
+backward (csrc/ppo_train.hip; the loop body is ``adafocus_amd.train.train_stage2_batch_sth``).
 """
 import math
 
@@ -108,12 +112,12 @@ class GFV(nn.Module):
         return fm.unflatten(0, (b, t)), logit.view(b, t, -1)
 
     def _stage(self, focuser_image, global_feat_map, global_feat_logit, step, args, prev_local_patch, with_baseline,
-               forced_action=None, baseline_action=None, train_classifier=False):
+               forced_action=None, baseline_action=None, train_classifier=False, sample=False, noise=None):
         if self.training and not train_classifier:
             raise RuntimeError("adafocus_amd: eval mode only (stage 3 trains the classifier through action_stage3)")
         with torch.no_grad():
             feat, local_patch, action, b, frames_total, ngroups = self._stage_features(
-                focuser_image, global_feat_map, step, args, prev_local_patch, with_baseline, forced_action, baseline_action)
+                focuser_image, global_feat_map, step, args, prev_local_patch, with_baseline, forced_action, baseline_action, sample, noise)
         per = b * frames_total
         glog = global_feat_logit if self.with_glancer else None
         if train_classifier:
@@ -126,7 +130,7 @@ class GFV(nn.Module):
         return logits, local_patch, action
 
     def _stage_features(self, focuser_image, global_feat_map, step, args, prev_local_patch, with_baseline, forced_action,
-                        baseline_action):
+                        baseline_action, sample=False, noise=None):
         nfg = args.num_segments_glancer // args.video_div
         nff = args.num_segments_focuser // args.video_div
         b, _, c, hh, ww = focuser_image.shape
@@ -137,7 +141,8 @@ class GFV(nn.Module):
             # pixel-major view of the map (free when it came from glance()) -> policy on the engine; the GRU state of
             # step i-1 is carried in focuser.memory.hidden for video_div > 1 (STH/evaluate.py:198, ppo_continuous.py:81-94)
             nhwc = seg.permute(0, 1, 3, 4, 2).contiguous().view(fb * nfg, fh, fw, fc_)
-            action = self.focuser.policy.policy_old.act_nhwc(nhwc, fb, nfg, self.focuser.memory, restart_batch=(step == 0))
+            action = self.focuser.policy.policy_old.act_nhwc(nhwc, fb, nfg, self.focuser.memory, restart_batch=(step == 0),
+                                                             training=sample, noise=noise)
         else:
             action = self.focuser.act(seg.reshape(fb, -1, fh, fw), restart_batch=(step == 0))
         if forced_action is not None:
@@ -216,13 +221,31 @@ class GFV(nn.Module):
         return logits[0], (logits[1] if with_baseline else None), patches4
 
     def action_stage2(self, focuser_image, global_feat_map, global_feat_logit, focus_time_step, args,
-                      prev_local_patch=None, training=True, with_baseline=True, forced_action=None, baseline_action=None):
-        """STH/models/gfv_net.py:136-188 -> (total_logit, baseline_logit, local_patch)."""
+                      prev_local_patch=None, training=True, with_baseline=True, forced_action=None, baseline_action=None, noise=None):
+        """STH/models/gfv_net.py:136-188 -> (total_logit, baseline_logit, local_patch).  training=True is the roll-out step of stage-2
+        training (STH/stage2.py:251-254): the action is SAMPLED from the continuous policy_old (state, action and log-probability go to
+        focuser.memory; `noise` (B, 2) injects the standard normals, `baseline_action` the baseline's draw).  It needs
+        `policy_train_mode()` first; the discrete policy's training inside this model is out of scope."""
         if training:
-            raise NotImplementedError("stage-2 policy training is out of scope; call with training=False")
+            if not getattr(self.focuser, "ppo_continuous", False):
+                raise NotImplementedError("action_stage2(training=True): stage-2 training of this model is implemented for the continuous "
+                                          "policy (ppo_continuous=True) only; call with training=False")
+            if not self.focuser.policy.policy_old.training:
+                raise NotImplementedError("action_stage2(training=True) is the stage-2 (PPO) roll-out: call model.policy_train_mode() first "
+                                          "(focuser.policy.policy_old is in eval mode)")
         logits, local_patch, _ = self._stage(focuser_image, global_feat_map, global_feat_logit, focus_time_step, args,
-                                             prev_local_patch, with_baseline, forced_action, baseline_action)
+                                             prev_local_patch, with_baseline, forced_action, baseline_action, sample=bool(training),
+                                             noise=noise)
         return logits[0], (logits[1] if with_baseline else None), local_patch
+
+    def policy_train_mode(self):
+        """STH/stage2.py:227-229: the model in eval mode, both policies in train mode.  Only focuser.policy.policy learns
+        (Focuser.update); `action_stage2(training=True)` checks for this mode."""
+        if self.focuser.policy is None:
+            raise NotImplementedError("policy_train_mode: a random-patch model has no policy to train")
+        self.eval()
+        self.focuser.policy.policy.train()
+        self.focuser.policy.policy_old.train()
 
     def action_stage3(self, focuser_image, global_feat_map, global_feat_logit, focus_time_step, args,
                       prev_local_patch=None, forced_action=None):
@@ -336,9 +359,17 @@ class Focuser(nn.Module):
         if self.random:
             return self.random_patching(kwargs["input"])
         if kwargs.get("training"):
-            raise NotImplementedError("training branch is out of scope")
-        action = self.act(kwargs["state"], kwargs.get("restart_batch", True))
+            if not self.ppo_continuous:
+                raise NotImplementedError("the training branch of this Focuser is implemented for the continuous policy only")
+            action = self.policy.select_action(kwargs["state"], self.memory, kwargs.get("restart_batch", True), True)
+        else:
+            action = self.act(kwargs["state"], kwargs.get("restart_batch", True))
         return get_patch(kwargs["input"], action, self.patch_size)
+
+    def update(self):
+        """STH/models/gfv_net.py:432-434: one PPO update from the stored roll-out, then the memory is cleared."""
+        self.policy.update(self.memory)
+        self.memory.clear_memory()
 
     def random_patching(self, imgs):
         return get_patch(imgs, torch.rand(imgs.size(0), 2).to(imgs.device), self.patch_size)

@@ -378,10 +378,10 @@ def rows_transpose(x, ni, nj):
 
 
 def ppo_wenc_grad(states, de1, e1, split_k=True):
-    """The 1x1 conv's weight gradient: states (pixels, C), de1 / e1 (pixels, 32) -> (32, C) = (de1 where e1 > 0)^T states.
-    split_k=False: the single-chain cross-check on the strided GEMM."""
+    """The 1x1 conv's weight gradient: states (pixels, C), de1 / e1 (pixels, 32 | 64) -> (32 | 64, C) = (de1 where e1 > 0)^T states
+    (e1 None: de1 as it is).  split_k=False: the single-chain cross-check on the strided GEMM."""
     L.need_gpu_f32(states, de1, e1)
-    states, de1, e1 = states.contiguous(), de1.contiguous(), e1.contiguous()
+    states, de1, e1 = states.contiguous(), de1.contiguous(), None if e1 is None else e1.contiguous()
     npix, cin = states.shape
     cmid = de1.shape[1]
     lib = L.load_library()
@@ -414,6 +414,136 @@ def ppo_encoder_backward(states, e1, e_bt, dx_bt, t, b, w_lin_pm):
                                               L.ptr(dx_bt.contiguous()), t, b, hw, cin, cmid, hid, L.ptr(w_lin_pm.contiguous()), L.ptr(dw_enc),
                                               L.ptr(dw_lin), L.ptr(db_lin), L.ptr(ws), ws_bytes, L.stream_ptr()), h)
     return dw_enc, dw_lin, db_lin
+
+
+# ---- stage-2 training of the continuous policy (Something-Something; csrc/ppo_train.hip) ------------------------------------
+def ppo_gauss_sample(mean, noise, sigma):
+    """mean (rows, 2), noise (rows, 2) standard normals -> (action (rows, 2) = 1 - relu(1 - relu(mean + sigma * noise)), the log-probability
+    (rows,) of the clamped action under N(mean, sigma^2 I))."""
+    L.need_gpu_f32(mean, noise)
+    if mean.dim() != 2 or mean.shape[1] != 2 or noise.shape != mean.shape:
+        raise ValueError("ppo_gauss_sample: mean and noise (rows, 2) expected")
+    mean, noise = mean.contiguous(), noise.contiguous()
+    rows = mean.shape[0]
+    action = torch.empty_like(mean)
+    logprob = torch.empty((rows,), device=mean.device, dtype=torch.float32)
+    h = _h(mean)
+    L.check(L.load_library().adaf_ppo_gauss_sample_f32(h, L.ptr(mean), L.ptr(noise), rows, C.c_float(sigma), L.ptr(action), L.ptr(logprob),
+                                                       L.stream_ptr()), h)
+    return action, logprob
+
+
+def _ppo_gauss_head(head, actions, sigma, batch_major, old_logprobs=None, returns=None, eps_clip=0.2, grads=None):
+    L.need_gpu_f32(head, actions, old_logprobs, returns, *(grads or ()))
+    head, actions = head.contiguous(), actions.contiguous()
+    if actions.dim() != 3 or actions.shape[2] != 2 or head.shape != (actions.shape[0] * actions.shape[1], 3):
+        raise ValueError("ppo gauss head: head (T*B, 3) and actions (T, B, 2) expected")
+    t, b = actions.shape[:2]
+    dev, fp = head.device, torch.float32
+    logprobs, values, entropy = (torch.empty((t, b), device=dev, dtype=fp) for _ in range(3))
+    loss_mode = old_logprobs is not None
+    loss = torch.empty((1,), device=dev, dtype=fp) if loss_mode else None
+    dhead = torch.empty_like(head) if (loss_mode or grads is not None) else None
+    lib = L.load_library()
+    ws_bytes = lib.adaf_ppo_head_workspace_bytes(t, b) if loss_mode else 0
+    ws = torch.empty(max(ws_bytes // 4, 1), device=dev, dtype=fp)
+    g = [None if x is None else x.contiguous() for x in (grads or (None, None))]
+    if loss_mode:
+        old_logprobs, returns = old_logprobs.contiguous(), returns.contiguous()
+    h = _h(head)
+    L.check(lib.adaf_ppo_gauss_head_f32(h, L.ptr(head), int(batch_major), t, b, L.ptr(actions), C.c_float(sigma), L.ptr(old_logprobs),
+                                        L.ptr(returns), C.c_float(eps_clip), L.ptr(g[0]), L.ptr(g[1]), L.ptr(logprobs), L.ptr(values),
+                                        L.ptr(entropy), L.ptr(loss), L.ptr(dhead), L.ptr(ws), ws_bytes, L.stream_ptr()), h)
+    return logprobs, values, entropy, loss, dhead
+
+
+def ppo_gauss_head_stats(head, actions, sigma, batch_major=True):
+    """head (T*B, 3) [mean logits | value] (rows b*T+t when batch_major), actions (T, B, 2) -> (logprobs, values, entropy), each (T, B)."""
+    return _ppo_gauss_head(head, actions, sigma, batch_major)[:3]
+
+
+def ppo_gauss_head_backward(head, actions, sigma, g_logprob, g_value, batch_major=True):
+    """Pull-back of upstream gradients of (logprobs, values) (each (T, B) or None; the entropy is a constant) to the head output."""
+    if g_logprob is None and g_value is None:
+        return torch.zeros_like(head)
+    return _ppo_gauss_head(head, actions, sigma, batch_major, grads=(g_logprob, g_value))[4]
+
+
+def ppo_gauss_loss_head(head, actions, sigma, old_logprobs, returns, eps_clip, batch_major=True):
+    """The Gaussian PPO loss head, forward and backward in one pass: -> (logprobs, values, entropy (T, B), loss.mean() (1,),
+    d loss.mean() / d head (T*B, 3))."""
+    return _ppo_gauss_head(head, actions, sigma, batch_major, old_logprobs=old_logprobs, returns=returns, eps_clip=eps_clip)
+
+
+def _bn_ws(lib, rows, cols, dev):
+    ws_bytes = lib.adaf_bn_train_workspace_bytes(rows, cols)
+    return torch.empty(max(ws_bytes // 4, 4), device=dev, dtype=torch.float32), ws_bytes
+
+
+def bn_train_forward(x, gamma, beta, running_mean=None, running_var=None, eps=1e-5, momentum=0.1, relu=True):
+    """BatchNorm with batch statistics over the rows of x (rows, cols) [+ ReLU]; running_mean / running_var are updated in place.
+    -> (y, mean (cols,), invstd (cols,)): with x, what bn_train_backward needs."""
+    L.need_gpu_f32(x, gamma, beta, running_mean, running_var)
+    if x.dim() != 2 or not x.is_contiguous():
+        raise ValueError("bn_train_forward: contiguous x (rows, cols) expected")
+    rows, cols = x.shape
+    if rows < 2:
+        raise ValueError("Expected more than 1 value per channel when training, got input size %s" % (tuple(x.shape),))
+    for r in (running_mean, running_var):
+        if r is not None and not r.is_contiguous():
+            raise ValueError("bn_train_forward: contiguous running statistics expected (they are updated in place)")
+    y = torch.empty_like(x)
+    mean = torch.empty((cols,), device=x.device, dtype=torch.float32)
+    invstd = torch.empty((cols,), device=x.device, dtype=torch.float32)
+    lib = L.load_library()
+    ws, ws_bytes = _bn_ws(lib, rows, cols, x.device)
+    h = _h(x)
+    L.check(lib.adaf_bn_train_forward_f32(h, L.ptr(x), rows, cols, L.ptr(gamma.contiguous()), L.ptr(beta.contiguous()), C.c_float(eps),
+                                          C.c_float(momentum), L.ptr(running_mean), L.ptr(running_var), int(bool(relu)), L.ptr(y), L.ptr(mean),
+                                          L.ptr(invstd), L.ptr(ws), ws_bytes, L.stream_ptr()), h)
+    return y, mean, invstd
+
+
+def bn_train_backward(x, y, dy, gamma, mean, invstd):
+    """Backward of bn_train_forward: y its output after ReLU (None: no ReLU) -> (dx, dgamma, dbeta)."""
+    L.need_gpu_f32(x, y, dy, gamma, mean, invstd)
+    x, dy = x.contiguous(), dy.contiguous()
+    rows, cols = x.shape
+    dx = torch.empty_like(x)
+    dgamma = torch.empty((cols,), device=x.device, dtype=torch.float32)
+    dbeta = torch.empty((cols,), device=x.device, dtype=torch.float32)
+    lib = L.load_library()
+    ws, ws_bytes = _bn_ws(lib, rows, cols, x.device)
+    h = _h(x)
+    L.check(lib.adaf_bn_train_backward_f32(h, L.ptr(x), L.ptr(None if y is None else y.contiguous()), L.ptr(dy), rows, cols,
+                                           L.ptr(gamma.contiguous()), L.ptr(mean), L.ptr(invstd), L.ptr(dx), L.ptr(dgamma), L.ptr(dbeta),
+                                           L.ptr(ws), ws_bytes, L.stream_ptr()), h)
+    return dx, dgamma, dbeta
+
+
+def ppo_encoder_bn_backward(states, e1, e_bt, dx_bt, t, b, w_lin_pm, bn=None):
+    """ppo_encoder_backward for 32 or 64 conv outputs, with or without BatchNorm.  bn = (c1, gamma1, mean1, invstd1, l1, gamma2, mean2,
+    invstd2): the raw conv / Linear outputs and the statistics of the forward ->
+    (dW_enc, dW_lin, db_lin[, dgamma1, dbeta1, dgamma2, dbeta2])."""
+    L.need_gpu_f32(states, e1, e_bt, dx_bt, w_lin_pm, *(bn or ()))
+    hw, cin = states.shape[1] * states.shape[2], states.shape[3]
+    hid = w_lin_pm.shape[0]
+    cmid = w_lin_pm.shape[1] // hw
+    lib = L.load_library()
+    ws_bytes = lib.adaf_ppo_encoder_bn_backward_workspace_bytes(t, b, hw, cin, cmid, hid, int(bn is not None))
+    dev, fp = states.device, torch.float32
+    ws = torch.empty(max(ws_bytes // 4, 4), device=dev, dtype=fp)
+    dw_enc = torch.empty((cmid, cin), device=dev, dtype=fp)
+    dw_lin = torch.empty((hid, cmid * hw), device=dev, dtype=fp)
+    db_lin = torch.empty((hid,), device=dev, dtype=fp)
+    extra = () if bn is None else tuple(torch.empty((n,), device=dev, dtype=fp) for n in (cmid, cmid, hid, hid))
+    bn_in = [None] * 8 if bn is None else [x.contiguous() for x in bn]
+    h = _h(states)
+    L.check(lib.adaf_ppo_encoder_bn_backward_f32(h, L.ptr(states.contiguous()), L.ptr(e1.contiguous()), L.ptr(e_bt.contiguous()),
+                                                 L.ptr(dx_bt.contiguous()), t, b, hw, cin, cmid, hid, L.ptr(w_lin_pm.contiguous()),
+                                                 *(L.ptr(x) for x in bn_in), L.ptr(dw_enc), L.ptr(dw_lin), L.ptr(db_lin),
+                                                 *(L.ptr(x) for x in (extra or [None] * 4)), L.ptr(ws), ws_bytes, L.stream_ptr()), h)
+    return (dw_enc, dw_lin, db_lin) + extra
 
 
 def fc_meanpool_forward(feat, batch, fc_w, fc_b, global_logit=None):

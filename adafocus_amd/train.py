@@ -7,6 +7,8 @@
 ``train_stage2_batch_fused`` is the same body with the roll-out as one batched pass (``GFV.rollout_act``: all T actions sampled first, one
 trunk pass over the B*T crops) and the rewards from one kernel; same contract, same predictions.
 
+``train_stage2_batch_sth`` is the loop body of the Something-Something tree (STH/stage2.py:233-270) with its continuous policy.
+
 Both CNNs and the classifier stay frozen and run on the HIP path; only ``focuser.policy.policy`` learns (``PPO.update``: HIP forward and
 backward, PyTorch's Adam step).
 """
@@ -15,7 +17,7 @@ import torch.nn.functional as F
 
 from . import hip_ops
 
-__all__ = ["get_reward", "train_stage2_batch", "train_stage2_batch_fused"]
+__all__ = ["get_reward", "train_stage2_batch", "train_stage2_batch_fused", "train_stage2_batch_sth"]
 
 
 def get_reward(args, confidence, confidence_last, baseline):
@@ -77,3 +79,31 @@ def train_stage2_batch_fused(model, images, target, args, uniforms=None):
     model.focuser.memory.rewards.extend(rewards[s:s + 1] for s in range(t))
     model.focuser.update()
     return preds, loss[0]
+
+
+def train_stage2_batch_sth(model, glancer_images, focuser_images, target, args, noise=None, baseline_actions=None):
+    """One batch of stage-2 training of the Something-Something model (STH/stage2.py:233-270; `model.policy_train_mode()` first).
+    glancer_images (B, Tg*3, g, g) already at the glance size, focuser_images (B, Tf*3, H, W), both normalised fp32 on the GPU, target (B,)
+    int64.  Glance, `video_div` roll-out steps with actions sampled from the continuous policy, reward = confidence - the random
+    baseline's confidence into model.focuser.memory.rewards, then model.focuser.update().  noise / baseline_actions: per step a (B, 2)
+    tensor (standard normals of the sample / the baseline's action) or None for the reference's draws.
+    Returns (the last step's prediction (B, C), its cross-entropy, the per-step rewards [(1, B)])."""
+    b = target.shape[0]
+    frames = focuser_images.view(b, args.num_segments_focuser, 3, focuser_images.shape[-2], focuser_images.shape[-1])
+    with torch.no_grad():
+        global_feat_map, global_feat_logit = model.glance(glancer_images)
+    index = target.view(-1, 1)
+    patches, rewards = None, []
+    pred = loss = None
+    for step in range(args.video_div):
+        pred, baseline_logit, patches = model.action_stage2(frames, global_feat_map, global_feat_logit, step, args, prev_local_patch=patches,
+                                                            training=True, noise=None if noise is None else noise[step],
+                                                            baseline_action=None if baseline_actions is None else baseline_actions[step])
+        loss = F.cross_entropy(pred, target)
+        confidence = torch.gather(F.softmax(pred.detach(), 1), dim=1, index=index).view(1, -1)
+        bsl_confidence = torch.gather(F.softmax(baseline_logit.detach(), 1), dim=1, index=index).view(1, -1)
+        reward = confidence - bsl_confidence
+        rewards.append(reward)
+        model.focuser.memory.rewards.append(reward)
+    model.focuser.update()
+    return pred, loss, rewards

@@ -602,7 +602,7 @@ int adaf_gru_cls_backward_f32(adaf_handle* h, const float* x, int ldx, int batch
  * adaf_ppo_rows_transpose_f32: out[j * ni + i, :] = in[i * nj + j, :] for rows of `width` floats ((T, B) <-> (B, T) row order).
  * adaf_ppo_wenc_grad_f32: the 1x1 conv's weight gradient dw_out [conv_out, channels] = sum over pixels of
  *   (de1[pixel, :] where e1[pixel, :] > 0, else 0) (x) states[pixel, :]; states [pixels, channels], de1 / e1 [pixels, conv_out].
- *   split_k = 1: the streaming form (conv_out == 32, channels % 128 == 0): one read of `states` with 16-byte loads, block partials in
+ *   split_k = 1: the streaming form (conv_out == 32 or 64, channels % 128 == 0): one read of `states` with 16-byte loads, block partials in
  *   MFMA accumulators, slices added in slice order.  split_k = 0: the masked gradient as a tensor + one ascending chain per output on the
  *   strided GEMM (the cross-check).  Workspace: adaf_ppo_wenc_grad_workspace_bytes(pixels, channels, conv_out).
  * adaf_ppo_encoder_backward_f32: the state encoder's backward from dx_bt [B, T, hidden] (the dx of adaf_gru_cls_backward_f32).
@@ -632,6 +632,54 @@ size_t adaf_ppo_encoder_backward_workspace_bytes(int steps, int batch, int map_p
 int adaf_ppo_encoder_backward_f32(adaf_handle* h, const float* states, const float* e1, const float* e_bt, const float* dx_bt, int steps,
                                   int batch, int map_pixels, int channels, int conv_out, int hidden, const float* w_lin_pm, float* dw_enc,
                                   float* dw_lin, float* db_lin, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- a11 training, continuous policy (stage 2 of the Something-Something tree; csrc/ppo_train.hip) -----------------------
+ * STH/models/ppo_continuous.py: 1x1 conv Tg*C -> 64 [BatchNorm2d] ReLU, Linear -> hidden [BatchNorm1d] ReLU, GRU, actor Linear(2) +
+ * Sigmoid, critic Linear(1); the action is a sample of N(mu, sigma^2 I) clamped to [0, 1]^2, sigma = action_std (a standard deviation).
+ * The GRU with both heads is adaf_gru_cls_train_forward_f32 / adaf_gru_cls_backward_f32 with classes = 3 (two mean logits | value).
+ * fp32, no atomics: the same inputs give the same bits.
+ *
+ * adaf_ppo_gauss_sample_f32: mean [rows, 2] (after the sigmoid), noise [rows, 2] standard normals drawn by the caller ->
+ *   action_out [rows, 2] = 1 - relu(1 - relu(mean + sigma * noise)), one fp32 rounding per operation in that order (nothing contracted),
+ *   logprob_out [rows] = -1/2 sum(((a - mean) / sigma)^2) - 2 log sigma - log 2 pi of the CLAMPED action.
+ * adaf_ppo_gauss_head_f32: adaf_ppo_head_f32 for head [T*B, 3] (columns 0, 1 the mean logits, column 2 the value; mu = sigmoid) and
+ *   actions [T, B, 2] fp32.  The entropy is the constant 1 + log 2 pi + 2 log sigma and takes no upstream gradient; the loss tail is the
+ *   discrete head's (one device function).  Workspace (loss mode): adaf_ppo_head_workspace_bytes(steps, batch).
+ * adaf_bn_train_forward_f32: BatchNorm with batch statistics over the rows of x [rows, cols] (BatchNorm1d; BatchNorm2d on a pixel-major
+ *   map with rows = images * pixels).  mean_out [cols]; invstd_out [cols] = 1 / sqrt(biased variance + eps), the variance as the mean of
+ *   squared deviations from mean_out (two passes, slice partials in row order, slices added in slice order, carried in double);
+ *   y_out = (x - mean) * invstd * gamma + beta, then ReLU when relu != 0.  running_mean / running_var [cols] (may be NULL) are updated in
+ *   place: (1 - momentum) * running + momentum * (mean | unbiased variance).  rows == 1 is ADAF_E_BADARG.
+ * adaf_bn_train_backward_f32: from dy [rows, cols], with dy_m = dy where y > 0 (y == NULL: dy as it is; y is the forward's output after
+ *   ReLU): dbeta_out = sum dy_m, dgamma_out = sum dy_m * xhat, dx_out = gamma * invstd / rows * (rows * dy_m - dbeta - xhat * dgamma),
+ *   xhat = (x - mean) * invstd recomputed from the forward's x, mean_out, invstd_out.
+ *   Workspace of both: adaf_bn_train_workspace_bytes(rows, cols).
+ * adaf_ppo_wenc_grad_f32 (above) also takes conv_out == 64 in its streaming form and e1 == NULL (de1 has its mask applied).
+ * adaf_ppo_encoder_bn_backward_f32: adaf_ppo_encoder_backward_f32 for 32 or 64 conv outputs, with or without BatchNorm.  With it (all
+ *   of c1 ... dbeta2 given): c1 [T*B*map_pixels, conv_out] and l1 [T*B, hidden] are the raw conv / Linear outputs, gamma / mean / invstd
+ *   the BatchNorm weights and the statistics of the forward, e1 / e_bt the outputs after BatchNorm + ReLU; dgamma1, dbeta1 [conv_out] and
+ *   dgamma2, dbeta2 [hidden] are filled too.  Without it (all NULL) it is adaf_ppo_encoder_backward_f32's chain.
+ *   Workspace: adaf_ppo_encoder_bn_backward_workspace_bytes(..., with_bn). */
+int adaf_ppo_gauss_sample_f32(adaf_handle* h, const float* mean, const float* noise, int rows, float sigma, float* action_out, float* logprob_out,
+                              void* stream);
+int adaf_ppo_gauss_head_f32(adaf_handle* h, const float* head, int head_batch_major, int steps, int batch, const float* actions, float sigma,
+                            const float* old_logprobs, const float* returns, float eps_clip, const float* g_logprob, const float* g_value,
+                            float* logprobs_out, float* values_out, float* entropy_out, float* loss_out, float* dhead_out, void* ws,
+                            size_t ws_bytes, void* stream);
+size_t adaf_bn_train_workspace_bytes(int rows, int cols);
+int adaf_bn_train_forward_f32(adaf_handle* h, const float* x, int rows, int cols, const float* gamma, const float* beta, float eps,
+                              float momentum, float* running_mean, float* running_var, int relu, float* y_out, float* mean_out,
+                              float* invstd_out, void* ws, size_t ws_bytes, void* stream);
+int adaf_bn_train_backward_f32(adaf_handle* h, const float* x, const float* y, const float* dy, int rows, int cols, const float* gamma,
+                               const float* mean, const float* invstd, float* dx_out, float* dgamma_out, float* dbeta_out, void* ws,
+                               size_t ws_bytes, void* stream);
+size_t adaf_ppo_encoder_bn_backward_workspace_bytes(int steps, int batch, int map_pixels, int channels, int conv_out, int hidden, int with_bn);
+int adaf_ppo_encoder_bn_backward_f32(adaf_handle* h, const float* states, const float* e1, const float* e_bt, const float* dx_bt, int steps,
+                                     int batch, int map_pixels, int channels, int conv_out, int hidden, const float* w_lin_pm,
+                                     const float* c1, const float* gamma1, const float* mean1, const float* invstd1, const float* l1,
+                                     const float* gamma2, const float* mean2, const float* invstd2, float* dw_enc, float* dw_lin,
+                                     float* db_lin, float* dgamma1, float* dbeta1, float* dgamma2, float* dbeta2, void* ws, size_t ws_bytes,
+                                     void* stream);
 
 /* ---- a8: linear classifier + temporal mean ---------------------------------------------
  * nn.Linear + ConsensusModule('avg') (+ glancer mean logits) -- STH/models/gfv_net.py:164-174,
