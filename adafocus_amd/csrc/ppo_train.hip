@@ -6,8 +6,10 @@
 //   ppo_rewards_kernel       confidence = softmax probability of the target class per (clip, step), one wave per clip, and the reward of
 //                            main_dist.py:574-581 from it; ppo_ce_last_kernel the mean cross-entropy of the last step
 //   ppo_returns_kernel       R_t = r_t + gamma R_{t+1}, then (R - mean) / (std + 1e-5) over all T*B entries (unbiased std), one block
-//   ppo_head_kernel          per row of the stacked head output [actor logits | critic value]: log-softmax, log-probability of the stored
-//                            action, entropy, value, the clipped-surrogate loss terms AND d loss.mean() / d head in the same pass
+//   ppo_head_kernel<Dist>    per row of the stacked head output [actor columns | critic value]: log-probability of the stored action and
+//                            entropy under the row's distribution, value, the clipped-surrogate loss terms AND d loss.mean() / d head in
+//                            the same pass.  ONE kernel for both policies; Dist = Categorical (log-softmax over A logits, int64 actions)
+//                            or Gaussian (see below) says what the actor columns mean
 //   ppo_loss_sum_kernel      the scalar loss from the per-row terms, summed in a fixed order
 //   ppo_wenc_splitk_kernel   dW_enc [32, C] = (relu-masked dE1)^T S over all T*B*h*w pixels: the state tensor S (257 MB at B = 64, T = 16) is
 //                            read ONCE with 16-byte loads; a block owns a pixel slice and a 128- or 256-channel chunk and keeps its 32 x chunk
@@ -17,8 +19,8 @@
 // The continuous policy of the Something-Something tree (STH/models/ppo_continuous.py) adds
 //   ppo_gauss_sample_kernel  a = 1 - relu(1 - relu(mu + sigma z)) from caller-drawn normals, one rounding per operation, and the
 //                            log-probability of the clamped action under N(mu, sigma^2 I)
-//   ppo_gauss_head_kernel    ppo_head_kernel's sibling for the stacked head [mean logits (2) | value]: sigmoid, Gaussian log-probability,
-//                            the constant entropy, and the same loss tail (one device function, ppo_loss_tail)
+//   Gaussian                 ppo_head_kernel's distribution for the stacked head [mean logits (2) | value]: sigmoid, Gaussian log-probability
+//                            of the stored (y, x), the constant entropy
 //   bn_* kernels             BatchNorm with batch statistics over the rows of a [rows, cols] matrix: two-pass column statistics (the mean,
 //                            then the squared deviations) as slice partials in row order + a fixed-order sum over the slices (in double), the running
 //                            statistics' update, normalise + affine (+ ReLU), and the backward (d gamma, d beta, dx)
@@ -192,7 +194,7 @@ __global__ __launch_bounds__(256) void ppo_returns_kernel(const float* rewards, 
 // ---- PPO head ---------------------------------------------------------------------------------------------------------------------------
 struct HeadArgs {
     const float* head;        // [T*B, A + 1]: row b * T + t when head_bt, else row t * B + b
-    const long long* action;  // [T, B]
+    const long long* action;  // [T, B] the stored discrete actions (Categorical only)
     const float* old_logprob; // [T, B] (loss mode)
     const float* returns;     // [T, B] (loss mode)
     const float* g_logprob;   // [T, B] upstream gradients (plain backward mode; any may be null = 0)
@@ -205,7 +207,7 @@ struct HeadArgs {
     float* dhead;             // [T*B, A + 1] in the head's row order (may be null)
     int T, B, A, head_bt, mode;   // mode 0: statistics only, 1: PPO loss + its gradient, 2: gradient from g_*
     float eps_clip;
-    const float* action_yx;   // [T, B, 2] the stored continuous actions and the policy's standard deviation (ppo_gauss_head_kernel only)
+    const float* action_yx;   // [T, B, 2] the stored continuous actions and the policy's standard deviation (Gaussian only; A = 2)
     float sigma;
 };
 
@@ -231,24 +233,75 @@ __device__ __forceinline__ PpoTail ppo_loss_tail(float lp_act, float old_lp, flo
     return o;
 }
 
+constexpr float kLog2Pi = 1.8378770664093453f;
+
+// log N(a; mu, sigma^2 I) of a two-dimensional action: -1/2 sum(((a - mu) / sigma)^2) - 2 log sigma - log 2 pi
+__device__ __forceinline__ float gauss_logprob(float a0, float a1, float mu0, float mu1, float sigma) {
+    const float z0 = (a0 - mu0) / sigma, z1 = (a1 - mu1) / sigma;
+    return -0.5f * (z0 * z0 + z1 * z1) - 2.f * logf(sigma) - kLog2Pi;
+}
+
+// The two distributions of ppo_head_kernel.  Constructed from row i's actor columns l: lp_act = the log-probability of the row's stored
+// action, ent = the entropy; pull_back writes d (g_lp * lp_act + g_ent * ent) / d l into the row's actor columns of dhead.
+// Categorical(softmax(l[0..A))): max, sum of exponentials and entropy in index order; the pull-back recomputes lp / p per column.
+struct Categorical {
+    const float* l;
+    int A, act;
+    float mx, lse, lp_act, ent;
+    static __device__ __forceinline__ int columns(const HeadArgs& h) { return h.A; }
+    __device__ __forceinline__ Categorical(const HeadArgs& h, const float* row, int i) : l(row), A(h.A) {
+        mx = l[0];
+        for (int a = 1; a < A; ++a) mx = fmaxf(mx, l[a]);
+        float total = 0.f;
+        for (int a = 0; a < A; ++a) total += expf(l[a] - mx);
+        lse = logf(total);
+        ent = 0.f;
+        for (int a = 0; a < A; ++a) {
+            const float lp = (l[a] - mx) - lse;
+            ent -= expf(lp) * lp;
+        }
+        act = (int)h.action[i];
+        lp_act = (l[act] - mx) - lse;
+    }
+    __device__ __forceinline__ void pull_back(float g_lp, float g_ent, float* d) const {
+        for (int a = 0; a < A; ++a) {
+            const float lp = (l[a] - mx) - lse, p = expf(lp);
+            d[a] = g_lp * ((a == act ? 1.f : 0.f) - p) - g_ent * p * (lp + ent);
+        }
+    }
+};
+
+// N(mu, sigma^2 I) over (y, x) for head rows [mean logit y, mean logit x, value] and stored actions [T, B, 2]: mu = sigmoid(logit) (the
+// engine's 1 / (1 + exp(-v))), the entropy is the constant 1 + log 2 pi + 2 log sigma (no gradient: g_ent is not read),
+// d logprob / d logit_k = (a_k - mu_k) / sigma^2 * mu_k (1 - mu_k)
+struct Gaussian {
+    float a0, a1, mu0, mu1, sigma, lp_act, ent;
+    static __device__ __forceinline__ int columns(const HeadArgs&) { return 2; }
+    __device__ __forceinline__ Gaussian(const HeadArgs& h, const float* l, int i) : sigma(h.sigma) {
+        a0 = h.action_yx[2 * (size_t)i];
+        a1 = h.action_yx[2 * (size_t)i + 1];
+        mu0 = 1.f / (1.f + expf(-l[0]));
+        mu1 = 1.f / (1.f + expf(-l[1]));
+        lp_act = gauss_logprob(a0, a1, mu0, mu1, h.sigma);
+        ent = 1.f + kLog2Pi + 2.f * logf(h.sigma);
+    }
+    __device__ __forceinline__ void pull_back(float g_lp, float, float* d) const {
+        const float inv_var = 1.f / (sigma * sigma);
+        d[0] = g_lp * ((a0 - mu0) * inv_var) * (mu0 * (1.f - mu0));
+        d[1] = g_lp * ((a1 - mu1) * inv_var) * (mu1 * (1.f - mu1));
+    }
+};
+
+// One thread per row; the value is the column behind the distribution's
+template <class Dist>
 __global__ void ppo_head_kernel(const HeadArgs h) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x, n = h.T * h.B;
     if (i >= n) return;
-    const int t = i / h.B, b = i - t * h.B, A = h.A;
+    const int t = i / h.B, b = i - t * h.B, A = Dist::columns(h);
     const size_t hrow = (size_t)(h.head_bt ? b * h.T + t : i) * (A + 1);
     const float* l = h.head + hrow;
-    float mx = l[0];
-    for (int a = 1; a < A; ++a) mx = fmaxf(mx, l[a]);
-    float total = 0.f;
-    for (int a = 0; a < A; ++a) total += expf(l[a] - mx);
-    const float lse = logf(total);
-    float ent = 0.f;
-    for (int a = 0; a < A; ++a) {
-        const float lp = (l[a] - mx) - lse;
-        ent -= expf(lp) * lp;
-    }
-    const int act = (int)h.action[i];
-    const float lp_act = (l[act] - mx) - lse, v = l[A];
+    const Dist dist(h, l, i);
+    const float lp_act = dist.lp_act, ent = dist.ent, v = l[A];
     if (h.logprob) h.logprob[i] = lp_act;
     if (h.value) h.value[i] = v;
     if (h.entropy) h.entropy[i] = ent;
@@ -268,10 +321,7 @@ __global__ void ppo_head_kernel(const HeadArgs h) {
     }
     if (!h.dhead) return;
     float* d = h.dhead + hrow;
-    for (int a = 0; a < A; ++a) {
-        const float lp = (l[a] - mx) - lse, p = expf(lp);
-        d[a] = g_lp * ((a == act ? 1.f : 0.f) - p) - g_ent * p * (lp + ent);
-    }
+    dist.pull_back(g_lp, g_ent, d);
     d[A] = g_v;
 }
 
@@ -289,14 +339,6 @@ __global__ __launch_bounds__(256) void ppo_loss_sum_kernel(const float* terms, i
 }
 
 // ---- the Gaussian policy (continuous actions) -----------------------------------------------------------------------------------------------
-constexpr float kLog2Pi = 1.8378770664093453f;
-
-// log N(a; mu, sigma^2 I) of a two-dimensional action: -1/2 sum(((a - mu) / sigma)^2) - 2 log sigma - log 2 pi
-__device__ __forceinline__ float gauss_logprob(float a0, float a1, float mu0, float mu1, float sigma) {
-    const float z0 = (a0 - mu0) / sigma, z1 = (a1 - mu1) / sigma;
-    return -0.5f * (z0 * z0 + z1 * z1) - 2.f * logf(sigma) - kLog2Pi;
-}
-
 // One thread per row.  The action is ppo_continuous.py:98-101 on the sample mu + sigma z with one fp32 rounding per operation, in that
 // order, nothing contracted: an interior value carries the torch expression's last bit (and floor(a * (H - P)) follows it)
 __global__ void ppo_gauss_sample_kernel(const float* mean, const float* noise, int rows, float sigma, float* action, float* logprob) {
@@ -310,42 +352,6 @@ __global__ void ppo_gauss_sample_kernel(const float* mean, const float* noise, i
         action[2 * r + k] = a[k];
     }
     logprob[r] = gauss_logprob(a[0], a[1], mean[2 * r], mean[2 * r + 1], sigma);
-}
-
-// ppo_head_kernel for head rows [mean logit y, mean logit x, value] and stored actions [T, B, 2]: mu = sigmoid(logit) (the engine's
-// 1 / (1 + exp(-v))), the entropy is the constant 1 + log 2 pi + 2 log sigma (no gradient),
-// d logprob / d logit_k = (a_k - mu_k) / sigma^2 * mu_k (1 - mu_k)
-__global__ void ppo_gauss_head_kernel(const HeadArgs h) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x, n = h.T * h.B;
-    if (i >= n) return;
-    const int t = i / h.B, b = i - t * h.B;
-    const size_t hrow = (size_t)(h.head_bt ? b * h.T + t : i) * 3;
-    const float* l = h.head + hrow;
-    const float a0 = h.action_yx[2 * (size_t)i], a1 = h.action_yx[2 * (size_t)i + 1];
-    const float mu0 = 1.f / (1.f + expf(-l[0])), mu1 = 1.f / (1.f + expf(-l[1]));
-    const float lp_act = gauss_logprob(a0, a1, mu0, mu1, h.sigma), v = l[2];
-    const float ent = 1.f + kLog2Pi + 2.f * logf(h.sigma);
-    if (h.logprob) h.logprob[i] = lp_act;
-    if (h.value) h.value[i] = v;
-    if (h.entropy) h.entropy[i] = ent;
-    if (h.mode == 0) return;
-    float g_lp, g_v;
-    if (h.mode == 1) {
-        const PpoTail tl = ppo_loss_tail(lp_act, h.old_logprob[i], h.returns[i], v, ent, h.eps_clip, n);
-        h.terms[i] = tl.term_pg;
-        h.terms[n + i] = tl.term_v;
-        g_lp = tl.g_lp;
-        g_v = tl.g_v;
-    } else {
-        g_lp = h.g_logprob ? h.g_logprob[i] : 0.f;
-        g_v = h.g_value ? h.g_value[i] : 0.f;
-    }
-    if (!h.dhead) return;
-    float* d = h.dhead + hrow;
-    const float inv_var = 1.f / (h.sigma * h.sigma);
-    d[0] = g_lp * ((a0 - mu0) * inv_var) * (mu0 * (1.f - mu0));
-    d[1] = g_lp * ((a1 - mu1) * inv_var) * (mu1 * (1.f - mu1));
-    d[2] = g_v;
 }
 
 // ---- BatchNorm with batch statistics over the rows of x [rows, cols] ---------------------------------------------------------------------
@@ -744,6 +750,72 @@ int run_encoder_backward(adaf_handle* h, const EncBackwardArgs& a, const EncBack
     return launch_wenc_grad(h, a.states, r.de1, a.e1, npix, a.channels, a.conv_out, 1, a.dw_enc, r.wws, st);
 }
 
+// Both head exports behind their own null-pointer and extent checks: mode validation, workspace check, the head kernel of the export's
+// distribution (action_yx: Gaussian with A = 2, else Categorical over n_actions) and the loss sum.  `name` starts every message.
+int run_ppo_head(adaf_handle* h, const char* name, const float* head, int head_batch_major, int steps, int batch, int n_actions,
+                 const int64_t* actions, const float* action_yx, float sigma, const float* old_logprobs, const float* returns, float eps_clip,
+                 const float* g_logprob, const float* g_value, const float* g_entropy, float* logprobs_out, float* values_out,
+                 float* entropy_out, float* loss_out, float* dhead_out, void* ws, size_t ws_bytes, void* stream) {
+    const bool loss_mode = old_logprobs || returns || loss_out;
+    const bool grad_mode = g_logprob || g_value || g_entropy;
+    if (loss_mode && (!old_logprobs || !returns || !loss_out || !ws)) return adaf_fail(h, ADAF_E_BADARG, "%s: the loss needs old_logprobs, returns, loss_out and a workspace", name);
+    if (loss_mode && grad_mode) return adaf_fail(h, ADAF_E_BADARG, "%s: either the PPO loss or upstream gradients", name);
+    if (grad_mode && !dhead_out) return adaf_fail(h, ADAF_E_BADARG, "%s: upstream gradients without dhead_out", name);
+    float* terms = static_cast<float*>(ws);       // (only the loss has a workspace; the kernel reads the argument in loss mode alone)
+    int rc;
+    if (loss_mode && (rc = adaf_check_ws(h, name, ws, ws_bytes, ppo_head_layout(ws, steps, batch, &terms), ADAF_WS_SIZE_FIRST))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    HeadArgs a = {};
+    a.head = head; a.action = reinterpret_cast<const long long*>(actions); a.action_yx = action_yx; a.sigma = sigma;
+    a.old_logprob = old_logprobs; a.returns = returns; a.g_logprob = g_logprob; a.g_value = g_value; a.g_entropy = g_entropy;
+    a.logprob = logprobs_out; a.value = values_out; a.entropy = entropy_out; a.terms = terms; a.dhead = dhead_out;
+    a.T = steps; a.B = batch; a.A = n_actions; a.head_bt = head_batch_major ? 1 : 0; a.mode = loss_mode ? 1 : (grad_mode ? 2 : 0);
+    a.eps_clip = eps_clip;
+    const int n = steps * batch;
+    if (action_yx) hipLaunchKernelGGL(ppo_head_kernel<Gaussian>, dim3((n + 63) / 64), dim3(64), 0, st, a);
+    else hipLaunchKernelGGL(ppo_head_kernel<Categorical>, dim3((n + 63) / 64), dim3(64), 0, st, a);
+    if (loss_mode) hipLaunchKernelGGL(ppo_loss_sum_kernel, dim3(1), dim3(256), 0, st, a.terms, n, loss_out);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? ADAF_OK : adaf_fail(h, ADAF_E_LAUNCH, "%s launch: %s", name, hipGetErrorString(e));
+}
+
+// Both encoder-backward exports: every check, the workspace layout, EncBackwardArgs, the chain.  The BatchNorm operands are null for the
+// plain chain.  The exports refuse different shapes and that difference is kept: `plain_32` (adaf_ppo_encoder_backward_f32) takes 32 conv
+// outputs only and any hidden size; the general export takes 32 or 64 outputs and refuses a hidden or map_pixels * conv_out that is no
+// multiple of 4, with or without BatchNorm.
+int encoder_backward(adaf_handle* h, const char* name, bool plain_32, const float* states, const float* e1, const float* e_bt,
+                     const float* dx_bt, int steps, int batch, int map_pixels, int channels, int conv_out, int hidden, const float* w_lin_pm,
+                     const float* c1, const float* gamma1, const float* mean1, const float* invstd1, const float* l1, const float* gamma2,
+                     const float* mean2, const float* invstd2, float* dw_enc, float* dw_lin, float* db_lin, float* dgamma1, float* dbeta1,
+                     float* dgamma2, float* dbeta2, void* ws, size_t ws_bytes, void* stream) {
+    if (!h) return ADAF_E_BADARG;
+    if (!states || !e1 || !e_bt || !dx_bt || !w_lin_pm || !dw_enc || !dw_lin || !db_lin || !ws) return adaf_fail(h, ADAF_E_BADARG, "%s: null pointer", name);
+    const bool bn = c1 != nullptr;
+    const void* bnp[] = {c1, gamma1, mean1, invstd1, l1, gamma2, mean2, invstd2, dgamma1, dbeta1, dgamma2, dbeta2};
+    for (const void* q : bnp)
+        if (!q != !bn) return adaf_fail(h, ADAF_E_BADARG, "%s: the BatchNorm operands go together (all or none)", name);
+    if (steps <= 0 || batch <= 0 || map_pixels <= 0 || channels <= 0 || conv_out <= 0 || hidden <= 0)
+        return adaf_fail(h, ADAF_E_BADARG, "%s: non-positive extent", name);
+    if (plain_32) {
+        if (conv_out != 32 || channels % 128) return adaf_fail(h, ADAF_E_LAYOUT, "%s: 32 conv outputs and channels %% 128 == 0 expected", name);
+    } else {
+        if (!sk_shape_ok(channels, conv_out)) return adaf_fail(h, ADAF_E_LAYOUT, "%s: 32 or 64 conv outputs and channels %% 128 == 0 expected", name);
+        if (hidden % 4 || (map_pixels * conv_out) % 4) return adaf_fail(h, ADAF_E_LAYOUT, "%s: hidden and map_pixels * conv_out must be multiples of 4", name);
+    }
+    if (!adaf_aligned16(states)) return adaf_fail(h, ADAF_E_LAYOUT, "%s: 16-byte alignment", name);
+    EncBackwardWs r;
+    int rc = adaf_check_ws(h, name, ws, ws_bytes, enc_backward_layout(ws, steps, batch, map_pixels, channels, conv_out, hidden, bn, &r), ADAF_WS_ALIGN_FIRST);
+    if (rc) return rc;
+    EncBackwardArgs a = {};
+    a.states = states; a.e1 = e1; a.e_bt = e_bt; a.dx_bt = dx_bt; a.w_lin_pm = w_lin_pm;
+    a.c1 = c1; a.gamma1 = gamma1; a.mean1 = mean1; a.invstd1 = invstd1; a.l1 = l1; a.gamma2 = gamma2; a.mean2 = mean2; a.invstd2 = invstd2;
+    a.dw_enc = dw_enc; a.dw_lin = dw_lin; a.db_lin = db_lin; a.dgamma1 = dgamma1; a.dbeta1 = dbeta1; a.dgamma2 = dgamma2; a.dbeta2 = dbeta2;
+    a.steps = steps; a.batch = batch; a.map_pixels = map_pixels; a.channels = channels; a.conv_out = conv_out; a.hidden = hidden;
+    if ((rc = run_encoder_backward(h, a, r, (hipStream_t)stream))) return rc;
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? ADAF_OK : adaf_fail(h, ADAF_E_LAUNCH, "%s launch: %s", name, hipGetErrorString(e));
+}
+
 }  // namespace
 
 extern "C" {
@@ -813,26 +885,8 @@ int adaf_ppo_head_f32(adaf_handle* h, const float* head, int head_batch_major, i
     if (!h) return ADAF_E_BADARG;
     if (!head || !actions) return adaf_fail(h, ADAF_E_BADARG, "ppo_head: null pointer");
     if (steps <= 0 || batch <= 0 || n_actions <= 0) return adaf_fail(h, ADAF_E_BADARG, "ppo_head: non-positive extent");
-    const bool loss_mode = old_logprobs || returns || loss_out;
-    const bool grad_mode = g_logprob || g_value || g_entropy;
-    if (loss_mode && (!old_logprobs || !returns || !loss_out || !ws)) return adaf_fail(h, ADAF_E_BADARG, "ppo_head: the loss needs old_logprobs, returns, loss_out and a workspace");
-    if (loss_mode && grad_mode) return adaf_fail(h, ADAF_E_BADARG, "ppo_head: either the PPO loss or upstream gradients");
-    if (grad_mode && !dhead_out) return adaf_fail(h, ADAF_E_BADARG, "ppo_head: upstream gradients without dhead_out");
-    float* terms = static_cast<float*>(ws);       // (only the loss has a workspace; the kernel reads the argument in loss mode alone)
-    int rc;
-    if (loss_mode && (rc = adaf_check_ws(h, "ppo_head", ws, ws_bytes, ppo_head_layout(ws, steps, batch, &terms), ADAF_WS_SIZE_FIRST))) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    HeadArgs a = {};
-    a.head = head; a.action = reinterpret_cast<const long long*>(actions); a.old_logprob = old_logprobs; a.returns = returns;
-    a.g_logprob = g_logprob; a.g_value = g_value; a.g_entropy = g_entropy;
-    a.logprob = logprobs_out; a.value = values_out; a.entropy = entropy_out; a.terms = terms; a.dhead = dhead_out;
-    a.T = steps; a.B = batch; a.A = n_actions; a.head_bt = head_batch_major ? 1 : 0; a.mode = loss_mode ? 1 : (grad_mode ? 2 : 0);
-    a.eps_clip = eps_clip;
-    const int n = steps * batch;
-    hipLaunchKernelGGL(ppo_head_kernel, dim3((n + 63) / 64), dim3(64), 0, st, a);
-    if (loss_mode) hipLaunchKernelGGL(ppo_loss_sum_kernel, dim3(1), dim3(256), 0, st, a.terms, n, loss_out);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? ADAF_OK : adaf_hip_fail(h, e, "ppo_head launch");
+    return run_ppo_head(h, "ppo_head", head, head_batch_major, steps, batch, n_actions, actions, nullptr, 0.f, old_logprobs, returns, eps_clip,
+                        g_logprob, g_value, g_entropy, logprobs_out, values_out, entropy_out, loss_out, dhead_out, ws, ws_bytes, stream);
 }
 
 int adaf_ppo_rows_transpose_f32(adaf_handle* h, const float* in, int ni, int nj, int width, float* out, void* stream) {
@@ -873,24 +927,9 @@ size_t adaf_ppo_encoder_backward_workspace_bytes(int steps, int batch, int map_p
 int adaf_ppo_encoder_backward_f32(adaf_handle* h, const float* states, const float* e1, const float* e_bt, const float* dx_bt, int steps,
                                   int batch, int map_pixels, int channels, int conv_out, int hidden, const float* w_lin_pm, float* dw_enc,
                                   float* dw_lin, float* db_lin, void* ws, size_t ws_bytes, void* stream) {
-    if (!h) return ADAF_E_BADARG;
-    if (!states || !e1 || !e_bt || !dx_bt || !w_lin_pm || !dw_enc || !dw_lin || !db_lin || !ws)
-        return adaf_fail(h, ADAF_E_BADARG, "ppo_encoder_backward: null pointer");
-    if (steps <= 0 || batch <= 0 || map_pixels <= 0 || channels <= 0 || conv_out <= 0 || hidden <= 0)
-        return adaf_fail(h, ADAF_E_BADARG, "ppo_encoder_backward: non-positive extent");
-    if (conv_out != 32 || channels % 128) return adaf_fail(h, ADAF_E_LAYOUT, "ppo_encoder_backward: 32 conv outputs and channels %% 128 == 0 expected");
-    if (!adaf_aligned16(states)) return adaf_fail(h, ADAF_E_LAYOUT, "ppo_encoder_backward: 16-byte alignment");
-    EncBackwardWs r;
-    int rc = adaf_check_ws(h, "ppo_encoder_backward", ws, ws_bytes, enc_backward_layout(ws, steps, batch, map_pixels, channels, conv_out, hidden, false, &r),
-                           ADAF_WS_ALIGN_FIRST);
-    if (rc) return rc;
-    EncBackwardArgs a = {};
-    a.states = states; a.e1 = e1; a.e_bt = e_bt; a.dx_bt = dx_bt; a.w_lin_pm = w_lin_pm;
-    a.dw_enc = dw_enc; a.dw_lin = dw_lin; a.db_lin = db_lin;
-    a.steps = steps; a.batch = batch; a.map_pixels = map_pixels; a.channels = channels; a.conv_out = conv_out; a.hidden = hidden;
-    if ((rc = run_encoder_backward(h, a, r, (hipStream_t)stream))) return rc;
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? ADAF_OK : adaf_hip_fail(h, e, "ppo_encoder_backward launch");
+    return encoder_backward(h, "ppo_encoder_backward", true, states, e1, e_bt, dx_bt, steps, batch, map_pixels, channels, conv_out, hidden, w_lin_pm,
+                            nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, dw_enc, dw_lin, db_lin, nullptr, nullptr, nullptr,
+                            nullptr, ws, ws_bytes, stream);
 }
 
 // ---- the continuous policy ------------------------------------------------------------------------------------------------
@@ -911,26 +950,8 @@ int adaf_ppo_gauss_head_f32(adaf_handle* h, const float* head, int head_batch_ma
     if (!h) return ADAF_E_BADARG;
     if (!head || !actions) return adaf_fail(h, ADAF_E_BADARG, "ppo_gauss_head: null pointer");
     if (steps <= 0 || batch <= 0 || !(sigma > 0.f)) return adaf_fail(h, ADAF_E_BADARG, "ppo_gauss_head: non-positive extent or sigma");
-    const bool loss_mode = old_logprobs || returns || loss_out;
-    const bool grad_mode = g_logprob || g_value;
-    if (loss_mode && (!old_logprobs || !returns || !loss_out || !ws)) return adaf_fail(h, ADAF_E_BADARG, "ppo_gauss_head: the loss needs old_logprobs, returns, loss_out and a workspace");
-    if (loss_mode && grad_mode) return adaf_fail(h, ADAF_E_BADARG, "ppo_gauss_head: either the PPO loss or upstream gradients");
-    if (grad_mode && !dhead_out) return adaf_fail(h, ADAF_E_BADARG, "ppo_gauss_head: upstream gradients without dhead_out");
-    float* terms = static_cast<float*>(ws);
-    int rc;
-    if (loss_mode && (rc = adaf_check_ws(h, "ppo_gauss_head", ws, ws_bytes, ppo_head_layout(ws, steps, batch, &terms), ADAF_WS_SIZE_FIRST))) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    HeadArgs a = {};
-    a.head = head; a.action_yx = actions; a.sigma = sigma; a.old_logprob = old_logprobs; a.returns = returns;
-    a.g_logprob = g_logprob; a.g_value = g_value;
-    a.logprob = logprobs_out; a.value = values_out; a.entropy = entropy_out; a.terms = terms; a.dhead = dhead_out;
-    a.T = steps; a.B = batch; a.A = 2; a.head_bt = head_batch_major ? 1 : 0; a.mode = loss_mode ? 1 : (grad_mode ? 2 : 0);
-    a.eps_clip = eps_clip;
-    const int n = steps * batch;
-    hipLaunchKernelGGL(ppo_gauss_head_kernel, dim3((n + 63) / 64), dim3(64), 0, st, a);
-    if (loss_mode) hipLaunchKernelGGL(ppo_loss_sum_kernel, dim3(1), dim3(256), 0, st, a.terms, n, loss_out);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? ADAF_OK : adaf_hip_fail(h, e, "ppo_gauss_head launch");
+    return run_ppo_head(h, "ppo_gauss_head", head, head_batch_major, steps, batch, 2, nullptr, actions, sigma, old_logprobs, returns, eps_clip,
+                        g_logprob, g_value, nullptr, logprobs_out, values_out, entropy_out, loss_out, dhead_out, ws, ws_bytes, stream);
 }
 
 size_t adaf_bn_train_workspace_bytes(int rows, int cols) {
@@ -979,30 +1000,9 @@ int adaf_ppo_encoder_bn_backward_f32(adaf_handle* h, const float* states, const 
                                      const float* gamma2, const float* mean2, const float* invstd2, float* dw_enc, float* dw_lin,
                                      float* db_lin, float* dgamma1, float* dbeta1, float* dgamma2, float* dbeta2, void* ws, size_t ws_bytes,
                                      void* stream) {
-    if (!h) return ADAF_E_BADARG;
-    if (!states || !e1 || !e_bt || !dx_bt || !w_lin_pm || !dw_enc || !dw_lin || !db_lin || !ws)
-        return adaf_fail(h, ADAF_E_BADARG, "ppo_encoder_bn_backward: null pointer");
-    const bool bn = c1 != nullptr;
-    const void* bnp[] = {c1, gamma1, mean1, invstd1, l1, gamma2, mean2, invstd2, dgamma1, dbeta1, dgamma2, dbeta2};
-    for (const void* q : bnp)
-        if (!q != !bn) return adaf_fail(h, ADAF_E_BADARG, "ppo_encoder_bn_backward: the BatchNorm operands go together (all or none)");
-    if (steps <= 0 || batch <= 0 || map_pixels <= 0 || channels <= 0 || conv_out <= 0 || hidden <= 0)
-        return adaf_fail(h, ADAF_E_BADARG, "ppo_encoder_bn_backward: non-positive extent");
-    if (!sk_shape_ok(channels, conv_out)) return adaf_fail(h, ADAF_E_LAYOUT, "ppo_encoder_bn_backward: 32 or 64 conv outputs and channels %% 128 == 0 expected");
-    if (hidden % 4 || (map_pixels * conv_out) % 4) return adaf_fail(h, ADAF_E_LAYOUT, "ppo_encoder_bn_backward: hidden and map_pixels * conv_out must be multiples of 4");
-    if (!adaf_aligned16(states)) return adaf_fail(h, ADAF_E_LAYOUT, "ppo_encoder_bn_backward: 16-byte alignment");
-    EncBackwardWs r;
-    int rc = adaf_check_ws(h, "ppo_encoder_bn_backward", ws, ws_bytes,
-                           enc_backward_layout(ws, steps, batch, map_pixels, channels, conv_out, hidden, bn, &r), ADAF_WS_ALIGN_FIRST);
-    if (rc) return rc;
-    EncBackwardArgs a = {};
-    a.states = states; a.e1 = e1; a.e_bt = e_bt; a.dx_bt = dx_bt; a.w_lin_pm = w_lin_pm;
-    a.c1 = c1; a.gamma1 = gamma1; a.mean1 = mean1; a.invstd1 = invstd1; a.l1 = l1; a.gamma2 = gamma2; a.mean2 = mean2; a.invstd2 = invstd2;
-    a.dw_enc = dw_enc; a.dw_lin = dw_lin; a.db_lin = db_lin; a.dgamma1 = dgamma1; a.dbeta1 = dbeta1; a.dgamma2 = dgamma2; a.dbeta2 = dbeta2;
-    a.steps = steps; a.batch = batch; a.map_pixels = map_pixels; a.channels = channels; a.conv_out = conv_out; a.hidden = hidden;
-    if ((rc = run_encoder_backward(h, a, r, (hipStream_t)stream))) return rc;
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? ADAF_OK : adaf_hip_fail(h, e, "ppo_encoder_bn_backward launch");
+    return encoder_backward(h, "ppo_encoder_bn_backward", false, states, e1, e_bt, dx_bt, steps, batch, map_pixels, channels, conv_out, hidden, w_lin_pm,
+                            c1, gamma1, mean1, invstd1, l1, gamma2, mean2, invstd2, dw_enc, dw_lin, db_lin, dgamma1, dbeta1, dgamma2, dbeta2, ws,
+                            ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -322,29 +322,40 @@ def ppo_returns(rewards, gamma):
     return out
 
 
-def _ppo_head(head, actions, batch_major, old_logprobs=None, returns=None, eps_clip=0.2, grads=None, want_dhead=True):
-    L.need_gpu_f32(head, old_logprobs, returns, *(grads or ()))
-    head = head.contiguous()
-    t, b = actions.shape
-    a = head.shape[1] - 1
-    if head.shape[0] != t * b or actions.dtype != torch.int64 or not actions.is_cuda:
-        raise ValueError("ppo head: head (T*B, A+1) and int64 GPU actions (T, B) expected")
-    actions = actions.contiguous()
+def _ppo_head(head, actions, batch_major, sigma=None, old_logprobs=None, returns=None, eps_clip=0.2, grads=None):
+    """The head kernel of csrc/ppo_train.hip in its three modes (statistics; PPO loss + its gradient when old_logprobs is given; pull-back
+    of `grads` = upstream (g_logprob, g_value, g_entropy)) for both distributions: sigma None is the categorical head with int64 actions
+    (T, B), a float the Gaussian head with that standard deviation and fp32 actions (T, B, 2) [no entropy gradient]."""
+    gauss = sigma is not None
+    L.need_gpu_f32(head, old_logprobs, returns, *(grads or ()), *((actions,) if gauss else ()))
+    head, actions = head.contiguous(), actions.contiguous()
+    if gauss:
+        if actions.dim() != 3 or actions.shape[2] != 2 or head.shape != (actions.shape[0] * actions.shape[1], 3):
+            raise ValueError("ppo gauss head: head (T*B, 3) and actions (T, B, 2) expected")
+        t, b = actions.shape[:2]
+    else:
+        t, b = actions.shape
+        if head.shape[0] != t * b or actions.dtype != torch.int64 or not actions.is_cuda:
+            raise ValueError("ppo head: head (T*B, A+1) and int64 GPU actions (T, B) expected")
     dev, fp = head.device, torch.float32
     logprobs, values, entropy = (torch.empty((t, b), device=dev, dtype=fp) for _ in range(3))
     loss_mode = old_logprobs is not None
     loss = torch.empty((1,), device=dev, dtype=fp) if loss_mode else None
-    dhead = torch.empty_like(head) if (want_dhead and (loss_mode or grads is not None)) else None
+    dhead = torch.empty_like(head) if (loss_mode or grads is not None) else None
     lib = L.load_library()
     ws_bytes = lib.adaf_ppo_head_workspace_bytes(t, b) if loss_mode else 0
     ws = torch.empty(max(ws_bytes // 4, 1), device=dev, dtype=fp)
-    g = [None if x is None else x.contiguous() for x in (grads or (None, None, None))]
+    g = [None if x is None else x.contiguous() for x in (grads or ())] + [None] * 3      # (kept alive until the launch: L.ptr holds no reference)
     if loss_mode:
         old_logprobs, returns = old_logprobs.contiguous(), returns.contiguous()
+    outs = (L.ptr(logprobs), L.ptr(values), L.ptr(entropy), L.ptr(loss), L.ptr(dhead), L.ptr(ws), ws_bytes, L.stream_ptr())
     h = _h(head)
-    L.check(lib.adaf_ppo_head_f32(h, L.ptr(head), int(batch_major), t, b, a, L.ptr(actions), L.ptr(old_logprobs), L.ptr(returns),
-                                  C.c_float(eps_clip), L.ptr(g[0]), L.ptr(g[1]), L.ptr(g[2]), L.ptr(logprobs), L.ptr(values), L.ptr(entropy),
-                                  L.ptr(loss), L.ptr(dhead), L.ptr(ws), ws_bytes, L.stream_ptr()), h)
+    if gauss:
+        L.check(lib.adaf_ppo_gauss_head_f32(h, L.ptr(head), int(batch_major), t, b, L.ptr(actions), C.c_float(sigma), L.ptr(old_logprobs),
+                                            L.ptr(returns), C.c_float(eps_clip), L.ptr(g[0]), L.ptr(g[1]), *outs), h)
+    else:
+        L.check(lib.adaf_ppo_head_f32(h, L.ptr(head), int(batch_major), t, b, head.shape[1] - 1, L.ptr(actions), L.ptr(old_logprobs),
+                                      L.ptr(returns), C.c_float(eps_clip), L.ptr(g[0]), L.ptr(g[1]), L.ptr(g[2]), *outs), h)
     return logprobs, values, entropy, loss, dhead
 
 
@@ -394,28 +405,6 @@ def ppo_wenc_grad(states, de1, e1, split_k=True):
     return dw
 
 
-def ppo_encoder_backward(states, e1, e_bt, dx_bt, t, b, w_lin_pm):
-    """Backward of the policy's state encoder (1x1 conv -> ReLU -> flatten -> Linear -> ReLU): states (T*B, h, w, C) pixel-major, e1
-    (T*B, h*w*32) and e_bt (B*T, H) its stored activations, dx_bt (B, T, H) the GRU's input gradient -> (dW_enc (32, C), dW_lin (H, 32*h*w)
-    in the nn.Linear layout, db_lin (H,))."""
-    L.need_gpu_f32(states, e1, e_bt, dx_bt, w_lin_pm)
-    hw, cin = states.shape[1] * states.shape[2], states.shape[3]
-    hid = w_lin_pm.shape[0]
-    cmid = w_lin_pm.shape[1] // hw
-    lib = L.load_library()
-    ws_bytes = lib.adaf_ppo_encoder_backward_workspace_bytes(t, b, hw, cin, cmid, hid)
-    ws = torch.empty(max(ws_bytes // 4, 4), device=states.device, dtype=torch.float32)
-    dev, fp = states.device, torch.float32
-    dw_enc = torch.empty((cmid, cin), device=dev, dtype=fp)
-    dw_lin = torch.empty((hid, cmid * hw), device=dev, dtype=fp)
-    db_lin = torch.empty((hid,), device=dev, dtype=fp)
-    h = _h(states)
-    L.check(lib.adaf_ppo_encoder_backward_f32(h, L.ptr(states.contiguous()), L.ptr(e1.contiguous()), L.ptr(e_bt.contiguous()),
-                                              L.ptr(dx_bt.contiguous()), t, b, hw, cin, cmid, hid, L.ptr(w_lin_pm.contiguous()), L.ptr(dw_enc),
-                                              L.ptr(dw_lin), L.ptr(db_lin), L.ptr(ws), ws_bytes, L.stream_ptr()), h)
-    return dw_enc, dw_lin, db_lin
-
-
 # ---- stage-2 training of the continuous policy (Something-Something; csrc/ppo_train.hip, DESIGN 3.12) ------------------------------------
 def ppo_gauss_sample(mean, noise, sigma):
     """mean (rows, 2), noise (rows, 2) standard normals -> (action (rows, 2) = 1 - relu(1 - relu(mean + sigma * noise)), the log-probability
@@ -433,46 +422,22 @@ def ppo_gauss_sample(mean, noise, sigma):
     return action, logprob
 
 
-def _ppo_gauss_head(head, actions, sigma, batch_major, old_logprobs=None, returns=None, eps_clip=0.2, grads=None):
-    L.need_gpu_f32(head, actions, old_logprobs, returns, *(grads or ()))
-    head, actions = head.contiguous(), actions.contiguous()
-    if actions.dim() != 3 or actions.shape[2] != 2 or head.shape != (actions.shape[0] * actions.shape[1], 3):
-        raise ValueError("ppo gauss head: head (T*B, 3) and actions (T, B, 2) expected")
-    t, b = actions.shape[:2]
-    dev, fp = head.device, torch.float32
-    logprobs, values, entropy = (torch.empty((t, b), device=dev, dtype=fp) for _ in range(3))
-    loss_mode = old_logprobs is not None
-    loss = torch.empty((1,), device=dev, dtype=fp) if loss_mode else None
-    dhead = torch.empty_like(head) if (loss_mode or grads is not None) else None
-    lib = L.load_library()
-    ws_bytes = lib.adaf_ppo_head_workspace_bytes(t, b) if loss_mode else 0
-    ws = torch.empty(max(ws_bytes // 4, 1), device=dev, dtype=fp)
-    g = [None if x is None else x.contiguous() for x in (grads or (None, None))]
-    if loss_mode:
-        old_logprobs, returns = old_logprobs.contiguous(), returns.contiguous()
-    h = _h(head)
-    L.check(lib.adaf_ppo_gauss_head_f32(h, L.ptr(head), int(batch_major), t, b, L.ptr(actions), C.c_float(sigma), L.ptr(old_logprobs),
-                                        L.ptr(returns), C.c_float(eps_clip), L.ptr(g[0]), L.ptr(g[1]), L.ptr(logprobs), L.ptr(values),
-                                        L.ptr(entropy), L.ptr(loss), L.ptr(dhead), L.ptr(ws), ws_bytes, L.stream_ptr()), h)
-    return logprobs, values, entropy, loss, dhead
-
-
 def ppo_gauss_head_stats(head, actions, sigma, batch_major=True):
     """head (T*B, 3) [mean logits | value] (rows b*T+t when batch_major), actions (T, B, 2) -> (logprobs, values, entropy), each (T, B)."""
-    return _ppo_gauss_head(head, actions, sigma, batch_major)[:3]
+    return _ppo_head(head, actions, batch_major, sigma)[:3]
 
 
 def ppo_gauss_head_backward(head, actions, sigma, g_logprob, g_value, batch_major=True):
     """Pull-back of upstream gradients of (logprobs, values) (each (T, B) or None; the entropy is a constant) to the head output."""
     if g_logprob is None and g_value is None:
         return torch.zeros_like(head)
-    return _ppo_gauss_head(head, actions, sigma, batch_major, grads=(g_logprob, g_value))[4]
+    return _ppo_head(head, actions, batch_major, sigma, grads=(g_logprob, g_value))[4]
 
 
 def ppo_gauss_loss_head(head, actions, sigma, old_logprobs, returns, eps_clip, batch_major=True):
     """The Gaussian PPO loss head, forward and backward in one pass: -> (logprobs, values, entropy (T, B), loss.mean() (1,),
     d loss.mean() / d head (T*B, 3))."""
-    return _ppo_gauss_head(head, actions, sigma, batch_major, old_logprobs=old_logprobs, returns=returns, eps_clip=eps_clip)
+    return _ppo_head(head, actions, batch_major, sigma, old_logprobs=old_logprobs, returns=returns, eps_clip=eps_clip)
 
 
 def _bn_ws(lib, rows, cols, dev):
@@ -521,10 +486,12 @@ def bn_train_backward(x, y, dy, gamma, mean, invstd):
     return dx, dgamma, dbeta
 
 
-def ppo_encoder_bn_backward(states, e1, e_bt, dx_bt, t, b, w_lin_pm, bn=None):
-    """ppo_encoder_backward for 32 or 64 conv outputs, with or without BatchNorm.  bn = (c1, gamma1, mean1, invstd1, l1, gamma2, mean2,
-    invstd2): the raw conv / Linear outputs and the statistics of the forward ->
-    (dW_enc, dW_lin, db_lin[, dgamma1, dbeta1, dgamma2, dbeta2])."""
+def ppo_encoder_backward(states, e1, e_bt, dx_bt, t, b, w_lin_pm, bn=None):
+    """Backward of the policy's state encoder (1x1 conv -> [BatchNorm2d] ReLU -> flatten -> Linear -> [BatchNorm1d] ReLU) for 32 or 64
+    conv outputs: states (T*B, h, w, C) pixel-major, e1 (T*B, h*w*cmid) and e_bt (B*T, H) its stored activations, dx_bt (B, T, H) the
+    GRU's input gradient; bn = (c1, gamma1, mean1, invstd1, l1, gamma2, mean2, invstd2): the raw conv / Linear outputs and the statistics
+    of the forward -> (dW_enc (cmid, C), dW_lin (H, cmid*h*w) in the nn.Linear layout, db_lin (H,)[, dgamma1, dbeta1, dgamma2, dbeta2]).
+    One entry point for both policies (adaf_ppo_encoder_bn_backward_f32): H and h*w*cmid are multiples of 4."""
     L.need_gpu_f32(states, e1, e_bt, dx_bt, w_lin_pm, *(bn or ()))
     hw, cin = states.shape[1] * states.shape[2], states.shape[3]
     hid = w_lin_pm.shape[0]
@@ -538,10 +505,10 @@ def ppo_encoder_bn_backward(states, e1, e_bt, dx_bt, t, b, w_lin_pm, bn=None):
     db_lin = torch.empty((hid,), device=dev, dtype=fp)
     extra = () if bn is None else tuple(torch.empty((n,), device=dev, dtype=fp) for n in (cmid, cmid, hid, hid))
     bn_in = [None] * 8 if bn is None else [x.contiguous() for x in bn]
+    states, e1, e_bt, dx_bt, w_lin_pm = (x.contiguous() for x in (states, e1, e_bt, dx_bt, w_lin_pm))      # (alive until the launch)
     h = _h(states)
-    L.check(lib.adaf_ppo_encoder_bn_backward_f32(h, L.ptr(states.contiguous()), L.ptr(e1.contiguous()), L.ptr(e_bt.contiguous()),
-                                                 L.ptr(dx_bt.contiguous()), t, b, hw, cin, cmid, hid, L.ptr(w_lin_pm.contiguous()),
-                                                 *(L.ptr(x) for x in bn_in), L.ptr(dw_enc), L.ptr(dw_lin), L.ptr(db_lin),
+    L.check(lib.adaf_ppo_encoder_bn_backward_f32(h, L.ptr(states), L.ptr(e1), L.ptr(e_bt), L.ptr(dx_bt), t, b, hw, cin, cmid, hid,
+                                                 L.ptr(w_lin_pm), *(L.ptr(x) for x in bn_in), L.ptr(dw_enc), L.ptr(dw_lin), L.ptr(db_lin),
                                                  *(L.ptr(x) for x in (extra or [None] * 4)), L.ptr(ws), ws_bytes, L.stream_ptr()), h)
     return (dw_enc, dw_lin, db_lin) + extra
 

@@ -6,21 +6,28 @@ Inference (``training=False``): the action is the mean; BatchNorm is folded from
 still draws ``dist.sample()`` and discards it, ppo_continuous.py:98,107 -- it only advances the global RNG).
 
 Stage-2 training (the module in train mode, ``GFV.policy_train_mode()``): ``act(training=True)`` samples
-``1 - relu(1 - relu(mu + sigma z))`` from caller-drawn normals and stores state, action and log-probability; ``evaluate`` is the policy
-forward over a stored roll-out through ``PolicyEvaluateFn`` (HIP forward that keeps the activations, HIP backward for every policy
-parameter); ``PPO_Continuous.update`` runs returns kernel -> K_epochs x {forward, Gaussian loss head, backward, Adam step}.  BatchNorm
+``1 - relu(1 - relu(mu + sigma z))`` from caller-drawn normals and stores state, action and log-probability; ``evaluate`` and
+``PPO_Continuous.update`` are the training core of ``policy_train.py``, shared with the discrete policy, with the Gaussian head (the
+policy forward over a stored roll-out through ``PolicyEvaluateFn``; returns kernel -> K_epochs x {forward, loss head, backward, Adam
+step}).  BatchNorm
 uses batch statistics on these paths (a roll-out step over B rows, evaluate over T*B rows) and updates the running ones.  ``action_std``
 is the standard deviation itself: the reference hands ``diag(action_var)`` to MultivariateNormal as ``scale_tril``."""
 import torch
 from torch import nn
 
 from . import hip_ops
+from .policy_train import PolicyEvaluateFn, PolicyTrainMixin, ppo_update  # noqa: F401  (PolicyEvaluateFn: the name it had here)
 from .ppo import Memory  # noqa: F401  (same class in both reference files)
 
 __all__ = ["ActorCritic", "PPO_Continuous", "Memory"]
 
 
-class ActorCritic(nn.Module):
+class ActorCritic(PolicyTrainMixin, nn.Module):
+    """The training core is policy_train.PolicyTrainMixin's; this class supplies the Gaussian distribution N(mu, action_std^2 I) over (y, x)
+    (constant entropy, fp32 actions (T, B, 2)), the train-mode requirement of its BatchNorm and the inference / roll-out surfaces."""
+    entropy_has_grad = False
+    needs_train_mode = True
+
     def __init__(self, feature_dim, state_dim, hidden_state_dim=1024, policy_conv=True, action_std=0.1, with_bn=False):
         super().__init__()
         if policy_conv:
@@ -103,55 +110,6 @@ class ActorCritic(nn.Module):
         return self.act_nhwc(nhwc, b, tg, memory, restart_batch)
 
     # ---- stage-2 training ---------------------------------------------------------------------------------------------------------------
-    @property
-    def with_bn(self):
-        return isinstance(self.state_encoder[1], nn.BatchNorm2d)
-
-    def _need_train_mode(self, what):
-        if not self.training:
-            raise NotImplementedError("%s is stage-2 (PPO) training: call model.policy_train_mode() first (this policy is in eval mode, "
-                                      "where BatchNorm would not use batch statistics)" % what)
-
-    def _hip_weights(self, hw):
-        """Engine-layout views of the conv and Linear weights (cached on the parameter versions): the conv filter as (64, 1, 1, Tg*C), the
-        Linear weight with pixel-major columns (the reference flattens (B, 64, h, w) channel-major)."""
-        conv, lin = self.state_encoder[0], self.state_encoder[4 if self.with_bn else 3]
-        sig = tuple((q.data_ptr(), q._version) for q in (conv.weight, lin.weight)) + (hw,)
-        if getattr(self, "_hipw_sig", None) != sig:
-            cmid = conv.weight.shape[0]
-            w_enc = conv.weight.detach().reshape(cmid, 1, 1, -1).contiguous()
-            w_lin = lin.weight.detach().view(-1, cmid, hw).permute(0, 2, 1).reshape(lin.weight.shape[0], hw * cmid).contiguous()
-            self._hipw, self._hipw_sig = (w_enc, w_lin), sig
-        return self._hipw
-
-    def _bn_forward(self, bn, x):
-        """BatchNorm with batch statistics + ReLU over the rows of x, as the module in train mode does it: running statistics and
-        num_batches_tracked move."""
-        if bn.momentum is None or not bn.track_running_stats or not bn.affine:
-            raise NotImplementedError("BatchNorm with momentum=None, without running statistics or without affine parameters")
-        out = hip_ops.bn_train_forward(x, bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var, bn.eps, bn.momentum)
-        bn.num_batches_tracked += 1
-        return out
-
-    def _encode_train(self, dense):
-        """The state encoder over dense pixel-major states (N, h, w, Tg*C), keeping what the backward needs: dict with e1 (N, h*w*64) and
-        e (N, hidden) after ReLU; with BatchNorm also the raw outputs c1 / l1 and the statistics they were normalised with."""
-        n, hh, ww, _ = dense.shape
-        hw = hh * ww
-        enc = self.state_encoder
-        w_enc, w_lin = self._hip_weights(hw)
-        if not self.with_bn:
-            e1 = hip_ops.conv2d_bn_act(dense, w_enc, act=hip_ops.ACT_RELU)
-            e = hip_ops.linear(e1.view(n, -1), w_lin, enc[3].bias.detach(), act=hip_ops.ACT_RELU)
-            return dict(e1=e1.view(n, -1), e=e, w_lin=w_lin)
-        cmid = w_enc.shape[0]
-        c1 = hip_ops.conv2d_bn_act(dense, w_enc).view(n * hw, cmid)
-        e1, mean1, invstd1 = self._bn_forward(enc[1], c1)
-        l1 = hip_ops.linear(e1.view(n, -1), w_lin, enc[4].bias.detach())
-        e, mean2, invstd2 = self._bn_forward(enc[5], l1)
-        return dict(e1=e1.view(n, -1), e=e, w_lin=w_lin, c1=c1, mean1=mean1, invstd1=invstd1, l1=l1, mean2=mean2, invstd2=invstd2,
-                    gamma1=enc[1].weight.detach(), gamma2=enc[5].weight.detach())
-
     def _act_train(self, featmap_nhwc, b, tg, memory, restart_batch, noise, state_ini):
         """ppo_continuous.py:78-109 with training=True: the action 1 - relu(1 - relu(mu + action_std * z)), z = `noise` (B, 2) standard
         normals (None: torch.randn on the device, one draw per step), its log-probability, and the memory filled as the reference fills
@@ -180,92 +138,17 @@ class ActorCritic(nn.Module):
         memory.logprobs.append(logprob)
         return action
 
-    def _states_dense(self, state):
-        """(T, B, Tg*C, h, w) [reference layout, or the permuted view of a dense pixel-major state] or (T, B, h, w, Tg*C) -> contiguous
-        (T, B, h, w, Tg*C)."""
-        if state.shape[2] == self.feature_dim and state.shape[-1] != self.feature_dim:
-            state = state.permute(0, 1, 3, 4, 2)
-        return state.contiguous()
+    def _evaluate_actions(self, action):
+        return action.detach().float()
 
-    def _train_forward(self, states_dense):
-        """The policy over a stored roll-out, keeping what the backward needs: states (T, B, h, w, Tg*C) -> dict with the stacked head
-        output `head` (B*T, 3) [mean logits | critic value], rows b * T + t."""
-        if not self.policy_conv:
-            raise NotImplementedError("the Linear state encoder (policy_conv=False) has no HIP backward: evaluate / update are implemented "
-                                      "for the 1x1-conv encoder only")
-        self._need_train_mode("evaluate / update")
-        t, b, hh, ww, c = states_dense.shape
-        n = t * b
-        if self.with_bn and n < 2:
-            raise ValueError("Expected more than 1 value per channel when training, got input size %s" % ((n, self.hidden_state_dim),))
-        s = states_dense.view(n, hh, ww, c)
-        fwd = self._encode_train(s)                                                         # rows t * B + b
-        e_bt = hip_ops.rows_transpose(fwd["e"], t, b)                                       # rows b * T + t
-        head_w = torch.cat([self.actor[0].weight.detach(), self.critic[0].weight.detach()], 0)
-        head_b = torch.cat([self.actor[0].bias.detach(), self.critic[0].bias.detach()], 0)
-        g = self.gru
-        w = [p.detach() for p in (g.weight_ih_l0, g.weight_hh_l0, g.bias_ih_l0, g.bias_hh_l0)]
-        head, gi, hs = hip_ops.gru_cls_train_forward(e_bt.view(b, t, -1), w[0], w[1], w[2], w[3], head_w, head_b, None)
-        fwd.update(states=s, e_bt=e_bt, gi=gi, hs=hs, head=head, head_w=head_w, w_ih=w[0], w_hh=w[1], b_hh=w[3], t=t, b=b)
-        del fwd["e"]
-        return fwd
+    def _head_stats(self, head, actions):
+        return hip_ops.ppo_gauss_head_stats(head, actions, self.action_std)
 
-    def _train_backward(self, fwd, dhead):
-        """Gradients of every policy parameter from d loss / d head (B*T, 3): {name: tensor} in the parameters' own layouts."""
-        t, b = fwd["t"], fwd["b"]
-        x = fwd["e_bt"].view(b, t, -1)
-        dx, dw_ih, dw_hh, db_ih, db_hh, dw_head, db_head = hip_ops.gru_cls_backward(x, fwd["w_ih"], fwd["w_hh"], fwd["b_hh"], fwd["head_w"],
-                                                                                    fwd["gi"], fwd["hs"], None, dhead, want_dx=True)
-        bn = tuple(fwd[k] for k in _BN_TENSORS) if self.with_bn else None
-        out = hip_ops.ppo_encoder_bn_backward(fwd["states"], fwd["e1"], fwd["e_bt"], dx, t, b, fwd["w_lin"], bn)
-        lin = 4 if self.with_bn else 3
-        grads = {"state_encoder.0.weight": out[0].view(out[0].shape[0], -1, 1, 1), "state_encoder.%d.weight" % lin: out[1],
-                 "state_encoder.%d.bias" % lin: out[2], "gru.weight_ih_l0": dw_ih, "gru.weight_hh_l0": dw_hh, "gru.bias_ih_l0": db_ih,
-                 "gru.bias_hh_l0": db_hh, "actor.0.weight": dw_head[:2], "actor.0.bias": db_head[:2], "critic.0.weight": dw_head[2:],
-                 "critic.0.bias": db_head[2:]}
-        if self.with_bn:
-            grads.update({"state_encoder.1.weight": out[3], "state_encoder.1.bias": out[4], "state_encoder.5.weight": out[5],
-                          "state_encoder.5.bias": out[6]})
-        return grads
+    def _head_backward(self, head, actions, g_logprob, g_value, g_entropy):
+        return hip_ops.ppo_gauss_head_backward(head, actions, self.action_std, g_logprob, g_value)
 
-    def evaluate(self, state, action):
-        """ppo_continuous.py:111-139: state (T, B, Tg*C, h, w) (or its dense pixel-major form), action (T, B, 2) -> (logprobs, state
-        values, entropy), each (T, B), differentiable with respect to every policy parameter (HIP forward and backward).  The entropy is
-        the constant 1 + log 2 pi + 2 log action_std."""
-        if not self.policy_conv:
-            raise NotImplementedError("the Linear state encoder (policy_conv=False) has no HIP backward: evaluate / update are implemented "
-                                      "for the 1x1-conv encoder only")
-        return PolicyEvaluateFn.apply(self, self._states_dense(state), action.detach().float(), *(p for _, p in self.named_parameters()))
-
-
-_BN_TENSORS = ("c1", "gamma1", "mean1", "invstd1", "l1", "gamma2", "mean2", "invstd2")
-_FWD_TENSORS = ("states", "e1", "e_bt", "gi", "hs", "head", "head_w", "w_ih", "w_hh", "b_hh", "w_lin")
-
-
-class PolicyEvaluateFn(torch.autograd.Function):
-    """ActorCritic.evaluate with a HIP backward: apply(policy, states (T, B, h, w, Tg*C), actions (T, B, 2), *parameters in
-    named_parameters() order) -> (logprobs, values, entropy).  As ppo.PolicyEvaluateFn: the parameters are inputs only so that autograd
-    routes their gradients, the forward reads them from the module; activations and weight views go through save_for_backward."""
-
-    @staticmethod
-    def forward(ctx, policy, states, actions, *params):
-        fwd = policy._train_forward(states)
-        keys = _FWD_TENSORS + (_BN_TENSORS if policy.with_bn else ())
-        ctx.policy, ctx.dims, ctx.keys = policy, (fwd["t"], fwd["b"]), keys
-        ctx.save_for_backward(actions, *(fwd[k] for k in keys))
-        out = hip_ops.ppo_gauss_head_stats(fwd["head"], actions, policy.action_std)
-        ctx.mark_non_differentiable(out[2])
-        return out
-
-    @staticmethod
-    def backward(ctx, g_logprob, g_value, g_entropy):
-        actions, *tensors = ctx.saved_tensors
-        policy = ctx.policy
-        fwd = dict(zip(ctx.keys, tensors), t=ctx.dims[0], b=ctx.dims[1])
-        dhead = hip_ops.ppo_gauss_head_backward(fwd["head"], actions, policy.action_std,
-                                                *(None if g is None else g.float() for g in (g_logprob, g_value)))
-        grads = policy._train_backward(fwd, dhead)
-        return (None, None, None) + tuple(grads[n] for n, _ in policy.named_parameters())
+    def _loss_head(self, head, actions, old_logprobs, returns, eps_clip):
+        return hip_ops.ppo_gauss_loss_head(head, actions, self.action_std, old_logprobs, returns, eps_clip)
 
 
 class PPO_Continuous:
@@ -290,29 +173,7 @@ class PPO_Continuous:
         return self.policy_old.act(state, memory, restart_batch, training)
 
     def update(self, memory):
-        """ppo_continuous.py:165-196: discounted, normalised returns; K_epochs x {policy forward over the stored roll-out, Gaussian PPO
-        loss head with its gradient, HIP backward, Adam step}; then policy_old <- policy, BatchNorm buffers included.  `last_loss` keeps
-        the last epoch's loss.mean() (a device tensor)."""
-        pol = self.policy
-        if not pol.policy_conv:
-            raise NotImplementedError("the Linear state encoder (policy_conv=False) has no HIP backward: evaluate / update are implemented "
-                                      "for the 1x1-conv encoder only")
-        pol._need_train_mode("update")
-        rewards = torch.cat([r.reshape(1, -1) for r in memory.rewards], 0).float()
-        returns = hip_ops.ppo_returns(rewards, self.gamma)
-        # the stacked states laid out once as dense pixel-major (T, B, h, w, Tg*C): the one large copy of the update
-        dense = [s.permute(0, 2, 3, 1) if s.shape[1] == pol.feature_dim and s.shape[-1] != pol.feature_dim else s for s in memory.states]
-        states = pol._states_dense((dense[0][None] if len(dense) == 1 else torch.stack(dense, 0)).detach())
-        actions = torch.stack(memory.actions, 0).detach()
-        old_logprobs = torch.stack(memory.logprobs, 0).detach()
-        params = dict(pol.named_parameters())
-        with torch.no_grad():
-            for _ in range(self.K_epochs):
-                fwd = pol._train_forward(states)
-                _, _, _, loss, dhead = hip_ops.ppo_gauss_loss_head(fwd["head"], actions, pol.action_std, old_logprobs, returns, self.eps_clip)
-                grads = pol._train_backward(fwd, dhead)
-                for n, g in grads.items():
-                    params[n].grad = g.contiguous()
-                self.optimizer.step()
-                self.last_loss = loss
-        self.policy_old.load_state_dict(self.policy.state_dict())
+        """ppo_continuous.py:165-196 (policy_train.ppo_update).  `last_loss` keeps the last epoch's loss.mean() (a device tensor)."""
+        loss = ppo_update(self.policy, self.policy_old, self.optimizer, memory, self.gamma, self.eps_clip, self.K_epochs)
+        if loss is not None:
+            self.last_loss = loss

@@ -1,4 +1,4 @@
-"""CPU model of the continuous policy's arithmetic (csrc/ppo_train.hip: ppo_gauss_sample_kernel, ppo_gauss_head_kernel), in torch ops
+"""CPU model of the continuous policy's arithmetic (csrc/ppo_train.hip: ppo_gauss_sample_kernel, ppo_head_kernel<Gaussian>), in torch ops
 on whatever dtype it is given: the sampled and clamped action, the Gaussian log-probability with sigma = action_std as the STANDARD
 DEVIATION, and the PPO loss head with its hand-written gradient.  tests/test_stage2_sth_host.py holds it to
 torch.distributions.MultivariateNormal(scale_tril=diag(action_var)) and to float64 autograd; the GPU tests compare the kernels with it."""

@@ -411,3 +411,61 @@ def test_one_step_act_training_needs_policy_train_mode():
     mem = model.focuser.memory
     assert len(mem.actions) == len(mem.logprobs) == len(mem.states) == 1 and mem.actions[0].shape == (b,)
     mem.clear_memory()
+
+
+# ---- 8. one training core for both policies -------------------------------------------------------------------------------------------------
+def test_evaluate_backward_equals_train_backward():
+    """evaluate runs through the one autograd class both policies share (policy_train.PolicyEvaluateFn), and loss.backward() through it
+    gives the gradients of _train_backward for the same d loss / d head: torch.equal for every parameter (B = 3, T = 5, A = 25; upstream
+    gradients of all three outputs)."""
+    from adafocus_amd import policy_train, ppo, ppo_continuous
+    assert ppo.PolicyEvaluateFn is policy_train.PolicyEvaluateFn and ppo_continuous.PolicyEvaluateFn is policy_train.PolicyEvaluateFn
+    b, t, a = 3, 5, 25
+    pol = _ppo(a=a, seed=300 + a).policy.to(DEV)
+    states = _rnd((t, b, 1280, 7, 7), 53, 0.5).to(DEV)
+    actions = torch.from_numpy(np.random.Generator(np.random.PCG64(95)).integers(0, a, size=(t, b))).to(DEV)
+    g = [_rnd((t, b), 90 + i).to(DEV) for i in range(3)]
+    logprobs, values, entropy = pol.evaluate(states, actions)
+    assert type(logprobs.grad_fn) is policy_train.PolicyEvaluateFn._backward_cls
+    pol.zero_grad(set_to_none=True)
+    ((logprobs * g[0]).sum() + (values * g[1]).sum() + (entropy * g[2]).sum()).backward()
+    with torch.no_grad():
+        fwd = pol._train_forward(pol._states_nhwc(states))
+        want = pol._train_backward(fwd, hip_ops.ppo_head_backward(fwd["head"], actions, *g))
+    assert tuple(n for n, _ in pol.named_parameters()) == PARAM_NAMES and set(want) == set(PARAM_NAMES)
+    for n, p in pol.named_parameters():
+        assert p.grad.abs().max() > 0 and torch.equal(p.grad, want[n].reshape(p.shape)), n
+    # sum() hands the backward expanded (stride-0) upstream gradients: the head wrapper lays them out itself
+    logprobs, values, entropy = pol.evaluate(states, actions)
+    pol.zero_grad(set_to_none=True)
+    (logprobs.sum() + 0.5 * values.sum()).backward()
+    with torch.no_grad():
+        dense = [torch.full((t, b), v, device=DEV) for v in (1.0, 0.5, 0.0)]
+        want = pol._train_backward(fwd, hip_ops.ppo_head_backward(fwd["head"], actions, *dense))
+        assert torch.equal(hip_ops.ppo_head_backward(fwd["head"], actions, dense[0].t().contiguous().t(), dense[1][:1].expand(t, b), None),
+                           hip_ops.ppo_head_backward(fwd["head"], actions, dense[0], dense[1], None))
+    for n, p in pol.named_parameters():
+        assert torch.equal(p.grad, want[n].reshape(p.shape)), n
+
+
+def test_encoder_backward_wrapper_equals_the_32_output_export():
+    """hip_ops.ppo_encoder_backward (the general entry point, bn=None) at the discrete policy's 32 conv outputs against a direct call of
+    adaf_ppo_encoder_backward_f32 on the same operands: torch.equal (T = 5, B = 3, 7 x 7 map, C = 128, H = 1024)."""
+    import ctypes as C
+    from adafocus_amd import _lib as L
+    t, b, hw, cin, cmid, hid = 5, 3, 49, 128, 32, 1024
+    states = _rnd((t * b, 7, 7, cin), 1010, 0.5).to(DEV)
+    e1 = _rnd((t * b, hw * cmid), 1012).clamp(min=0).to(DEV)
+    e_bt, dx = _rnd((b, t, hid), 1013).clamp(min=0).to(DEV), _rnd((b, t, hid), 1014, 0.1).to(DEV)
+    w_lin = _rnd((hid, hw * cmid), 1015, 0.02).to(DEV)
+    got = hip_ops.ppo_encoder_backward(states, e1, e_bt, dx, t, b, w_lin, bn=None)
+    lib, h = L.load_library(), L.handle(DEV)
+    need = lib.adaf_ppo_encoder_backward_workspace_bytes(t, b, hw, cin, cmid, hid)
+    assert need == lib.adaf_ppo_encoder_bn_backward_workspace_bytes(t, b, hw, cin, cmid, hid, 0) and need > 0
+    ws = torch.empty(need // 4, device=DEV)
+    want = [torch.empty(s, device=DEV) for s in ((cmid, cin), (hid, cmid * hw), (hid,))]
+    L.check(lib.adaf_ppo_encoder_backward_f32(h, L.ptr(states), L.ptr(e1), L.ptr(e_bt), L.ptr(dx), t, b, hw, cin, cmid, hid, L.ptr(w_lin),
+                                              *(L.ptr(w) for w in want), L.ptr(ws), C.c_size_t(need), L.stream_ptr()), h)
+    assert len(got) == 3
+    for x, y in zip(got, want):
+        assert x.shape == y.shape and y.abs().max() > 0 and torch.equal(x, y)

@@ -463,3 +463,37 @@ def test_train_stage2_batch_sth(vd):
     assert torch.equal(runs[0][0], runs[1][0]) and torch.equal(runs[0][1], runs[1][1]) and torch.equal(runs[0][2], runs[1][2])
     for n in runs[0][3]:
         assert torch.equal(runs[0][3][n], runs[1][3][n]), n
+
+
+# ---- 7. one training core for both policies -------------------------------------------------------------------------------------------------
+def test_evaluate_backward_equals_train_backward():
+    """The continuous policy with BatchNorm (B = 3, T = 2) through the autograd class it shares with the discrete one
+    (policy_train.PolicyEvaluateFn): loss.backward() on evaluate's outputs gives the gradients of _train_backward for the same
+    d loss / d head, torch.equal for every parameter.  The entropy is a constant of the distribution: it takes no gradient."""
+    from adafocus_amd import policy_train
+    b, t, feat, hw, h, sigma = 3, 2, 1280, 7, 1024, 0.25
+    pol = _ppo(feat, hw, h, True, sigma, 1919).policy.to(DEV)
+    states = _rnd((t, b, feat, hw, hw), 53, 0.5).to(DEV)
+    actions = torch.rand(t, b, 2, generator=torch.Generator().manual_seed(5)).to(DEV)
+    g = [_rnd((t, b), 95 + i).to(DEV) for i in range(2)]
+    logprobs, values, entropy = pol.evaluate(states, actions)
+    assert type(logprobs.grad_fn) is policy_train.PolicyEvaluateFn._backward_cls and not entropy.requires_grad
+    pol.zero_grad(set_to_none=True)
+    ((logprobs * g[0]).sum() + (values * g[1]).sum()).backward()
+    with torch.no_grad():
+        fwd = pol._train_forward(pol._states_dense(states))
+        want = pol._train_backward(fwd, hip_ops.ppo_gauss_head_backward(fwd["head"], actions, sigma, *g))
+    assert set(want) == {n for n, _ in pol.named_parameters()} and len(want) == 15
+    for n, p in pol.named_parameters():
+        assert torch.equal(p.grad, want[n].reshape(p.shape)), n
+        assert p.grad.abs().max() > 0 or n == "state_encoder.4.bias", n       # (BatchNorm1d removes that bias: zero in real arithmetic)
+    # sum() hands the backward expanded (stride-0) upstream gradients: the head wrapper lays them out itself
+    logprobs, values, entropy = pol.evaluate(states, actions)
+    pol.zero_grad(set_to_none=True)
+    (logprobs.sum() + 0.5 * values.sum()).backward()
+    with torch.no_grad():
+        fwd = pol._train_forward(pol._states_dense(states))
+        dense = [torch.full((t, b), v, device=DEV) for v in (1.0, 0.5)]
+        want = pol._train_backward(fwd, hip_ops.ppo_gauss_head_backward(fwd["head"], actions, sigma, *dense))
+    for n, p in pol.named_parameters():
+        assert torch.equal(p.grad, want[n].reshape(p.shape)), n

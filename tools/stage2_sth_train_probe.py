@@ -224,8 +224,8 @@ def main():
         res["gru_heads_bwd_ms"] = round(timed(gru_bwd, a.steps, a.warmup), 4)
         dx = gru_bwd()[0]
         bn = tuple(fwd[k] for k in ("c1", "gamma1", "mean1", "invstd1", "l1", "gamma2", "mean2", "invstd2"))
-        res["encoder_bwd_ms"] = round(timed(lambda: hip_ops.ppo_encoder_bn_backward(fwd["states"], fwd["e1"], fwd["e_bt"], dx, 1, B,
-                                                                                   fwd["w_lin"], bn), a.steps, a.warmup), 4)
+        res["encoder_bwd_ms"] = round(timed(lambda: hip_ops.ppo_encoder_backward(fwd["states"], fwd["e1"], fwd["e_bt"], dx, 1, B,
+                                                                                fwd["w_lin"], bn), a.steps, a.warmup), 4)
     assert hip_ops.gru_scan_timeouts() == 0
     del fwd, dx, bn
 
