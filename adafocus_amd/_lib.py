@@ -19,35 +19,115 @@ MATH_F32, MATH_F32_SPLIT_BF16, MATH_F16 = 0, 1, 2
 DTYPE_F32, DTYPE_F16 = 0, 1
 CONV_TILES = 4
 
-# every symbol include/adafocus.h declares (tests check the library exports all of them)
-SYMBOLS = (
-    "adaf_version", "adaf_create", "adaf_destroy", "adaf_last_error", "adaf_device_cus", "adaf_set_gru_persistent", "adaf_set_conv_pos_major", "adaf_gru_scan_timeouts", "adaf_set_global_option", "adaf_get_global_option",
-    "adaf_crop_gather_f32", "adaf_conv2d_bn_act_f32", "adaf_conv2d_naive_f32", "adaf_pack_conv_weight_f32",
-    "adaf_fold_bn_f32", "adaf_maxpool3x3s2_f32", "adaf_global_avgpool_f32", "adaf_temporal_shift_f32",
-    "adaf_resnet50_create", "adaf_resnet50_destroy", "adaf_resnet50_set_param", "adaf_resnet50_finalize",
-    "adaf_resnet50_workspace_bytes", "adaf_resnet50_forward", "adaf_resnet50_map_size", "adaf_resnet50_forward_map", "adaf_resnet50_launch_count",
-    "adaf_resnet50_forward_profiled", "adaf_resnet50_set_tiles", "adaf_resnet50_set_math", "adaf_resnet50_set_fusion", "adaf_resnet50_set_latency_rows", "adaf_resnet50_set_shift_place", "adaf_resnet50_forward_frames", "adaf_gru_cls_workspace_bytes",
-    "adaf_gru_cls_forward_f32", "adaf_fc_meanpool_forward_f32", "adaf_copy2d_f32",
-    "adaf_pack_dw_weight_f32", "adaf_dwconv3x3_bn_act_f32", "adaf_mobilenetv2_create", "adaf_mobilenetv2_destroy",
-    "adaf_mobilenetv2_set_param", "adaf_mobilenetv2_finalize", "adaf_mobilenetv2_workspace_bytes",
-    "adaf_mobilenetv2_forward", "adaf_mobilenetv2_set_fusion", "adaf_grid_actions_f32", "adaf_gru_seq_forward_f32",
-    "adaf_crop_gather_nhwc4_f32", "adaf_ingest_u8_f32", "adaf_crop_resize_f32", "adaf_resize_nearest_f32",
-    "adaf_conv2d_bn_act_f16", "adaf_pack_conv_weight_f16", "adaf_cast_f32_f16", "adaf_dwconv3x3_bn_act_f16",
-    "adaf_pack_dw_weight_kxk_f32", "adaf_dwconv_same_workspace_bytes", "adaf_dwconv_same_bn_act", "adaf_se_gate_f32", "adaf_conv1x1_gated_bn",
-    "adaf_effnet_create", "adaf_effnet_destroy", "adaf_effnet_feature_dim", "adaf_effnet_block_count", "adaf_effnet_block_info",
-    "adaf_effnet_set_dtype", "adaf_effnet_set_fusion", "adaf_effnet_whole_blocks", "adaf_effnet_fused_expand_blocks", "adaf_effnet_set_param", "adaf_effnet_finalize", "adaf_effnet_workspace_bytes", "adaf_effnet_forward",
-    "adaf_gru_cls_train_workspace_bytes", "adaf_gru_cls_train_forward_f32", "adaf_gru_cls_backward_workspace_bytes", "adaf_gru_cls_backward_f32",
-    "adaf_ppo_sample_f32", "adaf_ppo_returns_f32", "adaf_ppo_head_workspace_bytes", "adaf_ppo_head_f32", "adaf_ppo_rows_transpose_f32",
-    "adaf_ppo_wenc_grad_workspace_bytes", "adaf_ppo_wenc_grad_f32", "adaf_ppo_encoder_backward_workspace_bytes", "adaf_ppo_encoder_backward_f32",
-    "adaf_ppo_sample_actions_f32", "adaf_ppo_rewards_f32",
-    "adaf_ppo_gauss_sample_f32", "adaf_ppo_gauss_head_f32", "adaf_bn_train_workspace_bytes", "adaf_bn_train_forward_f32", "adaf_bn_train_backward_f32",
-    "adaf_ppo_encoder_bn_backward_workspace_bytes", "adaf_ppo_encoder_bn_backward_f32",
-)
-
 
 class ConvParams(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("n", "h", "w", "cin", "cout", "kh", "kw", "stride", "pad", "act",
                                        "tsm_segments", "tsm_div", "ldx", "ldo", "ldr", "tile")]
+
+
+vp, ip, fp, sz, cp = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_char_p
+# Every symbol include/adafocus.h declares, once: name -> (restype, argtypes).  load_library() applies the table; the tests hold it to
+# the header parameter by parameter and to the library's exports.  (Symbols of experiment builds are declared by the tools that use them.)
+PROTOTYPES = {
+    "adaf_version": (ip, []),
+    "adaf_last_error": (cp, [vp]),
+    "adaf_create": (ip, [ip, C.POINTER(vp)]),
+    "adaf_destroy": (ip, [vp]),
+    "adaf_device_cus": (ip, [vp]),
+    "adaf_set_gru_persistent": (ip, [vp, ip]),
+    "adaf_set_conv_pos_major": (ip, [vp, ip]),
+    "adaf_gru_scan_timeouts": (ip, [vp, C.POINTER(C.c_uint)]),
+    "adaf_set_global_option": (ip, [cp, C.c_double]),
+    "adaf_get_global_option": (C.c_double, [cp]),
+    "adaf_crop_gather_f32": (ip, [vp, vp, ip, ip, ip, ip, vp, ip, ip, ip, vp, ip, vp, vp]),
+    "adaf_conv2d_bn_act_f32": (ip, [vp, C.POINTER(ConvParams), vp, vp, vp, vp, vp, vp, vp]),
+    "adaf_conv2d_naive_f32": (ip, [vp, C.POINTER(ConvParams), vp, vp, vp, vp, vp, vp, vp]),
+    "adaf_pack_conv_weight_f32": (ip, [vp, vp, ip, ip, ip, ip, ip, vp, vp]),
+    "adaf_fold_bn_f32": (ip, [vp, vp, vp, vp, vp, fp, ip, vp, vp, vp]),
+    "adaf_maxpool3x3s2_f32": (ip, [vp, vp, ip, ip, ip, ip, vp, vp]),
+    "adaf_global_avgpool_f32": (ip, [vp, vp, ip, ip, ip, vp, ip, vp]),
+    "adaf_temporal_shift_f32": (ip, [vp, vp, ip, ip, ip, ip, ip, ip, vp, vp]),
+    "adaf_resnet50_create": (ip, [vp, C.POINTER(vp)]),
+    "adaf_resnet50_destroy": (ip, [vp]),
+    "adaf_resnet50_set_param": (ip, [vp, cp, vp, sz]),
+    "adaf_resnet50_finalize": (ip, [vp, vp]),
+    "adaf_resnet50_workspace_bytes": (sz, [vp, ip, ip]),
+    "adaf_resnet50_forward": (ip, [vp, vp, ip, ip, ip, ip, vp, ip, vp, sz, vp]),
+    "adaf_resnet50_forward_frames": (ip, [vp, vp, ip, ip, ip, ip, vp, ip, ip, ip, ip, ip, vp, ip, vp, sz, vp]),
+    "adaf_resnet50_map_size": (ip, [ip]),
+    "adaf_resnet50_forward_map": (ip, [vp, vp, ip, ip, ip, ip, vp, vp, ip, vp, sz, vp]),
+    "adaf_resnet50_launch_count": (ip, [vp]),
+    "adaf_resnet50_forward_profiled": (ip, [vp, vp, ip, ip, ip, ip, vp, ip, vp, sz, vp, vp, vp, vp, vp]),
+    "adaf_resnet50_set_tiles": (ip, [vp, vp, ip]),
+    "adaf_resnet50_set_math": (ip, [vp, ip]),
+    "adaf_resnet50_set_fusion": (ip, [vp, ip]),
+    "adaf_resnet50_set_latency_rows": (ip, [vp, ip]),
+    "adaf_resnet50_set_shift_place": (ip, [vp, ip]),
+    "adaf_gru_cls_workspace_bytes": (sz, [ip, ip, ip]),
+    "adaf_gru_cls_forward_f32": (ip, [vp, vp, ip, ip, ip, ip, ip, ip, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "adaf_fc_meanpool_forward_f32": (ip, [vp, vp, ip, ip, ip, ip, vp, vp, vp, ip, vp, vp, sz, vp]),
+    "adaf_copy2d_f32": (ip, [vp, vp, ip, vp, ip, ip, ip, vp]),
+    "adaf_pack_dw_weight_f32": (ip, [vp, vp, ip, vp, vp]),
+    "adaf_dwconv3x3_bn_act_f32": (ip, [vp, vp, ip, ip, ip, ip, ip, vp, vp, vp, ip, vp, vp]),
+    "adaf_mobilenetv2_create": (ip, [vp, C.POINTER(vp)]),
+    "adaf_mobilenetv2_destroy": (ip, [vp]),
+    "adaf_mobilenetv2_set_param": (ip, [vp, cp, vp, sz]),
+    "adaf_mobilenetv2_finalize": (ip, [vp, vp]),
+    "adaf_mobilenetv2_workspace_bytes": (sz, [vp, ip, ip, ip]),
+    "adaf_mobilenetv2_forward": (ip, [vp, vp, ip, ip, ip, ip, vp, vp, ip, vp, sz, vp]),
+    "adaf_mobilenetv2_set_fusion": (ip, [vp, ip]),
+    "adaf_grid_actions_f32": (ip, [vp, vp, ip, ip, vp, vp, vp, vp]),
+    "adaf_gru_seq_forward_f32": (ip, [vp, vp, ip, ip, ip, ip, ip, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "adaf_gru_cls_train_workspace_bytes": (sz, [ip, ip, ip]),
+    "adaf_gru_cls_train_forward_f32": (ip, [vp, vp, ip, ip, ip, ip, ip, ip] + [vp] * 12 + [sz, vp]),
+    "adaf_gru_cls_backward_workspace_bytes": (sz, [ip, ip, ip, ip]),
+    "adaf_gru_cls_backward_f32": (ip, [vp, vp, ip, ip, ip, ip, ip, ip] + [vp] * 16 + [sz, vp]),
+    "adaf_ppo_sample_f32": (ip, [vp, vp, ip, ip, ip, vp, vp, vp, vp, vp]),
+    "adaf_ppo_sample_actions_f32": (ip, [vp, vp, ip, ip, ip, ip, vp, vp, vp, vp, vp, vp]),
+    "adaf_ppo_rewards_f32": (ip, [vp, vp, vp, vp, ip, ip, ip, ip, vp, vp, vp, vp]),
+    "adaf_ppo_returns_f32": (ip, [vp, vp, ip, ip, fp, vp, vp]),
+    "adaf_ppo_head_workspace_bytes": (sz, [ip, ip]),
+    "adaf_ppo_head_f32": (ip, [vp, vp, ip, ip, ip, ip, vp, vp, vp, fp] + [vp] * 9 + [sz, vp]),
+    "adaf_ppo_rows_transpose_f32": (ip, [vp, vp, ip, ip, ip, vp, vp]),
+    "adaf_ppo_wenc_grad_workspace_bytes": (sz, [ip, ip, ip]),
+    "adaf_ppo_wenc_grad_f32": (ip, [vp, vp, vp, vp, ip, ip, ip, ip, vp, vp, sz, vp]),
+    "adaf_ppo_encoder_backward_workspace_bytes": (sz, [ip, ip, ip, ip, ip, ip]),
+    "adaf_ppo_encoder_backward_f32": (ip, [vp, vp, vp, vp, vp, ip, ip, ip, ip, ip, ip, vp, vp, vp, vp, vp, sz, vp]),
+    "adaf_ppo_gauss_sample_f32": (ip, [vp, vp, vp, ip, fp, vp, vp, vp]),
+    "adaf_ppo_gauss_head_f32": (ip, [vp, vp, ip, ip, ip, vp, fp, vp, vp, fp] + [vp] * 8 + [sz, vp]),
+    "adaf_bn_train_workspace_bytes": (sz, [ip, ip]),
+    "adaf_bn_train_forward_f32": (ip, [vp, vp, ip, ip, vp, vp, fp, fp, vp, vp, ip, vp, vp, vp, vp, sz, vp]),
+    "adaf_bn_train_backward_f32": (ip, [vp, vp, vp, vp, ip, ip] + [vp] * 7 + [sz, vp]),
+    "adaf_ppo_encoder_bn_backward_workspace_bytes": (sz, [ip] * 7),
+    "adaf_ppo_encoder_bn_backward_f32": (ip, [vp] * 5 + [ip] * 6 + [vp] * 17 + [sz, vp]),
+    "adaf_crop_gather_nhwc4_f32": (ip, [vp, vp, ip, ip, ip, vp, ip, ip, ip, vp, vp, vp]),
+    "adaf_ingest_u8_f32": (ip, [vp, vp, ip, ip, ip, ip, C.POINTER(fp), C.POINTER(fp), vp, vp]),
+    "adaf_crop_resize_f32": (ip, [vp, vp, ip, ip, ip, ip, ip, vp, ip, ip, vp, ip, ip, vp, ip, vp, vp]),
+    "adaf_resize_nearest_f32": (ip, [vp, vp, ip, ip, ip, ip, ip, ip, ip, vp, ip, vp]),
+    "adaf_conv2d_bn_act_f16": (ip, [vp, C.POINTER(ConvParams), vp, ip, vp, vp, vp, vp, vp, ip, vp]),
+    "adaf_pack_conv_weight_f16": (ip, [vp, vp, ip, ip, ip, ip, ip, vp, vp]),
+    "adaf_cast_f32_f16": (ip, [vp, vp, sz, vp, ip, vp]),
+    "adaf_dwconv3x3_bn_act_f16": (ip, [vp, vp, ip, ip, ip, ip, ip, vp, vp, vp, ip, vp, vp]),
+    "adaf_pack_dw_weight_kxk_f32": (ip, [vp, vp, ip, ip, vp, vp]),
+    "adaf_dwconv_same_workspace_bytes": (sz, [ip, ip, ip, ip, ip, ip, ip]),
+    "adaf_dwconv_same_bn_act": (ip, [vp, vp, ip, ip, ip, ip, ip, ip, ip, vp, vp, vp, ip, vp, vp, vp, sz, vp]),
+    "adaf_se_gate_f32": (ip, [vp, vp, ip, ip, vp, vp, ip, vp, vp, vp, vp]),
+    "adaf_conv1x1_gated_bn": (ip, [vp, vp, ip, ip, ip, ip, vp, vp, ip, vp, vp, vp, vp, vp]),
+    "adaf_effnet_create": (ip, [vp, fp, fp, C.POINTER(vp)]),
+    "adaf_effnet_destroy": (ip, [vp]),
+    "adaf_effnet_feature_dim": (ip, [vp]),
+    "adaf_effnet_block_count": (ip, [vp]),
+    "adaf_effnet_block_info": (ip, [vp, ip, C.POINTER(ip)]),
+    "adaf_effnet_set_dtype": (ip, [vp, ip]),
+    "adaf_effnet_set_fusion": (ip, [vp, ip]),
+    "adaf_effnet_whole_blocks": (ip, [vp, ip, ip]),
+    "adaf_effnet_fused_expand_blocks": (ip, [vp, ip, ip]),
+    "adaf_effnet_set_param": (ip, [vp, cp, vp, sz]),
+    "adaf_effnet_finalize": (ip, [vp, vp]),
+    "adaf_effnet_workspace_bytes": (sz, [vp, ip, ip, ip]),
+    "adaf_effnet_forward": (ip, [vp, vp, ip, ip, ip, ip, vp, vp, vp, ip, vp, sz, vp]),
+}
+SYMBOLS = tuple(PROTOTYPES)
 
 
 class AdafError(RuntimeError):
@@ -66,118 +146,9 @@ def load_library():
         raise AdafError("HIP extension not built: %s is missing (run `python -c 'import __graft_entry__ as g; "
                         "g.build()'` or `make -C adafocus_amd/csrc`)" % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    vp, ip, fp = C.c_void_p, C.c_int, C.c_float
-    lib.adaf_last_error.restype = C.c_char_p
-    lib.adaf_last_error.argtypes = [vp]
-    lib.adaf_create.argtypes = [ip, C.POINTER(vp)]
-    lib.adaf_destroy.argtypes = [vp]
-    lib.adaf_device_cus.argtypes = [vp]
-    lib.adaf_set_gru_persistent.argtypes = [vp, ip]
-    lib.adaf_set_conv_pos_major.argtypes = [vp, ip]
-    lib.adaf_gru_scan_timeouts.argtypes = [vp, C.POINTER(C.c_uint)]
-    lib.adaf_set_global_option.argtypes = [C.c_char_p, C.c_double]
-    lib.adaf_get_global_option.argtypes = [C.c_char_p]
-    lib.adaf_get_global_option.restype = C.c_double
-    lib.adaf_crop_gather_f32.argtypes = [vp, vp, ip, ip, ip, ip, vp, ip, ip, ip, vp, ip, vp, vp]
-    for name in ("adaf_conv2d_bn_act_f32", "adaf_conv2d_naive_f32"):
-        getattr(lib, name).argtypes = [vp, C.POINTER(ConvParams), vp, vp, vp, vp, vp, vp, vp]
-    lib.adaf_pack_conv_weight_f32.argtypes = [vp, vp, ip, ip, ip, ip, ip, vp, vp]
-    lib.adaf_fold_bn_f32.argtypes = [vp, vp, vp, vp, vp, fp, ip, vp, vp, vp]
-    lib.adaf_maxpool3x3s2_f32.argtypes = [vp, vp, ip, ip, ip, ip, vp, vp]
-    lib.adaf_global_avgpool_f32.argtypes = [vp, vp, ip, ip, ip, vp, ip, vp]
-    lib.adaf_temporal_shift_f32.argtypes = [vp, vp, ip, ip, ip, ip, ip, ip, vp, vp]
-    lib.adaf_resnet50_create.argtypes = [vp, C.POINTER(vp)]
-    lib.adaf_resnet50_destroy.argtypes = [vp]
-    lib.adaf_resnet50_set_param.argtypes = [vp, C.c_char_p, vp, C.c_size_t]
-    lib.adaf_resnet50_finalize.argtypes = [vp, vp]
-    lib.adaf_resnet50_workspace_bytes.restype = C.c_size_t
-    lib.adaf_resnet50_workspace_bytes.argtypes = [vp, ip, ip]
-    lib.adaf_resnet50_forward.argtypes = [vp, vp, ip, ip, ip, ip, vp, ip, vp, C.c_size_t, vp]
-    lib.adaf_resnet50_forward_frames.argtypes = [vp, vp, ip, ip, ip, ip, vp, ip, ip, ip, ip, ip, vp, ip, vp, C.c_size_t, vp]
-    lib.adaf_resnet50_map_size.argtypes = [ip]
-    lib.adaf_resnet50_forward_map.argtypes = [vp, vp, ip, ip, ip, ip, vp, vp, ip, vp, C.c_size_t, vp]
-    lib.adaf_resnet50_launch_count.argtypes = [vp]
-    lib.adaf_resnet50_forward_profiled.argtypes = [vp, vp, ip, ip, ip, ip, vp, ip, vp, C.c_size_t, vp, vp, vp, vp, vp]
-    lib.adaf_resnet50_set_tiles.argtypes = [vp, vp, ip]
-    lib.adaf_resnet50_set_math.argtypes = [vp, ip]
-    lib.adaf_resnet50_set_fusion.argtypes = [vp, ip]
-    lib.adaf_resnet50_set_latency_rows.argtypes = [vp, ip]
-    lib.adaf_resnet50_set_shift_place.argtypes = [vp, ip]
-    lib.adaf_gru_cls_workspace_bytes.restype = C.c_size_t
-    lib.adaf_gru_cls_workspace_bytes.argtypes = [ip, ip, ip]
-    lib.adaf_gru_cls_forward_f32.argtypes = [vp, vp, ip, ip, ip, ip, ip, ip, vp, vp, vp, vp, vp, vp, vp, vp, vp,
-                                             C.c_size_t, vp]
-    lib.adaf_fc_meanpool_forward_f32.argtypes = [vp, vp, ip, ip, ip, ip, vp, vp, vp, ip, vp, vp, C.c_size_t, vp]
-    lib.adaf_copy2d_f32.argtypes = [vp, vp, ip, vp, ip, ip, ip, vp]
-    lib.adaf_pack_dw_weight_f32.argtypes = [vp, vp, ip, vp, vp]
-    lib.adaf_dwconv3x3_bn_act_f32.argtypes = [vp, vp, ip, ip, ip, ip, ip, vp, vp, vp, ip, vp, vp]
-    lib.adaf_mobilenetv2_create.argtypes = [vp, C.POINTER(vp)]
-    lib.adaf_mobilenetv2_destroy.argtypes = [vp]
-    lib.adaf_mobilenetv2_set_param.argtypes = [vp, C.c_char_p, vp, C.c_size_t]
-    lib.adaf_mobilenetv2_finalize.argtypes = [vp, vp]
-    lib.adaf_mobilenetv2_workspace_bytes.restype = C.c_size_t
-    lib.adaf_mobilenetv2_workspace_bytes.argtypes = [vp, ip, ip, ip]
-    lib.adaf_mobilenetv2_forward.argtypes = [vp, vp, ip, ip, ip, ip, vp, vp, ip, vp, C.c_size_t, vp]
-    lib.adaf_mobilenetv2_set_fusion.argtypes = [vp, ip]
-    lib.adaf_grid_actions_f32.argtypes = [vp, vp, ip, ip, vp, vp, vp, vp]
-    lib.adaf_gru_seq_forward_f32.argtypes = [vp, vp, ip, ip, ip, ip, ip, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
-    lib.adaf_gru_cls_train_workspace_bytes.restype = C.c_size_t
-    lib.adaf_gru_cls_train_workspace_bytes.argtypes = [ip, ip, ip]
-    lib.adaf_gru_cls_train_forward_f32.argtypes = [vp, vp, ip, ip, ip, ip, ip, ip] + [vp] * 12 + [C.c_size_t, vp]
-    lib.adaf_gru_cls_backward_workspace_bytes.restype = C.c_size_t
-    lib.adaf_gru_cls_backward_workspace_bytes.argtypes = [ip, ip, ip, ip]
-    lib.adaf_gru_cls_backward_f32.argtypes = [vp, vp, ip, ip, ip, ip, ip, ip] + [vp] * 16 + [C.c_size_t, vp]
-    lib.adaf_ppo_sample_f32.argtypes = [vp, vp, ip, ip, ip, vp, vp, vp, vp, vp]
-    lib.adaf_ppo_sample_actions_f32.argtypes = [vp, vp, ip, ip, ip, ip, vp, vp, vp, vp, vp, vp]
-    lib.adaf_ppo_rewards_f32.argtypes = [vp, vp, vp, vp, ip, ip, ip, ip, vp, vp, vp, vp]
-    lib.adaf_ppo_returns_f32.argtypes = [vp, vp, ip, ip, fp, vp, vp]
-    lib.adaf_ppo_head_workspace_bytes.restype = C.c_size_t
-    lib.adaf_ppo_head_workspace_bytes.argtypes = [ip, ip]
-    lib.adaf_ppo_head_f32.argtypes = [vp, vp, ip, ip, ip, ip, vp, vp, vp, fp] + [vp] * 9 + [C.c_size_t, vp]
-    lib.adaf_ppo_rows_transpose_f32.argtypes = [vp, vp, ip, ip, ip, vp, vp]
-    lib.adaf_ppo_wenc_grad_workspace_bytes.restype = C.c_size_t
-    lib.adaf_ppo_wenc_grad_workspace_bytes.argtypes = [ip, ip, ip]
-    lib.adaf_ppo_wenc_grad_f32.argtypes = [vp, vp, vp, vp, ip, ip, ip, ip, vp, vp, C.c_size_t, vp]
-    lib.adaf_ppo_encoder_backward_workspace_bytes.restype = C.c_size_t
-    lib.adaf_ppo_encoder_backward_workspace_bytes.argtypes = [ip, ip, ip, ip, ip, ip]
-    lib.adaf_ppo_encoder_backward_f32.argtypes = [vp, vp, vp, vp, vp, ip, ip, ip, ip, ip, ip, vp, vp, vp, vp, vp, C.c_size_t, vp]
-    lib.adaf_ppo_gauss_sample_f32.argtypes = [vp, vp, vp, ip, fp, vp, vp, vp]
-    lib.adaf_ppo_gauss_head_f32.argtypes = [vp, vp, ip, ip, ip, vp, fp, vp, vp, fp] + [vp] * 8 + [C.c_size_t, vp]
-    lib.adaf_bn_train_workspace_bytes.restype = C.c_size_t
-    lib.adaf_bn_train_workspace_bytes.argtypes = [ip, ip]
-    lib.adaf_bn_train_forward_f32.argtypes = [vp, vp, ip, ip, vp, vp, fp, fp, vp, vp, ip, vp, vp, vp, vp, C.c_size_t, vp]
-    lib.adaf_bn_train_backward_f32.argtypes = [vp, vp, vp, vp, ip, ip] + [vp] * 7 + [C.c_size_t, vp]
-    lib.adaf_ppo_encoder_bn_backward_workspace_bytes.restype = C.c_size_t
-    lib.adaf_ppo_encoder_bn_backward_workspace_bytes.argtypes = [ip] * 7
-    lib.adaf_ppo_encoder_bn_backward_f32.argtypes = [vp] * 5 + [ip] * 6 + [vp] * 17 + [C.c_size_t, vp]
-    lib.adaf_crop_gather_nhwc4_f32.argtypes = [vp, vp, ip, ip, ip, vp, ip, ip, ip, vp, vp, vp]
-    lib.adaf_ingest_u8_f32.argtypes = [vp, vp, ip, ip, ip, ip, C.POINTER(C.c_float), C.POINTER(C.c_float), vp, vp]
-    lib.adaf_crop_resize_f32.argtypes = [vp, vp, ip, ip, ip, ip, ip, vp, ip, ip, vp, ip, ip, vp, ip, vp, vp]
-    lib.adaf_resize_nearest_f32.argtypes = [vp, vp, ip, ip, ip, ip, ip, ip, ip, vp, ip, vp]
-    lib.adaf_conv2d_bn_act_f16.argtypes = [vp, C.POINTER(ConvParams), vp, ip, vp, vp, vp, vp, vp, ip, vp]
-    lib.adaf_pack_conv_weight_f16.argtypes = [vp, vp, ip, ip, ip, ip, ip, vp, vp]
-    lib.adaf_cast_f32_f16.argtypes = [vp, vp, C.c_size_t, vp, ip, vp]
-    lib.adaf_dwconv3x3_bn_act_f16.argtypes = [vp, vp, ip, ip, ip, ip, ip, vp, vp, vp, ip, vp, vp]
-    lib.adaf_pack_dw_weight_kxk_f32.argtypes = [vp, vp, ip, ip, vp, vp]
-    lib.adaf_dwconv_same_workspace_bytes.restype = C.c_size_t
-    lib.adaf_dwconv_same_workspace_bytes.argtypes = [ip, ip, ip, ip, ip, ip, ip]
-    lib.adaf_dwconv_same_bn_act.argtypes = [vp, vp, ip, ip, ip, ip, ip, ip, ip, vp, vp, vp, ip, vp, vp, vp, C.c_size_t, vp]
-    lib.adaf_se_gate_f32.argtypes = [vp, vp, ip, ip, vp, vp, ip, vp, vp, vp, vp]
-    lib.adaf_conv1x1_gated_bn.argtypes = [vp, vp, ip, ip, ip, ip, vp, vp, ip, vp, vp, vp, vp, vp]
-    lib.adaf_effnet_create.argtypes = [vp, fp, fp, C.POINTER(vp)]
-    lib.adaf_effnet_destroy.argtypes = [vp]
-    lib.adaf_effnet_feature_dim.argtypes = [vp]
-    lib.adaf_effnet_block_count.argtypes = [vp]
-    lib.adaf_effnet_block_info.argtypes = [vp, ip, C.POINTER(C.c_int)]
-    lib.adaf_effnet_set_dtype.argtypes = [vp, ip]
-    lib.adaf_effnet_set_fusion.argtypes = [vp, ip]
-    lib.adaf_effnet_whole_blocks.argtypes = [vp, ip, ip]
-    lib.adaf_effnet_fused_expand_blocks.argtypes = [vp, ip, ip]
-    lib.adaf_effnet_set_param.argtypes = [vp, C.c_char_p, vp, C.c_size_t]
-    lib.adaf_effnet_finalize.argtypes = [vp, vp]
-    lib.adaf_effnet_workspace_bytes.restype = C.c_size_t
-    lib.adaf_effnet_workspace_bytes.argtypes = [vp, ip, ip, ip]
-    lib.adaf_effnet_forward.argtypes = [vp, vp, ip, ip, ip, ip, vp, vp, vp, ip, vp, C.c_size_t, vp]
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
     return lib
 
@@ -256,16 +227,22 @@ def on_current_device(*tensors):
 
 
 def ptr(t):
+    """The device pointer of t (None: NULL).  It holds NO reference to t: whoever calls this keeps t alive until the C call has returned
+    (hip_ops._call does, for every launch of the package)."""
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
-def need_gpu_f32(*tensors):
-    """Product-path guard: the HIP path is the only path."""
+def need_gpu(*tensors, f32=False):
+    """Product-path guard: the HIP path is the only path.  Every tensor (None is skipped) lives on the current GPU; f32: and is fp32."""
     for t in tensors:
         if t is None:
             continue
         if not t.is_cuda:
             raise AdafError("adafocus_amd runs on MI355X only: got a %s tensor (no CPU fallback exists)" % t.device)
-        if t.dtype != torch.float32:
+        if f32 and t.dtype != torch.float32:
             raise AdafError("adafocus_amd computes in fp32: got %s" % t.dtype)
     on_current_device(*tensors)
+
+
+def need_gpu_f32(*tensors):
+    need_gpu(*tensors, f32=True)

@@ -146,7 +146,7 @@ class GFV(nn.Module):
         """`input_prime = F.interpolate(images, (glance_size, glance_size))` of the reference's drivers (nearest mode,
         ACT/main_dist.py:331-332): the identity when glance_size equals the frame size (every shipped config), else one
         bit-exact resize launch.  images (B, T*3, H, W) planar or (B*T, H, W, 4) pixel-major; same layout back."""
-        if images.shape[-1] == 4 and images.shape[1] != 3:
+        if hip_ops.pixel_major(images):
             if images.shape[1] == self.glance_size:
                 return images
             return hip_ops.resize_nearest(images, self.glance_size, hip_ops.LAYOUT_NHWC4)
@@ -241,7 +241,7 @@ class GFV(nn.Module):
             # the gather rides in the trunk's first launch (adaf_resnet50_forward_frames): no patch tensor between get_patch and the local CNN
             net.features_from_frames(frames, actions, self.patch_size, out=flat[:, gdim:])
         else:
-            if frames.shape[-1] == 4 and frames.shape[1] != 3:
+            if hip_ops.pixel_major(frames):
                 patches = hip_ops.crop_gather_nhwc4(frames, actions, self.patch_size)
             else:
                 patches = get_patch_nhwc4(frames, actions, self.patch_size)

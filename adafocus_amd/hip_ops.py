@@ -13,8 +13,56 @@ from ._lib import MATH_F16, MATH_F32, MATH_F32_SPLIT_BF16  # noqa: F401
 from ._lib import DTYPE_F32, DTYPE_F16  # noqa: F401
 
 
-def _h(t):
-    return L.handle(t.device)
+def _ptrs(args):
+    return [L.ptr(a) if isinstance(a, torch.Tensor) else a for a in args]
+
+
+def _call(sym, where, *args, stream=True):
+    """Every handle-first C-ABI call: sym(handle of `where` (a tensor or a device), *args[, the current stream]), return code checked.
+    Tensors among `args` go as their data pointers, None as NULL, Python numbers and ctypes values as they are (the prototypes of
+    _lib.PROTOTYPES convert them).
+
+    THE OPERAND RULE.  L.ptr holds no reference, so a tensor must stay referenced until the C call has returned: a temporary that dies
+    earlier hands its block back to the caching allocator, and the next temporary made on the same stream gets that very block -- two
+    pointers to one buffer, and no error.  `args` is that reference.  So wrappers pass tensors here, temporaries such as
+    `t.contiguous()` or `_dense(t)` included, and never call L.ptr on an expression (tests/test_abi.py walks this file for it).  Once
+    the call has returned the launch is enqueued, and the allocator reuses a freed block in stream order only."""
+    h = L.handle(where.device if isinstance(where, torch.Tensor) else where)
+    L.check(getattr(L.load_library(), sym)(h, *_ptrs(args), *((L.stream_ptr(),) if stream else ())), h)
+
+
+def _dense(t):
+    return None if t is None else t.contiguous()
+
+
+def _workspace(query, device, *extents):
+    """-> (scratch tensor, the bytes `query`(*extents) asks for).  The tensor has 16 bytes at least, so it is a pointer even when
+    the call needs none."""
+    need = getattr(L.load_library(), query)(*extents)
+    return torch.empty(max((need + 3) // 4, 4), device=device, dtype=torch.float32), need
+
+
+def _gru_x(x):
+    """The GRU entry points read x (B,T,F) through its row stride: unit feature stride and a batch stride of T rows, else a copy."""
+    return x if x.stride(2) == 1 and x.stride(0) == x.shape[1] * x.stride(1) else x.contiguous()
+
+
+def pixel_major(frames):
+    """frames (N,H,W,4) pixel-major rather than (N,C,H,W) planar (four-pixel-wide RGB planes are planar)."""
+    return frames.shape[-1] == 4 and frames.shape[1] != 3
+
+
+def _frame_geometry(frames):
+    """-> (layout, n, channels, h, w) of planar or pixel-major frames."""
+    if pixel_major(frames):
+        n, hh, ww, _ = frames.shape
+        return LAYOUT_NHWC4, n, 3, hh, ww
+    n, c, hh, ww = frames.shape
+    return LAYOUT_NCHW, n, c, hh, ww
+
+
+def _current(device):
+    return torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
 
 
 def crop_gather(frames, actions, patch, frames_per_action=1, layout=LAYOUT_NCHW, return_coords=False):
@@ -35,10 +83,7 @@ def crop_gather(frames, actions, patch, frames_per_action=1, layout=LAYOUT_NCHW,
     else:
         out = torch.empty((n, p, p, 4), device=frames.device, dtype=torch.float32)
     coords = torch.empty((actions.shape[0], 2), device=frames.device, dtype=torch.int32) if return_coords else None
-    h = _h(frames)
-    L.check(L.load_library().adaf_crop_gather_f32(h, L.ptr(frames), n, c, hh, ww, L.ptr(actions), actions.shape[0],
-                                                  int(frames_per_action), p, L.ptr(out), layout, L.ptr(coords),
-                                                  L.stream_ptr()), h)
+    _call("adaf_crop_gather_f32", frames, frames, n, c, hh, ww, actions, actions.shape[0], int(frames_per_action), p, out, layout, coords)
     return (out, coords) if return_coords else out
 
 
@@ -49,8 +94,7 @@ def pack_conv_weight(w_oihw, cin_pad=None):
     co, ci, kh, kw = w.shape
     cp = cin_pad or ((ci + 3) // 4 * 4)
     out = torch.empty((co, kh, kw, cp), device=w.device, dtype=torch.float32)
-    h = _h(w)
-    L.check(L.load_library().adaf_pack_conv_weight_f32(h, L.ptr(w), co, ci, kh, kw, cp, L.ptr(out), L.stream_ptr()), h)
+    _call("adaf_pack_conv_weight_f32", w, w, co, ci, kh, kw, cp, out)
     return out
 
 
@@ -59,10 +103,7 @@ def fold_bn(gamma, beta, mean, var, eps=1e-5):
     c = gamma.numel()
     scale = torch.empty(c, device=gamma.device, dtype=torch.float32)
     bias = torch.empty(c, device=gamma.device, dtype=torch.float32)
-    h = _h(gamma)
-    L.check(L.load_library().adaf_fold_bn_f32(h, L.ptr(gamma.contiguous()), L.ptr(beta.contiguous()),
-                                              L.ptr(mean.contiguous()), L.ptr(var.contiguous()), C.c_float(eps), c,
-                                              L.ptr(scale), L.ptr(bias), L.stream_ptr()), h)
+    _call("adaf_fold_bn_f32", gamma, gamma.contiguous(), beta.contiguous(), mean.contiguous(), var.contiguous(), float(eps), c, scale, bias)
     return scale, bias
 
 
@@ -85,11 +126,7 @@ def conv2d_bn_act(x, w_ohwi, scale=None, bias=None, residual=None, stride=1, pad
         residual = residual.contiguous()
     p = L.ConvParams(n=n, h=hh, w=ww, cin=cin, cout=cout, kh=kh, kw=kw, stride=stride, pad=pad, act=act,
                      tsm_segments=tsm_segments, tsm_div=tsm_div, ldx=0, ldo=0, ldr=0, tile=tile)
-    h = _h(x)
-    lib = L.load_library()
-    fn = lib.adaf_conv2d_naive_f32 if naive else lib.adaf_conv2d_bn_act_f32
-    L.check(fn(h, C.byref(p), L.ptr(x), L.ptr(w_ohwi), L.ptr(scale), L.ptr(bias), L.ptr(residual), L.ptr(out),
-               L.stream_ptr()), h)
+    _call("adaf_conv2d_naive_f32" if naive else "adaf_conv2d_bn_act_f32", x, C.byref(p), x, w_ohwi, scale, bias, residual, out)
     return out
 
 
@@ -106,8 +143,7 @@ def maxpool3x3s2(x):
     x = x.contiguous()
     n, hh, ww, c = x.shape
     out = torch.empty((n, (hh - 1) // 2 + 1, (ww - 1) // 2 + 1, c), device=x.device, dtype=torch.float32)
-    h = _h(x)
-    L.check(L.load_library().adaf_maxpool3x3s2_f32(h, L.ptr(x), n, hh, ww, c, L.ptr(out), L.stream_ptr()), h)
+    _call("adaf_maxpool3x3s2_f32", x, x, n, hh, ww, c, out)
     return out
 
 
@@ -116,8 +152,7 @@ def global_avgpool(x):
     x = x.contiguous()
     n, hh, ww, c = x.shape
     out = torch.empty((n, c), device=x.device, dtype=torch.float32)
-    h = _h(x)
-    L.check(L.load_library().adaf_global_avgpool_f32(h, L.ptr(x), n, hh * ww, c, L.ptr(out), c, L.stream_ptr()), h)
+    _call("adaf_global_avgpool_f32", x, x, n, hh * ww, c, out, c)
     return out
 
 
@@ -130,9 +165,7 @@ def temporal_shift(x, n_segment, fold_div, layout=LAYOUT_NCHW):
     else:
         nt, hh, ww, c = x.shape
     out = torch.empty_like(x)
-    h = _h(x)
-    L.check(L.load_library().adaf_temporal_shift_f32(h, L.ptr(x), nt, c, hh * ww, int(n_segment), int(fold_div), layout,
-                                                     L.ptr(out), L.stream_ptr()), h)
+    _call("adaf_temporal_shift_f32", x, x, nt, c, hh * ww, int(n_segment), int(fold_div), layout, out)
     return out
 
 
@@ -141,19 +174,13 @@ def gru_cls_forward(x, w_ih, w_hh, b_ih, b_hh, fc_w, fc_b):
     strided view with stride 1) -> (logits (B*T,C), last (B,C))."""
     L.need_gpu_f32(x, w_ih, w_hh, b_ih, b_hh, fc_w, fc_b)
     b, t, f = x.shape
-    if x.stride(2) != 1 or x.stride(0) != t * x.stride(1):
-        x = x.contiguous()
+    x = _gru_x(x)
     hid, ncls = w_hh.shape[1], fc_w.shape[0]
-    lib = L.load_library()
-    ws_bytes = lib.adaf_gru_cls_workspace_bytes(b, t, hid)
-    ws = torch.empty(max(ws_bytes // 4, 1), device=x.device, dtype=torch.float32)
+    ws, ws_bytes = _workspace("adaf_gru_cls_workspace_bytes", x.device, b, t, hid)
     logits = torch.empty((b * t, ncls), device=x.device, dtype=torch.float32)
     last = torch.empty((b, ncls), device=x.device, dtype=torch.float32)
-    h = _h(x)
-    L.check(lib.adaf_gru_cls_forward_f32(h, L.ptr(x), x.stride(1), b, t, f, hid, ncls, L.ptr(w_ih.contiguous()),
-                                         L.ptr(w_hh.contiguous()), L.ptr(b_ih.contiguous()), L.ptr(b_hh.contiguous()),
-                                         L.ptr(fc_w.contiguous()), L.ptr(fc_b.contiguous()), L.ptr(logits), L.ptr(last),
-                                         L.ptr(ws), ws_bytes, L.stream_ptr()), h)
+    _call("adaf_gru_cls_forward_f32", x, x, x.stride(1), b, t, f, hid, ncls, w_ih.contiguous(), w_hh.contiguous(), b_ih.contiguous(),
+          b_hh.contiguous(), fc_w.contiguous(), fc_b.contiguous(), logits, last, ws, ws_bytes)
     return logits, last
 
 
@@ -162,22 +189,14 @@ def gru_cls_train_forward(x, w_ih, w_hh, b_ih, b_hh, fc_w, fc_b, mask=None):
     (0 or 1/(1-p)) or None -> (logits (B*T,C), gi (B*T,3H), hs (B,T,H)); gi and hs are what gru_cls_backward needs."""
     L.need_gpu_f32(x, w_ih, w_hh, b_ih, b_hh, fc_w, fc_b, mask)
     b, t, f = x.shape
-    if x.stride(2) != 1 or x.stride(0) != t * x.stride(1):
-        x = x.contiguous()
+    x = _gru_x(x)
     hid, ncls = w_hh.shape[1], fc_w.shape[0]
-    if mask is not None:
-        mask = mask.contiguous()
-    lib = L.load_library()
-    ws_bytes = lib.adaf_gru_cls_train_workspace_bytes(b, t, hid)
-    ws = torch.empty(max(ws_bytes // 4, 1), device=x.device, dtype=torch.float32)
+    ws, ws_bytes = _workspace("adaf_gru_cls_train_workspace_bytes", x.device, b, t, hid)
     gi = torch.empty((b * t, 3 * hid), device=x.device, dtype=torch.float32)
     hs = torch.empty((b, t, hid), device=x.device, dtype=torch.float32)
     logits = torch.empty((b * t, ncls), device=x.device, dtype=torch.float32)
-    h = _h(x)
-    L.check(lib.adaf_gru_cls_train_forward_f32(h, L.ptr(x), x.stride(1), b, t, f, hid, ncls, L.ptr(w_ih.contiguous()),
-                                               L.ptr(w_hh.contiguous()), L.ptr(b_ih.contiguous()), L.ptr(b_hh.contiguous()),
-                                               L.ptr(fc_w.contiguous()), L.ptr(fc_b.contiguous()), L.ptr(mask), L.ptr(gi), L.ptr(hs),
-                                               L.ptr(logits), None, L.ptr(ws), ws_bytes, L.stream_ptr()), h)
+    _call("adaf_gru_cls_train_forward_f32", x, x, x.stride(1), b, t, f, hid, ncls, w_ih.contiguous(), w_hh.contiguous(), b_ih.contiguous(),
+          b_hh.contiguous(), fc_w.contiguous(), fc_b.contiguous(), _dense(mask), gi, hs, logits, None, ws, ws_bytes)
     return logits, gi, hs
 
 
@@ -186,15 +205,9 @@ def gru_cls_backward(x, w_ih, w_hh, b_hh, fc_w, gi, hs, mask, dlogits, want_dx=T
     mask).  Returns (dx (B,T,F) or None, dW_ih, dW_hh, db_ih, db_hh, dW_fc, db_fc); deterministic (same inputs, same bits)."""
     L.need_gpu_f32(x, w_ih, w_hh, b_hh, fc_w, gi, hs, mask, dlogits)
     b, t, f = x.shape
-    if x.stride(2) != 1 or x.stride(0) != t * x.stride(1):
-        x = x.contiguous()
+    x = _gru_x(x)
     hid, ncls = w_hh.shape[1], fc_w.shape[0]
-    dlogits = dlogits.contiguous()
-    if mask is not None:
-        mask = mask.contiguous()
-    lib = L.load_library()
-    ws_bytes = lib.adaf_gru_cls_backward_workspace_bytes(b, t, hid, ncls)
-    ws = torch.empty(max(ws_bytes // 4, 1), device=x.device, dtype=torch.float32)
+    ws, ws_bytes = _workspace("adaf_gru_cls_backward_workspace_bytes", x.device, b, t, hid, ncls)
     dev, fp = x.device, torch.float32
     dx = torch.empty((b, t, f), device=dev, dtype=fp) if want_dx else None
     dw_ih = torch.empty((3 * hid, f), device=dev, dtype=fp)
@@ -203,11 +216,8 @@ def gru_cls_backward(x, w_ih, w_hh, b_hh, fc_w, gi, hs, mask, dlogits, want_dx=T
     db_hh = torch.empty((3 * hid,), device=dev, dtype=fp)
     dw_fc = torch.empty((ncls, hid), device=dev, dtype=fp)
     db_fc = torch.empty((ncls,), device=dev, dtype=fp)
-    h = _h(x)
-    L.check(lib.adaf_gru_cls_backward_f32(h, L.ptr(x), x.stride(1), b, t, f, hid, ncls, L.ptr(w_ih.contiguous()), L.ptr(w_hh.contiguous()),
-                                          L.ptr(b_hh.contiguous()), L.ptr(fc_w.contiguous()), L.ptr(gi), L.ptr(hs), L.ptr(mask),
-                                          L.ptr(dlogits), L.ptr(dx), L.ptr(dw_ih), L.ptr(dw_hh), L.ptr(db_ih), L.ptr(db_hh), L.ptr(dw_fc),
-                                          L.ptr(db_fc), L.ptr(ws), ws_bytes, L.stream_ptr()), h)
+    _call("adaf_gru_cls_backward_f32", x, x, x.stride(1), b, t, f, hid, ncls, w_ih.contiguous(), w_hh.contiguous(), b_hh.contiguous(),
+          fc_w.contiguous(), gi.contiguous(), hs.contiguous(), _dense(mask), dlogits.contiguous(), dx, dw_ih, dw_hh, db_ih, db_hh, dw_fc, db_fc, ws, ws_bytes)
     return dx, dw_ih, dw_hh, db_ih, db_hh, dw_fc, db_fc
 
 
@@ -247,9 +257,7 @@ def ppo_sample(logits, uniforms, want_probs=False):
     action = torch.empty((rows,), device=logits.device, dtype=torch.int64)
     logprob = torch.empty((rows,), device=logits.device, dtype=torch.float32)
     probs = torch.empty((rows, a), device=logits.device, dtype=torch.float32) if want_probs else None
-    h = _h(logits)
-    L.check(L.load_library().adaf_ppo_sample_f32(h, L.ptr(logits), a, rows, a, L.ptr(uniforms), L.ptr(action), L.ptr(logprob), L.ptr(probs),
-                                                 L.stream_ptr()), h)
+    _call("adaf_ppo_sample_f32", logits, logits, a, rows, a, uniforms, action, logprob, probs)
     return (action, logprob, probs) if want_probs else (action, logprob)
 
 
@@ -272,10 +280,7 @@ def ppo_sample_actions(logits, uniforms, table=None):
     action = torch.empty((t, b), device=logits.device, dtype=torch.int64)
     logprob = torch.empty((t, b), device=logits.device, dtype=torch.float32)
     coords = torch.empty((rows, 2), device=logits.device, dtype=torch.float32) if table is not None else None
-    h = _h(logits)
-    L.check(L.load_library().adaf_ppo_sample_actions_f32(h, L.ptr(logits), logits.stride(0), t, b, a, L.ptr(uniforms),
-                                                         L.ptr(None if table is None else table.contiguous()), L.ptr(action), L.ptr(logprob),
-                                                         L.ptr(coords), L.stream_ptr()), h)
+    _call("adaf_ppo_sample_actions_f32", logits, logits, logits.stride(0), t, b, a, uniforms, _dense(table), action, logprob, coords)
     return (action, logprob) if table is None else (action, logprob, coords)
 
 
@@ -304,9 +309,7 @@ def ppo_rewards(logits, base_logits, target, steps, kind, want_conf=False, want_
     rewards = torch.empty((t, b), device=dev, dtype=fp)
     conf = torch.empty((t, b), device=dev, dtype=fp) if want_conf else None
     ce = torch.empty((1,), device=dev, dtype=fp) if want_ce_last else None
-    h = _h(logits)
-    L.check(L.load_library().adaf_ppo_rewards_f32(h, L.ptr(logits), L.ptr(base_logits), L.ptr(target), t, b, logits.shape[1], kind,
-                                                  L.ptr(rewards), L.ptr(conf), L.ptr(ce), L.stream_ptr()), h)
+    _call("adaf_ppo_rewards_f32", logits, logits, base_logits, target, t, b, logits.shape[1], kind, rewards, conf, ce)
     out = (rewards,) + ((conf,) if want_conf else ()) + ((ce,) if want_ce_last else ())
     return out if len(out) > 1 else rewards
 
@@ -317,8 +320,7 @@ def ppo_returns(rewards, gamma):
     rewards = rewards.contiguous()
     t, b = rewards.shape
     out = torch.empty_like(rewards)
-    h = _h(rewards)
-    L.check(L.load_library().adaf_ppo_returns_f32(h, L.ptr(rewards), t, b, C.c_float(gamma), L.ptr(out), L.stream_ptr()), h)
+    _call("adaf_ppo_returns_f32", rewards, rewards, t, b, float(gamma), out)
     return out
 
 
@@ -342,20 +344,14 @@ def _ppo_head(head, actions, batch_major, sigma=None, old_logprobs=None, returns
     loss_mode = old_logprobs is not None
     loss = torch.empty((1,), device=dev, dtype=fp) if loss_mode else None
     dhead = torch.empty_like(head) if (loss_mode or grads is not None) else None
-    lib = L.load_library()
-    ws_bytes = lib.adaf_ppo_head_workspace_bytes(t, b) if loss_mode else 0
-    ws = torch.empty(max(ws_bytes // 4, 1), device=dev, dtype=fp)
-    g = [None if x is None else x.contiguous() for x in (grads or ())] + [None] * 3      # (kept alive until the launch: L.ptr holds no reference)
-    if loss_mode:
-        old_logprobs, returns = old_logprobs.contiguous(), returns.contiguous()
-    outs = (L.ptr(logprobs), L.ptr(values), L.ptr(entropy), L.ptr(loss), L.ptr(dhead), L.ptr(ws), ws_bytes, L.stream_ptr())
-    h = _h(head)
+    ws, ws_bytes = _workspace("adaf_ppo_head_workspace_bytes", dev, t, b) if loss_mode else (None, 0)      # (only the loss has one)
+    g = [_dense(x) for x in (grads or ())] + [None] * 3
+    loss_in = (_dense(old_logprobs), _dense(returns), float(eps_clip))
+    outs = (logprobs, values, entropy, loss, dhead, ws, ws_bytes)
     if gauss:
-        L.check(lib.adaf_ppo_gauss_head_f32(h, L.ptr(head), int(batch_major), t, b, L.ptr(actions), C.c_float(sigma), L.ptr(old_logprobs),
-                                            L.ptr(returns), C.c_float(eps_clip), L.ptr(g[0]), L.ptr(g[1]), *outs), h)
+        _call("adaf_ppo_gauss_head_f32", head, head, int(batch_major), t, b, actions, float(sigma), *loss_in, g[0], g[1], *outs)
     else:
-        L.check(lib.adaf_ppo_head_f32(h, L.ptr(head), int(batch_major), t, b, head.shape[1] - 1, L.ptr(actions), L.ptr(old_logprobs),
-                                      L.ptr(returns), C.c_float(eps_clip), L.ptr(g[0]), L.ptr(g[1]), L.ptr(g[2]), *outs), h)
+        _call("adaf_ppo_head_f32", head, head, int(batch_major), t, b, head.shape[1] - 1, actions, *loss_in, g[0], g[1], g[2], *outs)
     return logprobs, values, entropy, loss, dhead
 
 
@@ -383,8 +379,7 @@ def rows_transpose(x, ni, nj):
     x = x.contiguous()
     w = x.shape[-1]
     out = torch.empty_like(x)
-    h = _h(x)
-    L.check(L.load_library().adaf_ppo_rows_transpose_f32(h, L.ptr(x), int(ni), int(nj), w, L.ptr(out), L.stream_ptr()), h)
+    _call("adaf_ppo_rows_transpose_f32", x, x, int(ni), int(nj), w, out)
     return out
 
 
@@ -392,16 +387,12 @@ def ppo_wenc_grad(states, de1, e1, split_k=True):
     """The 1x1 conv's weight gradient: states (pixels, C), de1 / e1 (pixels, 32 | 64) -> (32 | 64, C) = (de1 where e1 > 0)^T states
     (e1 None: de1 as it is).  split_k=False: the single-chain cross-check on the strided GEMM."""
     L.need_gpu_f32(states, de1, e1)
-    states, de1, e1 = states.contiguous(), de1.contiguous(), None if e1 is None else e1.contiguous()
     npix, cin = states.shape
     cmid = de1.shape[1]
-    lib = L.load_library()
-    ws_bytes = lib.adaf_ppo_wenc_grad_workspace_bytes(npix, cin, cmid)
-    ws = torch.empty(max(ws_bytes // 4, 4), device=states.device, dtype=torch.float32)
+    ws, ws_bytes = _workspace("adaf_ppo_wenc_grad_workspace_bytes", states.device, npix, cin, cmid)
     dw = torch.empty((cmid, cin), device=states.device, dtype=torch.float32)
-    h = _h(states)
-    L.check(lib.adaf_ppo_wenc_grad_f32(h, L.ptr(states), L.ptr(de1), L.ptr(e1), npix, cin, cmid, int(bool(split_k)), L.ptr(dw), L.ptr(ws),
-                                       ws_bytes, L.stream_ptr()), h)
+    _call("adaf_ppo_wenc_grad_f32", states, states.contiguous(), de1.contiguous(), _dense(e1), npix, cin, cmid, int(bool(split_k)), dw, ws,
+          ws_bytes)
     return dw
 
 
@@ -416,9 +407,7 @@ def ppo_gauss_sample(mean, noise, sigma):
     rows = mean.shape[0]
     action = torch.empty_like(mean)
     logprob = torch.empty((rows,), device=mean.device, dtype=torch.float32)
-    h = _h(mean)
-    L.check(L.load_library().adaf_ppo_gauss_sample_f32(h, L.ptr(mean), L.ptr(noise), rows, C.c_float(sigma), L.ptr(action), L.ptr(logprob),
-                                                       L.stream_ptr()), h)
+    _call("adaf_ppo_gauss_sample_f32", mean, mean, noise, rows, float(sigma), action, logprob)
     return action, logprob
 
 
@@ -440,11 +429,6 @@ def ppo_gauss_loss_head(head, actions, sigma, old_logprobs, returns, eps_clip, b
     return _ppo_head(head, actions, batch_major, sigma, old_logprobs=old_logprobs, returns=returns, eps_clip=eps_clip)
 
 
-def _bn_ws(lib, rows, cols, dev):
-    ws_bytes = lib.adaf_bn_train_workspace_bytes(rows, cols)
-    return torch.empty(max(ws_bytes // 4, 4), device=dev, dtype=torch.float32), ws_bytes
-
-
 def bn_train_forward(x, gamma, beta, running_mean=None, running_var=None, eps=1e-5, momentum=0.1, relu=True):
     """BatchNorm with batch statistics over the rows of x (rows, cols) [+ ReLU]; running_mean / running_var are updated in place.
     -> (y, mean (cols,), invstd (cols,)): with x, what bn_train_backward needs."""
@@ -460,12 +444,9 @@ def bn_train_forward(x, gamma, beta, running_mean=None, running_var=None, eps=1e
     y = torch.empty_like(x)
     mean = torch.empty((cols,), device=x.device, dtype=torch.float32)
     invstd = torch.empty((cols,), device=x.device, dtype=torch.float32)
-    lib = L.load_library()
-    ws, ws_bytes = _bn_ws(lib, rows, cols, x.device)
-    h = _h(x)
-    L.check(lib.adaf_bn_train_forward_f32(h, L.ptr(x), rows, cols, L.ptr(gamma.contiguous()), L.ptr(beta.contiguous()), C.c_float(eps),
-                                          C.c_float(momentum), L.ptr(running_mean), L.ptr(running_var), int(bool(relu)), L.ptr(y), L.ptr(mean),
-                                          L.ptr(invstd), L.ptr(ws), ws_bytes, L.stream_ptr()), h)
+    ws, ws_bytes = _workspace("adaf_bn_train_workspace_bytes", x.device, rows, cols)
+    _call("adaf_bn_train_forward_f32", x, x, rows, cols, gamma.contiguous(), beta.contiguous(), float(eps), float(momentum), running_mean, running_var,
+          int(bool(relu)), y, mean, invstd, ws, ws_bytes)
     return y, mean, invstd
 
 
@@ -477,12 +458,9 @@ def bn_train_backward(x, y, dy, gamma, mean, invstd):
     dx = torch.empty_like(x)
     dgamma = torch.empty((cols,), device=x.device, dtype=torch.float32)
     dbeta = torch.empty((cols,), device=x.device, dtype=torch.float32)
-    lib = L.load_library()
-    ws, ws_bytes = _bn_ws(lib, rows, cols, x.device)
-    h = _h(x)
-    L.check(lib.adaf_bn_train_backward_f32(h, L.ptr(x), L.ptr(None if y is None else y.contiguous()), L.ptr(dy), rows, cols,
-                                           L.ptr(gamma.contiguous()), L.ptr(mean), L.ptr(invstd), L.ptr(dx), L.ptr(dgamma), L.ptr(dbeta),
-                                           L.ptr(ws), ws_bytes, L.stream_ptr()), h)
+    ws, ws_bytes = _workspace("adaf_bn_train_workspace_bytes", x.device, rows, cols)
+    _call("adaf_bn_train_backward_f32", x, x, _dense(y), dy, rows, cols, gamma.contiguous(), mean.contiguous(), invstd.contiguous(), dx, dgamma,
+          dbeta, ws, ws_bytes)
     return dx, dgamma, dbeta
 
 
@@ -496,20 +474,15 @@ def ppo_encoder_backward(states, e1, e_bt, dx_bt, t, b, w_lin_pm, bn=None):
     hw, cin = states.shape[1] * states.shape[2], states.shape[3]
     hid = w_lin_pm.shape[0]
     cmid = w_lin_pm.shape[1] // hw
-    lib = L.load_library()
-    ws_bytes = lib.adaf_ppo_encoder_bn_backward_workspace_bytes(t, b, hw, cin, cmid, hid, int(bn is not None))
     dev, fp = states.device, torch.float32
-    ws = torch.empty(max(ws_bytes // 4, 4), device=dev, dtype=fp)
+    ws, ws_bytes = _workspace("adaf_ppo_encoder_bn_backward_workspace_bytes", dev, t, b, hw, cin, cmid, hid, int(bn is not None))
     dw_enc = torch.empty((cmid, cin), device=dev, dtype=fp)
     dw_lin = torch.empty((hid, cmid * hw), device=dev, dtype=fp)
     db_lin = torch.empty((hid,), device=dev, dtype=fp)
     extra = () if bn is None else tuple(torch.empty((n,), device=dev, dtype=fp) for n in (cmid, cmid, hid, hid))
-    bn_in = [None] * 8 if bn is None else [x.contiguous() for x in bn]
-    states, e1, e_bt, dx_bt, w_lin_pm = (x.contiguous() for x in (states, e1, e_bt, dx_bt, w_lin_pm))      # (alive until the launch)
-    h = _h(states)
-    L.check(lib.adaf_ppo_encoder_bn_backward_f32(h, L.ptr(states), L.ptr(e1), L.ptr(e_bt), L.ptr(dx_bt), t, b, hw, cin, cmid, hid,
-                                                 L.ptr(w_lin_pm), *(L.ptr(x) for x in bn_in), L.ptr(dw_enc), L.ptr(dw_lin), L.ptr(db_lin),
-                                                 *(L.ptr(x) for x in (extra or [None] * 4)), L.ptr(ws), ws_bytes, L.stream_ptr()), h)
+    _call("adaf_ppo_encoder_bn_backward_f32", states, states.contiguous(), e1.contiguous(), e_bt.contiguous(), dx_bt.contiguous(), t, b, hw,
+          cin, cmid, hid, w_lin_pm.contiguous(), *(_dense(x) for x in (bn or [None] * 8)), dw_enc, dw_lin, db_lin, *(extra or [None] * 4), ws,
+          ws_bytes)
     return (dw_enc, dw_lin, db_lin) + extra
 
 
@@ -527,10 +500,8 @@ def fc_meanpool_forward(feat, batch, fc_w, fc_b, global_logit=None):
     if global_logit is not None:
         global_logit = global_logit.contiguous()
         tg = global_logit.shape[1]
-    h = _h(feat)
-    L.check(L.load_library().adaf_fc_meanpool_forward_f32(h, L.ptr(feat), batch, t, f, ncls, L.ptr(fc_w.contiguous()),
-                                                          L.ptr(fc_b.contiguous()), L.ptr(global_logit), tg, L.ptr(out),
-                                                          L.ptr(ws), ws.numel() * 4, L.stream_ptr()), h)
+    _call("adaf_fc_meanpool_forward_f32", feat, feat, batch, t, f, ncls, fc_w.contiguous(), fc_b.contiguous(), global_logit, tg, out, ws,
+          ws.numel() * 4)
     return out
 
 
@@ -540,9 +511,7 @@ def copy2d(src, dst_view):
     rows, cols = src.shape
     if src.stride(1) != 1 or dst_view.stride(1) != 1:
         raise ValueError("copy2d: unit inner stride required")
-    h = _h(src)
-    L.check(L.load_library().adaf_copy2d_f32(h, L.ptr(src), src.stride(0), L.ptr(dst_view), dst_view.stride(0), rows, cols,
-                                             L.stream_ptr()), h)
+    _call("adaf_copy2d_f32", src, src, src.stride(0), dst_view, dst_view.stride(0), rows, cols)
     return dst_view
 
 
@@ -589,12 +558,16 @@ class _NetEngine:
         self._h = L.handle(self.device)
         self._lib = L.load_library()
         net = C.c_void_p()
-        L.check(self._sym("create")(self._h, *create_args, C.byref(net)), self._h)
+        _call("adaf_%s_create" % self._ABI, self.device, *create_args, C.byref(net), stream=False)
         self._net = net
         self._scratch = _StreamScratch(self.device)
 
     def _sym(self, what):
         return getattr(self._lib, "adaf_%s_%s" % (self._ABI, what))
+
+    def _call(self, what, *args, stream=True):
+        """adaf_<_ABI>_<what>(net, *args[, the current stream]), checked: _call's operand rule for the calls that take the network first."""
+        L.check(self._sym(what)(self._net, *_ptrs(args), *((L.stream_ptr(),) if stream else ())), self._h)
 
     def __del__(self):
         try:
@@ -610,15 +583,15 @@ class _NetEngine:
     def load(self, params):
         """params: mapping parameter name -> fp32 tensor on this device.  The library reads them during finalize only (packed
         copies; include/adafocus.h), so every load registers the full set and the tensors may go when it returns."""
-        keep = []
+        keep = []                                # set_param records a pointer that finalize reads: dense copies live until then
         for name, t in params.items():
             if not self._wanted(name):
                 continue
             L.need_gpu_f32(t)
             t = t.detach().contiguous()
             keep.append(t)
-            L.check(self._sym("set_param")(self._net, name.encode(), L.ptr(t), t.numel()), self._h)
-        L.check(self._sym("finalize")(self._net, L.stream_ptr()), self._h)
+            self._call("set_param", name.encode(), t, t.numel(), stream=False)
+        self._call("finalize")
         del keep
 
 
@@ -656,27 +629,22 @@ class ResNet50Trunk(_NetEngine):
         if out is None:
             out = torch.empty((n, 2048), device=x.device, dtype=torch.float32)
         ws, need = self._workspace(n, p)
-        L.check(self._lib.adaf_resnet50_forward(self._net, L.ptr(x), n, p, int(tsm_segments), int(tsm_div), L.ptr(out),
-                                                out.stride(0), L.ptr(ws), need, L.stream_ptr()), self._h)
+        self._call("forward", x, n, p, int(tsm_segments), int(tsm_div), out, out.stride(0), ws, need)
         return out
 
     def forward_frames(self, frames, actions, patch, frames_per_action=1, tsm_segments=0, tsm_div=8, out=None):
         """get_patch + trunk in one call (adaf_resnet50_forward_frames): frames (N,3,H,W) planar or (N,H,W,4) pixel-major, actions
         (k * N / frames_per_action, 2) fp32 (y, x) -> (k * N, 2048); the stem gathers its own windows where its strip kernel applies."""
         L.need_gpu_f32(frames, actions, out)
-        L.on_current_device(frames, actions, out)
         x = frames.contiguous()
-        pixel_major = x.shape[-1] == 4 and x.shape[1] != 3
-        nf = x.shape[0]
-        hh, ww = (x.shape[1], x.shape[2]) if pixel_major else (x.shape[2], x.shape[3])
+        layout, nf, _, hh, ww = _frame_geometry(x)
         act = actions.contiguous()
         n = act.shape[0] // (nf // frames_per_action) * nf
         if out is None:
             out = torch.empty((n, 2048), device=x.device, dtype=torch.float32)
         ws, need = self._workspace(n, patch)
-        L.check(self._lib.adaf_resnet50_forward_frames(self._net, L.ptr(x), LAYOUT_NHWC4 if pixel_major else LAYOUT_NCHW, nf, hh, ww, L.ptr(act),
-                                                       act.shape[0], int(frames_per_action), int(patch), int(tsm_segments), int(tsm_div),
-                                                       L.ptr(out), out.stride(0), L.ptr(ws), need, L.stream_ptr()), self._h)
+        self._call("forward_frames", x, layout, nf, hh, ww, act, act.shape[0], int(frames_per_action), int(patch), int(tsm_segments),
+                   int(tsm_div), out, out.stride(0), ws, need)
         return out
 
     def forward_map(self, patches_nhwc4, tsm_segments=0, tsm_div=8):
@@ -688,8 +656,7 @@ class ResNet50Trunk(_NetEngine):
         fmap = torch.empty((n, s, s, 2048), device=x.device, dtype=torch.float32)
         feat = torch.empty((n, 2048), device=x.device, dtype=torch.float32)
         ws, need = self._workspace(n, p)
-        L.check(self._lib.adaf_resnet50_forward_map(self._net, L.ptr(x), n, p, int(tsm_segments), int(tsm_div), L.ptr(fmap), L.ptr(feat), 2048,
-                                                    L.ptr(ws), need, L.stream_ptr()), self._h)
+        self._call("forward_map", x, n, p, int(tsm_segments), int(tsm_div), fmap, feat, 2048, ws, need)
         return fmap, feat
 
     def profile(self, patches_nhwc4, tsm_segments=0, tsm_div=8):
@@ -704,28 +671,27 @@ class ResNet50Trunk(_NetEngine):
         fl = (C.c_double * k)()
         by = (C.c_double * k)()
         tl = (C.c_int * k)(*([-1] * k))
-        L.check(self._lib.adaf_resnet50_forward_profiled(self._net, L.ptr(x), n, p, int(tsm_segments), int(tsm_div),
-                                                         L.ptr(out), 2048, L.ptr(ws), need, L.stream_ptr(), ms, fl, by,
-                                                         tl), self._h)
+        self._call("forward_profiled", x, n, p, int(tsm_segments), int(tsm_div), out, 2048, ws, need, L.stream_ptr(), ms, fl, by, tl,
+                   stream=False)       # (the one call whose stream is not its last argument)
         return [dict(ms=ms[i], flops=fl[i], bytes=by[i], tile=tl[i]) for i in range(k) if tl[i] != -1]
 
     def set_fusion(self, on):
         """Stage-1 conv2 -> conv3 (-> next conv1) and stem + max-pool as single launches (default on; bit-identical)."""
-        L.check(self._lib.adaf_resnet50_set_fusion(self._net, int(on)), self._h)   # 2 = also the fused stem where it does not pay (tests)
+        self._call("set_fusion", int(on), stream=False)   # 2 = also the fused stem where it does not pay (tests)
 
     def set_shift_place(self, place):
         """'blockres' (default: the shift inside every Bottleneck conv1's operand load) or 'block' (the shift in front of the whole
         Bottleneck: conv1, downsample and identity read the shifted map) -- STH/ops/temporal_shift.py:99-142."""
         code = {"blockres": 0, "block": 1}[place]
-        L.check(self._lib.adaf_resnet50_set_shift_place(self._net, code), self._h)
+        self._call("set_shift_place", code, stream=False)
 
     def set_latency_rows(self, rows):
         """Convs whose GEMM has at most `rows` rows take the small-batch form (conv_lat.hip; bit-identical); 0 = never, < 0 = default."""
-        L.check(self._lib.adaf_resnet50_set_latency_rows(self._net, int(rows)), self._h)
+        self._call("set_latency_rows", int(rows), stream=False)
 
     def set_tiles(self, tiles):
         arr = (C.c_int * len(tiles))(*tiles)
-        L.check(self._lib.adaf_resnet50_set_tiles(self._net, arr, len(tiles)), self._h)
+        self._call("set_tiles", arr, len(tiles), stream=False)
 
     def set_math(self, mode):
         """"f32" (default: fp32 MFMA, exact FMA chain), "split_bf16" (opt-in: fp32 operands decomposed into three
@@ -733,32 +699,26 @@ class ResNet50Trunk(_NetEngine):
         filters on the f16 matrix pipe, fp32 accumulate / BN / residual, one rounding per stored value; the stem and the
         pooled features stay fp32) -- include/adafocus.h ADAF_MATH_*.  Switching into or out of "f16" clears tile overrides."""
         code = {"f32": MATH_F32, "split_bf16": MATH_F32_SPLIT_BF16, "f16": MATH_F16}.get(mode, mode)
-        L.check(self._lib.adaf_resnet50_set_math(self._net, int(code)), self._h)
+        self._call("set_math", int(code), stream=False)
 
 
 def set_gru_persistent(mode, device=None):
     """GRU scans: 0/False = two launches per step, 1/True = one persistent kernel (default), 2 = persistent kernel via
     hipLaunchCooperativeKernel (include/adafocus.h)."""
-    dev = torch.device(device if device is not None else ("cuda", torch.cuda.current_device()))
-    h = L.handle(dev)
-    L.check(L.load_library().adaf_set_gru_persistent(h, int(mode)), h)
+    _call("adaf_set_gru_persistent", _current(device), int(mode), stream=False)
 
 
 def gru_scan_timeouts(device=None):
     """Blocks of persistent GRU scans whose grid barrier timed out since the handle was created (they NaN-poison their
     outputs).  Synchronises the device; 0 = every scan completed normally."""
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-    h = L.handle(dev)
     n = C.c_uint(0)
-    L.check(L.load_library().adaf_gru_scan_timeouts(h, C.byref(n)), h)
+    _call("adaf_gru_scan_timeouts", _current(device), C.byref(n), stream=False)
     return int(n.value)
 
 
 def set_conv_pos_major(on, device=None):
     """k x k convs: position-major tiles with padding-tap skipping on / off (bit-identical; include/adafocus.h)."""
-    dev = torch.device(device if device is not None else ("cuda", torch.cuda.current_device()))
-    h = L.handle(dev)
-    L.check(L.load_library().adaf_set_conv_pos_major(h, int(on)), h)
+    _call("adaf_set_conv_pos_major", _current(device), int(on), stream=False)
 
 
 def pack_dw_weight(w_c133):
@@ -767,8 +727,7 @@ def pack_dw_weight(w_c133):
     w = w_c133.contiguous()
     c = w.shape[0]
     out = torch.empty((3, 3, c), device=w.device, dtype=torch.float32)
-    h = _h(w)
-    L.check(L.load_library().adaf_pack_dw_weight_f32(h, L.ptr(w), c, L.ptr(out), L.stream_ptr()), h)
+    _call("adaf_pack_dw_weight_f32", w, w, c, out)
     return out
 
 
@@ -778,10 +737,7 @@ def dwconv3x3_bn_act(x, w_33c, scale, bias, stride=1, act=ACT_RELU6):
     x = x.contiguous()
     n, hh, ww, c = x.shape
     out = torch.empty((n, (hh - 1) // stride + 1, (ww - 1) // stride + 1, c), device=x.device, dtype=torch.float32)
-    h = _h(x)
-    L.check(L.load_library().adaf_dwconv3x3_bn_act_f32(h, L.ptr(x), n, hh, ww, c, stride, L.ptr(w_33c.contiguous()),
-                                                       L.ptr(scale.contiguous()), L.ptr(bias.contiguous()), act,
-                                                       L.ptr(out), L.stream_ptr()), h)
+    _call("adaf_dwconv3x3_bn_act_f32", x, x, n, hh, ww, c, stride, w_33c.contiguous(), scale.contiguous(), bias.contiguous(), act, out)
     return out
 
 
@@ -792,9 +748,7 @@ def grid_actions(logits, table):
     rows, a = logits.shape
     idx = torch.empty((rows,), device=logits.device, dtype=torch.int64)
     act = torch.empty((rows, 2), device=logits.device, dtype=torch.float32)
-    h = _h(logits)
-    L.check(L.load_library().adaf_grid_actions_f32(h, L.ptr(logits), rows, a, L.ptr(table.contiguous()), L.ptr(idx), L.ptr(act),
-                                                   L.stream_ptr()), h)
+    _call("adaf_grid_actions_f32", logits, logits, rows, a, table.contiguous(), idx, act)
     return idx, act
 
 
@@ -804,28 +758,20 @@ def argmax_rows(logits):
     logits = logits.contiguous()
     rows, a = logits.shape
     idx = torch.empty((rows,), device=logits.device, dtype=torch.int64)
-    h = _h(logits)
-    L.check(L.load_library().adaf_grid_actions_f32(h, L.ptr(logits), rows, a, None, L.ptr(idx), None, L.stream_ptr()), h)
+    _call("adaf_grid_actions_f32", logits, logits, rows, a, None, idx, None)
     return idx
 
 
 def gru_seq_forward(x, w_ih, w_hh, b_ih, b_hh, h0=None):
     """nn.GRU(batch_first=True): x (B,T,F), h0 (B,H) or None (= zeros) -> hidden states (B,T,H)."""
     L.need_gpu_f32(x, w_ih, w_hh, b_ih, b_hh, h0)
-    if h0 is not None:
-        h0 = h0.contiguous()
     b, t, f = x.shape
-    if x.stride(2) != 1 or x.stride(0) != t * x.stride(1):
-        x = x.contiguous()
+    x = _gru_x(x)
     hid = w_hh.shape[1]
-    lib = L.load_library()
-    ws_bytes = lib.adaf_gru_cls_workspace_bytes(b, t, hid)
-    ws = torch.empty(max(ws_bytes // 4, 1), device=x.device, dtype=torch.float32)
+    ws, ws_bytes = _workspace("adaf_gru_cls_workspace_bytes", x.device, b, t, hid)
     hs = torch.empty((b, t, hid), device=x.device, dtype=torch.float32)
-    h = _h(x)
-    L.check(lib.adaf_gru_seq_forward_f32(h, L.ptr(x), x.stride(1), b, t, f, hid, L.ptr(w_ih.contiguous()),
-                                         L.ptr(w_hh.contiguous()), L.ptr(b_ih.contiguous()), L.ptr(b_hh.contiguous()),
-                                         L.ptr(h0), L.ptr(hs), L.ptr(ws), ws_bytes, L.stream_ptr()), h)
+    _call("adaf_gru_seq_forward_f32", x, x, x.stride(1), b, t, f, hid, w_ih.contiguous(), w_hh.contiguous(), b_ih.contiguous(),
+          b_hh.contiguous(), _dense(h0), hs, ws, ws_bytes)
     return hs
 
 
@@ -838,7 +784,7 @@ class MobileNetV2Net(_NetEngine):
         """Expand 1x1 -> depthwise 3x3 in one kernel for the high-resolution blocks (default on)."""
         # bit 0: fused kernels on; bit 2 (value 4): one frame chunk at a time instead of two side by side; bit 3 (value 8):
         # expand -> depthwise kernel + project launch instead of the whole-block kernel of b3 / b5 / b6 (A/B switches)
-        L.check(self._lib.adaf_mobilenetv2_set_fusion(self._net, int(on)), self._h)
+        self._call("set_fusion", int(on), stream=False)
 
     def forward(self, frames_nhwc4, tsm_segments=0, tsm_div=8, want_vec=True):
         """(N,S,S,4) -> featmap (N,S/32,S/32,1280) NHWC, featvec (N,1280) or None."""
@@ -852,8 +798,7 @@ class MobileNetV2Net(_NetEngine):
         fvec = torch.empty((n, 1280), device=x.device, dtype=torch.float32) if want_vec else None
         need = self._lib.adaf_mobilenetv2_workspace_bytes(self._net, n, s, int(tsm_segments))
         ws = self._scratch.get(need)     # per stream: consecutive batches' glancer passes may overlap
-        L.check(self._lib.adaf_mobilenetv2_forward(self._net, L.ptr(x), n, s, int(tsm_segments), int(tsm_div), L.ptr(fmap),
-                                                   L.ptr(fvec), 1280, L.ptr(ws), need, L.stream_ptr()), self._h)
+        self._call("forward", x, n, s, int(tsm_segments), int(tsm_div), fmap, fvec, 1280, ws, need)
         return fmap, fvec
 
 
@@ -870,8 +815,7 @@ def ingest_u8(clips_hwc_u8, frames, mean, std):
     out = torch.empty((b * frames, hh, ww, 4), device=x.device, dtype=torch.float32)
     m = (C.c_float * 3)(*[float(v) for v in mean])
     s = (C.c_float * 3)(*[float(v) for v in std])
-    h = _h(x)
-    L.check(L.load_library().adaf_ingest_u8_f32(h, L.ptr(x), b, int(frames), hh, ww, m, s, L.ptr(out), L.stream_ptr()), h)
+    _call("adaf_ingest_u8_f32", x, x, b, int(frames), hh, ww, m, s, out)
     return out
 
 
@@ -884,10 +828,7 @@ def crop_gather_nhwc4(frames_nhwc4, actions, patch, frames_per_action=1, return_
     p = int(patch)
     out = torch.empty((n, p, p, 4), device=x.device, dtype=torch.float32)
     coords = torch.empty((actions.shape[0], 2), device=x.device, dtype=torch.int32) if return_coords else None
-    h = _h(x)
-    L.check(L.load_library().adaf_crop_gather_nhwc4_f32(h, L.ptr(x), n, hh, ww, L.ptr(actions), actions.shape[0],
-                                                        int(frames_per_action), p, L.ptr(out), L.ptr(coords),
-                                                        L.stream_ptr()), h)
+    _call("adaf_crop_gather_nhwc4_f32", x, x, n, hh, ww, actions, actions.shape[0], int(frames_per_action), p, out, coords)
     return (out, coords) if return_coords else out
 
 
@@ -902,12 +843,7 @@ def crop_resize(frames, actions, patch, size=None, frames_per_action=1, layout=L
     L.need_gpu_f32(frames, actions)
     frames = frames.contiguous()
     actions = actions.contiguous()
-    in4 = frames.shape[-1] == 4 and frames.shape[1] != 3
-    if in4:
-        n, hh, ww, _ = frames.shape
-        c = 3
-    else:
-        n, c, hh, ww = frames.shape
+    in_layout, n, c, hh, ww = _frame_geometry(frames)
     p = int(patch)
     sizes, sdef = None, p
     if isinstance(size, torch.Tensor):
@@ -918,10 +854,8 @@ def crop_resize(frames, actions, patch, size=None, frames_per_action=1, layout=L
         sdef = int(size)
     out = torch.empty(_out_shape(n, c, p, p, layout), device=frames.device, dtype=torch.float32)
     coords = torch.empty((actions.shape[0], 2), device=frames.device, dtype=torch.int32) if return_coords else None
-    h = _h(frames)
-    L.check(L.load_library().adaf_crop_resize_f32(h, L.ptr(frames), LAYOUT_NHWC4 if in4 else LAYOUT_NCHW, n, c, hh, ww, L.ptr(actions),
-                                                  actions.shape[0], int(frames_per_action), L.ptr(sizes), sdef, p, L.ptr(out), layout,
-                                                  L.ptr(coords), L.stream_ptr()), h)
+    _call("adaf_crop_resize_f32", frames, frames, in_layout, n, c, hh, ww, actions, actions.shape[0], int(frames_per_action), sizes, sdef, p, out,
+          layout, coords)
     return (out, coords) if return_coords else out
 
 
@@ -930,38 +864,23 @@ def resize_nearest(frames, out_hw, layout=LAYOUT_NCHW):
     frames (N,C,H,W) planar or (N,H,W,4) pixel-major -> `layout`."""
     L.need_gpu_f32(frames)
     frames = frames.contiguous()
-    in4 = frames.shape[-1] == 4 and frames.shape[1] != 3
-    if in4:
-        n, hh, ww, _ = frames.shape
-        c = 3
-    else:
-        n, c, hh, ww = frames.shape
+    in_layout, n, c, hh, ww = _frame_geometry(frames)
     oh, ow = (int(out_hw), int(out_hw)) if isinstance(out_hw, int) else (int(out_hw[0]), int(out_hw[1]))
     out = torch.empty(_out_shape(n, c, oh, ow, layout), device=frames.device, dtype=torch.float32)
-    h = _h(frames)
-    L.check(L.load_library().adaf_resize_nearest_f32(h, L.ptr(frames), LAYOUT_NHWC4 if in4 else LAYOUT_NCHW, n, c, hh, ww, oh, ow,
-                                                     L.ptr(out), layout, L.stream_ptr()), h)
+    _call("adaf_resize_nearest_f32", frames, frames, in_layout, n, c, hh, ww, oh, ow, out, layout)
     return out
 
 
 # ---- N2: half-precision storage ---------------------------------------------------------------------------------
-def _need_gpu(*tensors):
-    for t in tensors:
-        if t is not None and not t.is_cuda:
-            raise L.AdafError("adafocus_amd runs on MI355X only: got a %s tensor" % t.device)
-    L.on_current_device(*tensors)
-
-
 def cast(x, dtype):
     """fp32 <-> fp16 element-wise conversion on the HIP side (round-to-nearest-even)."""
-    _need_gpu(x)
+    L.need_gpu(x)
     x = x.contiguous()
     to16 = dtype == torch.float16
     if x.dtype not in (torch.float32, torch.float16) or (x.dtype == torch.float16) == to16:
         raise ValueError("cast: fp32 -> fp16 or fp16 -> fp32")
     out = torch.empty(x.shape, device=x.device, dtype=dtype)
-    h = _h(x)
-    L.check(L.load_library().adaf_cast_f32_f16(h, L.ptr(x), x.numel(), L.ptr(out), 1 if to16 else 0, L.stream_ptr()), h)
+    _call("adaf_cast_f32_f16", x, x, x.numel(), out, 1 if to16 else 0)
     return out
 
 
@@ -972,8 +891,7 @@ def pack_conv_weight_f16(w_oihw, cin_pad=None):
     co, ci, kh, kw = w.shape
     cp = cin_pad or ((ci + 7) // 8 * 8)
     out = torch.empty((co, kh, kw, cp), device=w.device, dtype=torch.float16)
-    h = _h(w)
-    L.check(L.load_library().adaf_pack_conv_weight_f16(h, L.ptr(w), co, ci, kh, kw, cp, L.ptr(out), L.stream_ptr()), h)
+    _call("adaf_pack_conv_weight_f16", w, w, co, ci, kh, kw, cp, out)
     return out
 
 
@@ -982,7 +900,7 @@ def conv2d_bn_act_f16(x, w_ohwi, scale=None, bias=None, residual=None, stride=1,
     """adaf_conv2d_bn_act_f16: x (N,H,W,Cin) fp16 with fp16 weights (or fp32 x / w with an fp16 store), fp32 accumulate and
     epilogue, `out_dtype` store.  `tsm_segments` > 0: the temporal shift fused into a 1x1 conv's operand load, as conv2d_bn_act
     (fp16 operands move whole 16-byte chunks: cin / tsm_div a multiple of 8)."""
-    _need_gpu(x, w_ohwi, scale, bias, residual)
+    L.need_gpu(x, w_ohwi, scale, bias, residual)
     x = x.contiguous()
     w_ohwi = w_ohwi.contiguous()
     if x.dtype != w_ohwi.dtype:
@@ -1000,25 +918,20 @@ def conv2d_bn_act_f16(x, w_ohwi, scale=None, bias=None, residual=None, stride=1,
         residual = residual.contiguous()
     p = L.ConvParams(n=n, h=hh, w=ww, cin=cin, cout=cout, kh=kh, kw=kw, stride=stride, pad=pad, act=act, tsm_segments=int(tsm_segments),
                      tsm_div=int(tsm_div), ldx=0, ldo=0, ldr=0, tile=tile)
-    h = _h(x)
-    L.check(L.load_library().adaf_conv2d_bn_act_f16(h, C.byref(p), L.ptr(x), DTYPE_F16 if x.dtype == torch.float16 else DTYPE_F32,
-                                                    L.ptr(w_ohwi), L.ptr(scale), L.ptr(bias), L.ptr(residual), L.ptr(out),
-                                                    DTYPE_F16 if out_dtype == torch.float16 else DTYPE_F32, L.stream_ptr()), h)
+    _call("adaf_conv2d_bn_act_f16", x, C.byref(p), x, DTYPE_F16 if x.dtype == torch.float16 else DTYPE_F32, w_ohwi, scale, bias, residual, out,
+          DTYPE_F16 if out_dtype == torch.float16 else DTYPE_F32)
     return out
 
 
 def dwconv3x3_bn_act_f16(x, w_33c, scale, bias, stride=1, act=ACT_RELU6):
     """Depthwise 3x3 on fp16 activations (N,H,W,C); taps, BN affine and the sum in fp32."""
-    _need_gpu(x, w_33c, scale, bias)
+    L.need_gpu(x, w_33c, scale, bias)
     if x.dtype != torch.float16:
         raise ValueError("dwconv3x3_bn_act_f16: fp16 activations expected")
     x = x.contiguous()
     n, hh, ww, c = x.shape
     out = torch.empty((n, (hh - 1) // stride + 1, (ww - 1) // stride + 1, c), device=x.device, dtype=torch.float16)
-    h = _h(x)
-    L.check(L.load_library().adaf_dwconv3x3_bn_act_f16(h, L.ptr(x), n, hh, ww, c, stride, L.ptr(w_33c.contiguous()),
-                                                       L.ptr(scale.contiguous()), L.ptr(bias.contiguous()), act, L.ptr(out),
-                                                       L.stream_ptr()), h)
+    _call("adaf_dwconv3x3_bn_act_f16", x, x, n, hh, ww, c, stride, w_33c.contiguous(), scale.contiguous(), bias.contiguous(), act, out)
     return out
 
 
@@ -1037,31 +950,25 @@ def pack_dw_weight_kxk(w_c1kk):
     w = w_c1kk.contiguous()
     c, k = w.shape[0], w.shape[-1]
     out = torch.empty((k * k, c), device=w.device, dtype=torch.float32)
-    h = _h(w)
-    L.check(L.load_library().adaf_pack_dw_weight_kxk_f32(h, L.ptr(w), c, k, L.ptr(out), L.stream_ptr()), h)
+    _call("adaf_pack_dw_weight_kxk_f32", w, w, c, k, out)
     return out
 
 
 def dwconv_same_bn_act(x, w_kkc, scale, bias, k, stride=1, act=ACT_SWISH, want_pool=False):
     """Depthwise k x k with TensorFlow-SAME padding + BN affine + activation.  x (N,H,W,C) fp32 | fp16 NHWC ->
     (N,ceil(H/s),ceil(W/s),C) in x's dtype [, squeeze mean (N,C) fp32]."""
-    _need_gpu(x)
+    L.need_gpu(x)
     L.need_gpu_f32(w_kkc, scale, bias)
     x = x.contiguous()
     n, hh, ww, c = x.shape
     oh, ow = -(-hh // stride), -(-ww // stride)
     out = torch.empty((n, oh, ow, c), device=x.device, dtype=x.dtype)
-    lib = L.load_library()
-    pool = ws = None
-    need = 0
+    pool, ws, need = None, None, 0
     if want_pool:
         pool = torch.empty((n, c), device=x.device, dtype=torch.float32)
-        need = lib.adaf_dwconv_same_workspace_bytes(n, hh, ww, c, int(k), int(stride), _dt(x))
-        ws = torch.empty(max(need, 16), device=x.device, dtype=torch.uint8)
-    h = _h(x)
-    L.check(lib.adaf_dwconv_same_bn_act(h, L.ptr(x), _dt(x), n, hh, ww, c, int(k), int(stride), L.ptr(w_kkc.contiguous()),
-                                        L.ptr(scale.contiguous()), L.ptr(bias.contiguous()), int(act), L.ptr(out), L.ptr(pool),
-                                        L.ptr(ws), need, L.stream_ptr()), h)
+        ws, need = _workspace("adaf_dwconv_same_workspace_bytes", x.device, n, hh, ww, c, int(k), int(stride), _dt(x))
+    _call("adaf_dwconv_same_bn_act", x, x, _dt(x), n, hh, ww, c, int(k), int(stride), w_kkc.contiguous(), scale.contiguous(), bias.contiguous(),
+          int(act), out, pool, ws, need)
     return (out, pool) if want_pool else out
 
 
@@ -1071,29 +978,22 @@ def se_gate(pool_mean, w_reduce, b_reduce, w_expand, b_expand):
     n, c = pool_mean.shape
     sq = w_reduce.shape[0]
     gate = torch.empty((n, c), device=pool_mean.device, dtype=torch.float32)
-    h = _h(pool_mean)
-    L.check(L.load_library().adaf_se_gate_f32(h, L.ptr(pool_mean.contiguous()), n, c, L.ptr(w_reduce.reshape(sq, c).contiguous()),
-                                              L.ptr(b_reduce.contiguous()), sq, L.ptr(w_expand.reshape(c, sq).contiguous()),
-                                              L.ptr(b_expand.contiguous()), L.ptr(gate), L.stream_ptr()), h)
+    _call("adaf_se_gate_f32", pool_mean, pool_mean.contiguous(), n, c, w_reduce.reshape(sq, c).contiguous(), b_reduce.contiguous(), sq,
+          w_expand.reshape(c, sq).contiguous(), b_expand.contiguous(), gate)
     return gate
 
 
 def conv1x1_gated_bn(x, gate, w, scale=None, bias=None, residual=None):
     """x (N,H,W,Cin) fp32 | fp16, gate (N,Cin) fp32 or None, w (Cout,Cin) in x's dtype -> (N,H,W,Cout) in x's dtype."""
-    _need_gpu(x, w)
+    L.need_gpu(x, w)
     x = x.contiguous()
     n, hh, ww, cin = x.shape
     cout = w.shape[0]
     if w.dtype != x.dtype or (residual is not None and residual.dtype != x.dtype):
         raise L.AdafError("conv1x1_gated_bn: w / residual must have x's dtype")
     out = torch.empty((n, hh, ww, cout), device=x.device, dtype=x.dtype)
-    h = _h(x)
-    L.check(L.load_library().adaf_conv1x1_gated_bn(h, L.ptr(x), _dt(x), n, hh * ww, cin, L.ptr(gate.contiguous() if gate is not None else None),
-                                                   L.ptr(w.reshape(cout, cin).contiguous()), cout,
-                                                   L.ptr(scale.contiguous() if scale is not None else None),
-                                                   L.ptr(bias.contiguous() if bias is not None else None),
-                                                   L.ptr(residual.contiguous() if residual is not None else None), L.ptr(out),
-                                                   L.stream_ptr()), h)
+    _call("adaf_conv1x1_gated_bn", x, x, _dt(x), n, hh * ww, cin, _dense(gate), w.reshape(cout, cin).contiguous(), cout, _dense(scale),
+          _dense(bias), _dense(residual), out)
     return out
 
 
@@ -1102,7 +1002,7 @@ class EffNetNet(_NetEngine):
     _ABI = "effnet"
 
     def __init__(self, device, width, depth):
-        super().__init__(device, C.c_float(width), C.c_float(depth))
+        super().__init__(device, float(width), float(depth))
         self.feature_dim = self._lib.adaf_effnet_feature_dim(self._net)
         self.dtype = DTYPE_F32
         self.pad_size = 0          # default image size the SAME padding is computed for (0 = the input's own); the owner sets it
@@ -1111,18 +1011,18 @@ class EffNetNet(_NetEngine):
         out = []
         for i in range(self._lib.adaf_effnet_block_count(self._net)):
             info = (C.c_int * 8)()
-            L.check(self._lib.adaf_effnet_block_info(self._net, i, info), self._h)
+            self._call("block_info", i, info, stream=False)
             out.append(dict(zip(("k", "stride", "expand", "cin", "cout", "hid", "sq", "stem"), list(info))))
         return out
 
     def set_dtype(self, dtype):
         code = {"f32": DTYPE_F32, "f16": DTYPE_F16}.get(dtype, dtype)
-        L.check(self._lib.adaf_effnet_set_dtype(self._net, int(code)), self._h)
+        self._call("set_dtype", int(code), stream=False)
         self.dtype = int(code)
 
     def set_fusion(self, on):
         """fp16 storage: whole-image MBConv kernels for the stride-1 blocks on maps up to 9 x 9 (default on); off = the four-launch plan."""
-        L.check(self._lib.adaf_effnet_set_fusion(self._net, int(bool(on))), self._h)
+        self._call("set_fusion", int(bool(on)), stream=False)
 
     def whole_blocks(self, size, pad_size=None):
         """MBConv blocks of a forward at this input size that run as one launch each (csrc/mbconv_whole.hip)."""
@@ -1132,17 +1032,19 @@ class EffNetNet(_NetEngine):
         """MBConv blocks of a forward at this input size whose expand conv runs inside the depthwise launch (fp16 storage; effnet_kernels.hip XN > 0)."""
         return int(self._lib.adaf_effnet_fused_expand_blocks(self._net, int(size), int(self.pad_size if pad_size is None else pad_size)))
 
+    @staticmethod
+    def _same_size(size, pad_size, blocks):
+        """Map size after the stem (3 x 3, stride 2) and `blocks` for an input of `size`: every layer pads as TensorFlow-SAME would for
+        an image of pad_size (0 = size), whose own size shrinks by ceil(. / stride) alongside."""
+        hw, ps = size, pad_size or size
+        for k, s in [(3, 2)] + [(b["k"], b["stride"]) for b in blocks]:
+            tot = max((-(-ps // s) - 1) * s + k - ps, 0)
+            hw, ps = (hw + tot - k) // s + 1, -(-ps // s)
+        return hw
+
     def out_size(self, size, pad_size=0):
         """Spatial size of the feature map for an input of `size` (SAME padding computed for pad_size or size)."""
-        ps = pad_size or size
-
-        def step(hw, ps, k, s):
-            tot = max((-(-ps // s) - 1) * s + k - ps, 0)
-            return (hw + tot - k) // s + 1, -(-ps // s)
-        hw, ps = step(size, ps, 3, 2)
-        for b in self.blocks():
-            hw, ps = step(hw, ps, b["k"], b["stride"])
-        return hw
+        return self._same_size(size, pad_size, self.blocks())
 
     def forward(self, frames_nhwc4, pad_size=0, want_map=False, want_vec=True, out=None):
         """(N,S,S,4) fp32 -> (featmap (N,s,s,F) fp32 NHWC or None, featvec (N,F) or None).  `out`: write the vector into
@@ -1160,8 +1062,7 @@ class EffNetNet(_NetEngine):
             fvec = torch.empty((n, f), device=x.device, dtype=torch.float32)
         need = self._lib.adaf_effnet_workspace_bytes(self._net, n, s, int(pad_size))
         ws = self._scratch.get(need)
-        L.check(self._lib.adaf_effnet_forward(self._net, L.ptr(x), n, s, int(pad_size), -1, None, L.ptr(fmap), L.ptr(fvec), int(ld),
-                                              L.ptr(ws), need, L.stream_ptr()), self._h)
+        self._call("forward", x, n, s, int(pad_size), -1, None, fmap, fvec, int(ld), ws, need)
         return fmap, fvec
 
     def forward_blocks(self, frames_nhwc4, upto, pad_size=None):
@@ -1171,21 +1072,13 @@ class EffNetNet(_NetEngine):
         x = frames_nhwc4.contiguous()
         n, s = x.shape[0], x.shape[1]
         pad_size = self.pad_size if pad_size is None else pad_size
-        ps = pad_size or s
-
-        def step(hw, ps, k, st):
-            tot = max((-(-ps // st) - 1) * st + k - ps, 0)
-            return (hw + tot - k) // st + 1, -(-ps // st)
-        hw, ps = step(s, ps, 3, 2)
         blocks = self.blocks()
-        c = blocks[0]["stem"]
-        for b in blocks[:upto]:
-            hw, ps = step(hw, ps, b["k"], b["stride"])
-            c = b["cout"]
+        done = blocks[:upto]
+        hw = self._same_size(s, pad_size, done)
+        c = done[-1]["cout"] if done else blocks[0]["stem"]
         dt = torch.float16 if self.dtype == DTYPE_F16 else torch.float32
         out = torch.empty((n, hw, hw, c), device=x.device, dtype=dt)
         need = self._lib.adaf_effnet_workspace_bytes(self._net, n, s, int(pad_size))
         ws = self._scratch.get(need)
-        L.check(self._lib.adaf_effnet_forward(self._net, L.ptr(x), n, s, int(pad_size), int(upto), L.ptr(out), None, None, 0,
-                                              L.ptr(ws), need, L.stream_ptr()), self._h)
+        self._call("forward", x, n, s, int(pad_size), int(upto), out, None, None, 0, ws, need)
         return out

@@ -40,6 +40,70 @@ def test_loader_declares_prototypes():
     assert lib.adaf_resnet50_workspace_bytes(None, 1, 98) == 5 * 25 * 25 * 256 * 4   # odd stem size: stage-1 map is larger
 
 
+def _ctype_kind(t):
+    """'ptr' for anything a C pointer is passed as, else the ctypes type itself."""
+    if t in (ctypes.c_void_p, ctypes.c_char_p) or isinstance(t, type(ctypes.POINTER(ctypes.c_int))):
+        return "ptr"
+    return t
+
+
+def _c_kind(decl):
+    """The kind of a C parameter or return type as the header spells it ('const float* x', 'size_t ws_bytes', 'int')."""
+    if "*" in decl:
+        return "ptr"
+    words = [w for w in re.findall(r"\w+", decl) if w != "const"]
+    scalars = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t, "unsigned": ctypes.c_uint}
+    assert words and words[0] in scalars, decl
+    return scalars[words[0]]
+
+
+def test_prototype_table_matches_the_header_parameter_by_parameter():
+    """_lib.PROTOTYPES is the one statement of the ABI on the Python side: every adaf_* prototype of include/adafocus.h, comments
+    stripped, has its entry with the same return kind, the same number of parameters and the same kind for each (pointer ->
+    c_void_p / c_char_p / POINTER(...); int, float, double, size_t, unsigned -> their ctypes), and the table names nothing else."""
+    header = open(os.path.join(ROOT, "include", "adafocus.h")).read()
+    code = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", header, flags=re.S))
+    code = re.sub(r"^[ \t]*#[^\n]*", "", code, flags=re.M)                  # preprocessor lines
+    declared = {}
+    for ret, name, params in re.findall(r"([A-Za-z_][\w\s]*?[\s\*]+)(adaf_\w+)\s*\(([^()]*)\)\s*;", code):
+        assert name not in declared, name
+        params = [] if params.strip() in ("", "void") else params.split(",")
+        declared[name] = (_c_kind(ret), [_c_kind(p) for p in params])
+    assert set(declared) == set(_lib.PROTOTYPES), set(declared) ^ set(_lib.PROTOTYPES)
+    assert len(declared) > 90
+    for name, (ret, params) in declared.items():
+        restype, argtypes = _lib.PROTOTYPES[name]
+        assert _ctype_kind(restype) == ret, name
+        assert [_ctype_kind(t) for t in argtypes] == params, name
+    assert _lib.SYMBOLS == tuple(_lib.PROTOTYPES)
+    _ensure_built()
+    lib = _lib.load_library()
+    for name, (restype, argtypes) in _lib.PROTOTYPES.items():
+        fn = getattr(lib, name)
+        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name
+
+
+def test_hip_ops_takes_no_pointer_of_a_temporary():
+    """_lib.ptr holds no reference, so its argument must be something that outlives the launch: a plain name, an attribute or None.
+    A call, a conditional or a subscript can create a tensor that dies as soon as ptr returns, and the next such temporary then gets
+    the same block of the caching allocator (hip_ops._call's operand rule; tests/test_dense_operands_gpu.py shows it on the device)."""
+    import ast
+    src = open(os.path.join(ROOT, "adafocus_amd", "hip_ops.py")).read()
+    seen, bad = 0, []
+    for node in ast.walk(ast.parse(src)):
+        if not isinstance(node, ast.Call):
+            continue
+        f = node.func
+        if not (isinstance(f, ast.Attribute) and f.attr == "ptr" and isinstance(f.value, ast.Name) and f.value.id in ("L", "_lib")):
+            continue
+        seen += 1
+        for a in list(node.args) + [k.value for k in node.keywords]:
+            if not (isinstance(a, (ast.Name, ast.Attribute)) or (isinstance(a, ast.Constant) and a.value is None)):
+                bad.append((node.lineno, ast.unparse(a)))
+    assert seen >= 1, "hip_ops no longer converts tensors through _lib.ptr: point this test at what replaced it"
+    assert not bad, bad
+
+
 @pytest.mark.skipif(torch.cuda.is_available(), reason="checks the no-GPU behaviour")
 def test_no_gpu_fails_loudly():
     _ensure_built()
