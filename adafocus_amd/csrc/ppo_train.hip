@@ -130,11 +130,12 @@ __global__ __launch_bounds__(64) void ppo_rewards_kernel(const float* logits, co
 }
 
 // mean over clips of the cross-entropy of step T - 1: one block of four waves; wave w takes clips w, w + 4, ... of a chunk of 256 clips,
-// thread 0 adds the chunk's values in clip order
+// thread 0 adds the chunk's values in clip order -- in double: one fp32 chain over B clips drifts by B / 2 roundings of the running sum
+// (5.5e-7 of the mean at B = 257, where ATen's own fp32 mean of the same values is 6e-9 from float64; tests/test_heads_domain_gpu.py)
 __global__ __launch_bounds__(256) void ppo_ce_last_kernel(const float* logits, const long long* target, int T, int B, int C, float* out) {
     __shared__ float ce[256];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    float sum = 0.f;
+    double sum = 0.0;
     for (int b0 = 0; b0 < B; b0 += 256) {
         const int nb = min(256, B - b0);
         for (int k = wave; k < nb; k += 4) {
@@ -146,10 +147,10 @@ __global__ __launch_bounds__(256) void ppo_ce_last_kernel(const float* logits, c
         }
         __syncthreads();
         if (tid == 0)
-            for (int k = 0; k < nb; ++k) sum += ce[k];
+            for (int k = 0; k < nb; ++k) sum += (double)ce[k];
         __syncthreads();
     }
-    if (tid == 0) *out = sum / (float)B;
+    if (tid == 0) *out = (float)(sum / (double)B);
 }
 
 // ---- returns ----------------------------------------------------------------------------------------------------------------------------
