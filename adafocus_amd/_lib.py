@@ -126,6 +126,19 @@ PROTOTYPES = {
     "adaf_effnet_finalize": (ip, [vp, vp]),
     "adaf_effnet_workspace_bytes": (sz, [vp, ip, ip, ip]),
     "adaf_effnet_forward": (ip, [vp, vp, ip, ip, ip, ip, vp, vp, vp, ip, vp, sz, vp]),
+    "adaf_stem7x7_workspace_bytes": (sz, []),
+    "adaf_stem7x7_bn_relu_f32": (ip, [vp, vp, ip, ip, vp, vp, vp, vp, vp, sz, vp]),
+    "adaf_conv2d_wgrad_workspace_bytes": (sz, [C.POINTER(ConvParams)]),
+    "adaf_conv2d_wgrad_f32": (ip, [vp, C.POINTER(ConvParams), vp, vp, vp, vp, sz, vp]),
+    "adaf_pack_conv_dgrad_weight_f32": (ip, [vp, vp, vp, ip, ip, ip, ip, vp, vp]),
+    "adaf_conv2d_dgrad_workspace_bytes": (sz, [C.POINTER(ConvParams)]),
+    "adaf_conv2d_dgrad_f32": (ip, [vp, C.POINTER(ConvParams), vp, vp, vp, vp, sz, vp]),
+    "adaf_relu_backward_f32": (ip, [vp, vp, vp, vp, sz, vp, vp]),
+    "adaf_global_avgpool_backward_f32": (ip, [vp, vp, ip, vp, ip, ip, ip, vp, vp]),
+    "adaf_maxpool3x3s2_backward_f32": (ip, [vp, vp, vp, ip, ip, ip, ip, vp, vp]),
+    "adaf_temporal_shift_backward_f32": (ip, [vp, vp, ip, ip, ip, ip, ip, ip, vp, vp]),
+    "adaf_conv_bn_param_grad_workspace_bytes": (sz, [ip]),
+    "adaf_conv_bn_param_grad_f32": (ip, [vp, vp, ip, vp, vp, vp, vp, vp, fp, ip, ip, ip, ip, ip, vp, vp, vp, vp, sz, vp]),
 }
 SYMBOLS = tuple(PROTOTYPES)
 

@@ -1,0 +1,583 @@
+// Backward primitives of the ResNet trunk's convolutions (stage 3 of the Something-Something tree fine-tunes the local CNN with frozen
+// BatchNorm statistics: STH/stage3.py:189-193, 313-317).  fp32, NHWC activations, OHWI filters -- the engine's layouts.  No
+// atomics: every output element has one writer and every sum a fixed order, so the same inputs give the same bits.
+//
+//   conv_wgrad_splitk_kernel   G[o, kh, kw, i] = sum over output pixels of g[pixel, o] x[window(pixel, kh, kw), i]: a TN GEMM whose reduction
+//                              axis is the pixel axis.  ppo_wenc_splitk_kernel's design (ppo_train.hip) with an implicit im2col
+//                              on the way in: 16-byte loads, v_mfma_f32_32x32x2_f32 with K = a pixel pair, split-K over pixel slices, the
+//                              slice partials added in slice order by conv_wgrad_reduce_kernel
+//   conv_dgrad_pack_kernel     the filter transposed, rotated by 180 degrees, times the folded BN scale per output channel: the data
+//                              gradient is then a stride-1 convolution of the gradient map on the forward engine (conv_gemm.hip)
+//   conv_zero_insert_kernel    stride 2: a low-resolution map written into the even positions of a zeroed full-resolution one (gather form)
+//   relu_backward_kernel, avgpool_backward_kernel, maxpool_backward_kernel, tshift_backward_kernel, conv_colsum_*_kernel, conv_bn_param_grad_kernel
+#include "adaf_internal.h"
+
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+inline unsigned blocks_for(size_t n, int per = 256) { return (unsigned)((n + per - 1) / per); }
+
+// ---- weight gradient -----------------------------------------------------------------------------------------------------------------
+// grid (ceil(K / 128), cout / (32 MH), slices), 512 threads; K = kh * kw * cin is the filter's flattened (kh, kw, i) axis.  A block owns
+// output pixels [slice * pps, (slice + 1) * pps), filter rows [32 MH blockIdx.y, ...) and K columns [128 blockIdx.x, ...).  Lane (half, nl)
+// of a wave loads the 4 consecutive K columns 128 blockIdx.x + 4 nl ..: cin % 4 == 0, so they are 4 channels of ONE tap (kh, kw), and the
+// lane's window position per pixel is (oy s + kh - p, ox s + kw - p): range-checked, a padding tap multiplies zeros (the address is clamped
+// into the map, the value replaced).  Everything else is ppo_wenc_splitk_kernel: pixel groups of 8 dealt to the 8 waves in ascending order,
+// MFMA q takes component q of the load (output column nl of accumulator 4 mh + q is K column 128 blockIdx.x + 4 nl + q), lane half = pixel
+// parity, the eight wave partials meet in LDS in the fixed order ((w0 + w4) + (w2 + w6)) + ((w1 + w5) + (w3 + w7)).
+// Property (2) of DESIGN 3.7.3: a group's loads are requested behind a VALU read of the youngest MFMA result of the group before.
+constexpr int kWgThreads = 512, kWgWaves = 8, kWgU = 4;      // kWgU pixel pairs per group
+
+struct WgradArgs {
+    const float* x;      // [n, H, W, cin]
+    const float* g;      // [n, OH, OW, cout]
+    float* part;         // [slices, cout, K]
+    int npix;            // n * OH * OW
+    int cin, cout, K, H, W, OH, OW, KW, stride, pad;
+    int pps;             // pixels per slice (even)
+    int pointwise;       // 1x1 stride 1: the window of output pixel p is input pixel p
+};
+
+template <int MH>
+struct WgStage {
+    f32x4 b[kWgU];
+    float d[kWgU][MH];
+    bool okp[kWgU], okt[kWgU];
+};
+
+template <int MH>
+__global__ __launch_bounds__(kWgThreads) void conv_wgrad_splitk_kernel(WgradArgs a) {
+    constexpr int NA = 4 * MH;
+    __shared__ float red[2][NA * 16 * 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, nl = lane & 31;
+    const int kc = blockIdx.x * 128 + 4 * nl;                 // this lane's first K column
+    const bool kok = kc < a.K;                                // (K % 4 == 0: the four columns stand or fall together)
+    const int kcc = kok ? kc : 0;
+    const int tap = kcc / a.cin, ci = kcc - tap * a.cin, kh = tap / a.KW, kw = tap - kh * a.KW;
+    const int m0 = blockIdx.y * 32 * MH;
+    const int p0 = blockIdx.z * a.pps, p1 = min(a.npix, p0 + a.pps);
+    const int ngroups = (p1 - p0 + 2 * kWgU - 1) / (2 * kWgU);
+    const int ohw = a.OH * a.OW;
+    f32x16 acc[NA];
+#pragma unroll
+    for (int q = 0; q < NA; ++q)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[q][r] = 0.f;
+
+    // branch-free: a pixel past the slice reads the slice's last pixel and takes a zero gradient; a tap in the padding reads the clamped
+    // position and takes a zero input
+    auto load = [&](int grp, WgStage<MH>& s) {
+#pragma unroll
+        for (int u = 0; u < kWgU; ++u) {
+            const int pix = p0 + (grp * kWgU + u) * 2 + half, pc = min(pix, p1 - 1);
+            size_t xoff;
+            bool ok = kok;
+            if (a.pointwise) {
+                xoff = (size_t)pc * a.cin + ci;
+            } else {
+                const int img = pc / ohw, r = pc - img * ohw, oy = r / a.OW, ox = r - oy * a.OW;
+                const int iy = oy * a.stride + kh - a.pad, ix = ox * a.stride + kw - a.pad;
+                ok = ok && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
+                const int iyc = min(max(iy, 0), a.H - 1), ixc = min(max(ix, 0), a.W - 1);
+                xoff = (((size_t)img * a.H + iyc) * a.W + ixc) * a.cin + ci;
+            }
+            s.b[u] = *reinterpret_cast<const f32x4*>(a.x + xoff);
+#pragma unroll
+            for (int mh = 0; mh < MH; ++mh) s.d[u][mh] = a.g[(size_t)pc * a.cout + m0 + 32 * mh + nl];
+            s.okp[u] = pix < p1;
+            s.okt[u] = ok;
+        }
+    };
+    auto products = [&](const WgStage<MH>& s) {
+#pragma unroll
+        for (int u = 0; u < kWgU; ++u) {
+            f32x4 b;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) b[q] = s.okt[u] ? s.b[u][q] : 0.f;
+#pragma unroll
+            for (int mh = 0; mh < MH; ++mh) {
+                const float d = s.okp[u] ? s.d[u][mh] : 0.f;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) acc[4 * mh + q] = __builtin_amdgcn_mfma_f32_32x32x2f32(d, b[q], acc[4 * mh + q], 0, 0, 0);
+            }
+        }
+    };
+    WgStage<MH> st;
+    float fence = 0.f;
+    for (int grp = wave; grp < ngroups; grp += kWgWaves) {
+        load(grp, st);
+        __builtin_amdgcn_sched_barrier(0);
+        products(st);
+#pragma unroll
+        for (int q = 0; q < NA; ++q) fence += acc[q][15];
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    asm volatile("" ::"v"(fence));      // (keeps the fence adds alive; no instruction, the result is untouched)
+
+    auto put = [&](int buf) {
+#pragma unroll
+        for (int q = 0; q < NA; ++q)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) red[buf][(q * 16 + r) * 64 + lane] = acc[q][r];
+    };
+    auto add = [&](int buf) {
+#pragma unroll
+        for (int q = 0; q < NA; ++q)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[q][r] = acc[q][r] + red[buf][(q * 16 + r) * 64 + lane];
+    };
+    // (writers, readers) per phase: w4, w5 -> w0, w1;  w6, w7 -> w2, w3;  w2, w3 -> w0, w1;  w1 -> w0
+    const int wr0[4] = {4, 6, 2, 1}, rd0[4] = {0, 2, 0, 0};
+#pragma unroll
+    for (int ph = 0; ph < 4; ++ph) {
+        const int pairs = ph == 3 ? 1 : 2;
+        if (wave >= wr0[ph] && wave < wr0[ph] + pairs) put(wave - wr0[ph]);
+        __syncthreads();
+        if (wave >= rd0[ph] && wave < rd0[ph] + pairs) add(wave - rd0[ph]);
+        __syncthreads();
+    }
+    if (wave == 0 && kok) {
+        float* o = a.part + (size_t)blockIdx.z * a.cout * a.K + kc;
+#pragma unroll
+        for (int mh = 0; mh < MH; ++mh)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int m = (r & 3) + 8 * (r >> 2) + 4 * half;
+                const f32x4 v = {acc[4 * mh][r], acc[4 * mh + 1][r], acc[4 * mh + 2][r], acc[4 * mh + 3][r]};
+                *reinterpret_cast<f32x4*>(o + (size_t)(m0 + 32 * mh + m) * a.K) = v;
+            }
+    }
+}
+
+// G[i] = part[0][i] + part[1][i] + ... in slice order
+__global__ void conv_wgrad_reduce_kernel(const float* part, int slices, size_t n, float* out) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float v = 0.f;
+    for (int s = 0; s < slices; ++s) v += part[(size_t)s * n + i];
+    out[i] = v;
+}
+
+constexpr int kWgCus = 256;      // the slice count is planned for the MI355X's 256 CUs whatever the device reports: the query needs no handle
+
+struct WgradPlan { int mh, kchunks, mchunks, slices, pps, used; };
+// pixel slices: about one block per CU, at least 64 pixels (one round of the eight waves) per slice.  Plain arithmetic.
+WgradPlan wgrad_plan(long long npix, int cout, int K) {
+    WgradPlan p;
+    p.mh = cout % 64 == 0 ? 2 : 1;
+    p.kchunks = (K + 127) / 128;
+    p.mchunks = cout / (32 * p.mh);
+    const long long tiles = (long long)p.kchunks * p.mchunks, most = (npix + 63) / 64;
+    long long s = kWgCus / (tiles > 0 ? tiles : 1);
+    if (s > most) s = most;
+    if (s < 1) s = 1;
+    p.slices = (int)s;
+    p.pps = (int)(((npix + s - 1) / s + 1) / 2 * 2);
+    p.used = (int)((npix + p.pps - 1) / p.pps);
+    return p;
+}
+
+// ---- data gradient -------------------------------------------------------------------------------------------------------------------
+// o[i][kh][kw][c] = w[c][KH - 1 - kh][KW - 1 - kw][i] * scale[c]   (scale == nullptr: 1)
+__global__ void conv_dgrad_pack_kernel(const float* __restrict__ w, const float* __restrict__ scale, int cout, int kh, int kw, int cin,
+                                       float* __restrict__ o) {
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x, total = (size_t)cin * kh * kw * cout;
+    if (idx >= total) return;
+    const int c = (int)(idx % cout);
+    size_t t = idx / cout;
+    const int x = (int)(t % kw);
+    t /= kw;
+    const int y = (int)(t % kh), i = (int)(t / kh);
+    const float v = w[(((size_t)c * kh + (kh - 1 - y)) * kw + (kw - 1 - x)) * cin + i];
+    o[idx] = scale ? v * scale[c] : v;
+}
+
+// hi[n, y, x, :] = lo[n, y / 2, x / 2, :] where y and x are even, else 0; 4 channels per thread
+__global__ void conv_zero_insert_kernel(const float* __restrict__ lo, int n, int lh, int lw, int hh, int hw, int c4, float* __restrict__ hi) {
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x, total = (size_t)n * hh * hw * c4;
+    if (idx >= total) return;
+    const int cq = (int)(idx % c4);
+    size_t t = idx / c4;
+    const int x = (int)(t % hw);
+    t /= hw;
+    const int y = (int)(t % hh), img = (int)(t / hh);
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (!(y & 1) && !(x & 1) && (y >> 1) < lh && (x >> 1) < lw)
+        v = *reinterpret_cast<const f32x4*>(lo + ((((size_t)img * lh + (y >> 1)) * lw + (x >> 1)) * c4 + cq) * 4);
+    *reinterpret_cast<f32x4*>(hi + idx * 4) = v;
+}
+
+// ---- the one-pass kernels ------------------------------------------------------------------------------------------------------------
+// out = (dy [+ dy2]) where y > 0, else 0
+__global__ void relu_backward_kernel(const float* __restrict__ dy, const float* __restrict__ dy2, const float* __restrict__ y, size_t n,
+                                     float* __restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float v = dy2 ? dy[i] + dy2[i] : dy[i];
+    out[i] = y[i] > 0.f ? v : 0.f;
+}
+
+// out[img, p, c] = dfeat[img * ldd + c] / hw  (where y[img, p, c] > 0 when y is given)
+__global__ void avgpool_backward_kernel(const float* __restrict__ dfeat, int ldd, const float* __restrict__ y, size_t total, int hw, int c,
+                                        float* __restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const int ch = (int)(i % c);
+    const size_t img = i / c / hw;
+    const float v = dfeat[img * ldd + ch] / (float)hw;
+    out[i] = (!y || y[i] > 0.f) ? v : 0.f;
+}
+
+// MaxPool2d(3, 2, 1) backward, one thread per INPUT element: it inspects the at most four windows that contain it and adds the gradient of
+// those whose arg-max it is (ascending window order).  The arg-max of a window is its first maximum in row-major order (ATen's forward keeps
+// an element only when it is greater than the best so far): an element wins iff everything before it is smaller and nothing after it is larger.
+__global__ void maxpool_backward_kernel(const float* __restrict__ x, const float* __restrict__ g, int n, int h, int w, int c, int oh, int ow,
+                                        float* __restrict__ dx) {
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x, total = (size_t)n * h * w * c;
+    if (idx >= total) return;
+    const int ch = (int)(idx % c);
+    size_t t = idx / c;
+    const int ix = (int)(t % w);
+    t /= w;
+    const int iy = (int)(t % h), img = (int)(t / h);
+    const float me = x[idx];
+    const float* xi = x + (size_t)img * h * w * c + ch;
+    float sum = 0.f;
+    for (int oy = iy / 2; oy <= (iy + 1) / 2; ++oy) {           // windows with 2 oy - 1 <= iy <= 2 oy + 1
+        if (oy >= oh) continue;
+        for (int ox = ix / 2; ox <= (ix + 1) / 2; ++ox) {
+            if (ox >= ow) continue;
+            bool win = true;
+#pragma unroll
+            for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+                for (int kx = 0; kx < 3; ++kx) {
+                    const int yy = 2 * oy - 1 + ky, xx = 2 * ox - 1 + kx;
+                    if (yy < 0 || yy >= h || xx < 0 || xx >= w || (yy == iy && xx == ix)) continue;
+                    const float v = xi[((size_t)yy * w + xx) * c];
+                    const bool before = yy < iy || (yy == iy && xx < ix);
+                    win = win && (before ? v < me : v <= me);
+                }
+            if (win) sum += g[(((size_t)img * oh + oy) * ow + ox) * c + ch];
+        }
+    }
+    dx[idx] = sum;
+}
+
+// The adjoint of TemporalShift.shift (tshift_kernel of misc_ops.hip): the forward moves the first fold channels from t + 1 and the next fold
+// from t - 1, so their gradients travel the other way; zeros at the clip ends
+__global__ void tshift_backward_kernel(const float* __restrict__ g, long long total, int c, int hw, int T, int fold, int nhwc,
+                                       float* __restrict__ o) {
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= total) return;
+    const long long frame_elems = (long long)c * hw;
+    const long long f = idx / frame_elems;
+    const int within = (int)(idx - f * frame_elems);
+    const int ch = nhwc ? within % c : within / hw;
+    const int t = (int)(f % T);
+    float v;
+    if (ch < fold) v = (t > 0) ? g[idx - frame_elems] : 0.f;               // out[t - 1] read x[t]
+    else if (ch < 2 * fold) v = (t < T - 1) ? g[idx + frame_elems] : 0.f;  // out[t + 1] read x[t]
+    else v = g[idx];
+    o[idx] = v;
+}
+
+// Column sums of g [rows, cols] for the BatchNorm gradients, in the scheme of adaf_launch_colsum (slice partials, each over its rows in a
+// fixed order, then the slices in slice order) with more slices: a gradient map has up to 10^6 rows and as few as 64 columns, which the 32
+// slices of that launcher walk as 32 blocks.  grid (ceil(cols / 64), slices), 256 threads: thread (lane, c) adds rows r0 + lane, r0 + lane + 4,
+// ... of column c in ascending order, the four lanes meet as (l0 + l1) + (l2 + l3).
+__global__ __launch_bounds__(256) void conv_colsum_partial_kernel(const float* __restrict__ x, int rows, int cols, int per, float* __restrict__ part) {
+    __shared__ float red[4][64];
+    const int cl = threadIdx.x & 63, lane = threadIdx.x >> 6, c = blockIdx.x * 64 + cl;
+    const long long r0 = (long long)blockIdx.y * per;
+    const long long r1 = r0 + per < rows ? r0 + per : rows;
+    float v = 0.f;
+    if (c < cols)
+        for (long long r = r0 + lane; r < r1; r += 4) v += x[(size_t)r * cols + c];
+    red[lane][cl] = v;
+    __syncthreads();
+    if (lane == 0 && c < cols) part[(size_t)blockIdx.y * cols + c] = (red[0][cl] + red[1][cl]) + (red[2][cl] + red[3][cl]);
+}
+__global__ void conv_colsum_final_kernel(const float* __restrict__ part, int slices, int cols, float* __restrict__ out) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= cols) return;
+    float v = 0.f;
+    for (int s = 0; s < slices; ++s) v += part[(size_t)s * cols + c];
+    out[c] = v;
+}
+// slices by the column count alone (the workspace query knows no row count): about 2048 blocks, 32 slices at least
+inline int colsum_slices(int cols) {
+    const int s = 2048 / ((cols + 63) / 64);
+    return s < 32 ? 32 : s;
+}
+
+// One block of 256 threads per output channel o, from the unscaled weight gradient G (OHWI, cin_pad channels) and the forward's packed
+// filter W (the same layout):  dW[o] = scale[o] G[o] in PyTorch's OIHW layout with the cin real channels;  dbeta[o] = colsum[o];
+// dgamma[o] = invstd[o] (<W[o], G[o]> - mean[o] colsum[o]), invstd = 1 / sqrt(var + eps): nothing divides by gamma or by the folded scale.
+// The dot product: thread t adds its columns t, t + 256, ... in ascending order, then a fixed tree over the 256 partials.
+__global__ __launch_bounds__(256) void conv_bn_param_grad_kernel(const float* __restrict__ G, const float* __restrict__ W,
+                                                                  const float* __restrict__ scale, const float* __restrict__ mean,
+                                                                  const float* __restrict__ var, float eps, const float* __restrict__ colsum,
+                                                                  int khw, int cin, int cin_pad, float* __restrict__ dw_oihw,
+                                                                  float* __restrict__ dgamma, float* __restrict__ dbeta) {
+    __shared__ float red[256];
+    const int o = blockIdx.x, tid = threadIdx.x, K = khw * cin_pad;
+    const float* go = G + (size_t)o * K;
+    const float* wo = W + (size_t)o * K;
+    const float s = scale[o];
+    float dot = 0.f;
+    for (int k = tid; k < K; k += 256) {
+        const float gv = go[k];
+        dot += wo[k] * gv;
+        const int tap = k / cin_pad, i = k - tap * cin_pad;
+        if (dw_oihw && i < cin) dw_oihw[((size_t)o * cin + i) * khw + tap] = s * gv;
+    }
+    red[tid] = dot;
+    __syncthreads();
+#pragma unroll
+    for (int step = 128; step > 0; step >>= 1) {
+        if (tid < step) red[tid] = red[tid] + red[tid + step];
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const float cs = colsum[o];
+        if (dgamma) dgamma[o] = (red[0] - mean[o] * cs) / sqrtf(var[o] + eps);
+        if (dbeta) dbeta[o] = cs;
+    }
+}
+
+// ---- host side -----------------------------------------------------------------------------------------------------------------------
+struct ConvGeom { int oh, ow; long long npix_out, npix_in; int K; };
+// the checks both gradients share; x / g / out may be null in a query
+int conv_bwd_geom(adaf_handle* h, const char* who, const adaf_conv_params* p, ConvGeom* q) {
+    if (!p) return h ? adaf_fail(h, ADAF_E_BADARG, "%s: null pointer", who) : ADAF_E_BADARG;
+    if (p->n <= 0 || p->h <= 0 || p->w <= 0 || p->cin <= 0 || p->cout <= 0 || p->kh <= 0 || p->kw <= 0 || p->stride <= 0 || p->pad < 0)
+        return h ? adaf_fail(h, ADAF_E_BADARG, "%s: non-positive extent", who) : ADAF_E_BADARG;
+    q->oh = adaf_conv_out(p->h, p->kh, p->stride, p->pad);
+    q->ow = adaf_conv_out(p->w, p->kw, p->stride, p->pad);
+    if (q->oh <= 0 || q->ow <= 0) return h ? adaf_fail(h, ADAF_E_BADARG, "%s: empty output", who) : ADAF_E_BADARG;
+    q->npix_out = (long long)p->n * q->oh * q->ow;
+    q->npix_in = (long long)p->n * p->h * p->w;
+    if (q->npix_out > 0x7fffffffLL || q->npix_in > 0x7fffffffLL) return h ? adaf_fail(h, ADAF_E_BADARG, "%s: too many pixels", who) : ADAF_E_BADARG;
+    q->K = p->kh * p->kw * p->cin;
+    if (p->cin % 4 || p->cout % 4 || (p->ldx && p->ldx != p->cin) || (p->ldo && p->ldo != p->cout) || p->tsm_segments > 0)
+        return h ? adaf_fail(h, ADAF_E_LAYOUT, "%s: dense maps with cin %% 4 == 0 and cout %% 4 == 0, no fused temporal shift", who) : ADAF_E_LAYOUT;
+    return ADAF_OK;
+}
+
+size_t wgrad_layout(void* ws, const WgradPlan& pl, int cout, int K, float** part) {
+    AdafCarver c(ws);
+    *part = c.take<float>((size_t)pl.slices * cout * K, 16);
+    return c.off;
+}
+
+// stride 1: nothing.  1x1 stride 2: the low-resolution data gradient [n, oh, ow, cin].  k x k stride 2: the zero-inserted gradient [n, h, w, cout]
+size_t dgrad_layout(void* ws, const adaf_conv_params* p, const ConvGeom& q, float** buf) {
+    AdafCarver c(ws);
+    *buf = nullptr;
+    if (p->stride == 2) *buf = c.take<float>(p->kh == 1 && p->kw == 1 ? (size_t)q.npix_out * p->cin : (size_t)q.npix_in * p->cout, 16);
+    return c.off;
+}
+
+bool dgrad_shape_ok(const adaf_conv_params* p) {
+    if (p->kh != p->kw || p->pad > p->kh - 1) return false;
+    if (p->stride == 1) return true;
+    return p->stride == 2 && ((p->kh == 1 && p->pad == 0) || (p->kh == 3 && p->pad == 1));
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t adaf_conv2d_wgrad_workspace_bytes(const adaf_conv_params* p) {
+    ConvGeom q;
+    if (conv_bwd_geom(nullptr, "", p, &q) || p->cout % 32) return 0;
+    float* part;
+    return wgrad_layout(nullptr, wgrad_plan(q.npix_out, p->cout, q.K), p->cout, q.K, &part);
+}
+
+int adaf_conv2d_wgrad_f32(adaf_handle* h, const adaf_conv_params* p, const float* x, const float* g, float* dw_ohwi, void* ws,
+                          size_t ws_bytes, void* stream) {
+    if (!h) return ADAF_E_BADARG;
+    if (!x || !g || !dw_ohwi || !ws) return adaf_fail(h, ADAF_E_BADARG, "conv_wgrad: null pointer");
+    ConvGeom q;
+    int rc = conv_bwd_geom(h, "conv_wgrad", p, &q);
+    if (rc) return rc;
+    if (p->cout % 32) return adaf_fail(h, ADAF_E_LAYOUT, "conv_wgrad: cout=%d must be a multiple of 32", p->cout);
+    if (!adaf_aligned16(x) || !adaf_aligned16(g) || !adaf_aligned16(dw_ohwi)) return adaf_fail(h, ADAF_E_LAYOUT, "conv_wgrad: 16-byte alignment");
+    const WgradPlan pl = wgrad_plan(q.npix_out, p->cout, q.K);
+    float* part;
+    if ((rc = adaf_check_ws(h, "conv_wgrad", ws, ws_bytes, wgrad_layout(ws, pl, p->cout, q.K, &part), ADAF_WS_ALIGN_FIRST))) return rc;
+    WgradArgs a;
+    a.x = x; a.g = g; a.part = part; a.npix = (int)q.npix_out;
+    a.cin = p->cin; a.cout = p->cout; a.K = q.K; a.H = p->h; a.W = p->w; a.OH = q.oh; a.OW = q.ow; a.KW = p->kw; a.stride = p->stride; a.pad = p->pad;
+    a.pps = pl.pps;
+    a.pointwise = (p->kh == 1 && p->kw == 1 && p->stride == 1 && p->pad == 0) ? 1 : 0;
+    const dim3 grid(pl.kchunks, pl.mchunks, pl.used);
+    hipStream_t st = (hipStream_t)stream;
+    if (pl.mh == 2)
+        hipLaunchKernelGGL(conv_wgrad_splitk_kernel<2>, grid, dim3(kWgThreads), 0, st, a);
+    else
+        hipLaunchKernelGGL(conv_wgrad_splitk_kernel<1>, grid, dim3(kWgThreads), 0, st, a);
+    const size_t n = (size_t)p->cout * q.K;
+    hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3(blocks_for(n)), dim3(256), 0, st, part, pl.used, n, dw_ohwi);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? ADAF_OK : adaf_hip_fail(h, e, "conv_wgrad launch");
+}
+
+int adaf_pack_conv_dgrad_weight_f32(adaf_handle* h, const float* w_ohwi, const float* scale, int cout, int kh, int kw, int cin, float* w_dgrad,
+                                    void* stream) {
+    if (!h) return ADAF_E_BADARG;
+    if (!w_ohwi || !w_dgrad || cout <= 0 || kh <= 0 || kw <= 0 || cin <= 0) return adaf_fail(h, ADAF_E_BADARG, "pack_dgrad: bad arguments");
+    hipLaunchKernelGGL(conv_dgrad_pack_kernel, dim3(blocks_for((size_t)cin * kh * kw * cout)), dim3(256), 0, (hipStream_t)stream, w_ohwi, scale,
+                       cout, kh, kw, cin, w_dgrad);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? ADAF_OK : adaf_hip_fail(h, e, "pack_dgrad launch");
+}
+
+size_t adaf_conv2d_dgrad_workspace_bytes(const adaf_conv_params* p) {
+    ConvGeom q;
+    if (conv_bwd_geom(nullptr, "", p, &q) || !dgrad_shape_ok(p)) return 0;
+    float* buf;
+    return dgrad_layout(nullptr, p, q, &buf);
+}
+
+int adaf_conv2d_dgrad_f32(adaf_handle* h, const adaf_conv_params* p, const float* g, const float* w_dgrad, float* dx, void* ws, size_t ws_bytes,
+                          void* stream) {
+    if (!h) return ADAF_E_BADARG;
+    if (!g || !w_dgrad || !dx) return adaf_fail(h, ADAF_E_BADARG, "conv_dgrad: null pointer");
+    ConvGeom q;
+    int rc = conv_bwd_geom(h, "conv_dgrad", p, &q);
+    if (rc) return rc;
+    if (!dgrad_shape_ok(p))
+        return adaf_fail(h, ADAF_E_BADARG, "conv_dgrad: square filters with pad <= k - 1; stride 1, or stride 2 as 1x1 pad 0 / 3x3 pad 1");
+    if (!adaf_aligned16(g) || !adaf_aligned16(dx)) return adaf_fail(h, ADAF_E_LAYOUT, "conv_dgrad: 16-byte alignment");
+    float* buf;
+    const size_t need = dgrad_layout(ws, p, q, &buf);
+    if (need) {
+        if (!ws) return adaf_fail(h, ADAF_E_BADARG, "conv_dgrad: null workspace");
+        if ((rc = adaf_check_ws(h, "conv_dgrad", ws, ws_bytes, need, ADAF_WS_ALIGN_FIRST))) return rc;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const bool s2 = p->stride == 2, point = p->kh == 1;
+    // the engine launch: a stride-1 convolution of a gradient map with cout channels into a map with cin channels
+    adaf_conv_params e = {};
+    e.n = p->n; e.cin = p->cout; e.cout = p->cin; e.kh = p->kh; e.kw = p->kw; e.stride = 1; e.pad = p->kh - 1 - p->pad; e.act = ADAF_ACT_NONE;
+    const float* src = g;
+    float* dst = dx;
+    if (!s2) { e.h = q.oh; e.w = q.ow; }
+    else if (point) { e.h = q.oh; e.w = q.ow; dst = buf; }         // at the low resolution, scattered afterwards
+    else {                                                          // zero-inserted to the input's size: the border comes out right for odd and even maps
+        e.h = p->h; e.w = p->w; src = buf;
+        hipLaunchKernelGGL(conv_zero_insert_kernel, dim3(blocks_for((size_t)q.npix_in * (p->cout / 4))), dim3(256), 0, st, g, p->n, q.oh, q.ow,
+                           p->h, p->w, p->cout / 4, buf);
+    }
+    ConvArgs a;
+    if ((rc = adaf_make_conv_args(h, &e, src, w_dgrad, nullptr, nullptr, nullptr, dst, &a))) return rc;
+    if (a.OH != (s2 && point ? q.oh : p->h) || a.OW != (s2 && point ? q.ow : p->w)) return adaf_fail(h, ADAF_E_BADARG, "conv_dgrad: geometry");
+    if (adaf_launch_conv_gemm(a, 0, h->cus, st) < 0) return adaf_fail(h, ADAF_E_LAUNCH, "conv_dgrad: no tile");
+    if (s2 && point)
+        hipLaunchKernelGGL(conv_zero_insert_kernel, dim3(blocks_for((size_t)q.npix_in * (p->cin / 4))), dim3(256), 0, st, buf, p->n, q.oh, q.ow,
+                           p->h, p->w, p->cin / 4, dx);
+    hipError_t er = hipGetLastError();
+    return er == hipSuccess ? ADAF_OK : adaf_hip_fail(h, er, "conv_dgrad launch");
+}
+
+int adaf_relu_backward_f32(adaf_handle* h, const float* dy, const float* dy2, const float* y, size_t count, float* out, void* stream) {
+    if (!h) return ADAF_E_BADARG;
+    if (count == 0) return ADAF_OK;
+    if (!dy || !y || !out) return adaf_fail(h, ADAF_E_BADARG, "relu_backward: null pointer");
+    hipLaunchKernelGGL(relu_backward_kernel, dim3(blocks_for(count)), dim3(256), 0, (hipStream_t)stream, dy, dy2, y, count, out);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? ADAF_OK : adaf_hip_fail(h, e, "relu_backward launch");
+}
+
+int adaf_global_avgpool_backward_f32(adaf_handle* h, const float* dfeat, int ldd, const float* y, int n, int hw, int c, float* out, void* stream) {
+    if (!h) return ADAF_E_BADARG;
+    if (!dfeat || !out || n <= 0 || hw <= 0 || c <= 0) return adaf_fail(h, ADAF_E_BADARG, "avgpool_backward: bad arguments");
+    if (ldd == 0) ldd = c;
+    if (ldd < c) return adaf_fail(h, ADAF_E_BADARG, "avgpool_backward: row stride smaller than channels");
+    const size_t total = (size_t)n * hw * c;
+    hipLaunchKernelGGL(avgpool_backward_kernel, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)stream, dfeat, ldd, y, total, hw, c, out);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? ADAF_OK : adaf_hip_fail(h, e, "avgpool_backward launch");
+}
+
+int adaf_maxpool3x3s2_backward_f32(adaf_handle* h, const float* x, const float* g, int n, int hh, int ww, int c, float* dx, void* stream) {
+    if (!h) return ADAF_E_BADARG;
+    if (!x || !g || !dx || n <= 0 || hh <= 0 || ww <= 0 || c <= 0) return adaf_fail(h, ADAF_E_BADARG, "maxpool_backward: bad arguments");
+    const size_t total = (size_t)n * hh * ww * c;
+    hipLaunchKernelGGL(maxpool_backward_kernel, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)stream, x, g, n, hh, ww, c, (hh - 1) / 2 + 1,
+                       (ww - 1) / 2 + 1, dx);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? ADAF_OK : adaf_hip_fail(h, e, "maxpool_backward launch");
+}
+
+int adaf_temporal_shift_backward_f32(adaf_handle* h, const float* g, int nt, int c, int hw, int n_segment, int fold_div, int layout, float* out,
+                                     void* stream) {
+    if (!h) return ADAF_E_BADARG;
+    if (nt == 0) return ADAF_OK;
+    if (!g || !out || nt < 0 || c <= 0 || hw <= 0 || n_segment <= 0 || fold_div <= 0) return adaf_fail(h, ADAF_E_BADARG, "tshift_backward: bad arguments");
+    if (nt % n_segment) return adaf_fail(h, ADAF_E_BADARG, "tshift_backward: nt=%d not a multiple of n_segment=%d", nt, n_segment);
+    if (layout != ADAF_LAYOUT_NCHW && layout != ADAF_LAYOUT_NHWC) return adaf_fail(h, ADAF_E_LAYOUT, "tshift_backward: layout");
+    if (g == out) return adaf_fail(h, ADAF_E_BADARG, "tshift_backward: in-place shift is not supported");
+    const long long total = (long long)nt * c * hw;
+    hipLaunchKernelGGL(tshift_backward_kernel, dim3(blocks_for((size_t)total)), dim3(256), 0, (hipStream_t)stream, g, total, c, hw, n_segment,
+                       c / fold_div, layout == ADAF_LAYOUT_NHWC ? 1 : 0, out);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? ADAF_OK : adaf_hip_fail(h, e, "tshift_backward launch");
+}
+
+// The stem of the training walk: the trunk's own stem kernel (stem.hip), whose k order is not the generic engine's -- with it the walk's
+// features are the eval engine's bit for bit.  The workspace holds the filter bank in that kernel's layout.
+size_t adaf_stem7x7_workspace_bytes(void) { return adaf_stem_weight_floats() * sizeof(float); }
+
+int adaf_stem7x7_bn_relu_f32(adaf_handle* h, const float* patches_nhwc4, int n, int patch, const float* w_oihw, const float* scale,
+                             const float* bias, float* out, void* ws, size_t ws_bytes, void* stream) {
+    if (!h) return ADAF_E_BADARG;
+    if (!patches_nhwc4 || !w_oihw || !scale || !bias || !out || !ws) return adaf_fail(h, ADAF_E_BADARG, "stem7x7: null pointer");
+    if (n <= 0 || patch <= 0) return adaf_fail(h, ADAF_E_BADARG, "stem7x7: non-positive extent");
+    if ((long long)n * patch * patch > 0x7fffffffLL) return adaf_fail(h, ADAF_E_BADARG, "stem7x7: too many pixels");
+    if (!adaf_aligned16(patches_nhwc4) || !adaf_aligned16(out) || !adaf_aligned16(scale) || !adaf_aligned16(bias))
+        return adaf_fail(h, ADAF_E_LAYOUT, "stem7x7: 16-byte alignment");
+    int rc = adaf_check_ws(h, "stem7x7", ws, ws_bytes, adaf_stem7x7_workspace_bytes(), ADAF_WS_ALIGN_FIRST);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    adaf_launch_pack_stem_weight(w_oihw, static_cast<float*>(ws), st);
+    adaf_launch_stem7x7(patches_nhwc4, n, patch, static_cast<const float*>(ws), scale, bias, out, h->cus, st);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? ADAF_OK : adaf_hip_fail(h, e, "stem7x7 launch");
+}
+
+size_t adaf_conv_bn_param_grad_workspace_bytes(int cout) {
+    if (cout <= 0) return 0;
+    AdafCarver c(nullptr);
+    c.take<float>((size_t)colsum_slices(cout) * cout, 16);
+    c.take<float>((size_t)cout, 16);
+    return c.off;
+}
+
+int adaf_conv_bn_param_grad_f32(adaf_handle* h, const float* g, int pixels, const float* dw_ohwi, const float* w_ohwi, const float* scale,
+                                const float* mean, const float* var, float eps, int cout, int kh, int kw, int cin, int cin_pad, float* dw_oihw,
+                                float* dgamma, float* dbeta, void* ws, size_t ws_bytes, void* stream) {
+    if (!h) return ADAF_E_BADARG;
+    if (!g || !dw_ohwi || !w_ohwi || !scale || !mean || !var || !ws) return adaf_fail(h, ADAF_E_BADARG, "conv_bn_param_grad: null pointer");
+    if (pixels <= 0 || cout <= 0 || kh <= 0 || kw <= 0 || cin <= 0 || cin_pad < cin) return adaf_fail(h, ADAF_E_BADARG, "conv_bn_param_grad: bad extent");
+    int rc = adaf_check_ws(h, "conv_bn_param_grad", ws, ws_bytes, adaf_conv_bn_param_grad_workspace_bytes(cout), ADAF_WS_ALIGN_FIRST);
+    if (rc) return rc;
+    AdafCarver c(ws);
+    const int slices = colsum_slices(cout), per = (pixels + slices - 1) / slices;
+    float* part = c.take<float>((size_t)slices * cout, 16);
+    float* cs = c.take<float>((size_t)cout, 16);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(conv_colsum_partial_kernel, dim3((cout + 63) / 64, slices), dim3(256), 0, st, g, pixels, cout, per, part);
+    hipLaunchKernelGGL(conv_colsum_final_kernel, dim3((cout + 255) / 256), dim3(256), 0, st, part, slices, cout, cs);
+    hipLaunchKernelGGL(conv_bn_param_grad_kernel, dim3(cout), dim3(256), 0, st, dw_ohwi, w_ohwi, scale, mean, var, eps, cs, kh * kw, cin, cin_pad,
+                       dw_oihw, dgamma, dbeta);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? ADAF_OK : adaf_hip_fail(h, e, "conv_bn_param_grad launch");
+}
+
+}  // extern "C"

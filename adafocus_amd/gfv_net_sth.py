@@ -11,6 +11,10 @@ requested, rides in the SAME pass as a second half of the batch -- then ``adaf_f
 Stage-2 training (``policy_train_mode()``: only ``focuser.policy.policy`` learns) runs the roll-out through
 ``action_stage2(training=True)`` with actions sampled from the continuous policy and the PPO update through ``Focuser.update()`` with a HIP
 backward (csrc/ppo_train.hip; the loop body is ``adafocus_amd.train.train_stage2_batch_sth``).
+
+Stage-3 training (``stage3_train_mode()``): the classifier Linear and, as in the reference's recipe, the local CNN's convolutions and
+BatchNorm affine parameters learn through ``action_stage3`` (csrc/conv_bwd.hip, trunk_train.py; the loop body is
+``adafocus_amd.train.train_stage3_batch_sth``).
 """
 import math
 
@@ -32,20 +36,22 @@ __all__ = ["GFV", "Glancer", "Focuser", "PatchSampler"]
 
 
 class _FcMeanPool(torch.autograd.Function):
-    """mean_t FC(f_t) (+ mean_t glancer logits) with a backward for the CLASSIFIER parameters -- all that stage 3 of this
-    build trains (STH/stage3.py:351-353 with the local CNN frozen).  Forward = adaf_fc_meanpool_forward_f32; backward =
-    two GEMMs on the conv engine:  dW = g^T . mean_t(f)  and  db = g^T . 1  (d mean_t FC(f_t) / dW = mean_t f_t)."""
+    """mean_t FC(f_t) (+ mean_t glancer logits) with a backward for the classifier parameters and, when the features carry a graph
+    (the local CNN is fine-tuned: stage3_train_mode), for the features (STH/stage3.py:351-353).  Forward =
+    adaf_fc_meanpool_forward_f32; backward = GEMMs on the conv engine:  dW = g^T . mean_t(f),  db = g^T . 1
+    (d mean_t FC(f_t) / dW = mean_t f_t)  and  dfeat[b, t] = (g[b] W) / T for every frame row of clip b."""
 
     @staticmethod
     def forward(ctx, feat, weight, bias, glog, batch):
-        ctx.save_for_backward(feat)
+        ctx.save_for_backward(feat, weight.detach())
         ctx.batch = batch
         return hip_ops.fc_meanpool_forward(feat, batch, weight.detach(), bias.detach(), glog)
 
     @staticmethod
     def backward(ctx, g):
-        (feat,) = ctx.saved_tensors
+        feat, weight = ctx.saved_tensors
         b = ctx.batch
+        g = g.contiguous()
         t = feat.shape[0] // b
         mean_feat = hip_ops.global_avgpool(feat.view(b, t, 1, -1))              # (B, F) = mean_t f_t
         bp = (b + 3) // 4 * 4                                                     # the engine wants K % 4 == 0
@@ -57,7 +63,19 @@ class _FcMeanPool(torch.autograd.Function):
         ones[0, :b] = 1.0
         dw = hip_ops.linear(gt, mt)                                               # (C, F)
         db = hip_ops.linear(gt, ones)[:, 0].contiguous()                          # (C,)
-        return None, dw, db, None, None
+        dfeat = None
+        if ctx.needs_input_grad[0]:
+            # (g W) / T once per clip on the engine (the 1 / T rides as the per-column scale: one rounding after the sum), then the
+            # same row for each of the clip's T frames
+            cp = (g.shape[1] + 3) // 4 * 4
+            gp = torch.zeros((b, cp), device=g.device, dtype=torch.float32)
+            gp[:, :g.shape[1]] = g
+            wt = torch.zeros((weight.shape[1], cp), device=g.device, dtype=torch.float32)
+            wt[:, :g.shape[1]] = weight.t()
+            inv_t = torch.full((weight.shape[1],), 1.0 / t, device=g.device, dtype=torch.float32)
+            row = hip_ops.conv2d_bn_act(gp.view(b, 1, 1, cp), wt.view(weight.shape[1], 1, 1, cp), inv_t, None)
+            dfeat = row.view(b, 1, -1).expand(b, t, weight.shape[1]).reshape(b * t, -1)
+        return dfeat, dw, db, None, None
 
 
 class GFV(nn.Module):
@@ -112,17 +130,27 @@ class GFV(nn.Module):
         return fm.unflatten(0, (b, t)), logit.view(b, t, -1)
 
     def _stage(self, focuser_image, global_feat_map, global_feat_logit, step, args, prev_local_patch, with_baseline,
-               forced_action=None, baseline_action=None, train_classifier=False, sample=False, noise=None):
+               forced_action=None, baseline_action=None, train_classifier=False, sample=False, noise=None, train_local=False,
+               dropout_mask=None):
         if self.training and not train_classifier:
             raise RuntimeError("adafocus_amd: eval mode only (stage 3 trains the classifier through action_stage3)")
+        if train_local and args.video_div != 1:
+            raise NotImplementedError("stage-3 training of the local CNN is implemented for video_div == 1 only, as the reference asserts "
+                                      "(STH/stage3.py:347); got video_div = %d" % args.video_div)
         with torch.no_grad():
             feat, local_patch, action, b, frames_total, ngroups = self._stage_features(
-                focuser_image, global_feat_map, step, args, prev_local_patch, with_baseline, forced_action, baseline_action, sample, noise)
+                focuser_image, global_feat_map, step, args, prev_local_patch, with_baseline, forced_action, baseline_action, sample, noise,
+                patches_only=train_local)
         per = b * frames_total
         glog = global_feat_logit if self.with_glancer else None
+        if train_local:
+            # STH/models/gfv_net.py:213-216: the action and the crop are constants, the patches go through the local CNN with grad
+            feat = self.focuser.net.features_train_nhwc4(feat)
         if train_classifier:
-            # stage 3 (STH/stage3.py:351-353): the patches and local features are constants, the classifier learns
-            f = self.dropout(feat[:per]) if self.training else feat[:per]
+            # stage 3 (STH/stage3.py:351-353): the classifier learns; with train_local the features carry the trunk's graph
+            f = feat[:per]
+            if self.training:
+                f = self.dropout(f) if dropout_mask is None else f * dropout_mask.to(device=f.device, dtype=f.dtype)
             return [_FcMeanPool.apply(f, self.classifier.weight, self.classifier.bias, glog, b)], local_patch, action
         with torch.no_grad():
             logits = [hip_ops.fc_meanpool_forward(feat[g * per:(g + 1) * per], b, self.classifier.weight.detach(),
@@ -130,7 +158,7 @@ class GFV(nn.Module):
         return logits, local_patch, action
 
     def _stage_features(self, focuser_image, global_feat_map, step, args, prev_local_patch, with_baseline, forced_action,
-                        baseline_action, sample=False, noise=None):
+                        baseline_action, sample=False, noise=None, patches_only=False):
         nfg = args.num_segments_glancer // args.video_div
         nff = args.num_segments_focuser // args.video_div
         b, _, c, hh, ww = focuser_image.shape
@@ -164,7 +192,9 @@ class GFV(nn.Module):
             groups.append(nchw_to_nhwc4(base_patch.reshape(b * frames_total, 3, p, p)))
         # the temporal shift views its input as clips of num_segments_focuser frames -- fixed at construction, as in the
         # reference (tsn.py / temporal_shift.py:103): with video_div > 1 the partial passes shift across clip pairs
-        feat = self.focuser.net.features_nhwc4(torch.cat(groups, 0) if len(groups) > 1 else groups[0])
+        patches4 = torch.cat(groups, 0) if len(groups) > 1 else groups[0]
+        # (patches_only: the pixel-major patches in place of the features -- the caller runs the differentiable walk on them)
+        feat = patches4 if patches_only else self.focuser.net.features_nhwc4(patches4)
         return feat, local_patch, action, b, frames_total, len(groups)
 
     # ---- the same two calls for frames that are already normalised pixel-major (uint8 ingest, evaluate.validate_sth) ----------
@@ -247,16 +277,34 @@ class GFV(nn.Module):
         self.focuser.policy.policy.train()
         self.focuser.policy.policy_old.train()
 
+    def stage3_train_mode(self, train_local=True):
+        """The mode of STH/stage3.py:313-317: the model in train mode, glancer, focuser and both policies in eval mode (BatchNorm on its
+        running statistics, dropout live).  train_local = the local CNN is fine-tuned as the reference's optimizer asks
+        (STH/stage3.py:189-193 lists focuser.net.get_optim_policies()): action_stage3 then runs the patches through the differentiable
+        trunk walk (trunk_train.py).  train_local=False trains the classifier Linear only, on the engine's features."""
+        self.train()
+        self.glancer.eval()
+        self.focuser.eval()
+        if self.focuser.policy is not None:
+            self.focuser.policy.policy.eval()
+            self.focuser.policy.policy_old.eval()
+        self.focuser.net.base_model.set_trainable(train_local)
+
     def action_stage3(self, focuser_image, global_feat_map, global_feat_logit, focus_time_step, args,
-                      prev_local_patch=None, forced_action=None):
+                      prev_local_patch=None, forced_action=None, dropout_mask=None):
         """STH/models/gfv_net.py:190-225 -> (total_logit, local_patch).  In eval mode this is the inference forward.  With
         grad enabled and the classifier's parameters requiring grad (stage-3 training, STH/stage3.py:313-317,351-353:
         model.train() with glancer / focuser / policy in eval mode) `total_logit` carries an autograd graph into
-        classifier.weight / classifier.bias; the local CNN runs without grad on the HIP trunk (its fine-tuning -- the
-        reference's optimizer also lists the focuser backbone -- is training code beyond this build's scope)."""
+        classifier.weight / classifier.bias.  After `stage3_train_mode()` (the local CNN is trainable) the graph also reaches every conv
+        weight and BatchNorm weight / bias of the focuser's ResNet that requires grad, through the HIP backward of trunk_train.py: the
+        action and the crop are computed without grad, as in the reference (:196-212).  Otherwise the local CNN runs without grad on
+        the engine.  dropout_mask (B * Tf, 2048), the multipliers 0 or 1 / (1 - p), replaces the dropout's own draw in training mode
+        (as RecurrentClassifier.forward(mask=)); video_div > 1 with a trainable local CNN raises (STH/stage3.py:347)."""
         train = self.training and torch.is_grad_enabled() and self.classifier.weight.requires_grad
+        local = train and self.focuser.net.base_model.trainable
         logits, local_patch, _ = self._stage(focuser_image, global_feat_map, global_feat_logit, focus_time_step, args,
-                                             prev_local_patch, False, forced_action, train_classifier=train)
+                                             prev_local_patch, False, forced_action, train_classifier=train, train_local=local,
+                                             dropout_mask=dropout_mask)
         return logits[0], local_patch
 
     @torch.no_grad()

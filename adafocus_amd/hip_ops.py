@@ -486,6 +486,135 @@ def ppo_encoder_backward(states, e1, e_bt, dx_bt, t, b, w_lin_pm, bn=None):
     return (dw_enc, dw_lin, db_lin) + extra
 
 
+# ---- stage-3 training of the local CNN: backward of the trunk's convolutions (csrc/conv_bwd.hip) -----------------------------
+def _bwd_params(x_shape, w_shape, stride, pad):
+    n, hh, ww, cin = x_shape
+    cout, kh, kw, cin_w = w_shape
+    if cin_w != cin:
+        raise ValueError("conv backward: the map has %d channels, the filter expects %d" % (cin, cin_w))
+    p = L.ConvParams(n=n, h=hh, w=ww, cin=cin, cout=cout, kh=kh, kw=kw, stride=stride, pad=pad, act=ACT_NONE, tsm_segments=0, tsm_div=0, ldx=0,
+                     ldo=0, ldr=0, tile=0)
+    return p, (n, (hh + 2 * pad - kh) // stride + 1, (ww + 2 * pad - kw) // stride + 1, cout)
+
+
+def stem7x7_bn_relu(patches_nhwc4, w_oihw, scale, bias):
+    """The trunk's stem on its own kernel: (N,P,P,4) patches, w (64,3,7,7) in PyTorch's layout, folded BN -> (N,OH,OH,64) after ReLU;
+    the bits of the ResNet50Trunk's stem (the generic engine adds the 147 products in another order)."""
+    L.need_gpu_f32(patches_nhwc4, w_oihw, scale, bias)
+    x, w, scale, bias = (t.contiguous() for t in (patches_nhwc4, w_oihw, scale, bias))
+    n, p, p2, c = x.shape
+    if c != 4 or p != p2 or tuple(w.shape) != (64, 3, 7, 7):
+        raise ValueError("stem7x7_bn_relu: square (N,P,P,4) patches and a (64,3,7,7) filter expected")
+    oh = (p - 1) // 2 + 1
+    ws, ws_bytes = _workspace("adaf_stem7x7_workspace_bytes", x.device)
+    out = torch.empty((n, oh, oh, 64), device=x.device, dtype=torch.float32)
+    _call("adaf_stem7x7_bn_relu_f32", x, x, n, p, w, scale, bias, out, ws, ws_bytes)
+    return out
+
+
+def conv2d_wgrad(x, g, w_shape, stride=1, pad=0):
+    """The UNSCALED weight gradient of a convolution: x (N,H,W,Cin), g (N,OH,OW,Cout) the gradient at the convolution's output, w_shape
+    (Cout,KH,KW,Cin) -> (Cout,KH,KW,Cin).  Deterministic (same inputs, same bits)."""
+    L.need_gpu_f32(x, g)
+    x, g = x.contiguous(), g.contiguous()
+    p, g_shape = _bwd_params(x.shape, w_shape, stride, pad)
+    if tuple(g.shape) != g_shape:
+        raise ValueError("conv2d_wgrad: gradient of shape %s expected, got %s" % (g_shape, tuple(g.shape)))
+    ws, ws_bytes = _workspace("adaf_conv2d_wgrad_workspace_bytes", x.device, C.byref(p))
+    dw = torch.empty(tuple(w_shape), device=x.device, dtype=torch.float32)
+    _call("adaf_conv2d_wgrad_f32", x, C.byref(p), x, g, dw, ws, ws_bytes)
+    return dw
+
+
+def pack_conv_dgrad_weight(w_ohwi, scale=None):
+    """(Cout,KH,KW,Cin) -> (Cin,KH,KW,Cout): transposed, rotated by 180 degrees, times scale per output channel -- conv2d_dgrad's filter."""
+    L.need_gpu_f32(w_ohwi, scale)
+    w_ohwi = w_ohwi.contiguous()
+    cout, kh, kw, cin = w_ohwi.shape
+    out = torch.empty((cin, kh, kw, cout), device=w_ohwi.device, dtype=torch.float32)
+    _call("adaf_pack_conv_dgrad_weight_f32", w_ohwi, w_ohwi, _dense(scale), cout, kh, kw, cin, out)
+    return out
+
+
+def conv2d_dgrad(g, w_dgrad, x_shape, stride=1, pad=0):
+    """The gradient at a convolution's input, on the forward engine: g (N,OH,OW,Cout), w_dgrad of pack_conv_dgrad_weight, x_shape
+    (N,H,W,Cin) -> (N,H,W,Cin)."""
+    L.need_gpu_f32(g, w_dgrad)
+    g, w_dgrad = g.contiguous(), w_dgrad.contiguous()
+    cin, kh, kw, cout = w_dgrad.shape
+    p, g_shape = _bwd_params(x_shape, (cout, kh, kw, cin), stride, pad)
+    if tuple(g.shape) != g_shape:
+        raise ValueError("conv2d_dgrad: gradient of shape %s expected, got %s" % (g_shape, tuple(g.shape)))
+    ws, ws_bytes = _workspace("adaf_conv2d_dgrad_workspace_bytes", g.device, C.byref(p))
+    dx = torch.empty(tuple(x_shape), device=g.device, dtype=torch.float32)
+    _call("adaf_conv2d_dgrad_f32", g, C.byref(p), g, w_dgrad, dx, ws, ws_bytes)
+    return dx
+
+
+def relu_backward(dy, y, dy2=None):
+    """(dy [+ dy2]) where y > 0, else 0: ReLU backward with the residual join's second gradient."""
+    L.need_gpu_f32(dy, y, dy2)
+    dy, y, dy2 = dy.contiguous(), y.contiguous(), _dense(dy2)
+    if dy.shape != y.shape or (dy2 is not None and dy2.shape != y.shape):
+        raise ValueError("relu_backward: shapes differ")
+    out = torch.empty_like(y)
+    _call("adaf_relu_backward_f32", y, dy, dy2, y, y.numel(), out)
+    return out
+
+
+def global_avgpool_backward(dfeat, y_shape, y=None):
+    """dfeat (N,C) -> (N,H,W,C) = dfeat / (H W) on every pixel; y given: zero where y <= 0 (the ReLU in front of the pool folded in)."""
+    L.need_gpu_f32(dfeat, y)
+    dfeat, y = dfeat.contiguous(), _dense(y)
+    n, hh, ww, c = y_shape
+    if tuple(dfeat.shape) != (n, c) or (y is not None and tuple(y.shape) != tuple(y_shape)):
+        raise ValueError("global_avgpool_backward: shapes differ")
+    out = torch.empty(tuple(y_shape), device=dfeat.device, dtype=torch.float32)
+    _call("adaf_global_avgpool_backward_f32", dfeat, dfeat, c, y, n, hh * ww, c, out)
+    return out
+
+
+def maxpool3x3s2_backward(x, g):
+    """nn.MaxPool2d(3, 2, 1) backward: x (N,H,W,C) the pool's input, g (N,OH,OW,C) -> (N,H,W,C); ATen's arg-max on ties."""
+    L.need_gpu_f32(x, g)
+    x, g = x.contiguous(), g.contiguous()
+    n, hh, ww, c = x.shape
+    if tuple(g.shape) != (n, (hh - 1) // 2 + 1, (ww - 1) // 2 + 1, c):
+        raise ValueError("maxpool3x3s2_backward: gradient shape")
+    dx = torch.empty_like(x)
+    _call("adaf_maxpool3x3s2_backward_f32", x, x, g, n, hh, ww, c, dx)
+    return dx
+
+
+def temporal_shift_backward(g, n_segment, fold_div, layout=LAYOUT_NCHW):
+    """The adjoint of temporal_shift (same arguments)."""
+    L.need_gpu_f32(g)
+    g = g.contiguous()
+    if layout == LAYOUT_NCHW:
+        nt, c, hh, ww = g.shape
+    else:
+        nt, hh, ww, c = g.shape
+    out = torch.empty_like(g)
+    _call("adaf_temporal_shift_backward_f32", g, g, nt, c, hh * ww, int(n_segment), int(fold_div), layout, out)
+    return out
+
+
+def conv_bn_param_grad(g, dw_ohwi, w_ohwi, scale, mean, var, eps, cin, want_dw=True, want_affine=True):
+    """Parameter gradients of conv + BatchNorm(eval) from g (N,OH,OW,Cout), the unscaled dw_ohwi of conv2d_wgrad and the forward's packed
+    filter: -> (dW (Cout,cin,KH,KW) = scale * dw or None, dgamma, dbeta (Cout,) or None).  Nothing divides by gamma."""
+    L.need_gpu_f32(g, dw_ohwi, w_ohwi, scale, mean, var)
+    g, dw_ohwi, w_ohwi, scale, mean, var = (t.contiguous() for t in (g, dw_ohwi, w_ohwi, scale, mean, var))
+    cout, kh, kw, cin_pad = w_ohwi.shape
+    dev = g.device
+    ws, ws_bytes = _workspace("adaf_conv_bn_param_grad_workspace_bytes", dev, cout)
+    dw = torch.empty((cout, cin, kh, kw), device=dev, dtype=torch.float32) if want_dw else None
+    dgamma = torch.empty((cout,), device=dev, dtype=torch.float32) if want_affine else None
+    dbeta = torch.empty((cout,), device=dev, dtype=torch.float32) if want_affine else None
+    _call("adaf_conv_bn_param_grad_f32", g, g, g.numel() // cout, dw_ohwi, w_ohwi, scale, mean, var, float(eps), cout, kh, kw, int(cin), cin_pad,
+          dw, dgamma, dbeta, ws, ws_bytes)
+    return dw, dgamma, dbeta
+
+
 def fc_meanpool_forward(feat, batch, fc_w, fc_b, global_logit=None):
     """mean_t FC(f_t) (+ mean_t glancer logits) -- STH/models/gfv_net.py:164-174.
     feat (B*T,F); global_logit (B,Tg,C) or None -> (B,C)."""

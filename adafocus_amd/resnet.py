@@ -138,6 +138,28 @@ class ResNet(nn.Module):
         """The arithmetic the trunk runs with ("f32" | "split_bf16" | "f16")."""
         return getattr(self, "_math", None) or DEFAULT_MATH
 
+    def set_trainable(self, on):
+        """Stage-3 fine-tuning of the Something-Something tree (STH/stage3.py:189-193): on = ``features_train_nhwc4`` is available, the
+        walk of trunk_train.py with a HIP backward into every conv weight and BatchNorm weight / bias that requires grad.  Off (the
+        default) nothing changes.  fp32 only: with set_math("split_bf16" | "f16") the training walk raises NotImplementedError."""
+        self._trainable = bool(on)
+
+    @property
+    def trainable(self):
+        return getattr(self, "_trainable", False)
+
+    def features_train_nhwc4(self, patches_nhwc4):
+        """features_nhwc4 with an autograd graph into the trunk's parameters: BatchNorm on its running statistics (the module is in eval
+        mode, as STH/stage3.py:313-317 puts the focuser), the same bits as the eval engine's features.  After optimizer.step() the
+        parameter versions change and the next features_nhwc4 re-packs the engine's weights (_sync)."""
+        if not self.trainable:
+            raise RuntimeError("adafocus_amd.ResNet: the training walk is off; call set_trainable(True) first")
+        if self.training:
+            raise RuntimeError("adafocus_amd.ResNet trains with frozen BatchNorm statistics only (stage 3: the focuser is in eval mode); "
+                               "BatchNorm in batch-statistics mode is not implemented")
+        from . import trunk_train
+        return trunk_train.trunk_features(self, patches_nhwc4)
+
     # ---- reference surface --------------------------------------------------------------
     def features_nhwc4(self, patches_nhwc4, out=None):
         """Fast path used by the Focuser: (N,P,P,4) pixel-major patches -> (N,2048)."""

@@ -11,13 +11,16 @@ trunk pass over the B*T crops) and the rewards from one kernel; same contract, s
 
 Both CNNs and the classifier stay frozen and run on the HIP path; only ``focuser.policy.policy`` learns (``PPO.update``: HIP forward and
 backward, PyTorch's Adam step).
+
+``train_stage3_batch_sth`` is the stage-3 loop body of the Something-Something tree (STH/stage3.py:339-375 without AMP): the classifier
+Linear and the local CNN learn (HIP forward and backward, PyTorch's SGD step on .grad); glancer and policy stay frozen.
 """
 import torch
 import torch.nn.functional as F
 
 from . import hip_ops
 
-__all__ = ["get_reward", "train_stage2_batch", "train_stage2_batch_fused", "train_stage2_batch_sth"]
+__all__ = ["get_reward", "train_stage2_batch", "train_stage2_batch_fused", "train_stage2_batch_sth", "train_stage3_batch_sth"]
 
 
 def get_reward(args, confidence, confidence_last, baseline):
@@ -107,3 +110,23 @@ def train_stage2_batch_sth(model, glancer_images, focuser_images, target, args, 
         model.focuser.memory.rewards.append(reward)
     model.focuser.update()
     return pred, loss, rewards
+
+
+def train_stage3_batch_sth(model, glancer_images, focuser_images, target, args, optimizer, dropout_mask=None):
+    """One batch of stage-3 training of the Something-Something model (STH/stage3.py:339-375, the branch without AMP;
+    `model.stage3_train_mode()` first, optimizer = SGD(model.focuser.net.get_optim_policies() + [classifier]) as :189-193 builds it).
+    glancer_images (B, Tg*3, g, g) already at the glance size, focuser_images (B, Tf*3, H, W), both normalised fp32 on the GPU, target (B,)
+    int64.  zero_grad, glance without grad, action_stage3, cross-entropy, backward, optimizer.step().  dropout_mask (B*Tf, 2048) steers the
+    dropout's draw (None: nn.Dropout's own).  Returns (the prediction (B, C), the loss)."""
+    if args.video_div != 1:
+        raise NotImplementedError("stage 3 is implemented for video_div == 1 only, as the reference asserts (STH/stage3.py:347)")
+    b = target.shape[0]
+    frames = focuser_images.view(b, args.num_segments_focuser, 3, focuser_images.shape[-2], focuser_images.shape[-1])
+    optimizer.zero_grad()
+    with torch.no_grad():
+        global_feat_map, global_feat_logit = model.glance(glancer_images)
+    pred, _ = model.action_stage3(frames, global_feat_map, global_feat_logit, 0, args, prev_local_patch=None, dropout_mask=dropout_mask)
+    loss = F.cross_entropy(pred, target)
+    loss.backward()
+    optimizer.step()
+    return pred.detach(), loss.detach()

@@ -34,6 +34,7 @@ class TSN(nn.Module):
         self.modality, self.num_segments, self.reshape = modality, num_segments, False
         self.is_shift, self.shift_div, self.shift_place = is_shift, shift_div, shift_place
         self.new_length = 1
+        self._enable_pbn = bool(partial_bn)      # STH/models/tsn.py:86-88
         self._stripped = False
         object.__setattr__(self, "_in_init", True)
         self.base_model = ResNet(num_classes=1000, layers=DEPTHS[base_model])
@@ -104,8 +105,44 @@ class TSN(nn.Module):
     def features_from_frames(self, frames, actions, patch_size, frames_per_action=1, out=None):
         return self.base_model.features_from_frames(frames, actions, patch_size, frames_per_action, out=out)
 
+    def features_train_nhwc4(self, patches_nhwc4):
+        return self.base_model.features_train_nhwc4(patches_nhwc4)
+
+    def train(self, mode=True):
+        """STH/models/tsn.py:146-162: with partial BN, train mode freezes the affine parameters of every BatchNorm2d of the base model
+        but the first (requires_grad = False; they stay frozen afterwards, as in the reference).  BatchNorm statistics are frozen in
+        every mode here: the trunk runs BatchNorm on its running statistics only."""
+        super().train(mode)
+        if getattr(self, "_enable_pbn", False) and mode:
+            bns = [m for m in self.base_model.modules() if isinstance(m, nn.BatchNorm2d)]
+            for m in bns[1:]:
+                m.eval()
+                m.weight.requires_grad = False
+                m.bias.requires_grad = False
+        return self
+
     def partialBN(self, enable):
         self._enable_pbn = enable
+
+    def get_optim_policies(self):
+        """STH/models/tsn.py:167-213: the five parameter groups stage 3 hands to SGD, with the reference's names, lr_mult and decay_mult.
+        The first convolution's weight; (no convolution has a bias: both bias groups are empty); every other convolution's weight;
+        the BatchNorm weights and biases -- all of them, or with partial BN only the first BatchNorm's."""
+        convs = [m for m in self.modules() if isinstance(m, nn.Conv2d)]
+        bns = [m for m in self.modules() if isinstance(m, nn.BatchNorm2d)]
+        for m in self.modules():
+            if not m._modules and not isinstance(m, (nn.Conv2d, nn.BatchNorm2d)) and list(m.parameters()) and m is not self.base_model.fc:
+                raise ValueError("New atomic module type: %s. Need to give it a learning policy" % type(m))
+        first_w, normal_w = [convs[0].weight], [m.weight for m in convs[1:]]
+        first_b = [convs[0].bias] if convs[0].bias is not None else []
+        normal_b = [m.bias for m in convs[1:] if m.bias is not None]
+        bn = [p for m in (bns[:1] if getattr(self, "_enable_pbn", False) else bns) for p in m.parameters()]
+        flow = self.modality == "Flow"
+        return [{"params": first_w, "lr_mult": 5 if flow else 1, "decay_mult": 1, "name": "first_conv_weight"},
+                {"params": first_b, "lr_mult": 10 if flow else 2, "decay_mult": 0, "name": "first_conv_bias"},
+                {"params": normal_w, "lr_mult": 1, "decay_mult": 1, "name": "normal_weight"},
+                {"params": normal_b, "lr_mult": 2, "decay_mult": 0, "name": "normal_bias"},
+                {"params": bn, "lr_mult": 1, "decay_mult": 0, "name": "BN scale/shift"}]
 
     @property
     def feature_dim(self):

@@ -681,6 +681,65 @@ int adaf_ppo_encoder_bn_backward_f32(adaf_handle* h, const float* states, const 
                                      float* db_lin, float* dgamma1, float* dbeta1, float* dgamma2, float* dbeta2, void* ws, size_t ws_bytes,
                                      void* stream);
 
+/* ---- a4/a5 training (stage 3 of the Something-Something tree): backward of the trunk's convolutions (csrc/conv_bwd.hip) ----
+ * STH/stage3.py:189-193 hands focuser.net.get_optim_policies() to the optimizer and :313-317 keeps the focuser in eval mode: every
+ * convolution and BatchNorm affine parameter of the TSM-ResNet is fine-tuned with FROZEN BatchNorm statistics.  The forward is
+ * adaf_conv2d_bn_act_f32 per layer with the layer outputs kept; these are the adjoints.  fp32, dense NHWC maps (ldx / ldo 0 or the
+ * channel count), OHWI filters, no atomics: the same inputs give the same bits.  adaf_conv_params.act / tile / tsm_* are not read
+ * (tsm_segments > 0 is ADAF_E_LAYOUT: shift the map first, adaf_temporal_shift_f32).
+ *
+ * adaf_conv2d_wgrad_f32: dw_ohwi[o, kh, kw, i] = sum over output pixels (n, y, x) of g[n, y, x, o] * x[n, y s + kh - p, x s + kw - p, i],
+ *   taps in the padding read zeros.  x [n, h, w, cin], g [n, oh, ow, cout] the gradient at the convolution's output (in front of the BN
+ *   affine: UNSCALED), dw_ohwi [cout, kh, kw, cin].  Any kh, kw, stride, pad; cin % 4 == 0, cout % 32 == 0.  One split-K launch over
+ *   pixel slices on v_mfma_f32_32x32x2_f32 with 16-byte loads, then the slice partials added in slice order.
+ *   Workspace: adaf_conv2d_wgrad_workspace_bytes(p) (the slice partials; 0 for a description the call refuses).
+ * adaf_pack_conv_dgrad_weight_f32: w_dgrad[i, kh, kw, o] = w_ohwi[o, KH-1-kh, KW-1-kw, i] * scale[o] (scale may be NULL = 1): the filter
+ *   transposed and rotated by 180 degrees with the folded BN scale multiplied in.
+ * adaf_conv2d_dgrad_f32: dx [n, h, w, cin] = the gradient at the convolution's input from g [n, oh, ow, cout] and w_dgrad, as a stride-1
+ *   convolution on the forward engine (adaf_conv2d_bn_act_f32's kernels: the same fma chains whatever the tile).  Square filters with
+ *   pad <= k - 1.  stride 1: one engine launch.  stride 2, 1x1 pad 0: the engine at the low resolution into the workspace, then scattered
+ *   into the even positions of a zeroed dx.  stride 2, 3x3 pad 1: g zero-inserted to h x w in the workspace (even and odd h, w), then the
+ *   stride-1 form.  Anything else is ADAF_E_BADARG.  Workspace: adaf_conv2d_dgrad_workspace_bytes(p): 0 for stride 1 (ws may be NULL).
+ * adaf_relu_backward_f32: out[i] = (dy[i] + dy2[i]) where y[i] > 0, else 0 (dy2 may be NULL): ReLU backward with the residual join.
+ * adaf_global_avgpool_backward_f32: out[img, pixel, ch] = dfeat[img * ldd + ch] / hw, zero where y[img, pixel, ch] <= 0 when y is given
+ *   (the last block's ReLU folded in); ldd 0 = c.
+ * adaf_maxpool3x3s2_backward_f32: nn.MaxPool2d(3, 2, 1) backward in gather form: x [n, hh, ww, c] the pool's input, g [n, oh, ow, c];
+ *   dx[pixel] = sum of g over the at most four windows whose arg-max the pixel is.  A window's arg-max is its first maximum in row-major
+ *   order, as in ATen.
+ * adaf_temporal_shift_backward_f32: the adjoint of adaf_temporal_shift_f32 (same arguments): the first fold channels take the gradient
+ *   of frame t - 1, the next fold that of frame t + 1, zeros at the clip ends.  A move, hence exact.
+ * adaf_conv_bn_param_grad_f32: the parameter gradients of conv + BatchNorm(eval) from g [pixels, cout], the UNSCALED dw_ohwi of
+ *   adaf_conv2d_wgrad_f32 and the forward's filter w_ohwi (both [cout, kh, kw, cin_pad]); scale = gamma / sqrt(var + eps) as adaf_fold_bn_f32:
+ *   dw_oihw [cout, cin, kh, kw] = scale[o] * dw_ohwi[o] (PyTorch's layout, the cin real channels); dbeta[o] = sum_p g[p, o];
+ *   dgamma[o] = (<w_ohwi[o], dw_ohwi[o]> - mean[o] * dbeta[o]) / sqrt(var[o] + eps) -- the pre-BN map is never needed, and nothing divides
+ *   by gamma or by scale (gamma = 0 is a legal checkpoint value).  dw_oihw, dgamma, dbeta may each be NULL = not wanted.
+ *   Workspace: adaf_conv_bn_param_grad_workspace_bytes(cout).
+ * adaf_stem7x7_bn_relu_f32: the trunk's stem as a launch of its own -- conv 7x7 / 2 / pad 3 of patches_nhwc4 [n, patch, patch, 4] with
+ *   w_oihw [64, 3, 7, 7] (PyTorch's layout), BN affine (scale, bias [64]) and ReLU into out [n, oh, oh, 64] -- on the stem kernel the
+ *   adaf_resnet50_* object uses (its k order differs from adaf_conv2d_bn_act_f32's: these are the trunk's bits).
+ *   Workspace: adaf_stem7x7_workspace_bytes() (the filter bank in the kernel's layout).
+ * The workspace queries are plain arithmetic (no device needed). */
+size_t adaf_stem7x7_workspace_bytes(void);
+int adaf_stem7x7_bn_relu_f32(adaf_handle* h, const float* patches_nhwc4, int n, int patch, const float* w_oihw, const float* scale,
+                             const float* bias, float* out, void* ws, size_t ws_bytes, void* stream);
+size_t adaf_conv2d_wgrad_workspace_bytes(const adaf_conv_params* p);
+int adaf_conv2d_wgrad_f32(adaf_handle* h, const adaf_conv_params* p, const float* x, const float* g, float* dw_ohwi, void* ws,
+                          size_t ws_bytes, void* stream);
+int adaf_pack_conv_dgrad_weight_f32(adaf_handle* h, const float* w_ohwi, const float* scale, int cout, int kh, int kw, int cin, float* w_dgrad,
+                                    void* stream);
+size_t adaf_conv2d_dgrad_workspace_bytes(const adaf_conv_params* p);
+int adaf_conv2d_dgrad_f32(adaf_handle* h, const adaf_conv_params* p, const float* g, const float* w_dgrad, float* dx, void* ws, size_t ws_bytes,
+                          void* stream);
+int adaf_relu_backward_f32(adaf_handle* h, const float* dy, const float* dy2, const float* y, size_t count, float* out, void* stream);
+int adaf_global_avgpool_backward_f32(adaf_handle* h, const float* dfeat, int ldd, const float* y, int n, int hw, int c, float* out, void* stream);
+int adaf_maxpool3x3s2_backward_f32(adaf_handle* h, const float* x, const float* g, int n, int hh, int ww, int c, float* dx, void* stream);
+int adaf_temporal_shift_backward_f32(adaf_handle* h, const float* g, int nt, int c, int hw, int n_segment, int fold_div, int layout, float* out,
+                                     void* stream);
+size_t adaf_conv_bn_param_grad_workspace_bytes(int cout);
+int adaf_conv_bn_param_grad_f32(adaf_handle* h, const float* g, int pixels, const float* dw_ohwi, const float* w_ohwi, const float* scale,
+                                const float* mean, const float* var, float eps, int cout, int kh, int kw, int cin, int cin_pad, float* dw_oihw,
+                                float* dgamma, float* dbeta, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- a8: linear classifier + temporal mean ---------------------------------------------
  * nn.Linear + ConsensusModule('avg') (+ glancer mean logits) -- STH/models/gfv_net.py:164-174,
  * STH/ops/basic_ops.py:17-26.  feat [B*T, F]; global_logit [B, Tg, C] or NULL; out [B, C];
