@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stddef.h>
 #include <string>
+#include <mutex>
 
 #include "../../include/adafocus.h"
 #include <type_traits>
@@ -25,8 +26,24 @@ struct adaf_handle {
     int scan_resident = 0;   // scan blocks the device can hold at once (occupancy query)
     int scan_slots = 1;      // min(4, scan_resident / blocks per scan)
     int bptt_resident = 0;   // blocks of the persistent GRU backward scan (gru_bptt.hip) the device can hold at once
+    // Is a ResNet trunk forward of this handle in flight on ANOTHER stream?  The trunk leaves an event behind each forward
+    // (adaf_note_forward), one per caller stream, least recently used slot reused; adaf_launches_beside(h, st) asks whether any other
+    // stream's event is still pending.  That is a caller that pipelines batches over streams: MFMA-bound trunks beside each other, the
+    // regime the conv planner's busy pricing was measured in (conv_gemm.hip conv_tile_cost).  The glancer leaves no mark: beside its
+    // HBM-bound depthwise work (GFV.offline_forward_pipelined's front stream) the busy picks measured 0.9 % slower
+    // (profiles/tile_regime_ab.md).  Never during stream capture: an event query is not allowed there, and where a graph is replayed is not known
+    // when it is captured, so a capture gets the plan of a launch that has the device to itself.  Guarded by a mutex: host threads may
+    // drive one handle on several streams; the answer depends on what the device is doing, not on the order of the calls.
+    static constexpr int kWatched = 8;
+    hipStream_t watch_key[kWatched] = {};
+    hipEvent_t watch_done[kWatched] = {};
+    unsigned long long watch_used[kWatched] = {};
+    unsigned long long watch_tick = 0;
+    std::mutex watch_mu;
     std::string err;
 };
+bool adaf_launches_beside(adaf_handle* h, hipStream_t st);
+void adaf_note_forward(adaf_handle* h, hipStream_t st);
 
 // Helper streams for networks that run two frame chunks side by side (adaf_mobilenetv2, adaf_effnet): one (stream, fork event, join event) per
 // CALLER stream, so forwards issued from different streams do not serialise their second chunks on one shared helper.  At most kMax entries:
@@ -142,6 +159,9 @@ struct AdafOptions {
     int gru_graph_persistent = 0; // "gru_graph_persistent": 1 = a stream capture keeps the persistent GRU scan (the caller guarantees exclusive use of the device
                                   // while the graph replays); 0 = captures take the launch-per-step form, which has no grid barrier to starve
     int gru_scan_slices = 2;      // "gru_scan_slices": clip slices a persistent GRU scan may be cut into (1 | 2; gru_scan.hip)
+    int conv_tile_regime = 1;     // "conv_tile_regime": 1 = a trunk forward issued while the handle has a trunk forward in flight on another stream has its automatic tiles
+                                  // priced for launches that run beside others (conv_gemm.hip conv_tile_cost); 0 = never (one block per CU is a whole round: the
+                                  // picks before it), 2 = always; bit-identical, A/B
 };
 AdafOptions& adaf_options();
 
@@ -345,8 +365,8 @@ void adaf_launch_colsum(const float* x, int rows, int cols, int ld, float* part,
 void adaf_launch_rows_scale(const float* x, const float* mask, float* out, int rows, int width, int steps, bool shift, hipStream_t s);
 
 // conv_gemm.hip
-int adaf_launch_conv_gemm(const ConvArgs& a, int tile, int cus, hipStream_t s);  // returns chosen tile (>0) or <0
-int adaf_pick_conv_tile(int M, int N, int K, int cus);
+// returns chosen tile (>0) or <0; beside: the caller's launches overlap those of other streams (the automatic tile is priced for that)
+int adaf_launch_conv_gemm(const ConvArgs& a, int tile, int cus, hipStream_t s, bool beside = false);
 int adaf_launch_conv_lat(const ConvArgs& a, hipStream_t s);   // conv_lat.hip: small-batch form (tile id 95), 1 = launched, 0 = not eligible
 int adaf_launch_conv_pool(ConvArgs a, int hw, float* pool_out, int pool_ld, hipStream_t s);   // 1 = launched (tile id 96), 0 = not eligible
 int adaf_launch_conv_pool16(ConvArgs a, int hw, float* pool_out, int pool_ld, hipStream_t s); // fp16 operands (EfficientNet's head); same return

@@ -89,7 +89,7 @@ struct OptKey { const char* name; double lo, hi; };
 // (round 6: the switches that measured as no-gain and had no user are gone -- conv_lean, pm_fill, resize_lds_kb, mb_wave, dw3_variant, gru_barrier)
 const OptKey kOptKeys[] = {{"conv_pool", 0, 1}, {"mb_strip", 0, 1}, {"mbv2_chunk", 1, 1 << 20}, {"latency_rows", 0, 1 << 30}, {"latency_linear_rows", 0, 1 << 30},
                            {"effnet_plan", 0, 511}, {"effnet_chunk", 1, 1 << 20}, {"gru_scan_slices", 1, 2}, {"effnet_fused_blocks", 0, 4294967295.0},
-                           {"stem_rows", 0, 2}, {"split_stage1_f32", 0, 1}, {"gru_graph_persistent", 0, 1}, {"split_lean", 0, 1}, {"tsm_lean", 0, 1}};
+                           {"stem_rows", 0, 2}, {"split_stage1_f32", 0, 1}, {"gru_graph_persistent", 0, 1}, {"split_lean", 0, 1}, {"tsm_lean", 0, 1}, {"conv_tile_regime", 0, 2}};
 int find_opt(const char* key) {
     if (!key) return -1;
     for (size_t i = 0; i < sizeof(kOptKeys) / sizeof(kOptKeys[0]); ++i)
@@ -145,9 +145,46 @@ int adaf_destroy(adaf_handle* h) {
     if (h)
         for (int i = 0; i < 4; ++i)
             if (h->scan_done[i]) (void)hipEventDestroy(h->scan_done[i]);
+    if (h)
+        for (int i = 0; i < adaf_handle::kWatched; ++i)
+            if (h->watch_done[i]) (void)hipEventDestroy(h->watch_done[i]);
     delete h;
     return ADAF_OK;
 }
+
+}  // extern "C"
+
+namespace {
+bool stream_capturing(hipStream_t st) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    (void)hipStreamIsCapturing(st, &cap);
+    return cap != hipStreamCaptureStatusNone;
+}
+}  // namespace
+
+bool adaf_launches_beside(adaf_handle* h, hipStream_t st) {
+    if (!h || stream_capturing(st)) return false;
+    std::lock_guard<std::mutex> lock(h->watch_mu);
+    for (int i = 0; i < adaf_handle::kWatched; ++i)
+        if (h->watch_done[i] && h->watch_used[i] && h->watch_key[i] != st && hipEventQuery(h->watch_done[i]) == hipErrorNotReady) return true;
+    return false;
+}
+
+void adaf_note_forward(adaf_handle* h, hipStream_t st) {
+    if (!h || stream_capturing(st)) return;
+    std::lock_guard<std::mutex> lock(h->watch_mu);
+    int slot = 0;
+    for (int i = 0; i < adaf_handle::kWatched; ++i) {
+        if (h->watch_used[i] && h->watch_key[i] == st) { slot = i; break; }
+        if (h->watch_used[i] < h->watch_used[slot]) slot = i;      // a free slot (0) or the least recently used one
+    }
+    if (!h->watch_done[slot] && hipEventCreateWithFlags(&h->watch_done[slot], hipEventDisableTiming) != hipSuccess) { h->watch_done[slot] = nullptr; return; }
+    h->watch_key[slot] = st;
+    h->watch_used[slot] = ++h->watch_tick;
+    (void)hipEventRecord(h->watch_done[slot], st);
+}
+
+extern "C" {
 
 const char* adaf_last_error(const adaf_handle* h) { return h ? h->err.c_str() : "null handle"; }
 int adaf_device_cus(const adaf_handle* h) { return h ? h->cus : 0; }
@@ -174,7 +211,8 @@ int adaf_set_global_option(const char* key, double value) {
         case 10: o.split_stage1_f32 = (int)value; break;
         case 11: o.gru_graph_persistent = (int)value; break;
         case 12: o.split_lean = (int)value; break;
-        default: o.tsm_lean = (int)value; break;
+        case 13: o.tsm_lean = (int)value; break;
+        default: o.conv_tile_regime = (int)value; break;
     }
     return ADAF_OK;
 }
@@ -196,6 +234,7 @@ double adaf_get_global_option(const char* key) {
         case 11: return o.gru_graph_persistent;
         case 12: return o.split_lean;
         case 13: return o.tsm_lean;
+        case 14: return o.conv_tile_regime;
         default: return __builtin_nan("");
     }
 }

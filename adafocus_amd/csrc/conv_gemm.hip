@@ -1696,15 +1696,20 @@ struct TileRow {
     TileFamily fam;
     int fallback;      // the id that takes a shape this row's kernel cannot (0: none, the conv is refused)
     int presplit;      // the pre-split row the automatic split choice moves to when the weights are pre-split (0: none)
-    float eff;         // rows the cost model chooses among: relative MFMA efficiency of the main loop, refined from profiles/ measurements
+    float eff;         // rows the cost model chooses among: relative efficiency of a launch that has the device to itself, from event-bracketed
+                       // sweeps (tools/conv_probe.py) -- the regime of the fp16 and split families and of option conv_tile_regime = 0
+    float eff_busy;    // the same rows, for launches that run beside others (profiles/tile_regime_ab.md).  128 x 64 and 64 x 64: the MFMA-busy share
+                       // of the position-major kernels' own loops (0.83 / 0.76; counter runs serialise dispatches, so these are not figures under
+                       // overlap, and the dense 128 x 64 kernel reads 0.71 with the short-K conv3s in it).  128 x 128 and 64 x 128 are FITTED: the ratios
+                       // to 128 x 64 of the serial sweeps (-2 %) and of the three-stream A/B table
 };
 constexpr int kTileAutoSplit = 40;      // not a tile: the automatic choice among the split tiles
 // Everything above 4 is reachable only through an explicit override (tools/conv_probe.py, tests) or the rules of resolve_f32_tile.
 constexpr TileRow kTileTable[] = {
-    {1, 128, 128, 2, 2, TF_REG, 0, 0, 1.00f},
-    {2, 128, 64, 2, 2, TF_REG, 0, 0, 1.02f},
-    {3, 64, 64, 2, 2, TF_REG, 0, 0, 0.98f},
-    {4, 64, 128, 2, 2, TF_REG, 0, 0, 0.99f},
+    {1, 128, 128, 2, 2, TF_REG, 0, 0, 1.00f, 0.80f},
+    {2, 128, 64, 2, 2, TF_REG, 0, 0, 1.02f, 0.82f},
+    {3, 64, 64, 2, 2, TF_REG, 0, 0, 0.98f, 0.76f},
+    {4, 64, 128, 2, 2, TF_REG, 0, 0, 0.99f, 0.79f},
     {5, 256, 128, 4, 2, TF_REG, 0, 0, 0.f},            // 8 waves, 1 block/CU
     {21, 128, 128, 2, 2, TF_DMA_TOP, 1, 0, 0.f},
     {22, 128, 64, 2, 2, TF_DMA_TOP, 2, 0, 0.f},
@@ -1829,10 +1834,12 @@ double conv_tap_fill(const ConvArgs& a) {
 // Position-major tiles with padding-tap skipping: a k x k conv, enough images sharing a pixel position to fill the tile rows, and at least
 // 4 % of the products padding.  On the split-bf16 pipe (pre-split rows; round 5) a skipped tap is whole MFMA steps of exact zeros, so the
 // result is bit-identical to the row-major split tile; pm_allow == 2 (all taps walked, an experiment) exists on the fp32 pipe only.
+bool pos_major_conv(const ConvArgs& a) {        // the conv's side of the gate: the same for every tile
+    const int ohw = a.OH * a.OW;
+    return !conv_is_dense(a) && a.KH * a.KW > 1 && a.KH * a.KW <= 32 && conv_images(a) * ohw == a.M && ohw <= 4096 && conv_tap_fill(a) < 0.96;
+}
 bool pos_major_gate(const ConvArgs& a, const TileRow& r) {
-    const int ohw = a.OH * a.OW, images = conv_images(a);
-    return has_pos_major_form(r) && (r.fam == TF_PRESPLIT ? a.pm_allow == 1 : a.pm_allow != 0) && !conv_is_dense(a) && a.KH * a.KW > 1 &&
-           a.KH * a.KW <= 32 && images * ohw == a.M && images >= r.bm && ohw <= 4096 && conv_tap_fill(a) < 0.96;
+    return has_pos_major_form(r) && (r.fam == TF_PRESPLIT ? a.pm_allow == 1 : a.pm_allow != 0) && pos_major_conv(a) && conv_images(a) >= r.bm;
 }
 // A conv1 with the fused temporal shift on the lean K loop (round 6): whole 32-channel slices on either side of the fold boundaries, every
 // row's frame neighbours inside the tensor (2 GB: the buffer form's offsets stay below the out-of-range marker)
@@ -1854,13 +1861,49 @@ bool conv_glds16_ok(const ConvArgs& a) {
     return (a.K / 2) % 32 == 0 && (a.cin / 2) % 32 == 0 && a.KH * a.KW <= 32;
 }
 
+// ---- what a tile costs -----------------------------------------------------------------------------------------------------------------
+// How much of the CU time a launch's uneven spread of blocks leaves idle is taken by launches that run beside it (other streams of a
+// pipelined caller): 0 = none, the launch pays its busiest CU's whole blocks; 1 = all, only the padding of a tile counts.  Fitted to
+// profiles/tile_regime_ab.md at 1024 patches of 96^2 under three streams.  Above 0.63: stage 4's conv1 and conv2 as 576 blocks of 128 x 64
+// (2.25 per CU) beat 1152 blocks of 64 x 64, and stage 3's as 1152 beat 2304 (above 0.29).  Below 1: launches of a few blocks (8 patches) keep
+// the tile that spreads them over the CUs.  On ONE stream nothing fills the gaps -- every one of these moves costs more there than it gains
+// here -- which is why the regime is the caller's to name (plan_conv's `beside`) and not a property of the conv.
+constexpr double kNeighbourFill = 0.75;
+
+// The price of a conv on a tile, in MFMA work per CU; pure.  M x N outputs as `groups` independent row ranges (1; the pixel positions of
+// position-major tiles, M = the images of one position) on `cus` CUs: the tile's area over its loop efficiency, times a mean, weighted by
+// the fill, of the blocks per CU on average (what the launch costs where neighbours fill every gap) and on the busiest CU (where nothing
+// does).  busy = false is a launch that has the device to itself: the busiest CU's whole blocks and the serial efficiencies.  K is the same
+// for every tile and cancels.  (How many blocks of a tile a CU holds at once does not enter: they share the CU's matrix pipe, so a CU's time
+// is the sum of its blocks' work however many of them are resident.)
+double conv_tile_cost(long long M, int N, int K, const TileRow& r, int cus, bool busy, int groups = 1) {
+    (void)K;
+    const long long blocks = (long long)groups * ((M + r.bm - 1) / r.bm) * ((N + r.bn - 1) / r.bn);
+    const double fill = busy ? kNeighbourFill : 0.0;
+    const double per_cu = fill * (double)blocks / cus + (1.0 - fill) * (double)((blocks + cus - 1) / cus);
+    return per_cu * r.bm * r.bn / (busy ? r.eff_busy : r.eff);
+}
+// The cheapest of the rows the cost model chooses among: a register-staged id, which the planner moves to the family it wants (family_tile_like).
+// A row taller than a group (position-major tiles need as many images as tile rows) is priced row-major, as it would run.
+int pick_tile(long long M, int N, int K, int cus, bool busy, int groups = 1, long long group_rows = 0) {
+    int best = 1;
+    double best_t = 1e300;
+    for (const TileRow& r : kTileTable) {
+        if (r.eff <= 0.f) continue;
+        const bool grouped = groups > 1 && group_rows >= r.bm;
+        const double cost = grouped ? conv_tile_cost(group_rows, N, K, r, cus, busy, groups) : conv_tile_cost(M, N, K, r, cus, busy);
+        if (cost < best_t * 0.999) { best_t = cost; best = r.id; }
+    }
+    return best;
+}
+
 // 32-wide column tiles when 64-wide ones would spend >= 20 % of the MFMA columns on padding (cout = 16, 24, 32, 96, 160: MobileNetV2's
 // project convs)
 bool narrow_output(const ConvArgs& a) { return (((a.N + 63) / 64) * 64 - a.N) * 5 >= a.N; }
 long long row_tiles(const ConvArgs& a, int bm) { return (a.M + bm - 1) / bm; }
 
 // The fp32 tile a conv takes: `tile` as asked for (0 = automatic, kTileAutoSplit), moved along the rows' fallback ids until one takes the shape.
-int resolve_f32_tile(const ConvArgs& a, int tile, int cus) {
+int resolve_f32_tile(const ConvArgs& a, int tile, int cus, bool beside) {
     const bool dma_ok = adaf_conv_glds_ok(a);
     const bool presplit_ok = a.wsp != nullptr && (a.K & 31) == 0 && dma_ok;
     if (tile == kTileAutoSplit) {   // split tiles, automatic: the bigger the wave tile the fewer split instructions per product
@@ -1868,12 +1911,17 @@ int resolve_f32_tile(const ConvArgs& a, int tile, int cus) {
         if (dma_ok) {
             if (a.N <= 64) tile = family_tile(TF_SPLIT6, 128, 64);
             else if (row_tiles(a, 128) * ((a.N + 127) / 128) * 2 >= cus) tile = family_tile(TF_SPLIT6, 128, 128);
-            else tile = family_tile_like(TF_SPLIT6, adaf_pick_conv_tile(a.M, a.N, a.K, cus));   // tiny problems: fill the CUs first
+            else tile = family_tile_like(TF_SPLIT6, pick_tile(a.M, a.N, a.K, cus, false));   // tiny problems: fill the CUs first
             if (presplit_ok) tile = kTileTable[tile_index(tile)].presplit;
         }
     }
     if (tile <= 0) {
-        tile = adaf_pick_conv_tile(a.M, a.N, a.K, cus);
+        // where the caller's launches run beside others the fp32 DMA tiles are priced for that, a k x k conv that will take position-major
+        // tiles by the blocks of that form; the families whose loops were not measured that way (above, and the fp16 tiles) keep the serial regime
+        const int regime = adaf_options().conv_tile_regime;      // 0 never, 1 where the caller says so, 2 always (A/B)
+        const bool busy = (regime == 2 || (regime == 1 && beside)) && dma_ok;
+        const bool pm = busy && a.pm_allow != 0 && pos_major_conv(a);
+        tile = pm ? pick_tile(a.M, a.N, a.K, cus, busy, a.OH * a.OW, conv_images(a)) : pick_tile(a.M, a.N, a.K, cus, busy);
         if (dma_ok) {
             tile = family_tile_like(TF_DMA_MID, tile);
             // narrow outputs: 128 x 32 tiles when there are enough row tiles to fill the device; with fewer rows but a long reduction
@@ -1897,14 +1945,14 @@ void plan_row_major(ConvPlan& p, const ConvArgs& a, int tile, int bm_rows) {
     p.a.nblocks = ((a.M + bm_rows - 1) / bm_rows) * p.a.tiles_n;
 }
 
-// The plan of one conv.  Pure: no HIP call, no launch; reads adaf_options().
-ConvPlan plan_conv(const ConvArgs& a, int tile, int cus) {
+// The plan of one conv.  Pure: no HIP call, no launch; reads adaf_options().  beside: the launch overlaps launches of other streams.
+ConvPlan plan_conv(const ConvArgs& a, int tile, int cus, bool beside = false) {
     ConvPlan p(a);
     const bool dense = conv_is_dense(a);
     if (a.in16) {    // operands fp16; output fp16 or fp32; residual (if any) fp16.  `a` arrives in ELEMENT units; the loader counts 32-bit words
         if (!conv_glds16_ok(a) || (a.res && !a.res16)) return p;
         if (tile < kTileF16Lo || tile > kTileF16Hi) {      // not an id adaf_conv2d_bn_act_f16 passes on: the automatic choice
-            tile = family_tile_like(TF_F16, adaf_pick_conv_tile(a.M, a.N, a.K, cus));
+            tile = family_tile_like(TF_F16, pick_tile(a.M, a.N, a.K, cus, false));
             if (narrow_output(a) && row_tiles(a, 128) >= cus) tile = family_tile(TF_F16, 128, 32);
         }
         if (tile_index(tile) < 0) return p;
@@ -1927,7 +1975,7 @@ ConvPlan plan_conv(const ConvArgs& a, int tile, int cus) {
         p.row = tile_index(p.tile = tile);
         return p;
     }
-    tile = resolve_f32_tile(a, tile, cus);
+    tile = resolve_f32_tile(a, tile, cus, beside);
     if (tile < 0) return p;
     const TileRow& r = kTileTable[tile_index(tile)];
     plan_row_major(p, a, tile, r.bm);
@@ -2054,23 +2102,9 @@ int launch_conv_pool(const ConvArgs& a, int hw, float* pool_out, int pool_ld, Po
 
 }  // namespace
 
-int adaf_pick_conv_tile(int M, int N, int K, int cus) {
-    (void)K;
-    int best = 1;
-    double best_t = 1e300;
-    for (const TileRow& r : kTileTable) {
-        if (r.eff <= 0.f) continue;
-        const long long blocks = (long long)((M + r.bm - 1) / r.bm) * ((N + r.bn - 1) / r.bn);
-        const long long rounds = (blocks + cus - 1) / cus;
-        const double cost = (double)rounds * r.bm * r.bn / r.eff;
-        if (cost < best_t * 0.999) { best_t = cost; best = r.id; }
-    }
-    return best;   // a register-staged id; the planner moves it to the family it wants (family_tile_like)
-}
-
 bool adaf_conv_tile_exists(int tile) { return tile == kTileAutoSplit || tile_index(tile) >= 0; }
 
-int adaf_launch_conv_gemm(const ConvArgs& a, int tile, int cus, hipStream_t s) { return launch_plan(plan_conv(a, tile, cus), s); }
+int adaf_launch_conv_gemm(const ConvArgs& a, int tile, int cus, hipStream_t s, bool beside) { return launch_plan(plan_conv(a, tile, cus, beside), s); }
 
 // The trunk's last conv3 with the global average pool in its epilogue (conv_epilogue_pool): 1x1 / stride 1 fp32.  1 = launched, 0 = not eligible.
 int adaf_launch_conv_pool(ConvArgs a, int hw, float* pool_out, int pool_ld, hipStream_t s) {
@@ -2092,11 +2126,11 @@ int adaf_launch_conv_pool16_rounded(ConvArgs a, int hw, float* pool_out, int poo
 }
 
 // Debug hook (not in include/adafocus.h): the plan of a conv, without a device.  `flags` carries what the params do not: ADAF_PLAN_* bits
-// below, pm_allow in bits 4-5, the pooled epilogue's pixels per image in bits 8 and up (0 = the plain conv).  Fills up to `n` ints of `out` in
+// below, pm_allow in bits 4-5, BESIDE (the caller's launches overlap others') in bit 7, the pooled epilogue's pixels per image in bits 8 and up (0 = the plain conv).  Fills up to `n` ints of `out` in
 // the order of kPlanFields (tests/test_conv_plan_host.py, tools/conv_launch_digest.py name them) and returns 0, or the code with which the
 // C ABI's own validation (adaf_make_conv_args, adaf_set_conv_dtypes) refuses the conv before it plans.
 extern "C" int adaf_conv_plan_debug(const adaf_conv_params* p, int flags, int cus, int* out, int n) {
-    enum { IN16 = 1, OUT16 = 2, RES16 = 4, PRESPLIT = 8, VEC_EPI = 64 };
+    enum { IN16 = 1, OUT16 = 2, RES16 = 4, PRESPLIT = 8, VEC_EPI = 64, BESIDE = 128 };
     alignas(16) static const float operand[4] = {0.f, 0.f, 0.f, 0.f};      // stands for every operand: the planner looks at no operand's contents
     alignas(16) static float result[4];
     if (!out || cus <= 0) return ADAF_E_BADARG;
@@ -2110,8 +2144,8 @@ extern "C" int adaf_conv_plan_debug(const adaf_conv_params* p, int flags, int cu
     a.vec_epi = a.vec_epi && (flags & VEC_EPI);
     const int hw = flags >> 8;
     const ConvPlan c = hw > 0 ? plan_conv_pool(a, hw, operand, p->cout, !a.in16 ? POOL_F32 : a.res16 ? POOL_F16_ROUNDED : POOL_F16)
-                              : plan_conv(a, p->tile, cus);
-    const TileRow r = c.row >= 0 ? kTileTable[c.row] : TileRow{0, 0, 0, 0, 0, TF_REG, 0, 0, 0.f};
+                              : plan_conv(a, p->tile, cus, (flags & BESIDE) != 0);
+    const TileRow r = c.row >= 0 ? kTileTable[c.row] : TileRow{0, 0, 0, 0, 0, TF_REG, 0, 0, 0.f, 0.f};
     const int kPlanFields[] = {c.tile, r.bm, r.bn, r.wgm, r.wgn, (int)r.fam, r.fallback, family_pipe(r.fam), family_split(r.fam),
                                r.fam == TF_PRESPLIT, c.dt, c.dense, c.gather, c.special, c.lean, c.pos_major, c.pool, c.a.tiles_n, c.a.nblocks,
                                c.a.pm_images, c.a.pm_groups, c.a.vec_epi, c.a.K, c.a.cin, c.a.ldx, c.a.tsm_fold};

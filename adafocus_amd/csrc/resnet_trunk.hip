@@ -109,9 +109,9 @@ size_t trunk_layout(const adaf_resnet50* net, int n, int patch, void* ws, float*
 inline const float* as_f32(const void* p) { return static_cast<const float*>(p); }   // fp16 buffers travel as float* through ConvArgs
 
 // Walks the trunk in the arithmetic net->math names; `rec` (optional) gets one hipEvent before each launch plus one at the end.
-int run_trunk(adaf_resnet50* net, const float* x4, int n, int P, int tsm_T, int tsm_div, float* feat, int ldfeat,
-              void* ws, size_t ws_bytes, hipStream_t st, std::vector<hipEvent_t>* rec, std::vector<Launch>* info, float* featmap = nullptr,
-              const FrameSrc* src = nullptr) {
+int walk_trunk(adaf_resnet50* net, const float* x4, int n, int P, int tsm_T, int tsm_div, float* feat, int ldfeat,
+               void* ws, size_t ws_bytes, hipStream_t st, std::vector<hipEvent_t>* rec, std::vector<Launch>* info, float* featmap,
+               const FrameSrc* src) {
     adaf_handle* h = net->h;
     if (src) x4 = src->frames;
     if (!net->finalized) return adaf_fail(h, ADAF_E_STATE, "resnet50: finalize() has not been called");
@@ -131,6 +131,7 @@ int run_trunk(adaf_resnet50* net, const float* x4, int n, int P, int tsm_T, int 
     const int lat_rows = net->lat_rows >= 0 ? net->lat_rows : adaf_options().latency_rows;
     const bool lat_ok = lat_rows > 0 && tsm_T == 0 && net->math == ADAF_MATH_F32;     // (run_trunk's tsm_T: either shift placement)
     const bool fuse = net->fuse;
+    const bool beside = adaf_launches_beside(h, st);      // the handle has work in flight on another stream: this forward's launches overlap it
     // shift_place = 'block' (STH/ops/temporal_shift.py:104-121): TemporalShift wraps the whole Bottleneck, so conv1, the downsample
     // conv AND the identity see the shifted block input.  The shifted map is materialised in a sixth slab in front of every block and
     // the block then runs exactly as a block without a shift (every fused form applies, except the next block's conv1 riding in a
@@ -193,8 +194,8 @@ int run_trunk(adaf_resnet50* net, const float* x4, int n, int P, int tsm_T, int 
         const double bytes = eb * ((double)n * hh * ww * L.cin + (double)a.M * L.cout * (res ? 2 : 1) + (double)L.cout * L.k * L.k * L.cin);
         mark(2.0 * macs, bytes, 0);
         const bool want_lat = lat_ok && a.M <= lat_rows && li > 0 && !net->tiles[li];
-        int used = adaf_launch_conv_gemm(a, want_lat ? 95 : p.tile, h->cus, st);
-        if (used < 0 && want_lat) used = adaf_launch_conv_gemm(a, p.tile, h->cus, st);   // the latency form declined the shape: the engine takes it
+        int used = adaf_launch_conv_gemm(a, want_lat ? 95 : p.tile, h->cus, st, beside);
+        if (used < 0 && want_lat) used = adaf_launch_conv_gemm(a, p.tile, h->cus, st, beside);   // the latency form declined the shape: the engine takes it
         if (used < 0) return adaf_fail(h, ADAF_E_LAUNCH, "resnet50%s: no kernel for tile id %d (conv launch %d)", tag, p.tile, li);
         if (info && !info->empty()) info->back().tile = used;
         *oh = a.OH; *ow = a.OW;
@@ -400,6 +401,15 @@ int adaf_resnet50_set_param(adaf_resnet50* net, const char* name, const float* d
     net->params.set(name, dev_ptr, numel);
     net->finalized = false;
     return ADAF_OK;
+}
+
+// A forward: the walk, then the mark other streams' forwards look for (adaf_handle: watch_*).
+static int run_trunk(adaf_resnet50* net, const float* x4, int n, int P, int tsm_T, int tsm_div, float* feat, int ldfeat,
+              void* ws, size_t ws_bytes, hipStream_t st, std::vector<hipEvent_t>* rec, std::vector<Launch>* info, float* featmap = nullptr,
+              const FrameSrc* src = nullptr) {
+    const int rc = walk_trunk(net, x4, n, P, tsm_T, tsm_div, feat, ldfeat, ws, ws_bytes, st, rec, info, featmap, src);
+    if (rc == ADAF_OK) adaf_note_forward(net->h, st);
+    return rc;
 }
 
 // Three bf16 planes of every packed filter bank except the stem's (idempotent; used by the split tiles 6x).

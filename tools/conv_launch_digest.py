@@ -27,14 +27,15 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 PLAN_FIELDS = ("tile", "bm", "bn", "wgm", "wgn", "family", "fallback", "pipe", "split", "presplit", "dt", "dense", "gather", "special", "lean",
                "pos_major", "pool", "tiles_n", "nblocks", "pm_images", "pm_groups", "vec_epi", "K", "cin", "ldx", "fold")
 FAMILIES = ("reg", "dma_top", "dma_mid", "bar23", "split6", "split9", "presplit", "f16", "lat")
-F_IN16, F_OUT16, F_RES16, F_PRESPLIT, F_VEC_EPI = 1, 2, 4, 8, 64
+F_IN16, F_OUT16, F_RES16, F_PRESPLIT, F_VEC_EPI, F_BESIDE = 1, 2, 4, 8, 64, 128
 ENGINE_IDS = [0, 1, 2, 3, 4, 5, 21, 22, 23, 24, 25, 26, 31, 32, 33, 34, 38, 39, 40, 41, 42, 43, 44, 45, 46, 51, 52, 53, 54,
               61, 62, 63, 64, 65, 66, 67, 71, 72, 73, 74, 81, 82, 83, 84, 88, 95]
 F16_IDS = [0, 81, 82, 83, 84, 88]
 
 
-def plan_flags(in16=False, out16=False, res16=False, presplit=False, pm_allow=1, vec_epi=True, pool_hw=0):
-    return (F_IN16 * in16 | F_OUT16 * out16 | F_RES16 * res16 | F_PRESPLIT * presplit | (pm_allow & 3) << 4 | F_VEC_EPI * vec_epi | pool_hw << 8)
+def plan_flags(in16=False, out16=False, res16=False, presplit=False, pm_allow=1, vec_epi=True, pool_hw=0, beside=False):
+    return (F_IN16 * in16 | F_OUT16 * out16 | F_RES16 * res16 | F_PRESPLIT * presplit | (pm_allow & 3) << 4 | F_VEC_EPI * vec_epi |
+            F_BESIDE * beside | pool_hw << 8)
 
 
 def conv_plan(lib, params, flags, cus):
