@@ -356,11 +356,17 @@ bool adaf_gru_bptt_persistent_ok(int batch, int hidden, int resident_blocks);
 hipError_t adaf_launch_gru_bptt(const float* dy, const float* gi, const float* gh, const float* bhh, const float* hs, const float* whh,
                                 float* dgi, float* dgh, float* carry, unsigned* bar, unsigned* timeouts, int batch, int steps, int hidden,
                                 bool persistent, bool cooperative, hipStream_t s);
+
+// train_common.hip (what the backward passes share)
 // C[m, n] = sum_k A[m * a_m + k * a_k] B[k * b_k + n * b_n] (* mul[m * ldm + n] when mul != nullptr); deterministic (no atomics)
 void adaf_launch_gemm_strided(const float* A, long long a_m, long long a_k, const float* B, long long b_k, long long b_n, float* C, int ldc,
                               const float* mul, int ldm, int M, int N, int K, hipStream_t s);
-size_t adaf_colsum_partial_floats(int cols);
-void adaf_launch_colsum(const float* x, int rows, int cols, int ld, float* part, float* out, hipStream_t s);
+// out[i] = part[0 * n + i] + part[1 * n + i] + ... in slice order (i < n)
+void adaf_launch_slice_sum(const float* part, int slices, size_t n, float* out, hipStream_t s);
+// out[c] = sum over rows of x[r * ld + c], as row-slice partials (part: adaf_colsum_partial_floats floats) and their slice sum.  lanes = 1:
+// one lane per column, 32 slices; lanes = 4: four lanes per column and about 2048 blocks, for tall dense maps (ld == cols)
+size_t adaf_colsum_partial_floats(int cols, int lanes);
+void adaf_launch_colsum(const float* x, int rows, int cols, int ld, int lanes, float* part, float* out, hipStream_t s);
 // out = x * mask (mask == nullptr: a copy), or with shift: out[b, t] = x[b, t - 1], out[b, 0] = 0 (rows = B * steps of `width` floats)
 void adaf_launch_rows_scale(const float* x, const float* mask, float* out, int rows, int width, int steps, bool shift, hipStream_t s);
 

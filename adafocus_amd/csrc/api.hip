@@ -688,7 +688,7 @@ static size_t gru_backward_layout(void* ws, int batch, int steps, int hidden, in
     r->dgi = c.take<float>(wide);
     r->dgh = c.take<float>(wide);
     r->carry = c.take<float>((size_t)batch * hidden);
-    r->part = c.take<float>(adaf_colsum_partial_floats(3 * hidden > classes ? 3 * hidden : classes));
+    r->part = c.take<float>(adaf_colsum_partial_floats(3 * hidden > classes ? 3 * hidden : classes, 1));
     r->bar = c.take<unsigned>((size_t)steps + 1, 256);
     return c.off;
 }
@@ -717,7 +717,7 @@ int adaf_gru_cls_backward_f32(adaf_handle* h, const float* x, int ldx, int batch
     // FC + dropout: dW_fc = dlogits^T (hs * mask), db_fc = column sums, dY = (dlogits W_fc) * mask
     adaf_launch_rows_scale(hs, mask, hd, rows, hidden, steps, false, st);
     adaf_launch_gemm_strided(dlogits, 1, classes, hd, hidden, 1, dw_fc, hidden, nullptr, 0, classes, hidden, rows, st);
-    adaf_launch_colsum(dlogits, rows, classes, classes, part, db_fc, st);
+    adaf_launch_colsum(dlogits, rows, classes, classes, 1, part, db_fc, st);
     adaf_launch_gemm_strided(dlogits, classes, 1, fc_w, hidden, 1, dy, hidden, mask, hidden, rows, hidden, classes, st);
     // gh = W_hh h_t + b_hh of every step in one engine GEMM (row (b, t) is step t+1's hidden projection)
     if ((rc = linear_launch(h, hs, rows, hidden, hidden, h3, w_hh, b_hh, gh, 0, st))) return rc;
@@ -743,8 +743,8 @@ int adaf_gru_cls_backward_f32(adaf_handle* h, const float* x, int ldx, int batch
     adaf_launch_rows_scale(hs, nullptr, hd, rows, hidden, steps, true, st);
     adaf_launch_gemm_strided(dgi, 1, h3, x, ldx, 1, dw_ih, feat, nullptr, 0, h3, feat, rows, st);
     adaf_launch_gemm_strided(dgh, 1, h3, hd, hidden, 1, dw_hh, hidden, nullptr, 0, h3, hidden, rows, st);
-    adaf_launch_colsum(dgi, rows, h3, h3, part, db_ih, st);
-    adaf_launch_colsum(dgh, rows, h3, h3, part, db_hh, st);
+    adaf_launch_colsum(dgi, rows, h3, h3, 1, part, db_ih, st);
+    adaf_launch_colsum(dgh, rows, h3, h3, 1, part, db_hh, st);
     if (dx) adaf_launch_gemm_strided(dgi, h3, 1, w_ih, feat, 1, dx, feat, nullptr, 0, rows, feat, h3, st);
     e = hipGetLastError();
     return e == hipSuccess ? ADAF_OK : adaf_hip_fail(h, e, "gru_cls backward");

@@ -2,181 +2,27 @@
 // BatchNorm statistics: STH/stage3.py:189-193, 313-317).  fp32, NHWC activations, OHWI filters -- the engine's layouts.  No
 // atomics: every output element has one writer and every sum a fixed order, so the same inputs give the same bits.
 //
-//   conv_wgrad_splitk_kernel   G[o, kh, kw, i] = sum over output pixels of g[pixel, o] x[window(pixel, kh, kw), i]: a TN GEMM whose reduction
-//                              axis is the pixel axis.  ppo_wenc_splitk_kernel's design (ppo_train.hip) with an implicit im2col
-//                              on the way in: 16-byte loads, v_mfma_f32_32x32x2_f32 with K = a pixel pair, split-K over pixel slices, the
-//                              slice partials added in slice order by conv_wgrad_reduce_kernel
+//   the weight gradient        G[o, kh, kw, i] = sum over output pixels of g[pixel, o] x[window(pixel, kh, kw), i]: a TN GEMM whose reduction
+//                              axis is the pixel axis, on splitk_wgrad_kernel (splitk_wgrad.h) -- its window source (an implicit
+//                              im2col), or its pointwise source for a 1x1 stride-1 convolution --, the slice partials added in slice order
+//                              by the slice sum of train_common.hip
 //   conv_dgrad_pack_kernel     the filter transposed, rotated by 180 degrees, times the folded BN scale per output channel: the data
 //                              gradient is then a stride-1 convolution of the gradient map on the forward engine (conv_gemm.hip)
 //   conv_zero_insert_kernel    stride 2: a low-resolution map written into the even positions of a zeroed full-resolution one (gather form)
-//   relu_backward_kernel, avgpool_backward_kernel, maxpool_backward_kernel, tshift_backward_kernel, conv_colsum_*_kernel, conv_bn_param_grad_kernel
+//   relu_backward_kernel, avgpool_backward_kernel, maxpool_backward_kernel, tshift_backward_kernel, conv_bn_param_grad_kernel
 #include "adaf_internal.h"
+#include "splitk_wgrad.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 inline unsigned blocks_for(size_t n, int per = 256) { return (unsigned)((n + per - 1) / per); }
 
-// ---- weight gradient -----------------------------------------------------------------------------------------------------------------
-// grid (ceil(K / 128), cout / (32 MH), slices), 512 threads; K = kh * kw * cin is the filter's flattened (kh, kw, i) axis.  A block owns
-// output pixels [slice * pps, (slice + 1) * pps), filter rows [32 MH blockIdx.y, ...) and K columns [128 blockIdx.x, ...).  Lane (half, nl)
-// of a wave loads the 4 consecutive K columns 128 blockIdx.x + 4 nl ..: cin % 4 == 0, so they are 4 channels of ONE tap (kh, kw), and the
-// lane's window position per pixel is (oy s + kh - p, ox s + kw - p): range-checked, a padding tap multiplies zeros (the address is clamped
-// into the map, the value replaced).  Everything else is ppo_wenc_splitk_kernel: pixel groups of 8 dealt to the 8 waves in ascending order,
-// MFMA q takes component q of the load (output column nl of accumulator 4 mh + q is K column 128 blockIdx.x + 4 nl + q), lane half = pixel
-// parity, the eight wave partials meet in LDS in the fixed order ((w0 + w4) + (w2 + w6)) + ((w1 + w5) + (w3 + w7)).
-// Property (2) of DESIGN 3.7.3: a group's loads are requested behind a VALU read of the youngest MFMA result of the group before.
-constexpr int kWgThreads = 512, kWgWaves = 8, kWgU = 4;      // kWgU pixel pairs per group
-
-struct WgradArgs {
-    const float* x;      // [n, H, W, cin]
-    const float* g;      // [n, OH, OW, cout]
-    float* part;         // [slices, cout, K]
-    int npix;            // n * OH * OW
-    int cin, cout, K, H, W, OH, OW, KW, stride, pad;
-    int pps;             // pixels per slice (even)
-    int pointwise;       // 1x1 stride 1: the window of output pixel p is input pixel p
-};
-
-template <int MH>
-struct WgStage {
-    f32x4 b[kWgU];
-    float d[kWgU][MH];
-    bool okp[kWgU], okt[kWgU];
-};
-
-template <int MH>
-__global__ __launch_bounds__(kWgThreads) void conv_wgrad_splitk_kernel(WgradArgs a) {
-    constexpr int NA = 4 * MH;
-    __shared__ float red[2][NA * 16 * 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, nl = lane & 31;
-    const int kc = blockIdx.x * 128 + 4 * nl;                 // this lane's first K column
-    const bool kok = kc < a.K;                                // (K % 4 == 0: the four columns stand or fall together)
-    const int kcc = kok ? kc : 0;
-    const int tap = kcc / a.cin, ci = kcc - tap * a.cin, kh = tap / a.KW, kw = tap - kh * a.KW;
-    const int m0 = blockIdx.y * 32 * MH;
-    const int p0 = blockIdx.z * a.pps, p1 = min(a.npix, p0 + a.pps);
-    const int ngroups = (p1 - p0 + 2 * kWgU - 1) / (2 * kWgU);
-    const int ohw = a.OH * a.OW;
-    f32x16 acc[NA];
-#pragma unroll
-    for (int q = 0; q < NA; ++q)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[q][r] = 0.f;
-
-    // branch-free: a pixel past the slice reads the slice's last pixel and takes a zero gradient; a tap in the padding reads the clamped
-    // position and takes a zero input
-    auto load = [&](int grp, WgStage<MH>& s) {
-#pragma unroll
-        for (int u = 0; u < kWgU; ++u) {
-            const int pix = p0 + (grp * kWgU + u) * 2 + half, pc = min(pix, p1 - 1);
-            size_t xoff;
-            bool ok = kok;
-            if (a.pointwise) {
-                xoff = (size_t)pc * a.cin + ci;
-            } else {
-                const int img = pc / ohw, r = pc - img * ohw, oy = r / a.OW, ox = r - oy * a.OW;
-                const int iy = oy * a.stride + kh - a.pad, ix = ox * a.stride + kw - a.pad;
-                ok = ok && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
-                const int iyc = min(max(iy, 0), a.H - 1), ixc = min(max(ix, 0), a.W - 1);
-                xoff = (((size_t)img * a.H + iyc) * a.W + ixc) * a.cin + ci;
-            }
-            s.b[u] = *reinterpret_cast<const f32x4*>(a.x + xoff);
-#pragma unroll
-            for (int mh = 0; mh < MH; ++mh) s.d[u][mh] = a.g[(size_t)pc * a.cout + m0 + 32 * mh + nl];
-            s.okp[u] = pix < p1;
-            s.okt[u] = ok;
-        }
-    };
-    auto products = [&](const WgStage<MH>& s) {
-#pragma unroll
-        for (int u = 0; u < kWgU; ++u) {
-            f32x4 b;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) b[q] = s.okt[u] ? s.b[u][q] : 0.f;
-#pragma unroll
-            for (int mh = 0; mh < MH; ++mh) {
-                const float d = s.okp[u] ? s.d[u][mh] : 0.f;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) acc[4 * mh + q] = __builtin_amdgcn_mfma_f32_32x32x2f32(d, b[q], acc[4 * mh + q], 0, 0, 0);
-            }
-        }
-    };
-    WgStage<MH> st;
-    float fence = 0.f;
-    for (int grp = wave; grp < ngroups; grp += kWgWaves) {
-        load(grp, st);
-        __builtin_amdgcn_sched_barrier(0);
-        products(st);
-#pragma unroll
-        for (int q = 0; q < NA; ++q) fence += acc[q][15];
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    asm volatile("" ::"v"(fence));      // (keeps the fence adds alive; no instruction, the result is untouched)
-
-    auto put = [&](int buf) {
-#pragma unroll
-        for (int q = 0; q < NA; ++q)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) red[buf][(q * 16 + r) * 64 + lane] = acc[q][r];
-    };
-    auto add = [&](int buf) {
-#pragma unroll
-        for (int q = 0; q < NA; ++q)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[q][r] = acc[q][r] + red[buf][(q * 16 + r) * 64 + lane];
-    };
-    // (writers, readers) per phase: w4, w5 -> w0, w1;  w6, w7 -> w2, w3;  w2, w3 -> w0, w1;  w1 -> w0
-    const int wr0[4] = {4, 6, 2, 1}, rd0[4] = {0, 2, 0, 0};
-#pragma unroll
-    for (int ph = 0; ph < 4; ++ph) {
-        const int pairs = ph == 3 ? 1 : 2;
-        if (wave >= wr0[ph] && wave < wr0[ph] + pairs) put(wave - wr0[ph]);
-        __syncthreads();
-        if (wave >= rd0[ph] && wave < rd0[ph] + pairs) add(wave - rd0[ph]);
-        __syncthreads();
-    }
-    if (wave == 0 && kok) {
-        float* o = a.part + (size_t)blockIdx.z * a.cout * a.K + kc;
-#pragma unroll
-        for (int mh = 0; mh < MH; ++mh)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = (r & 3) + 8 * (r >> 2) + 4 * half;
-                const f32x4 v = {acc[4 * mh][r], acc[4 * mh + 1][r], acc[4 * mh + 2][r], acc[4 * mh + 3][r]};
-                *reinterpret_cast<f32x4*>(o + (size_t)(m0 + 32 * mh + m) * a.K) = v;
-            }
-    }
-}
-
-// G[i] = part[0][i] + part[1][i] + ... in slice order
-__global__ void conv_wgrad_reduce_kernel(const float* part, int slices, size_t n, float* out) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    float v = 0.f;
-    for (int s = 0; s < slices; ++s) v += part[(size_t)s * n + i];
-    out[i] = v;
-}
-
-constexpr int kWgCus = 256;      // the slice count is planned for the MI355X's 256 CUs whatever the device reports: the query needs no handle
-
-struct WgradPlan { int mh, kchunks, mchunks, slices, pps, used; };
-// pixel slices: about one block per CU, at least 64 pixels (one round of the eight waves) per slice.  Plain arithmetic.
+// the weight gradient's launch: M = cout as one or two sets of 32 filter rows per block, K = kh * kw * cin in chunks of 128.  The slices
+// are planned for the MI355X's 256 CUs whatever the device reports: the query needs no handle
+struct WgradPlan { int mh; SkPlan sk; };
 WgradPlan wgrad_plan(long long npix, int cout, int K) {
-    WgradPlan p;
-    p.mh = cout % 64 == 0 ? 2 : 1;
-    p.kchunks = (K + 127) / 128;
-    p.mchunks = cout / (32 * p.mh);
-    const long long tiles = (long long)p.kchunks * p.mchunks, most = (npix + 63) / 64;
-    long long s = kWgCus / (tiles > 0 ? tiles : 1);
-    if (s > most) s = most;
-    if (s < 1) s = 1;
-    p.slices = (int)s;
-    p.pps = (int)(((npix + s - 1) / s + 1) / 2 * 2);
-    p.used = (int)((npix + p.pps - 1) / p.pps);
-    return p;
+    const int mh = cout % 64 == 0 ? 2 : 1;
+    return {mh, splitk_plan(npix, (long long)((K + 127) / 128) * (cout / (32 * mh)), kSkCus)};
 }
 
 // ---- data gradient -------------------------------------------------------------------------------------------------------------------
@@ -284,35 +130,6 @@ __global__ void tshift_backward_kernel(const float* __restrict__ g, long long to
     o[idx] = v;
 }
 
-// Column sums of g [rows, cols] for the BatchNorm gradients, in the scheme of adaf_launch_colsum (slice partials, each over its rows in a
-// fixed order, then the slices in slice order) with more slices: a gradient map has up to 10^6 rows and as few as 64 columns, which the 32
-// slices of that launcher walk as 32 blocks.  grid (ceil(cols / 64), slices), 256 threads: thread (lane, c) adds rows r0 + lane, r0 + lane + 4,
-// ... of column c in ascending order, the four lanes meet as (l0 + l1) + (l2 + l3).
-__global__ __launch_bounds__(256) void conv_colsum_partial_kernel(const float* __restrict__ x, int rows, int cols, int per, float* __restrict__ part) {
-    __shared__ float red[4][64];
-    const int cl = threadIdx.x & 63, lane = threadIdx.x >> 6, c = blockIdx.x * 64 + cl;
-    const long long r0 = (long long)blockIdx.y * per;
-    const long long r1 = r0 + per < rows ? r0 + per : rows;
-    float v = 0.f;
-    if (c < cols)
-        for (long long r = r0 + lane; r < r1; r += 4) v += x[(size_t)r * cols + c];
-    red[lane][cl] = v;
-    __syncthreads();
-    if (lane == 0 && c < cols) part[(size_t)blockIdx.y * cols + c] = (red[0][cl] + red[1][cl]) + (red[2][cl] + red[3][cl]);
-}
-__global__ void conv_colsum_final_kernel(const float* __restrict__ part, int slices, int cols, float* __restrict__ out) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= cols) return;
-    float v = 0.f;
-    for (int s = 0; s < slices; ++s) v += part[(size_t)s * cols + c];
-    out[c] = v;
-}
-// slices by the column count alone (the workspace query knows no row count): about 2048 blocks, 32 slices at least
-inline int colsum_slices(int cols) {
-    const int s = 2048 / ((cols + 63) / 64);
-    return s < 32 ? 32 : s;
-}
-
 // One block of 256 threads per output channel o, from the unscaled weight gradient G (OHWI, cin_pad channels) and the forward's packed
 // filter W (the same layout):  dW[o] = scale[o] G[o] in PyTorch's OIHW layout with the cin real channels;  dbeta[o] = colsum[o];
 // dgamma[o] = invstd[o] (<W[o], G[o]> - mean[o] colsum[o]), invstd = 1 / sqrt(var + eps): nothing divides by gamma or by the folded scale.
@@ -369,7 +186,7 @@ int conv_bwd_geom(adaf_handle* h, const char* who, const adaf_conv_params* p, Co
 
 size_t wgrad_layout(void* ws, const WgradPlan& pl, int cout, int K, float** part) {
     AdafCarver c(ws);
-    *part = c.take<float>((size_t)pl.slices * cout * K, 16);
+    *part = c.take<float>((size_t)pl.sk.slices * cout * K, 16);
     return c.off;
 }
 
@@ -410,19 +227,19 @@ int adaf_conv2d_wgrad_f32(adaf_handle* h, const adaf_conv_params* p, const float
     const WgradPlan pl = wgrad_plan(q.npix_out, p->cout, q.K);
     float* part;
     if ((rc = adaf_check_ws(h, "conv_wgrad", ws, ws_bytes, wgrad_layout(ws, pl, p->cout, q.K, &part), ADAF_WS_ALIGN_FIRST))) return rc;
-    WgradArgs a;
-    a.x = x; a.g = g; a.part = part; a.npix = (int)q.npix_out;
-    a.cin = p->cin; a.cout = p->cout; a.K = q.K; a.H = p->h; a.W = p->w; a.OH = q.oh; a.OW = q.ow; a.KW = p->kw; a.stride = p->stride; a.pad = p->pad;
-    a.pps = pl.pps;
-    a.pointwise = (p->kh == 1 && p->kw == 1 && p->stride == 1 && p->pad == 0) ? 1 : 0;
-    const dim3 grid(pl.kchunks, pl.mchunks, pl.used);
     hipStream_t st = (hipStream_t)stream;
-    if (pl.mh == 2)
-        hipLaunchKernelGGL(conv_wgrad_splitk_kernel<2>, grid, dim3(kWgThreads), 0, st, a);
+    const int npix = (int)q.npix_out;
+    auto launch = [&](const auto& src) {
+        if (pl.mh == 2)
+            splitk_wgrad_launch<1, 2>(src, part, npix, q.K, p->cout, pl.sk, st);
+        else
+            splitk_wgrad_launch<1, 1>(src, part, npix, q.K, p->cout, pl.sk, st);
+    };
+    if (p->kh == 1 && p->kw == 1 && p->stride == 1 && p->pad == 0)      // the window of output pixel p is input pixel p
+        launch(SkPointwise<false>{x, g, nullptr, q.K, p->cout});
     else
-        hipLaunchKernelGGL(conv_wgrad_splitk_kernel<1>, grid, dim3(kWgThreads), 0, st, a);
-    const size_t n = (size_t)p->cout * q.K;
-    hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3(blocks_for(n)), dim3(256), 0, st, part, pl.used, n, dw_ohwi);
+        launch(SkWindow{x, g, p->cin, p->cout, p->h, p->w, q.oh, q.ow, p->kw, p->stride, p->pad});
+    adaf_launch_slice_sum(part, pl.sk.used, (size_t)p->cout * q.K, dw_ohwi, st);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? ADAF_OK : adaf_hip_fail(h, e, "conv_wgrad launch");
 }
@@ -554,7 +371,7 @@ int adaf_stem7x7_bn_relu_f32(adaf_handle* h, const float* patches_nhwc4, int n, 
 size_t adaf_conv_bn_param_grad_workspace_bytes(int cout) {
     if (cout <= 0) return 0;
     AdafCarver c(nullptr);
-    c.take<float>((size_t)colsum_slices(cout) * cout, 16);
+    c.take<float>(adaf_colsum_partial_floats(cout, 4), 16);
     c.take<float>((size_t)cout, 16);
     return c.off;
 }
@@ -568,12 +385,10 @@ int adaf_conv_bn_param_grad_f32(adaf_handle* h, const float* g, int pixels, cons
     int rc = adaf_check_ws(h, "conv_bn_param_grad", ws, ws_bytes, adaf_conv_bn_param_grad_workspace_bytes(cout), ADAF_WS_ALIGN_FIRST);
     if (rc) return rc;
     AdafCarver c(ws);
-    const int slices = colsum_slices(cout), per = (pixels + slices - 1) / slices;
-    float* part = c.take<float>((size_t)slices * cout, 16);
+    float* part = c.take<float>(adaf_colsum_partial_floats(cout, 4), 16);
     float* cs = c.take<float>((size_t)cout, 16);
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(conv_colsum_partial_kernel, dim3((cout + 63) / 64, slices), dim3(256), 0, st, g, pixels, cout, per, part);
-    hipLaunchKernelGGL(conv_colsum_final_kernel, dim3((cout + 255) / 256), dim3(256), 0, st, part, slices, cout, cs);
+    adaf_launch_colsum(g, pixels, cout, cout, 4, part, cs, st);      // a gradient map: up to 10^6 rows and as few as 64 columns
     hipLaunchKernelGGL(conv_bn_param_grad_kernel, dim3(cout), dim3(256), 0, st, dw_ohwi, w_ohwi, scale, mean, var, eps, cs, kh * kw, cin, cin_pad,
                        dw_oihw, dgamma, dbeta);
     hipError_t e = hipGetLastError();

@@ -11,9 +11,10 @@
 //                            the same pass.  ONE kernel for both policies; Dist = Categorical (log-softmax over A logits, int64 actions)
 //                            or Gaussian (see below) says what the actor columns mean
 //   ppo_loss_sum_kernel      the scalar loss from the per-row terms, summed in a fixed order
-//   ppo_wenc_splitk_kernel   dW_enc [32, C] = (relu-masked dE1)^T S over all T*B*h*w pixels: the state tensor S (257 MB at B = 64, T = 16) is
-//                            read ONCE with 16-byte loads; a block owns a pixel slice and a 128- or 256-channel chunk and keeps its 32 x chunk
-//                            partial in MFMA accumulators; ppo_wenc_reduce_kernel adds the slices in slice order
+//   launch_wenc_grad         dW_enc [32, C] = (relu-masked dE1)^T S over all T*B*h*w pixels: the state tensor S (257 MB at B = 64, T = 16) is
+//                            read ONCE with 16-byte loads by splitk_wgrad_kernel (splitk_wgrad.h) on its pointwise source; a block owns a
+//                            pixel slice and a 128- or 256-channel chunk and keeps its 32 x chunk partial in MFMA accumulators; the slice
+//                            sum of train_common.hip adds the slices in slice order
 //   small layout kernels     (T, B) <-> (B, T) row permutation (with the ReLU mask), the Linear gradient's pixel-major -> nn.Linear permutation
 //
 // The continuous policy of the Something-Something tree (STH/models/ppo_continuous.py) adds
@@ -24,14 +25,12 @@
 //   bn_* kernels             BatchNorm with batch statistics over the rows of a [rows, cols] matrix: two-pass column statistics (the mean,
 //                            then the squared deviations) as slice partials in row order + a fixed-order sum over the slices (in double), the running
 //                            statistics' update, normalise + affine (+ ReLU), and the backward (d gamma, d beta, dx)
-//   ppo_wenc_splitk_kernel   also with 64 conv outputs (two 32-row accumulator sets at 128 channels per block) and with a gradient
+//   launch_wenc_grad         also with 64 conv outputs (two 32-row accumulator sets at 128 channels per block) and with a gradient
 //                            whose mask is already applied (no E1 operand)
 //
 // fp32 throughout, no atomics: the same inputs give the same bits.  Every kernel compiles to zero scratch.
 #include "adaf_internal.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "splitk_wgrad.h"
 
 namespace {
 
@@ -495,155 +494,21 @@ __global__ void ppo_relu_mask_kernel(const float* x, const float* gate, float* o
 }
 
 // ---- split-K weight gradient of the 1x1 conv --------------------------------------------------------------------------------------------
-// grid (C / (128 NQ), slices), 512 threads.  A block owns pixels [slice * pps, (slice + 1) * pps) and channels [chunk * 128 NQ, ...).  Its
-// pixels go to its 8 waves in groups of 8 (group g to wave g % 8, ascending); a wave walks its groups with v_mfma_f32_32x32x2_f32 products:
-// M = the 32 conv outputs, N = 32 lanes x 4 channels of a 16-byte load (MFMA q takes component q: output column nl of accumulator 4 j + q is
-// channel 128 j + 4 nl + q of the chunk), K = 2 pixels per product (lane half = pixel parity).  The eight wave partials meet in LDS in the
-// fixed order ((w0 + w4) + (w2 + w6)) + ((w1 + w5) + (w3 + w7)) and wave 0 writes the block's partial [32, chunk] into part[slice].
-//
-// Property (2) of DESIGN 3 (a returning load is not interlocked against an MFMA that still reads or writes its landing register): a group's
-// loads are requested behind a VALU read (an add into `fence`) of the youngest MFMA result -- every product that read the landing registers
-// has retired by then --, pinned by scheduling barriers.
-constexpr int kSkThreads = 512, kSkWaves = 8, kSkU = 4;      // kSkU pixel pairs per group
-
-// MH sets of 32 conv outputs (1 or 2): with two, conv output 32 mh + m is row m of the accumulators of set mh, both sets fed by the same
-// state fragments.  GATED = false: the gradient has its mask applied already (after a BatchNorm backward) and no E1 is read.
-template <int NQ, int MH>
-struct SkStage {
-    f32x4 b[kSkU][NQ];
-    float d[kSkU][MH], e[kSkU][MH];
-    bool ok[kSkU];
-};
-
-template <int NQ, int MH, bool GATED>
-__global__ __launch_bounds__(kSkThreads) void ppo_wenc_splitk_kernel(const float* __restrict__ S, const float* __restrict__ dE1,
-                                                                      const float* __restrict__ E1, float* __restrict__ part, int npix,
-                                                                      int cin, int pps) {
-    constexpr int NA = 4 * NQ * MH, CM = 32 * MH;
-    __shared__ float red[2][NA * 16 * 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, nl = lane & 31;
-    const int c0 = blockIdx.x * 128 * NQ;
-    const int p0 = blockIdx.y * pps, p1 = min(npix, p0 + pps);
-    const int ngroups = (p1 - p0 + 2 * kSkU - 1) / (2 * kSkU);
-    f32x16 acc[NA];
-#pragma unroll
-    for (int q = 0; q < NA; ++q)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[q][r] = 0.f;
-
-    // branch-free: a pixel past the slice reads the slice's last pixel (a cache hit) and takes a zero gradient
-    auto load = [&](int g, SkStage<NQ, MH>& s) {
-#pragma unroll
-        for (int u = 0; u < kSkU; ++u) {
-            const int pix = p0 + (g * kSkU + u) * 2 + half, pc = min(pix, p1 - 1);
-            const float* sp = S + (size_t)pc * cin + c0 + 4 * nl;
-#pragma unroll
-            for (int j = 0; j < NQ; ++j) s.b[u][j] = *reinterpret_cast<const f32x4*>(sp + 128 * j);
-#pragma unroll
-            for (int mh = 0; mh < MH; ++mh) {
-                s.d[u][mh] = dE1[(size_t)pc * CM + 32 * mh + nl];
-                s.e[u][mh] = GATED ? E1[(size_t)pc * CM + 32 * mh + nl] : 1.f;
-            }
-            s.ok[u] = pix < p1;
-        }
-    };
-
-    auto products = [&](const SkStage<NQ, MH>& s) {
-#pragma unroll
-        for (int u = 0; u < kSkU; ++u) {
-#pragma unroll
-            for (int mh = 0; mh < MH; ++mh) {
-                const float a = s.ok[u] && s.e[u][mh] > 0.f ? s.d[u][mh] : 0.f;     // the ReLU mask of the conv output, applied on the way in
-#pragma unroll
-                for (int j = 0; j < NQ; ++j)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const int k = 4 * (mh * NQ + j) + q;
-                        acc[k] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, s.b[u][j][q], acc[k], 0, 0, 0);
-                    }
-            }
-        }
-    };
-    // per group: requests, products, then a VALU read (an add into `fence`) of the youngest MFMA result, pinned by scheduling barriers: the
-    // next group's loads are requested only after every product that read the landing registers has retired.  The latency of a group's
-    // loads is covered by the block's other seven waves
-    SkStage<NQ, MH> st;
-    float fence = 0.f;
-    for (int g = wave; g < ngroups; g += kSkWaves) {
-        load(g, st);
-        __builtin_amdgcn_sched_barrier(0);
-        products(st);
-#pragma unroll
-        for (int q = 0; q < NA; ++q) fence += acc[q][15];      // (every accumulator: the compiler orders the independent chains as it likes)
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    asm volatile("" ::"v"(fence));      // (keeps the fence adds alive; no instruction, the result is untouched)
-
-    // the eight partials, pairwise through two LDS buffers
-    auto put = [&](int buf) {
-#pragma unroll
-        for (int q = 0; q < NA; ++q)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) red[buf][(q * 16 + r) * 64 + lane] = acc[q][r];
-    };
-    auto add = [&](int buf) {
-#pragma unroll
-        for (int q = 0; q < NA; ++q)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[q][r] = acc[q][r] + red[buf][(q * 16 + r) * 64 + lane];
-    };
-    // (writers, readers) per phase: w4, w5 -> w0, w1;  w6, w7 -> w2, w3;  w2, w3 -> w0, w1;  w1 -> w0
-    const int wr0[4] = {4, 6, 2, 1}, rd0[4] = {0, 2, 0, 0};
-#pragma unroll
-    for (int ph = 0; ph < 4; ++ph) {
-        const int pairs = ph == 3 ? 1 : 2;
-        if (wave >= wr0[ph] && wave < wr0[ph] + pairs) put(wave - wr0[ph]);
-        __syncthreads();
-        if (wave >= rd0[ph] && wave < rd0[ph] + pairs) add(wave - rd0[ph]);
-        __syncthreads();
-    }
-    if (wave == 0) {
-        float* o = part + (size_t)blockIdx.y * CM * cin + c0 + 4 * nl;
-#pragma unroll
-        for (int mh = 0; mh < MH; ++mh)
-#pragma unroll
-            for (int j = 0; j < NQ; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int m = (r & 3) + 8 * (r >> 2) + 4 * half, k = 4 * (mh * NQ + j);
-                    const f32x4 v = {acc[k][r], acc[k + 1][r], acc[k + 2][r], acc[k + 3][r]};
-                    *reinterpret_cast<f32x4*>(o + (size_t)(32 * mh + m) * cin + 128 * j) = v;
-                }
-    }
-}
-
-// dW[i] = part[0][i] + part[1][i] + ... in slice order
-__global__ void ppo_wenc_reduce_kernel(const float* part, int slices, int n, float* out) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    float v = 0.f;
-    for (int s = 0; s < slices; ++s) v += part[(size_t)s * n + i];
-    out[i] = v;
-}
-
-// pixel slices of the split-K launch: about one block per CU, at least 64 pixels per slice (plain arithmetic: the workspace query uses it).
-// A block takes 256 channels of 32 conv outputs where the channel count allows, else (and always with 64 outputs) 128
-int sk_slices(int npix, int cin, int cmid, int cus) {
-    const int chunks = (cmid == 32 && cin % 256 == 0) ? cin / 256 : cin / 128;
-    int s = cus / (chunks > 0 ? chunks : 1);
-    const int most = (npix + 63) / 64;
-    if (s > most) s = most;
-    return s < 1 ? 1 : s;
-}
-constexpr int kSkCus = 256;     // the workspace is sized for the MI355X's 256 CUs whatever the device reports (never fewer slices than used)
+// The core of splitk_wgrad.h on its pointwise source: M = the 32 or 64 conv outputs, K = the channels, the ReLU mask of the conv output
+// (e1) as the source's gate.  A block takes 256 channels of 32 conv outputs where the channel count allows, else (and always with 64
+// outputs, as two 32-row accumulator sets) 128
 bool sk_shape_ok(int cin, int cmid) { return (cmid == 32 || cmid == 64) && cin > 0 && cin % 128 == 0; }
+bool sk_wide(int cin, int cmid) { return cmid == 32 && cin % 256 == 0; }
+SkPlan sk_plan(int npix, int cin, int cmid, int cus) { return splitk_plan(npix, sk_wide(cin, cmid) ? cin / 256 : cin / 128, cus); }
 
-template <int NQ, int MH>
-void launch_sk(bool gated, dim3 grid, hipStream_t st, const float* states, const float* de1, const float* e1, float* ws, int npix, int cin, int pps) {
-    if (gated)
-        hipLaunchKernelGGL((ppo_wenc_splitk_kernel<NQ, MH, true>), grid, dim3(kSkThreads), 0, st, states, de1, e1, ws, npix, cin, pps);
+template <bool GATED>
+void launch_sk(const SkPointwise<GATED>& src, float* part, int npix, const SkPlan& pl, hipStream_t st) {
+    if (src.M == 64)
+        splitk_wgrad_launch<1, 2>(src, part, npix, src.K, src.M, pl, st);
+    else if (sk_wide(src.K, src.M))
+        splitk_wgrad_launch<2, 1>(src, part, npix, src.K, src.M, pl, st);
     else
-        hipLaunchKernelGGL((ppo_wenc_splitk_kernel<NQ, MH, false>), grid, dim3(kSkThreads), 0, st, states, de1, e1, ws, npix, cin, pps);
+        splitk_wgrad_launch<1, 1>(src, part, npix, src.K, src.M, pl, st);
 }
 
 // e1 == nullptr: de1 has its mask applied already
@@ -651,16 +516,12 @@ int launch_wenc_grad(adaf_handle* h, const float* states, const float* de1, cons
                      float* dw, float* ws, hipStream_t st) {
     if (split_k) {
         if (!sk_shape_ok(cin, cmid)) return adaf_fail(h, ADAF_E_LAYOUT, "ppo_wenc_grad: the split-K form needs 32 or 64 conv outputs and channels %% 128 == 0");
-        const int cus = h->cus < kSkCus ? h->cus : kSkCus;
-        const int slices = sk_slices(npix, cin, cmid, cus), pps = ((npix + slices - 1) / slices + 1) / 2 * 2;
-        const int used = (npix + pps - 1) / pps;
-        if (cmid == 64)
-            launch_sk<1, 2>(e1 != nullptr, dim3(cin / 128, used), st, states, de1, e1, ws, npix, cin, pps);
-        else if (cin % 256 == 0)
-            launch_sk<2, 1>(e1 != nullptr, dim3(cin / 256, used), st, states, de1, e1, ws, npix, cin, pps);
+        const SkPlan pl = sk_plan(npix, cin, cmid, h->cus < kSkCus ? h->cus : kSkCus);
+        if (e1)
+            launch_sk(SkPointwise<true>{states, de1, e1, cin, cmid}, ws, npix, pl, st);
         else
-            launch_sk<1, 1>(e1 != nullptr, dim3(cin / 128, used), st, states, de1, e1, ws, npix, cin, pps);
-        hipLaunchKernelGGL(ppo_wenc_reduce_kernel, dim3((cmid * cin + 255) / 256), dim3(256), 0, st, ws, used, cmid * cin, dw);
+            launch_sk(SkPointwise<false>{states, de1, nullptr, cin, cmid}, ws, npix, pl, st);
+        adaf_launch_slice_sum(ws, pl.used, (size_t)cmid * cin, dw, st);
     } else {
         // the single-chain form: the masked gradient as a tensor, then dW[m, c] = sum_i masked[i, m] S[i, c] as one ascending chain per output
         const size_t n = (size_t)npix * cmid;
@@ -671,7 +532,7 @@ int launch_wenc_grad(adaf_handle* h, const float* states, const float* de1, cons
 }
 
 size_t wenc_sk_floats(int npix, int cin, int cmid) {
-    return sk_shape_ok(cin, cmid) ? (size_t)sk_slices(npix, cin, cmid, kSkCus) * cmid * cin : 0;
+    return sk_shape_ok(cin, cmid) ? (size_t)sk_plan(npix, cin, cmid, kSkCus).slices * cmid * cin : 0;
 }
 
 // ---- workspace layouts: each written once, measured by the query (null base) and carved by the call -----------------------------------
@@ -695,7 +556,7 @@ size_t enc_backward_layout(void* ws, int steps, int batch, int map_pixels, int c
     r->de = c.take<float>(rows * hidden);
     r->de1 = c.take<float>(rows * mid);
     r->dwl = c.take<float>((size_t)hidden * mid);
-    r->part = c.take<float>(adaf_colsum_partial_floats(hidden));
+    r->part = c.take<float>(adaf_colsum_partial_floats(hidden, 1));
     r->wws = c.take<float>(wenc_sk_floats((int)(rows * map_pixels), channels, conv_out));
     r->dl = r->dc = nullptr;
     r->bnp = nullptr;
@@ -741,7 +602,7 @@ int run_encoder_backward(adaf_handle* h, const EncBackwardArgs& a, const EncBack
         const size_t n = (size_t)hidden * mid;
         hipLaunchKernelGGL(ppo_lin_grad_permute_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, r.dwl, a.dw_lin, hidden, a.map_pixels, a.conv_out);
     }
-    adaf_launch_colsum(dl, rows, hidden, hidden, r.part, a.db_lin, st);
+    adaf_launch_colsum(dl, rows, hidden, hidden, 1, r.part, a.db_lin, st);
     adaf_launch_gemm_strided(dl, hidden, 1, a.w_lin_pm, mid, 1, r.de1, mid, nullptr, 0, rows, mid, hidden, st);
     const int npix = rows * a.map_pixels;
     if (bn) {      // the ReLU mask goes into the BatchNorm backward; the conv's gradient arrives dense

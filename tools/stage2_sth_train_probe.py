@@ -88,21 +88,21 @@ def splitk_calls(sets, calls, split_k=True):
 
 
 def splitk_from_trace(d):
-    us = {"ppo_wenc_splitk": [], "ppo_wenc_reduce": []}
+    us = {"splitk_wgrad_kernel": [], "slice_sum_kernel": []}
     for f in glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True):
         for r in csv.DictReader(open(f)):
             for k in us:
                 if k in r["Kernel_Name"]:
                     us[k].append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
-    if not us["ppo_wenc_splitk"]:
+    if not us["splitk_wgrad_kernel"]:
         raise SystemExit("no split-K launches in the trace under %s" % d)
     chunks = CIN // 128
     slices = max(1, min(256 // chunks, (NPIX + 63) // 64))
-    k_us, r_us = statistics.median(us["ppo_wenc_splitk"]), statistics.median(us["ppo_wenc_reduce"])
+    k_us, r_us = statistics.median(us["splitk_wgrad_kernel"]), statistics.median(us["slice_sum_kernel"])
     state_bytes = NPIX * CIN * 4
     k_bytes = state_bytes + NPIX * CMID * 4 * chunks + slices * CMID * CIN * 4        # states once, the 64-wide gradient per chunk, partials
-    return dict(wenc_splitk_launches=len(us["ppo_wenc_splitk"]), wenc_splitk_kernel_us=round(k_us, 2),
-                wenc_splitk_kernel_us_min_max=[round(min(us["ppo_wenc_splitk"]), 2), round(max(us["ppo_wenc_splitk"]), 2)],
+    return dict(wenc_splitk_launches=len(us["splitk_wgrad_kernel"]), wenc_splitk_kernel_us=round(k_us, 2),
+                wenc_splitk_kernel_us_min_max=[round(min(us["splitk_wgrad_kernel"]), 2), round(max(us["splitk_wgrad_kernel"]), 2)],
                 wenc_reduce_kernel_us=round(r_us, 2), wenc_splitk_state_bytes=state_bytes, wenc_splitk_kernel_bytes=k_bytes,
                 wenc_splitk_state_frac_of_6p3_tb_s=round(state_bytes / (k_us * 1e-6) / HBM_BPS, 3),
                 wenc_splitk_bytes_frac_of_6p3_tb_s=round(k_bytes / (k_us * 1e-6) / HBM_BPS, 3))
