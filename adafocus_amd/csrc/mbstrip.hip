@@ -19,6 +19,13 @@
 //   * all addresses are per-wave constants plus a row stride: the loop has no index arithmetic.
 // Same products in the same order per output as mb_stem_b1_w_kernel and the unfused launches (the 16x16x4 chain takes its k lanes
 // in the order DESIGN 3.8 established: {0,4,1,5} then {2,6,3,7} of every 8-k group = the 32x32x2 chain): bit-identical.
+//
+// Layout of the file: the PHASES of the walk, each once (expand band, band -> ring, the tap passes, depthwise affine, project chain),
+// then the four kernels, which compose them and add what is their own -- the stem's input window and register-resident taps, the
+// segment walk of the whole blocks, the even | odd ring of the stride-2 block, the chunk groups and temporal-shift offsets of the
+// expand -> depthwise kernel.  The phases are forced inline and differ by compile-time facts only; every kernel is the device code it
+// was with the phases written out (tools/codeobj_compare.py).  What reads the kernel's argument block -- the tap-table fill, the chunk
+// operand loads, the project epilogue -- stays in the kernels: as functions those parts compile to other instructions (LABNOTES, "Strip kernels: the phases of the walk, each once").
 #include <type_traits>
 
 #include "adaf_internal.h"
@@ -30,12 +37,21 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 // Ablation build (tools/exp/build_mbs_abl.sh, never the product library): MBS_ABL bits switch parts of the kernels OFF to see what each costs --
 // 1 the expand / stem MFMA chains, 2 the project MFMA chains, 4 the depthwise tap FMAs, 8 the ring reads of the taps, 16 the pixel loads.
+// Each bit is tested in one place: expand_band, project, pkfma, ringr, bload.
 #ifndef MBS_ABL
 #define MBS_ABL 0
 #endif
 
 namespace {
 constexpr int ABL = MBS_ABL;
+
+constexpr int SW_OW = 14;                    // output columns of a strip
+constexpr int SW_EP = 36;                    // floats per pixel of the ring (32 channels + 4: conflict-free 16-byte reads)
+constexpr int SW_ROWF = 18 * SW_EP;          // 16 columns + 2 the idle lanes n = 14, 15 read past
+constexpr int SW_RING = 4 * SW_ROWF;
+constexpr int SW_TAPF = 11 * 8;              // floats per (chunk, k group) of the tap table: 9 taps | depthwise scale | depthwise bias, 8 channels each
+constexpr int S2_ROWF = 34 * SW_EP;          // a row of the stride-2 block's ring: 32 columns + 2 the idle lanes read past, even | odd halves of 17
+constexpr int S2_RING = 3 * S2_ROWF;
 
 // k offset (inside a 32-channel slice) that lane group g supplies as its q-th product of the 16x16x4 chain
 __device__ __forceinline__ int kq(int g, int q) { return 8 * (q >> 1) + (g >> 1) + 4 * (g & 1) + 2 * (q & 1); }
@@ -66,12 +82,184 @@ __device__ __forceinline__ void pkfma(f32x2& acc, f32x2 a, f32x2 b) {
 #endif
 }
 
-constexpr int SW_OW = 14;                    // output columns of a strip
-constexpr int SW_EP = 36;                    // floats per pixel of the ring (32 channels + 4: conflict-free 16-byte reads)
-constexpr int SW_ROWF = 18 * SW_EP;          // 16 columns + 2 the idle lanes n = 14, 15 read past
-constexpr int SW_RING = 4 * SW_ROWF;
+// ---- a lane's 8 channels (of a ring pixel, of a row of the tap table) as the four packed pairs the tap FMAs take
+__device__ __forceinline__ void pairs(f32x4 a, f32x4 b, f32x2 (&v)[4]) {
+    v[0] = f32x2{a.x, a.y}; v[1] = f32x2{a.z, a.w}; v[2] = f32x2{b.x, b.y}; v[3] = f32x2{b.z, b.w};
+}
+__device__ __forceinline__ void ring8(const float* p, f32x2 (&v)[4]) {
+    const f32x4 va = ringr(p), vb = ringr(p + 4);
+    pairs(va, vb, v);
+}
+__device__ __forceinline__ void tab8(const float* p, f32x2 (&v)[4]) {
+    const f32x4 ta = *reinterpret_cast<const f32x4*>(p), tb = *reinterpret_cast<const f32x4*>(p + 4);
+    pairs(ta, tb, v);
+}
+__device__ __forceinline__ void store8(float* o, const float* d) {
+    *reinterpret_cast<f32x4*>(o) = f32x4{d[0], d[1], d[2], d[3]};
+    *reinterpret_cast<f32x4*>(o + 4) = f32x4{d[4], d[5], d[6], d[7]};
+}
 
+// ---- where the taps of a pass come from: tap t = 3 ky + kx of the lane's 8 channels
+struct TableTaps {       // the chunk's rows of the LDS table, read at use
+    const float* tc;
+    __device__ __forceinline__ void operator()(int t, f32x2 (&v)[4]) const { tab8(tc + t * 8, v); }
+};
+struct RegTaps {         // registers, filled from the table once per chunk: the stride-2 block's (they fit beside its 32 accumulators)
+    const f32x2 (&tap)[9][4];
+    __device__ __forceinline__ void operator()(int t, f32x2 (&v)[4]) const {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = tap[t][i];
+    }
+};
+
+// ---- work items: x = q n + r.  Every kernel cuts blockIdx.x * 4 + wave into (frame, [segment | chunk group], strip) with it.
+__device__ __forceinline__ void divmod(int x, int n, int& q, int& r) { q = x / n; r = x - q * n; }
+
+// ---- expand band: 32 pixels x 32 channels = KK x NS4 products of the 32x32x2 chain, then BN + ReLU6 on accumulator pairs.
+// THE ORDERING RULE OF THIS FILE ("a load may not land in an MFMA's registers", DESIGN / LABNOTES round 5): a returning load is not interlocked
+// against an MFMA that still has to read the register it lands in; a VALU read of an MFMA's result is.  The affine below reads the chain's
+// result, so when this returns every MFMA that reads af / bf has retired -- and, issued earlier, so has every project MFMA of the step
+// before.  The kernels request their next operands only behind it, fenced by two sched_barrier(0): the next pixels and (in a chunk's last
+// step) the next chunk's filter rows and affine into af / bf / esc / ebi; a chunk's project rows wp in its step 0, which has no project
+// products of its own.
+template <int KK, int NS4 = 4>
+__device__ __forceinline__ f32x16 expand_band(const f32x4 (&af)[KK], const f32x4 (&bf)[KK], float sc, float bi) {
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma unroll
+    for (int kk = 0; kk < KK; ++kk)
+#pragma unroll
+        for (int s4 = 0; s4 < NS4; ++s4)
+            if (!(ABL & 1)) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[kk][s4], bf[kk][s4], acc, 0, 0, 0);
+    const f32x2 sc2 = {sc, sc}, bi2 = {bi, bi};
+#pragma unroll
+    for (int r = 0; r < 16; r += 2) {
+        const f32x2 v = __builtin_elementwise_fma(f32x2{acc[r], acc[r + 1]}, sc2, bi2);
+        acc[r] = __builtin_amdgcn_fmed3f(v.x, 0.f, 6.f);
+        acc[r + 1] = __builtin_amdgcn_fmed3f(v.y, 0.f, 6.f);
+    }
+    return acc;
+}
+
+// ---- four-slot ring of the stride-1 walks: expanded row rho (relative to the walk's first output row) lives in slot rho & 3.
+// Row e = 0 .. 3 of the four rows 2 s - 3 .. 2 s that step s (parity par) taps; the step itself writes e = 2, 3.
+constexpr int ring4(int par, int e) { return (2 * par + 1 + e) & 3; }
+
+// A band (accumulator row r: expanded row r >> 3, column (r & 3) + 8 ((r >> 2) & 1) + 4 half) into its two ring slots.  Pixels outside the map are
+// the depthwise conv's zero padding: rows -1 / H (ztop / zbot) and columns -1 / W (left / right strips) are forced to zero first.  (All four are
+// wave-uniform: the empty asm keeps each a branch -- if-converted they are selects in every step of every strip.)  The first wave_barrier:
+// the previous step's tap reads are issued (same-wave LDS traffic runs in order); the second: the writes are, before this step's taps.
+template <int PAR>
+__device__ __forceinline__ void band_to_ring(f32x16& acc, float* ewr, bool ztop, bool zbot, bool left, bool right, int half) {
+    if (ztop) {
+        asm volatile("");
+#pragma unroll
+        for (int r = 0; r < 8; ++r) acc[r] = 0.f;
+    }
+    if (zbot) {
+        asm volatile("");
+#pragma unroll
+        for (int r = 8; r < 16; ++r) acc[r] = 0.f;
+    }
+    if (left) { asm volatile(""); if (half == 0) { acc[0] = 0.f; acc[8] = 0.f; } }       // (ec = 0: rows r = 0, 8 of half 0)
+    if (right) { asm volatile(""); if (half == 1) { acc[7] = 0.f; acc[15] = 0.f; } }     // (ec = 15: rows r = 7, 15 of half 1)
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int r = 0; r < 16; ++r) ewr[ring4(PAR, r < 8 ? 2 : 3) * SW_ROWF + ((r & 3) + 8 * ((r >> 2) & 1)) * SW_EP] = acc[r];
+    __builtin_amdgcn_wave_barrier();
+}
+
+// ---- depthwise taps, stride 1, taps from the chunk's rows tc of the LDS table: the two output rows that step s completes (sum[0]: rows
+// e = 0 .. 2 of the ring, sum[1]: e = 1 .. 3).  A ring pixel is read once and feeds both; a row's taps are fetched once (tcur) and serve the
+// second output row one ring row later (tprev).  (The stem keeps its nine taps in registers and has this pass in its own form.)
+template <int PAR>
+__device__ __forceinline__ void taps_two_rows(const float* erd, const float* tc, f32x2 (&sum)[2][4]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { sum[0][i] = f32x2{0.f, 0.f}; sum[1][i] = f32x2{0.f, 0.f}; }
+    f32x2 tprev[3][4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        f32x2 tcur[3][4];
+        if (e < 3) {
+#pragma unroll
+            for (int kx = 0; kx < 3; ++kx) tab8(tc + (e * 3 + kx) * 8, tcur[kx]);
+        }
+#pragma unroll
+        for (int kx = 0; kx < 3; ++kx) {
+            f32x2 v[4];
+            ring8(erd + ring4(PAR, e) * SW_ROWF + kx * SW_EP, v);
+            if (e < 3) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) pkfma(sum[0][i], v[i], tcur[kx][i]);
+            }
+            if (e > 0) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) pkfma(sum[1][i], v[i], tprev[kx][i]);
+            }
+        }
+        if (e < 3) {
+#pragma unroll
+            for (int kx = 0; kx < 3; ++kx)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) tprev[kx][i] = tcur[kx][i];
+        }
+    }
+}
+
+// ---- depthwise taps, stride 2: ring row ky of the three under one output row.  EO: the even | odd ring of the stride-2 block (tap kx of output
+// column n is expanded column 2 n + kx = position n | 17 + n | n + 1); otherwise the four-slot ring, erd at column 2 n.
+template <bool EO, class Taps>
+__device__ __forceinline__ void taps_ring_row(const float* prow, int ky, Taps taps, f32x2 (&sum)[4]) {
+#pragma unroll
+    for (int kx = 0; kx < 3; ++kx) {
+        f32x2 t4[4], v[4];
+        taps(ky * 3 + kx, t4);
+        ring8(prow + (EO ? (kx == 1 ? 17 : kx == 2 ? 1 : 0) : kx) * SW_EP, v);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) pkfma(sum[i], v[i], t4[i]);
+    }
+}
+
+// ---- depthwise BN + ReLU6 of NR output rows: the tap sums become the 8 values per row that the lane stores or feeds to the project chain
+template <int NR>
+__device__ __forceinline__ void dw_affine(const f32x2 (&sum)[NR][4], const f32x2 (&dsc)[4], const f32x2 (&dbi)[4], float (&d)[NR][8]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        f32x2 r[NR];
+#pragma unroll
+        for (int j = 0; j < NR; ++j) r[j] = __builtin_elementwise_fma(sum[j][i], dsc[i], dbi[i]);
+#pragma unroll
+        for (int j = 0; j < NR; ++j) { d[j][2 * i] = __builtin_amdgcn_fmed3f(r[j].x, 0.f, 6.f); d[j][2 * i + 1] = __builtin_amdgcn_fmed3f(r[j].y, 0.f, 6.f); }
+    }
+}
+// ... with scale and bias from rows 9, 10 of the chunk's tap table
+template <int NR>
+__device__ __forceinline__ void dw_affine_table(const f32x2 (&sum)[NR][4], const float* tc, float (&d)[NR][8]) {
+    const f32x4 sa = *reinterpret_cast<const f32x4*>(tc + 72), sb = *reinterpret_cast<const f32x4*>(tc + 76);
+    const f32x4 ba = *reinterpret_cast<const f32x4*>(tc + 80), bb = *reinterpret_cast<const f32x4*>(tc + 84);
+    f32x2 dsc[4], dbi[4];
+    pairs(sa, sb, dsc);
+    pairs(ba, bb, dbi);
+    dw_affine<NR>(sum, dsc, dbi, d);
+}
+
+// ---- project chain: C[cout][pixel] += sum_k Wp[cout][k] D[pixel][k] over this lane's 8 k, for NR pixel rows x NM blocks of 16 output channels;
+// the lane's accumulator is output channels 16 m + 4 g .. + 3 of pixel n
+template <int NR, int NM>
+__device__ __forceinline__ void project(const float (&wp)[NM][8], const float (&d)[NR][8], f32x4 (&P)[NR][NM]) {
+#pragma unroll
+    for (int q = 0; q < 8 && !(ABL & 2); ++q)
+#pragma unroll
+        for (int m = 0; m < NM; ++m)
+#pragma unroll
+            for (int j = 0; j < NR; ++j) P[j][m] = __builtin_amdgcn_mfma_f32_16x16x4f32(wp[m][q], d[j][q], P[j][m], 0, 0, 0);
+}
+
+
+// ---------------------------------------------------------------------------------------------------------------------------------
 // Stem (3x3 / 2, 3 -> 32, BN, ReLU6) -> block 1 (depthwise 3x3, BN, ReLU6 -> project 32 -> 16, BN).  Requires S == 2 * H1, H1 % 14 == 0.
+// Its own: the 3x3 / 2 input window as the band's A operand (five k pairs of taps against bs), one set of taps and affines in registers.
 __global__ __launch_bounds__(256, 2) void mb_stem_b1_s_kernel(const MbStemArgs a) {
     __shared__ __attribute__((aligned(16))) float Eall[4][SW_RING];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -80,7 +268,8 @@ __global__ __launch_bounds__(256, 2) void mb_stem_b1_s_kernel(const MbStemArgs a
     const int nstrips = a.tiles_x;
     const int strip = blockIdx.x * 4 + wave;
     if (strip >= a.n * nstrips) return;
-    const int img = strip / nstrips, sx = strip - img * nstrips;
+    int img, sx;
+    divmod(strip, nstrips, img, sx);
     const int ox0 = sx * SW_OW;
     const bool left = sx == 0, right = sx == nstrips - 1;
     const int S = a.S, H1 = a.H1;
@@ -115,14 +304,14 @@ __global__ __launch_bounds__(256, 2) void mb_stem_b1_s_kernel(const MbStemArgs a
 #pragma unroll
         for (int q = 0; q < 8; q += 2) tap[t][q >> 1] = f32x2{a.wd[t * 32 + kq(g, q)], a.wd[t * 32 + kq(g, q + 1)]};
     f32x2 dsc[4], dbi[4];
-    float wp[8];
+    float wp[1][8];
 #pragma unroll
     for (int q = 0; q < 8; q += 2) {
         dsc[q >> 1] = f32x2{a.sd[kq(g, q)], a.sd[kq(g, q + 1)]};
         dbi[q >> 1] = f32x2{a.bd[kq(g, q)], a.bd[kq(g, q + 1)]};
     }
 #pragma unroll
-    for (int q = 0; q < 8; ++q) wp[q] = a.wp[n * 32 + kq(g, q)];
+    for (int q = 0; q < 8; ++q) wp[0][q] = a.wp[n * 32 + kq(g, q)];
     const f32x4 psc = *reinterpret_cast<const f32x4*>(a.sp + 4 * g), pbi = *reinterpret_cast<const f32x4*>(a.bp + 4 * g);
     const float* erd = Ew + n * SW_EP + 8 * g;
     float* const orow0 = a.out + ((size_t)img * H1 * H1 + ox0 + n) * 16 + 4 * g;      // output row 0 of this lane's column
@@ -139,98 +328,49 @@ __global__ __launch_bounds__(256, 2) void mb_stem_b1_s_kernel(const MbStemArgs a
     __builtin_amdgcn_wave_barrier();
 
     const int nsteps = H1 / 2 + 1;
-    // PAR = s & 1: the E rows 2 s - 1, 2 s of step s live in ring slots (3, 0) for even s and (1, 2) for odd s
     auto step = [&](auto PAR, int s) {
-        constexpr int par = decltype(PAR)::value;
-        constexpr int SL0 = par ? 1 : 3, SL1 = par ? 2 : 0;
+        constexpr int par = decltype(PAR)::value;       // s & 1
         if (left) {       // (wave-uniform: the empty asm keeps it a branch -- if-converted it is 12 selects in every step of every strip)
             asm volatile("");
             af[0] = zl0 ? zero4 : af[0];
             af[1] = zl1 ? zero4 : af[1];
             af[3] = zl0 ? zero4 : af[3];
         }
-        f32x16 acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-        for (int kk = 0; kk < 5; ++kk)
-#pragma unroll
-            for (int s4 = 0; s4 < 3; ++s4)      // (the fourth "channel" of a pixel-major frame has zero filter entries: its five products add +-0 to an
-                                                //  accumulator that is +0 or non-zero at that point -- the same bits without them, a quarter of the chain gone)
-                if (!(ABL & 1)) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[kk][s4], bs[kk][s4], acc, 0, 0, 0);
-        // BN + ReLU6; stem outputs outside the map are the depthwise conv's zero padding
-        {
-            const f32x2 sc2 = {ssc, ssc}, bi2 = {sbi, sbi};
-#pragma unroll
-            for (int r = 0; r < 16; r += 2) {
-                const f32x2 v = __builtin_elementwise_fma(f32x2{acc[r], acc[r + 1]}, sc2, bi2);
-                acc[r] = __builtin_amdgcn_fmed3f(v.x, 0.f, 6.f);
-                acc[r + 1] = __builtin_amdgcn_fmed3f(v.y, 0.f, 6.f);
-            }
-        }
-        // The next step's pixels are requested only HERE: a returning load is not interlocked against an MFMA that still has to read the
-        // register it lands in (DESIGN / LABNOTES "a load may not land in an MFMA's registers", round 5) -- the VALU reads of the chain's
-        // result above are, so past this point every MFMA that reads af[] has retired.
-        __builtin_amdgcn_sched_barrier(0);
+        // (NS4 = 3: the fourth "channel" of a pixel-major frame has zero filter entries: its five products add +-0 to an accumulator that is +0 or
+        //  non-zero at that point -- the same bits without them, a quarter of the chain gone)
+        f32x16 acc = expand_band<5, 3>(af, bs, ssc, sbi);
+        __builtin_amdgcn_sched_barrier(0);      // (the chain has retired: see expand_band)
         if (s + 1 < nsteps) fetch();
         __builtin_amdgcn_sched_barrier(0);
-        if (s == 0) {
-            asm volatile("");
-#pragma unroll
-            for (int r = 0; r < 8; ++r) acc[r] = 0.f;           // E row -1
-        }
-        if (s == nsteps - 1) {
-            asm volatile("");
-#pragma unroll
-            for (int r = 8; r < 16; ++r) acc[r] = 0.f;          // E row H1
-        }
-        if (left) { asm volatile(""); if (half == 0) { acc[0] = 0.f; acc[8] = 0.f; } }     // E column -1   (ec = 0: rows r = 0, 8 of half 0)
-        if (right) { asm volatile(""); if (half == 1) { acc[7] = 0.f; acc[15] = 0.f; } }   // E column H1   (ec = 15: rows r = 7, 15 of half 1)
-        __builtin_amdgcn_wave_barrier();        // the previous step's tap reads are issued (same-wave LDS traffic runs in order)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) ewr[(r < 8 ? SL0 : SL1) * SW_ROWF + ((r & 3) + 8 * ((r >> 2) & 1)) * SW_EP] = acc[r];
-        __builtin_amdgcn_wave_barrier();
+        band_to_ring<par>(acc, ewr, s == 0, s == nsteps - 1, left, right, half);
         if (s > 0) {
-            // ---- depthwise 3x3 of output rows y0 = 2 s - 2, y1 = 2 s - 1 from E rows 2 s - 3 .. 2 s
-            constexpr int R0 = par ? 3 : 1, R1 = par ? 0 : 2, R2 = SL0, R3 = SL1;
-            constexpr int slot[4] = {R0, R1, R2, R3};
-            f32x2 s0[4], s1[4];
+            // ---- depthwise 3x3 of output rows 2 s - 2, 2 s - 1 from E rows 2 s - 3 .. 2 s, project 32 -> 16 + BN
+            f32x2 sum[2][4];
+            float d[2][8];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) { s0[i] = f32x2{0.f, 0.f}; s1[i] = f32x2{0.f, 0.f}; }
+            for (int i = 0; i < 4; ++i) { sum[0][i] = f32x2{0.f, 0.f}; sum[1][i] = f32x2{0.f, 0.f}; }
 #pragma unroll
             for (int e = 0; e < 4; ++e)
 #pragma unroll
                 for (int kx = 0; kx < 3; ++kx) {
-                    const float* p = erd + slot[e] * SW_ROWF + kx * SW_EP;
-                    const f32x4 va = ringr(p), vb = ringr(p + 4);
-                    const f32x2 v[4] = {{va.x, va.y}, {va.z, va.w}, {vb.x, vb.y}, {vb.z, vb.w}};
+                    f32x2 v[4];
+                    ring8(erd + ring4(par, e) * SW_ROWF + kx * SW_EP, v);
                     if (e < 3) {
 #pragma unroll
-                        for (int i = 0; i < 4; ++i) pkfma(s0[i], v[i], tap[e * 3 + kx][i]);
+                        for (int i = 0; i < 4; ++i) pkfma(sum[0][i], v[i], tap[e * 3 + kx][i]);
                     }
                     if (e > 0) {
 #pragma unroll
-                        for (int i = 0; i < 4; ++i) pkfma(s1[i], v[i], tap[(e - 1) * 3 + kx][i]);
+                        for (int i = 0; i < 4; ++i) pkfma(sum[1][i], v[i], tap[(e - 1) * 3 + kx][i]);
                     }
                 }
-            float d0[8], d1[8];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const f32x2 r0 = __builtin_elementwise_fma(s0[i], dsc[i], dbi[i]), r1 = __builtin_elementwise_fma(s1[i], dsc[i], dbi[i]);
-                d0[2 * i] = __builtin_amdgcn_fmed3f(r0.x, 0.f, 6.f); d0[2 * i + 1] = __builtin_amdgcn_fmed3f(r0.y, 0.f, 6.f);
-                d1[2 * i] = __builtin_amdgcn_fmed3f(r1.x, 0.f, 6.f); d1[2 * i + 1] = __builtin_amdgcn_fmed3f(r1.y, 0.f, 6.f);
-            }
-            // ---- project 32 -> 16 + BN: C[cout][pixel] = sum_k Wp[cout][k] D[pixel][k]; this lane gets couts 4 g .. 4 g + 3 of pixel n
-            f32x4 p0 = zero4, p1 = zero4;
-#pragma unroll
-            for (int q = 0; q < 8 && !(ABL & 2); ++q) {
-                p0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wp[q], d0[q], p0, 0, 0, 0);
-                p1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wp[q], d1[q], p1, 0, 0, 0);
-            }
+            dw_affine<2>(sum, dsc, dbi, d);
+            f32x4 p[2][1] = {{zero4}, {zero4}};
+            project<2, 1>(wp, d, p);
             if (ostore) {
                 f32x4 o0, o1;
 #pragma unroll
-                for (int i = 0; i < 4; ++i) { o0[i] = fmaf(p0[i], psc[i], pbi[i]) + 0.f; o1[i] = fmaf(p1[i], psc[i], pbi[i]) + 0.f; }
+                for (int i = 0; i < 4; ++i) { o0[i] = fmaf(p[0][0][i], psc[i], pbi[i]) + 0.f; o1[i] = fmaf(p[1][0][i], psc[i], pbi[i]) + 0.f; }
                 float* optr = orow0 + (size_t)(2 * s - 2) * H1 * 16;
                 *reinterpret_cast<f32x4*>(optr) = o0;
                 *reinterpret_cast<f32x4*>(optr + (size_t)H1 * 16) = o1;
@@ -253,11 +393,10 @@ __global__ __launch_bounds__(256, 2) void mb_stem_b1_s_kernel(const MbStemArgs a
 // straight into the B operand of the project conv's 16x16x4 chain.  The project accumulators of all SEG rows stay in registers across
 // the chunks (SEG / 2 row pairs x 2 rows x two 16-channel blocks), so the project conv sums its k slices in the conv engine's order
 // (slices of 32, a partial last slice zero-filled): bit-identical to mb_block_w_kernel and to the three separate launches.
-// The depthwise taps and affines of every chunk sit in LDS in the order the lanes consume them ([chunk][k group][tap][8]): a lane's
-// 8 channels x 9 taps would be 72 registers next to 64 of accumulators.  The input needs no padding select at all: expanded pixels
-// outside the map are forced to zero (the depthwise conv pads the EXPANDED map), rows outside the frame load as zeros anyway.
-constexpr int SW_SEG = 8;                    // output rows of a segment
-constexpr int SW_TAPF = 11 * 8;              // floats per (chunk, k group): 9 taps | depthwise scale | depthwise bias, 8 channels each
+// The depthwise taps and affines of every chunk sit in LDS in the order the lanes consume them (Tall[chunk][k group][9 taps | scale |
+// bias][8]): a lane's 8 channels x 9 taps would be 72 registers next to 64 of accumulators.  The input needs no padding select at all:
+// expanded pixels outside the map are forced to zero (the depthwise conv pads the EXPANDED map), rows outside the frame load as zeros anyway.
+constexpr int SW_SEG = 8;                   // output rows of a segment
 constexpr int SW_MAXCH = 6;                  // chunks (hid <= 192)
 
 template <int CIN>
@@ -267,7 +406,7 @@ __global__ __launch_bounds__(256, 2) void mb_block_s_kernel(const MbFuseArgs a) 
     __shared__ __attribute__((aligned(16))) float Tall[SW_MAXCH * 4 * SW_TAPF];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int hid = a.hid, nchunks = (hid + 31) >> 5;
-    for (int idx = tid; idx < nchunks * 4 * SW_TAPF; idx += 256) {
+    for (int idx = tid; idx < nchunks * 4 * SW_TAPF; idx += 256) {       // the tap table, a group's 8 channels in kq order, channels past hid zero
         const int q = idx & 7, t = (idx >> 3) % 11, cg = idx / SW_TAPF;
         const int ch = 32 * (cg >> 2) + kq(cg & 3, q);
         float v = 0.f;
@@ -280,8 +419,9 @@ __global__ __launch_bounds__(256, 2) void mb_block_s_kernel(const MbFuseArgs a) 
     const int nstrips = a.tiles_x, nsegs = a.tiles_y;
     const int item = blockIdx.x * 4 + wave;
     if (item >= a.n * nstrips * nsegs) return;
-    const int img = item / (nstrips * nsegs), rem = item - img * (nstrips * nsegs);
-    const int seg = rem / nstrips, sx = rem - seg * nstrips;        // (the strips of a row segment are neighbours: they share input lines)
+    int img, rem, seg, sx;
+    divmod(item, nstrips * nsegs, img, rem);
+    divmod(rem, nstrips, seg, sx);                                  // (the strips of a row segment are neighbours: they share input lines)
     const int ox0 = sx * SW_OW, y0 = seg * SW_SEG;
     const int H = a.H, W = a.W;
     const int rows = H - y0 < SW_SEG ? H - y0 : SW_SEG;             // output rows of this segment (even)
@@ -308,10 +448,7 @@ __global__ __launch_bounds__(256, 2) void mb_block_s_kernel(const MbFuseArgs a) 
 #pragma unroll
         for (int j = 0; j < 2; ++j) { P[i][j][0] = zero4; P[i][j][1] = zero4; }
 
-    // Chunk operands.  bf / af are read by the expand chain, wp by the project chains: a global load may only target them once a VALU
-    // instruction has read the result of an MFMA issued after their last reader (see the stem kernel) -- so the next chunk's bf and its
-    // first pixels are requested in the chunk's LAST step behind the epilogue, and wp of a chunk in its step 0 behind the epilogue (by
-    // then the previous chunk's project chains have retired; step 0 has no project products of its own).
+    // chunk operands: requested behind the expand band only (see expand_band)
     f32x4 bf[KK], af[KK];
     float esc, ebi, wp[2][8];
     auto load_bf = [&](int c) {
@@ -351,24 +488,8 @@ __global__ __launch_bounds__(256, 2) void mb_block_s_kernel(const MbFuseArgs a) 
         auto step = [&](auto SC) {
             constexpr int s = decltype(SC)::value;
             constexpr int par = s & 1;
-            constexpr int SL0 = par ? 1 : 3, SL1 = par ? 2 : 0;
-            f32x16 acc;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-            for (int kk = 0; kk < KK; ++kk)
-#pragma unroll
-                for (int s4 = 0; s4 < 4; ++s4) if (!(ABL & 1)) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[kk][s4], bf[kk][s4], acc, 0, 0, 0);
-            {
-                const f32x2 sc2 = {esc, esc}, bi2 = {ebi, ebi};
-#pragma unroll
-                for (int r = 0; r < 16; r += 2) {
-                    const f32x2 v = __builtin_elementwise_fma(f32x2{acc[r], acc[r + 1]}, sc2, bi2);
-                    acc[r] = __builtin_amdgcn_fmed3f(v.x, 0.f, 6.f);
-                    acc[r + 1] = __builtin_amdgcn_fmed3f(v.y, 0.f, 6.f);
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);      // (the chain has retired: see above)
+            f32x16 acc = expand_band<KK>(af, bf, esc, ebi);
+            __builtin_amdgcn_sched_barrier(0);
             if (s == 0) load_wp(c);
             if (s + 1 < NST && s + 1 < nsteps) fetch(s + 1);
             else if (c + 1 < nchunks) {
@@ -377,78 +498,13 @@ __global__ __launch_bounds__(256, 2) void mb_block_s_kernel(const MbFuseArgs a) 
                 fetch(0);
             }
             __builtin_amdgcn_sched_barrier(0);
-            if (s == 0) {
-                if (top) {
-                    asm volatile("");
-#pragma unroll
-                    for (int r = 0; r < 8; ++r) acc[r] = 0.f;       // expanded row -1
-                }
-            } else if (bottom && s == nsteps - 1) {
-                asm volatile("");
-#pragma unroll
-                for (int r = 8; r < 16; ++r) acc[r] = 0.f;          // expanded row H
-            }
-            if (left) { asm volatile(""); if (half == 0) { acc[0] = 0.f; acc[8] = 0.f; } }      // expanded column -1
-            if (right) { asm volatile(""); if (half == 1) { acc[7] = 0.f; acc[15] = 0.f; } }    // expanded column W
-            __builtin_amdgcn_wave_barrier();
-#pragma unroll
-            for (int r = 0; r < 16; ++r) ewr[(r < 8 ? SL0 : SL1) * SW_ROWF + ((r & 3) + 8 * ((r >> 2) & 1)) * SW_EP] = acc[r];
-            __builtin_amdgcn_wave_barrier();
+            band_to_ring<par>(acc, ewr, s == 0 && top, s > 0 && bottom && s == nsteps - 1, left, right, half);
             if constexpr (s > 0) {
-                constexpr int slot[4] = {par ? 3 : 1, par ? 0 : 2, SL0, SL1};
-                f32x2 s0[4], s1[4];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) { s0[i] = f32x2{0.f, 0.f}; s1[i] = f32x2{0.f, 0.f}; }
-                f32x2 tprev[3][4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    f32x2 tcur[3][4];
-                    if (e < 3) {
-#pragma unroll
-                        for (int kx = 0; kx < 3; ++kx) {
-                            const f32x4 ta = *reinterpret_cast<const f32x4*>(tc + (e * 3 + kx) * 8), tb = *reinterpret_cast<const f32x4*>(tc + (e * 3 + kx) * 8 + 4);
-                            tcur[kx][0] = f32x2{ta.x, ta.y}; tcur[kx][1] = f32x2{ta.z, ta.w}; tcur[kx][2] = f32x2{tb.x, tb.y}; tcur[kx][3] = f32x2{tb.z, tb.w};
-                        }
-                    }
-#pragma unroll
-                    for (int kx = 0; kx < 3; ++kx) {
-                        const float* p = erd + slot[e] * SW_ROWF + kx * SW_EP;
-                        const f32x4 va = ringr(p), vb = ringr(p + 4);
-                        const f32x2 v[4] = {{va.x, va.y}, {va.z, va.w}, {vb.x, vb.y}, {vb.z, vb.w}};
-                        if (e < 3) {
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) pkfma(s0[i], v[i], tcur[kx][i]);
-                        }
-                        if (e > 0) {
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) pkfma(s1[i], v[i], tprev[kx][i]);
-                        }
-                    }
-                    if (e < 3) {
-#pragma unroll
-                        for (int kx = 0; kx < 3; ++kx)
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) tprev[kx][i] = tcur[kx][i];
-                    }
-                }
-                const f32x4 sa = *reinterpret_cast<const f32x4*>(tc + 72), sb = *reinterpret_cast<const f32x4*>(tc + 76);
-                const f32x4 ba = *reinterpret_cast<const f32x4*>(tc + 80), bb = *reinterpret_cast<const f32x4*>(tc + 84);
-                const f32x2 dsc[4] = {{sa.x, sa.y}, {sa.z, sa.w}, {sb.x, sb.y}, {sb.z, sb.w}}, dbi[4] = {{ba.x, ba.y}, {ba.z, ba.w}, {bb.x, bb.y}, {bb.z, bb.w}};
-                float d0[8], d1[8];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const f32x2 r0 = __builtin_elementwise_fma(s0[i], dsc[i], dbi[i]), r1 = __builtin_elementwise_fma(s1[i], dsc[i], dbi[i]);
-                    d0[2 * i] = __builtin_amdgcn_fmed3f(r0.x, 0.f, 6.f); d0[2 * i + 1] = __builtin_amdgcn_fmed3f(r0.y, 0.f, 6.f);
-                    d1[2 * i] = __builtin_amdgcn_fmed3f(r1.x, 0.f, 6.f); d1[2 * i + 1] = __builtin_amdgcn_fmed3f(r1.y, 0.f, 6.f);
-                }
-#pragma unroll
-                for (int q = 0; q < 8 && !(ABL & 2); ++q) {
-#pragma unroll
-                    for (int m = 0; m < 2; ++m) {
-                        P[s - 1][0][m] = __builtin_amdgcn_mfma_f32_16x16x4f32(wp[m][q], d0[q], P[s - 1][0][m], 0, 0, 0);
-                        P[s - 1][1][m] = __builtin_amdgcn_mfma_f32_16x16x4f32(wp[m][q], d1[q], P[s - 1][1][m], 0, 0, 0);
-                    }
-                }
+                f32x2 sum[2][4];
+                float d[2][8];
+                taps_two_rows<par>(erd, tc, sum);
+                dw_affine_table<2>(sum, tc, d);
+                project<2, 2>(wp, d, P[s - 1]);
             }
         };
         step(std::integral_constant<int, 0>{});
@@ -499,8 +555,6 @@ __global__ __launch_bounds__(256, 2) void mb_block_s_kernel(const MbFuseArgs a) 
 // project launch and its read of the depthwise map are gone.  Same products in the same order as mb_expand_dw_w_kernel + the engine's
 // 1x1 conv: bit-identical.
 constexpr int S2_SEG = 4;
-constexpr int S2_ROWF = 34 * SW_EP;          // 32 columns + 2 the idle lanes read past, even | odd halves of 17
-constexpr int S2_RING = 3 * S2_ROWF;
 
 template <int CIN>
 __global__ __launch_bounds__(256, 2) void mb_block_s2_kernel(const MbFuseArgs a) {
@@ -509,7 +563,7 @@ __global__ __launch_bounds__(256, 2) void mb_block_s2_kernel(const MbFuseArgs a)
     __shared__ __attribute__((aligned(16))) float Tall[SW_MAXCH * 4 * SW_TAPF];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int hid = a.hid, nchunks = (hid + 31) >> 5;
-    for (int idx = tid; idx < nchunks * 4 * SW_TAPF; idx += 256) {
+    for (int idx = tid; idx < nchunks * 4 * SW_TAPF; idx += 256) {       // the tap table, a group's 8 channels in kq order, channels past hid zero
         const int q = idx & 7, t = (idx >> 3) % 11, cg = idx / SW_TAPF;
         const int ch = 32 * (cg >> 2) + kq(cg & 3, q);
         float v = 0.f;
@@ -522,8 +576,9 @@ __global__ __launch_bounds__(256, 2) void mb_block_s2_kernel(const MbFuseArgs a)
     const int nstrips = a.tiles_x, nsegs = a.tiles_y;
     const int item = blockIdx.x * 4 + wave;
     if (item >= a.n * nstrips * nsegs) return;
-    const int img = item / (nstrips * nsegs), rem = item - img * (nstrips * nsegs);
-    const int seg = rem / nstrips, sx = rem - seg * nstrips;
+    int img, rem, seg, sx;
+    divmod(item, nstrips * nsegs, img, rem);
+    divmod(rem, nstrips, seg, sx);
     const int ox0 = sx * SW_OW, y0 = seg * S2_SEG;
     const int H = a.H, W = a.W, OH = a.OH, OW = a.OW;
     const int rows = OH - y0 < S2_SEG ? OH - y0 : S2_SEG;
@@ -540,14 +595,14 @@ __global__ __launch_bounds__(256, 2) void mb_block_s2_kernel(const MbFuseArgs a)
 
     // ---- depthwise / project roles: (output column n, k group g)
     const int n = lane & 15, g = lane >> 4;
-    const float* erd = Ew + n * SW_EP + 8 * g;              // tap kx of output column n: expanded column 2 n + kx -> position n | 17 + n | n + 1
+    const float* erd = Ew + n * SW_EP + 8 * g;
     const float* tw = Tall + g * SW_TAPF;
 
-    f32x4 P[S2_SEG][2];
+    f32x4 P[S2_SEG][1][2];              // [row][.][16-channel block]
 #pragma unroll
-    for (int i = 0; i < S2_SEG; ++i) { P[i][0] = zero4; P[i][1] = zero4; }
+    for (int i = 0; i < S2_SEG; ++i) { P[i][0][0] = zero4; P[i][0][1] = zero4; }
 
-    // chunk operands: requested behind VALU reads of MFMA results only (see the kernels above)
+    // chunk operands: requested behind the expand bands only (see expand_band)
     f32x4 bf[KK], afa[KK], afb[KK];
     float esc, ebi, wp[2][8];
     auto load_bf = [&](int c) {
@@ -589,32 +644,16 @@ __global__ __launch_bounds__(256, 2) void mb_block_s2_kernel(const MbFuseArgs a)
     fetch(0);
     for (int c = 0; c < nchunks; ++c) {
         const float* tc = tw + c * 4 * SW_TAPF;
-        // the chunk's taps and depthwise affine: 8 channels x (9 + 2) of this lane's k group, from the table
+        // the chunk's taps: 8 channels x 9 of this lane's k group, from the table
         f32x2 tap[9][4];
 #pragma unroll
-        for (int t = 0; t < 9; ++t) {
-            const f32x4 ta = *reinterpret_cast<const f32x4*>(tc + t * 8), tb = *reinterpret_cast<const f32x4*>(tc + t * 8 + 4);
-            tap[t][0] = f32x2{ta.x, ta.y}; tap[t][1] = f32x2{ta.z, ta.w}; tap[t][2] = f32x2{tb.x, tb.y}; tap[t][3] = f32x2{tb.z, tb.w};
-        }
+        for (int t = 0; t < 9; ++t) tab8(tc + t * 8, tap[t]);
         auto step = [&](auto SC) {
             constexpr int s = decltype(SC)::value;
             constexpr int SLA = (2 * s) % 3, SLB = (2 * s + 1) % 3, SLP = (2 * s + 2) % 3;      // (2 s - 1) % 3
-            // one expanded row = one band: chain -> BN / ReLU6 -> ring, row A (absent in step 0) then row B
+            // one expanded row = one band into one ring slot, row A (absent in step 0) then row B
             auto band = [&](const f32x4 (&af)[KK], int slotf, bool zero_row) {
-                f32x16 acc;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-                for (int kk = 0; kk < KK; ++kk)
-#pragma unroll
-                    for (int s4 = 0; s4 < 4; ++s4) if (!(ABL & 1)) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[kk][s4], bf[kk][s4], acc, 0, 0, 0);
-                const f32x2 sc2 = {esc, esc}, bi2 = {ebi, ebi};
-#pragma unroll
-                for (int r = 0; r < 16; r += 2) {
-                    const f32x2 v = __builtin_elementwise_fma(f32x2{acc[r], acc[r + 1]}, sc2, bi2);
-                    acc[r] = __builtin_amdgcn_fmed3f(v.x, 0.f, 6.f);
-                    acc[r + 1] = __builtin_amdgcn_fmed3f(v.y, 0.f, 6.f);
-                }
+                f32x16 acc = expand_band<KK>(af, bf, esc, ebi);
                 if (zero_row) {
                     asm volatile("");
 #pragma unroll
@@ -627,7 +666,7 @@ __global__ __launch_bounds__(256, 2) void mb_block_s2_kernel(const MbFuseArgs a)
             __builtin_amdgcn_wave_barrier();        // the previous step's tap reads are issued
             if (s > 0) band(afa, SLA * S2_ROWF, false);
             band(afb, SLB * S2_ROWF, s == 0 && top);
-            __builtin_amdgcn_sched_barrier(0);      // (both chains have retired: their results were read)
+            __builtin_amdgcn_sched_barrier(0);      // (both chains have retired)
             if (s == 0) load_wp(c);
             if (s + 1 < NST && s + 1 < nsteps) fetch(s + 1);
             else if (c + 1 < nchunks) {
@@ -639,35 +678,17 @@ __global__ __launch_bounds__(256, 2) void mb_block_s2_kernel(const MbFuseArgs a)
             __builtin_amdgcn_wave_barrier();
             if constexpr (s > 0) {
                 constexpr int slot[3] = {SLP, SLA, SLB};
-                f32x2 s0[4];
+                f32x2 sum[1][4];
+                float d[1][8];
 #pragma unroll
-                for (int i = 0; i < 4; ++i) s0[i] = f32x2{0.f, 0.f};
+                for (int i = 0; i < 4; ++i) sum[0][i] = f32x2{0.f, 0.f};
 #pragma unroll
                 for (int ky = 0; ky < 3; ++ky) {
-#pragma unroll
-                    for (int kx = 0; kx < 3; ++kx) {
-                        const float* p = erd + slot[ky] * S2_ROWF + (kx == 1 ? 17 : kx == 2 ? 1 : 0) * SW_EP;
-                        const f32x4 va = ringr(p), vb = ringr(p + 4);
-                        const f32x2 v[4] = {{va.x, va.y}, {va.z, va.w}, {vb.x, vb.y}, {vb.z, vb.w}};
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) pkfma(s0[i], v[i], tap[ky * 3 + kx][i]);
-                    }
+                    taps_ring_row<true>(erd + slot[ky] * S2_ROWF, ky, RegTaps{tap}, sum[0]);
                     __builtin_amdgcn_sched_barrier(0);      // (one expanded row's reads in flight at a time: 24 registers, not 72)
                 }
-                const f32x4 sa = *reinterpret_cast<const f32x4*>(tc + 72), sb = *reinterpret_cast<const f32x4*>(tc + 76);
-                const f32x4 ba = *reinterpret_cast<const f32x4*>(tc + 80), bb = *reinterpret_cast<const f32x4*>(tc + 84);
-                const f32x2 dsc[4] = {{sa.x, sa.y}, {sa.z, sa.w}, {sb.x, sb.y}, {sb.z, sb.w}}, dbi[4] = {{ba.x, ba.y}, {ba.z, ba.w}, {bb.x, bb.y}, {bb.z, bb.w}};
-                float d0[8];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const f32x2 r0 = __builtin_elementwise_fma(s0[i], dsc[i], dbi[i]);
-                    d0[2 * i] = __builtin_amdgcn_fmed3f(r0.x, 0.f, 6.f); d0[2 * i + 1] = __builtin_amdgcn_fmed3f(r0.y, 0.f, 6.f);
-                }
-#pragma unroll
-                for (int q = 0; q < 8 && !(ABL & 2); ++q) {
-                    P[s - 1][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(wp[0][q], d0[q], P[s - 1][0], 0, 0, 0);
-                    P[s - 1][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(wp[1][q], d0[q], P[s - 1][1], 0, 0, 0);
-                }
+                dw_affine_table<1>(sum, tc, d);
+                project<1, 2>(wp, d, P[s - 1]);
             }
         };
         step(std::integral_constant<int, 0>{});
@@ -689,7 +710,7 @@ __global__ __launch_bounds__(256, 2) void mb_block_s2_kernel(const MbFuseArgs a)
                         const size_t gi = (((size_t)img * OH + y0 + i) * OW + ox0 + n) * a.cout + co;
                         f32x4 v;
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) v[r] = fmaf(P[i][m][r], psc[r], pbi[r]);
+                        for (int r = 0; r < 4; ++r) v[r] = fmaf(P[i][0][m][r], psc[r], pbi[r]);
                         if (a.res) {
                             const f32x4 rr = *reinterpret_cast<const f32x4*>(a.res + gi);
                             v.x += rr.x; v.y += rr.y; v.z += rr.z; v.w += rr.w;
@@ -717,10 +738,10 @@ template <int CIN, int STRIDE = 1>
 __global__ __launch_bounds__(256, 2) void mb_expand_dw_s_kernel(const MbFuseArgs a) {
     constexpr int KK = CIN / 8;
     __shared__ __attribute__((aligned(16))) float Eall[4][SW_RING];
-    __shared__ __attribute__((aligned(16))) float Tall[XD_MAXCH * 4 * SW_TAPF];      // [chunk][octet][9 taps | scale | bias][8]
+    __shared__ __attribute__((aligned(16))) float Tall[XD_MAXCH * 4 * SW_TAPF];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int hid = a.hid, nchunks = hid >> 5;
-    for (int idx = tid; idx < nchunks * 4 * SW_TAPF; idx += 256) {
+    for (int idx = tid; idx < nchunks * 4 * SW_TAPF; idx += 256) {       // the tap table, 8 consecutive channels per group (hid % 32 == 0)
         const int q = idx & 7, t = (idx >> 3) % 11, cg = idx / SW_TAPF;
         const int ch = 8 * cg + q;                       // (32 (cg >> 2) + 8 (cg & 3) + q)
         Tall[idx] = t < 9 ? a.wd[(size_t)t * hid + ch] : t == 9 ? a.sd[ch] : a.bd[ch];
@@ -732,12 +753,12 @@ __global__ __launch_bounds__(256, 2) void mb_expand_dw_s_kernel(const MbFuseArgs
     // strip per frame, 512 waves for a 512-frame chunk would leave three quarters of the wave slots empty.  The waves of a block take the groups
     // of one strip: they read the same pixels at about the same time.
     const int nstrips = a.tiles_x, ngroups = a.tiles_y;
-    int strip = blockIdx.x * 4 + wave;
-    if (strip >= a.n * nstrips * ngroups) return;
-    const int cgrp = strip % ngroups;
-    strip /= ngroups;
+    const int item = blockIdx.x * 4 + wave;
+    if (item >= a.n * nstrips * ngroups) return;
+    int strip, cgrp, img, sx;
+    divmod(item, ngroups, strip, cgrp);
     const int c_lo = (nchunks * cgrp) / ngroups, c_hi = (nchunks * (cgrp + 1)) / ngroups;
-    const int img = strip / nstrips, sx = strip - img * nstrips;
+    divmod(strip, nstrips, img, sx);
     const int ox0 = sx * SW_OW;
     const bool left = sx == 0, right = sx == nstrips - 1;
     const int H = a.H, W = a.W;
@@ -748,7 +769,7 @@ __global__ __launch_bounds__(256, 2) void mb_expand_dw_s_kernel(const MbFuseArgs
     const int er = nl >> 4, ec = nl & 15;
     // (temporal shift of the block's input, MbFuseArgs::tsm_T: the descriptor spans the frame's CLIP, a lane's k group reads its own frame, the next or
     //  the previous one, and a neighbour outside the clip is out of range = zeros.  Out-of-image pixels then land in a neighbouring frame instead of out
-    //  of range: every one of them is overwritten by the row / column masks below.)
+    //  of range: every one of them is overwritten by the row / column masks of band_to_ring.)
     const int tsmT = a.tsm_T, tfr = tsmT > 0 ? img % tsmT : 0, fbytes = H * W * CIN * 4;
     __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.x + (size_t)(img - tfr) * H * W * CIN), 0,
                                                                      (tsmT > 0 ? tsmT : 1) * fbytes, 0x00020000);
@@ -792,135 +813,36 @@ __global__ __launch_bounds__(256, 2) void mb_expand_dw_s_kernel(const MbFuseArgs
         const float* tc = tw + c * 4 * SW_TAPF;
         float* optr = obase + 32 * c;
         auto step = [&](auto PAR, int s) {
-            constexpr int par = decltype(PAR)::value;
-            constexpr int SL0 = par ? 1 : 3, SL1 = par ? 2 : 0;
-            f32x16 acc;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-            for (int kk = 0; kk < KK; ++kk)
-#pragma unroll
-                for (int s4 = 0; s4 < 4; ++s4) if (!(ABL & 1)) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[kk][s4], bf[kk][s4], acc, 0, 0, 0);
-            {
-                const f32x2 sc2 = {esc, esc}, bi2 = {ebi, ebi};
-#pragma unroll
-                for (int r = 0; r < 16; r += 2) {
-                    const f32x2 v = __builtin_elementwise_fma(f32x2{acc[r], acc[r + 1]}, sc2, bi2);
-                    acc[r] = __builtin_amdgcn_fmed3f(v.x, 0.f, 6.f);
-                    acc[r + 1] = __builtin_amdgcn_fmed3f(v.y, 0.f, 6.f);
-                }
-            }
-            // (the chain has retired -- its result was read: the landing registers of the next requests are free; see the stem kernel)
-            __builtin_amdgcn_sched_barrier(0);
+            constexpr int par = decltype(PAR)::value;       // s & 1
+            f32x16 acc = expand_band<KK>(af, bf, esc, ebi);
+            __builtin_amdgcn_sched_barrier(0);      // (the chain has retired: see expand_band)
             if (s + 1 < nsteps) fetch(s + 1);
             else if (c + 1 < c_hi) {
                 load_bf(c + 1);
                 fetch(0);
             }
             __builtin_amdgcn_sched_barrier(0);
-            if (s == 0) {
-                asm volatile("");
-#pragma unroll
-                for (int r = 0; r < 8; ++r) acc[r] = 0.f;           // expanded row -1
-            }
-            if (s == nsteps - 1) {
-                asm volatile("");
-#pragma unroll
-                for (int r = 8; r < 16; ++r) acc[r] = 0.f;          // expanded row H
-            }
-            if (left) { asm volatile(""); if (half == 0) { acc[0] = 0.f; acc[8] = 0.f; } }      // expanded column -1
-            if (right) { asm volatile(""); if (half == 1) { acc[7] = 0.f; acc[15] = 0.f; } }    // expanded column W
-            __builtin_amdgcn_wave_barrier();
-#pragma unroll
-            for (int r = 0; r < 16; ++r) ewr[(r < 8 ? SL0 : SL1) * SW_ROWF + ((r & 3) + 8 * ((r >> 2) & 1)) * SW_EP] = acc[r];
-            __builtin_amdgcn_wave_barrier();
+            band_to_ring<par>(acc, ewr, s == 0, s == nsteps - 1, left, right, half);
             if (s > 0 && STRIDE == 2) {
                 // output row s - 1 from expanded rows 2 s - 3, 2 s - 2 (the previous step's) and 2 s - 1 (this step's first)
-                constexpr int slot[3] = {par ? 3 : 1, par ? 0 : 2, SL0};
-                f32x2 s0[4];
+                f32x2 sum[1][4];
+                float d[1][8];
 #pragma unroll
-                for (int i = 0; i < 4; ++i) s0[i] = f32x2{0.f, 0.f};
+                for (int i = 0; i < 4; ++i) sum[0][i] = f32x2{0.f, 0.f};
 #pragma unroll
-                for (int e = 0; e < 3; ++e) {
-#pragma unroll
-                    for (int kx = 0; kx < 3; ++kx) {
-                        const f32x4 ta = *reinterpret_cast<const f32x4*>(tc + (e * 3 + kx) * 8), tb = *reinterpret_cast<const f32x4*>(tc + (e * 3 + kx) * 8 + 4);
-                        const f32x2 t4[4] = {{ta.x, ta.y}, {ta.z, ta.w}, {tb.x, tb.y}, {tb.z, tb.w}};
-                        const float* p = erd + slot[e] * SW_ROWF + kx * SW_EP;
-                        const f32x4 va = ringr(p), vb = ringr(p + 4);
-                        const f32x2 v[4] = {{va.x, va.y}, {va.z, va.w}, {vb.x, vb.y}, {vb.z, vb.w}};
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) pkfma(s0[i], v[i], t4[i]);
-                    }
-                }
-                const f32x4 sa = *reinterpret_cast<const f32x4*>(tc + 72), sb = *reinterpret_cast<const f32x4*>(tc + 76);
-                const f32x4 ba = *reinterpret_cast<const f32x4*>(tc + 80), bb = *reinterpret_cast<const f32x4*>(tc + 84);
-                const f32x2 dsc[4] = {{sa.x, sa.y}, {sa.z, sa.w}, {sb.x, sb.y}, {sb.z, sb.w}}, dbi[4] = {{ba.x, ba.y}, {ba.z, ba.w}, {bb.x, bb.y}, {bb.z, bb.w}};
-                float d0[8];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const f32x2 r0 = __builtin_elementwise_fma(s0[i], dsc[i], dbi[i]);
-                    d0[2 * i] = __builtin_amdgcn_fmed3f(r0.x, 0.f, 6.f); d0[2 * i + 1] = __builtin_amdgcn_fmed3f(r0.y, 0.f, 6.f);
-                }
-                if (ostore) {
-                    float* o = optr + (size_t)(s - 1) * OWs * hid;
-                    *reinterpret_cast<f32x4*>(o) = f32x4{d0[0], d0[1], d0[2], d0[3]};
-                    *reinterpret_cast<f32x4*>(o + 4) = f32x4{d0[4], d0[5], d0[6], d0[7]};
-                }
+                for (int e = 0; e < 3; ++e) taps_ring_row<false>(erd + ring4(par, e) * SW_ROWF, e, TableTaps{tc}, sum[0]);
+                dw_affine_table<1>(sum, tc, d);
+                if (ostore) store8(optr + (size_t)(s - 1) * OWs * hid, d[0]);
             }
             if (s > 0 && STRIDE == 1) {
-                constexpr int slot[4] = {par ? 3 : 1, par ? 0 : 2, SL0, SL1};
-                f32x2 s0[4], s1[4];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) { s0[i] = f32x2{0.f, 0.f}; s1[i] = f32x2{0.f, 0.f}; }
-                f32x2 tprev[3][4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    f32x2 tcur[3][4];
-                    if (e < 3) {
-#pragma unroll
-                        for (int kx = 0; kx < 3; ++kx) {
-                            const f32x4 ta = *reinterpret_cast<const f32x4*>(tc + (e * 3 + kx) * 8), tb = *reinterpret_cast<const f32x4*>(tc + (e * 3 + kx) * 8 + 4);
-                            tcur[kx][0] = f32x2{ta.x, ta.y}; tcur[kx][1] = f32x2{ta.z, ta.w}; tcur[kx][2] = f32x2{tb.x, tb.y}; tcur[kx][3] = f32x2{tb.z, tb.w};
-                        }
-                    }
-#pragma unroll
-                    for (int kx = 0; kx < 3; ++kx) {
-                        const float* p = erd + slot[e] * SW_ROWF + kx * SW_EP;
-                        const f32x4 va = ringr(p), vb = ringr(p + 4);
-                        const f32x2 v[4] = {{va.x, va.y}, {va.z, va.w}, {vb.x, vb.y}, {vb.z, vb.w}};
-                        if (e < 3) {
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) pkfma(s0[i], v[i], tcur[kx][i]);
-                        }
-                        if (e > 0) {
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) pkfma(s1[i], v[i], tprev[kx][i]);
-                        }
-                    }
-                    if (e < 3) {
-#pragma unroll
-                        for (int kx = 0; kx < 3; ++kx)
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) tprev[kx][i] = tcur[kx][i];
-                    }
-                }
-                const f32x4 sa = *reinterpret_cast<const f32x4*>(tc + 72), sb = *reinterpret_cast<const f32x4*>(tc + 76);
-                const f32x4 ba = *reinterpret_cast<const f32x4*>(tc + 80), bb = *reinterpret_cast<const f32x4*>(tc + 84);
-                const f32x2 dsc[4] = {{sa.x, sa.y}, {sa.z, sa.w}, {sb.x, sb.y}, {sb.z, sb.w}}, dbi[4] = {{ba.x, ba.y}, {ba.z, ba.w}, {bb.x, bb.y}, {bb.z, bb.w}};
-                float d0[8], d1[8];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const f32x2 r0 = __builtin_elementwise_fma(s0[i], dsc[i], dbi[i]), r1 = __builtin_elementwise_fma(s1[i], dsc[i], dbi[i]);
-                    d0[2 * i] = __builtin_amdgcn_fmed3f(r0.x, 0.f, 6.f); d0[2 * i + 1] = __builtin_amdgcn_fmed3f(r0.y, 0.f, 6.f);
-                    d1[2 * i] = __builtin_amdgcn_fmed3f(r1.x, 0.f, 6.f); d1[2 * i + 1] = __builtin_amdgcn_fmed3f(r1.y, 0.f, 6.f);
-                }
+                f32x2 sum[2][4];
+                float d[2][8];
+                taps_two_rows<par>(erd, tc, sum);
+                dw_affine_table<2>(sum, tc, d);
                 if (ostore) {
                     float* o = optr + (size_t)(2 * s - 2) * W * hid;
-                    *reinterpret_cast<f32x4*>(o) = f32x4{d0[0], d0[1], d0[2], d0[3]};
-                    *reinterpret_cast<f32x4*>(o + 4) = f32x4{d0[4], d0[5], d0[6], d0[7]};
-                    *reinterpret_cast<f32x4*>(o + (size_t)W * hid) = f32x4{d1[0], d1[1], d1[2], d1[3]};
-                    *reinterpret_cast<f32x4*>(o + (size_t)W * hid + 4) = f32x4{d1[4], d1[5], d1[6], d1[7]};
+                    store8(o, d[0]);
+                    store8(o + (size_t)W * hid, d[1]);
                 }
             }
         };
