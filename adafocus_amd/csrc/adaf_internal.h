@@ -298,6 +298,15 @@ __device__ __forceinline__ float adaf_wave_sum(float v) {
     const auto r = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, v), __builtin_bit_cast(unsigned, v), false, false);
     return v + __builtin_bit_cast(float, (threadIdx.x & 32) ? r[0] : r[1]);                                // lane ^ 32
 }
+
+// XCD-aware, bijective block remap: hardware places block b on XCD b % 8; give every XCD a
+// contiguous range of tiles so the blocks that share an A row-panel hit the same L2.
+// (conv_gemm.hip's three GEMM kernels, and dw_same_kernel of effnet_kernels.hip, which says what ITS neighbouring work items share.)
+__device__ __forceinline__ int xcd_tile(int bid, int nblocks) {
+    const int q = nblocks >> 3, r = nblocks & 7;
+    const int xcd = bid & 7, idx = bid >> 3;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+}
 #endif
 
 // mbconv_whole.hip: whole-image MBConv blocks (EfficientNet, fp16 storage)

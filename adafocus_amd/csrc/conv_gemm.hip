@@ -69,6 +69,77 @@ __device__ __forceinline__ void split3(const f32x4 v0, const f32x4 v1, u32x4& H,
 __device__ __forceinline__ f32x16 mfma_bf16(const u32x4 a, const u32x4 b, const f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }
+// ---- parts the GEMM kernels share ---------------------------------------------------------------------------------------------------
+// Each of these is a function because every kernel that takes it compiles to the instructions it had with the part written out
+// (tools/codeobj_compare.py).  The fragment offsets, the fragment read, the slice step and the K-loop drivers are NOT: moved into a
+// function they change most instantiations, so conv_gemm_glds_kernel and phase 1 of conv_fused_tail_kernel each write them out
+// (LABNOTES, "Conv engine kernels").
+//
+// The slice image of an operand in LDS (direct-to-LDS kernels) is [rows][32 floats] = 8 chunks of 16 bytes per row, NO padding: the DMA
+// writes base + lane * 16 B.  A wave instruction fills 8 consecutive rows x 128 B; lane -> (row = 8*g + lane/8, slot = lane%8).  Bank
+// conflicts are avoided by an XOR swizzle: chunk c of a row lives in slot c ^ ((row>>1)&7), applied on the per-lane GLOBAL source
+// address (slot -> chunk) and again on the fragment read (chunk -> slot).
+__device__ __forceinline__ int slice_chunk(int row, int slot) { return slot ^ ((row >> 1) & 7); }
+
+// A 64-bit value that is wave-uniform by construction: pin it to SGPRs.
+__device__ __forceinline__ unsigned long long pin_sgpr(unsigned long long v) {
+    return ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)(v >> 32)) << 32) |
+           (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)v);
+}
+// Scalar-base LDS-DMA (the LEAN note at conv_gemm_glds_kernel's operand source): global_load_lds_dwordx4 voffset, s[base:base+1] -- a constant per-lane
+// byte offset, a wave-uniform base the SALU advances, 16 bytes per lane to LDS byte address `lds` + lane * 16.
+__device__ __forceinline__ void lds_dma_sbase(const float* sbase, unsigned voff, unsigned lds) {
+    const unsigned l = (unsigned)__builtin_amdgcn_readfirstlane(lds);
+    const unsigned long long sb = pin_sgpr((unsigned long long)sbase);
+    // (s_nop: the M0 write -> LDS-DMA read hazard the compiler pads for its own builtin is ours to pad inside an asm block)
+    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(l), "v"(voff), "s"(sb) : "memory", "m0");   // (m0 is named so that the compiler does not merge its own M0 initialisations across this block; the "reserved register" warning is expected)
+}
+
+// sub-step s4 of an 8-k step: one v_mfma_f32_32x32x2_f32 per tile pair on element s4 of the wave's 16-byte fragments
+template <int TM, int TN>
+__device__ __forceinline__ void mfma_step(f32x16 (&acc)[TM][TN], const f32x4 (&af)[TM], const f32x4 (&bf)[TN], int s4) {
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i][s4], bf[j][s4], acc[i][j], 0, 0, 0);
+}
+
+// Row-major decode of an output row: m -> (image, pixel inside the image = rem, oy, ox).  A position-major tile index decodes the same
+// way into (image group, the tile's pixel): group-major order, so consecutive tiles (= one XCD's share, see xcd_tile) are all pixel
+// positions of the SAME images and the rows an XCD gathers stay within a few image groups and in its L2 (position-major order made every
+// XCD touch every image: measured 3x less gain).
+struct OutPix { int img, rem, oy, ox; };
+__device__ __forceinline__ OutPix out_pixel(const ConvArgs& a, int m) {
+    const int ohw = a.OH * a.OW;
+    const int img = m / ohw;
+    const int rem = m - img * ohw;
+    const int oy = rem / a.OW;
+    const int ox = rem - oy * a.OW;
+    return {img, rem, oy, ox};
+}
+// The K walk of a k x k filter: one filter tap's 32-channel slice per step (cin % 32 == 0).  Called for kt = 0, 1, 2, ..., so the
+// (tap, channel offset) pair is advanced incrementally -- scalar adds, no division.  SKIP (position-major tiles): a move to a new
+// tap goes on to the next tap in `walk`, the ones that touch the image (wave-uniform; the centre tap always does).
+template <bool SKIP>
+__device__ __forceinline__ void tap_walk_step(int kt, const ConvArgs& a, unsigned walk, int& tap, int& c0, int& kh, int& kw) {
+    bool moved = false;
+    if (kt == 0) { c0 = 0; tap = 0; kh = 0; kw = 0; moved = true; }
+    else {
+        c0 += 32;
+        if (c0 == a.cin) {
+            c0 = 0;
+            ++tap;
+            if (++kw == a.KW) { kw = 0; ++kh; }
+            moved = true;
+        }
+    }
+    if (SKIP && moved) {
+        while (!((walk >> tap) & 1u)) {
+            ++tap;
+            if (++kw == a.KW) { kw = 0; ++kh; }
+        }
+    }
+}
 
 // sig: 0 = nothing left to do, 1 = sigmoid, 2 = swish (v * sigmoid(v); efficientnet_pytorch utils.py MemoryEfficientSwish)
 // The logistic function is 1 / (1 + 2^(-v log2 e)) on the hardware's exp2 / reciprocal units (v_exp_f32, v_rcp_f32: 1 ulp each,
@@ -123,15 +194,11 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a0, float* smem, f
             const f32x2 sc0 = {sc.x, sc.y}, sc1 = {sc.z, sc.w}, bi0 = {bi.x, bi.y}, bi1 = {bi.z, bi.w};
             const unsigned vo = (unsigned)(((size_t)rsub * rstride * a.ldo + n) * 4);
             const unsigned vr = (unsigned)(((size_t)rsub * rstride * a.ldr + n) * 4);
-            auto uni = [](unsigned long long v) {       // wave-uniform by construction: pin to SGPRs
-                return ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)(v >> 32)) << 32) |
-                       (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)v);
-            };
             const size_t row0 = (size_t)mrow0 * rstride + roff;
-            const unsigned long long obase = uni((unsigned long long)a.out + row0 * a.ldo * 4);
-            const unsigned long long rbase = uni((unsigned long long)a.res + row0 * a.ldr * 4);
-            const unsigned long long ostep = uni((unsigned long long)RPI * rstride * a.ldo * 4);
-            const unsigned long long rstep = uni((unsigned long long)RPI * rstride * a.ldr * 4);
+            const unsigned long long obase = pin_sgpr((unsigned long long)a.out + row0 * a.ldo * 4);
+            const unsigned long long rbase = pin_sgpr((unsigned long long)a.res + row0 * a.ldr * 4);
+            const unsigned long long ostep = pin_sgpr((unsigned long long)RPI * rstride * a.ldo * 4);
+            const unsigned long long rstep = pin_sgpr((unsigned long long)RPI * rstride * a.ldr * 4);
             constexpr int GPB = (32 / RPI) / 4, NGR = TM * GPB;     // groups of four row steps
             typedef __attribute__((address_space(1))) char gchar;      // (global address space: plain pointers made from
             typedef __attribute__((address_space(1))) f32x4 gf32x4;    //  integers would be FLAT accesses)
@@ -390,14 +457,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void conv_gemm_kernel(const ConvArg
     const int wave = tid >> 6;
     const int wm = wave / WGN, wn = wave % WGN;
 
-    // XCD-aware, bijective block remap: hardware places block b on XCD b % 8; give every XCD a
-    // contiguous range of tiles so the blocks that share an A row-panel hit the same L2.
-    int bid = blockIdx.x;
-    {
-        const int q = a.nblocks >> 3, r = a.nblocks & 7;
-        const int xcd = bid & 7, idx = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int bid = xcd_tile(blockIdx.x, a.nblocks);
     const int tile_m = bid / a.tiles_n;
     const int tile_n = bid - tile_m * a.tiles_n;
     const int m0 = tile_m * BM, n0 = tile_n * BN;
@@ -424,14 +484,10 @@ __global__ __launch_bounds__(64 * WGM * WGN) void conv_gemm_kernel(const ConvArg
             }
             a_iy[p] = a_ix[p] = 0;
         } else {
-            const int ohw = a.OH * a.OW;
-            const int img = mm / ohw;
-            const int rem = mm - img * ohw;
-            const int oy = rem / a.OW;
-            const int ox = rem - oy * a.OW;
-            a_pix[p] = img * a.H * a.W;
-            a_iy[p] = oy * a.stride - a.pad;
-            a_ix[p] = ox * a.stride - a.pad;
+            const OutPix px = out_pixel(a, mm);
+            a_pix[p] = px.img * a.H * a.W;
+            a_iy[p] = px.oy * a.stride - a.pad;
+            a_ix[p] = px.ox * a.stride - a.pad;
             a_off[p] = 0;
         }
     }
@@ -522,21 +578,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void conv_gemm_kernel(const ConvArg
 #pragma unroll
             for (int j = 0; j < TN; ++j) bf[j] = *reinterpret_cast<const f32x4*>(Bs + j * 32 * LDP + kk * 8);
 #pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i].x, bf[j].x, acc[i][j], 0, 0, 0);
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i].y, bf[j].y, acc[i][j], 0, 0, 0);
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i].z, bf[j].z, acc[i][j], 0, 0, 0);
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i].w, bf[j].w, acc[i][j], 0, 0, 0);
+            for (int s4 = 0; s4 < 4; ++s4) mfma_step(acc, af, bf, s4);
         }
         if (FLAGS & 1) __builtin_amdgcn_s_setprio(0);
         __builtin_amdgcn_sched_barrier(0);
@@ -554,37 +596,14 @@ __global__ __launch_bounds__(64 * WGM * WGN) void conv_gemm_kernel(const ConvArg
 // ~17 % of the MFMA time and are NOT hidden by the co-resident wave; the LDS-DMA form has no
 // register round trip, no ds_write pass and (pointers advanced by a constant per slice) almost no
 // address arithmetic.
-//   - LDS image per operand: [rows][32 floats], NO padding (the DMA writes base + lane*16 B).
-//     Bank conflicts are avoided by an XOR swizzle of the 16-byte chunk index with (row>>1)&7,
-//     applied on the per-lane GLOBAL source address and again on the fragment read.
-//   - a wave instruction fills 8 consecutive rows x 128 B; lane -> (row = 8*g + lane/8, slot = lane%8).
+//   - LDS image per operand: the unpadded, swizzled [rows][32 floats] slice image (slice_chunk above).
 //   - requirements (checked by the launcher): 1x1/stride 1: K % 4 == 0 (a partial last slice is zero-filled);
 //     other filters: cin % 32 == 0, KH*KW <= 32.
 //   - 2 LDS stages; per slice: s_waitcnt vmcnt(0) ; s_barrier ; issue DMA for the next slice ; multiply.
-// SPECIAL = the launch has a fused temporal shift or a K that is not a multiple of 32: only then does the DMA
-// issue path carry the per-slice source fix-ups (kept out of the common instantiation so the K loop is
-// straight-line code between the MFMA groups).
-// EMU = 0: v_mfma_f32_32x32x2_f32 (the default, exact fp32 FMA chain).  EMU = 6 / 9: the fragments are split into
-// three bf16 parts after the LDS read and multiplied with 6 / 9 v_mfma_f32_32x32x16_bf16 per 16 k (see split3).
-// BSP (split tiles only): the weights come pre-split as three bf16 planes (ConvArgs::wsp); their LDS image is
-// [plane][BN rows][64 B] with the 16-byte chunk index XOR-ed with (row>>2)&3, and a fragment is one ds_read_b128.
-// DT (half-precision STORAGE, N2 / BASELINE config 5): bit 0 = fp16 output, bit 1 = fp16 residual, bit 2 = fp16 operands
-// (x and w): a k slice is then 64 halfs -- the same 128 bytes per row, so the DMA, the LDS image and its swizzle are
-// byte-identical and the loader simply counts in 32-bit words (the launcher halves K / cin / ldx); a lane's 16-byte
-// fragment is exactly the 8 halfs one v_mfma_f32_32x32x16_f16 wants (lanes 0-31: k 0..7, lanes 32-63: k 8..15 of a
-// 16-k step = chunk 2 kk + (lane >> 5), the f32 mapping).  Accumulation, BN and activation stay fp32.
-// PM (k x k filters, fp32 pipe): POSITION-MAJOR tiles with padding-tap skipping.  A tile's BM rows are the SAME output
-// pixel of BM consecutive images (instead of BM consecutive pixels), so every row has the same set of filter taps inside
-// the image and the taps that only multiply padding are skipped for the whole tile -- no DMA, no MFMA: on the 3x3 maps of
-// stage 4 the corner / edge / centre pixels use 4 / 6 / 9 of the 9 taps (5.4 on average: 40 % of the products of the
-// row-major form are zeros), on 6x6 maps 7.1, on 12x12 8.0.  A skipped slice contributes exact zeros, so the result is
-// BIT-IDENTICAL to the row-major kernel.  Tile t = (image group g = t / (OH*OW), pixel p = t % (OH*OW)).
-// LEAN (1x1/stride-1 launches without fix-ups, and position-major tiles): NO vector ALU work in the K loop.  On gfx950 the fp32
-// MFMA and the fp32/int VALU issue to the same lanes, so every v_add in the loop is a cycle the matrix pipe does not get
-// (DESIGN.md section 3.4).  The DMA is issued in its scalar-base form -- global_load_lds_dwordx4 voffset, s[base:base+1] --
-// with a per-lane 32-bit byte offset that never changes and a wave-uniform base the SALU advances per slice (the compiler
-// builtin only emits the 64-bit-VGPR-address form: one v_lshl_add_u64 per instruction per slice).  Rows past the end of the
-// problem read a valid row instead of the zero block (their outputs are discarded by the epilogue), so no select either.
+// The kernel reads in four sections -- SET-UP (tile, position-major geometry), OPERAND SOURCE (per-lane state of each form, the
+// per-slice walk `prep`, one DMA instruction `issue_one`), SCHEDULE (three K loops: the split tiles' production schedule, the
+// barrier-2/3 variant, the paired-slice loop) and EPILOGUE -- and each flag is described at the part that implements it:
+// PM at the set-up; LEAN, LEAN + SPECIAL and SPECIAL at the operand source; EMU / BSP and DT at the schedules.
 template <int BM, int BN, int WGM, int WGN, bool DENSE, int PIPE, bool SPECIAL, int EMU, bool BSP = false, int DT = 0, bool PM = false,
           bool LEAN = false, bool POOL = false>
 __global__ __launch_bounds__(64 * WGM * WGN, (BM == 128 && BN == 128 && WGM * WGN == 4) ? 2 : 1)   // 128x128: two blocks per CU
@@ -595,11 +614,6 @@ void conv_gemm_glds_kernel(const ConvArgs a) {
     static_assert(!LEAN || ((DENSE || PM) && PIPE == 1 && ((EMU == 0 && !BSP) || (EMU != 0 && BSP)) &&
                             (!SPECIAL || (DENSE && EMU == 0 && DT == 0 && !POOL))),
                   "lean K loop: plain fp32-pipe launches, split tiles with pre-split weights, or (LEAN + SPECIAL) the fp32 pipe's temporally shifted conv1");
-    // LEAN + SPECIAL = the lean K loop for a conv1 with the fused temporal shift (K and the shifted fold multiples of 32, checked by the launcher):
-    // the activations are DMA-ed with the RANGE-CHECKED buffer form (buffer_load_dwordx4 ... lds), which writes ZEROS to LDS for a lane whose
-    // offset is out of range (tools/exp/buffer_load_lds_oob.hip) -- so the rows at clip ends get their zeros from a constant per-lane offset
-    // instead of a per-lane source select per slice: three constant offsets per row (own frame, next frame, previous frame), a wave-uniform
-    // choice per slice, the slice's position in the SGPR offset.
     constexpr bool LTSM = LEAN && SPECIAL;
     constexpr int NW = WGM * WGN;
     constexpr int TM = BM / WGM / 32, TN = BN / WGN / 32;
@@ -613,35 +627,32 @@ void conv_gemm_glds_kernel(const ConvArgs a) {
     static_assert(BM % (8 * NW) == 0 && BN % (8 * NW) == 0, "staging shape");
     __shared__ __attribute__((aligned(16))) float smem[SMEM];
 
+    // ==== set-up: the wave's place in the block, the block's tile =======================================================================
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WGN, wn = wave % WGN;
 
-    int bid = blockIdx.x;
-    {
-        const int q = a.nblocks >> 3, r = a.nblocks & 7;
-        const int xcd = bid & 7, idx = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int bid = xcd_tile(blockIdx.x, a.nblocks);
     const int tile_m = bid / a.tiles_n;
     const int tile_n = bid - tile_m * a.tiles_n;
     int m0 = tile_m * (POOL ? a.pool_rows : BM);      // (pooled epilogue: a tile holds whole images; its last BM - pool_rows rows repeat the next tile's)
     const int n0 = tile_n * BN;
+    // PM (k x k filters, fp32 pipe): POSITION-MAJOR tiles with padding-tap skipping.  A tile's BM rows are the SAME output
+    // pixel of BM consecutive images (instead of BM consecutive pixels), so every row has the same set of filter taps inside
+    // the image and the taps that only multiply padding are skipped for the whole tile -- no DMA, no MFMA: on the 3x3 maps of
+    // stage 4 the corner / edge / centre pixels use 4 / 6 / 9 of the 9 taps (5.4 on average: 40 % of the products of the
+    // row-major form are zeros), on 6x6 maps 7.1, on 12x12 8.0.  A skipped slice contributes exact zeros, so the result is
+    // BIT-IDENTICAL to the row-major kernel.  Tile t = (image group g = t / (OH*OW), pixel p = t % (OH*OW)).
     // position-major: this tile's pixel, its first image, and the taps inside the image (uniform over the tile)
     int pm_p = 0, pm_iy0 = 0, pm_ix0 = 0;
     unsigned pm_mask = 0;
     if (PM) {
-        // group-major order: consecutive tiles (= one XCD's share, see the remap above) are all pixel positions of the SAME
-        // images, so the rows an XCD gathers stay within a few image groups and in its L2 (position-major order made
-        // every XCD touch every image: measured 3x less gain)
-        const int ohw = a.OH * a.OW;
-        const int g = tile_m / ohw;
-        pm_p = tile_m - g * ohw;
-        m0 = g * BM;                                       // first IMAGE of the tile
-        const int oy = pm_p / a.OW, ox = pm_p - oy * a.OW;
-        pm_iy0 = oy * a.stride - a.pad;
-        pm_ix0 = ox * a.stride - a.pad;
+        const OutPix px = out_pixel(a, tile_m);            // (image group, the tile's pixel)
+        pm_p = px.rem;
+        m0 = px.img * BM;                                  // first IMAGE of the tile
+        pm_iy0 = px.oy * a.stride - a.pad;
+        pm_ix0 = px.ox * a.stride - a.pad;
         for (int kh = 0; kh < a.KH; ++kh)
             for (int kw = 0; kw < a.KW; ++kw)
                 if ((unsigned)(pm_iy0 + kh) < (unsigned)a.H && (unsigned)(pm_ix0 + kw) < (unsigned)a.W) pm_mask |= 1u << (kh * a.KW + kw);
@@ -650,18 +661,44 @@ void conv_gemm_glds_kernel(const ConvArgs a) {
     // the position-major row order from the gain of the skipping)
     const unsigned pm_walk = (PM && a.pm_allow == 2) ? ((1u << (a.KH * a.KW)) - 1u) : pm_mask;
 
-    // ---- per-lane source bookkeeping ------------------------------------------------------
+    // ==== operand source: per-lane state of each form, the per-slice walk, one DMA instruction ==========================================
+    // LEAN (1x1/stride-1 launches without fix-ups, and position-major tiles): NO vector ALU work in the K loop.  On gfx950 the fp32
+    // MFMA and the fp32/int VALU issue to the same lanes, so every v_add in the loop is a cycle the matrix pipe does not get
+    // (DESIGN.md section 3.4).  The DMA is issued in its scalar-base form -- global_load_lds_dwordx4 voffset, s[base:base+1] --
+    // with a per-lane 32-bit byte offset that never changes and a wave-uniform base the SALU advances per slice (the compiler
+    // builtin only emits the 64-bit-VGPR-address form: one v_lshl_add_u64 per instruction per slice).  Rows past the end of the
+    // problem read a valid row instead of the zero block (their outputs are discarded by the epilogue), so no select either.
+    // LEAN + SPECIAL = the lean K loop for a conv1 with the fused temporal shift (K and the shifted fold multiples of 32, checked by the launcher):
+    // the activations are DMA-ed with the RANGE-CHECKED buffer form (buffer_load_dwordx4 ... lds), which writes ZEROS to LDS for a lane whose
+    // offset is out of range (tools/exp/buffer_load_lds_oob.hip) -- so the rows at clip ends get their zeros from a constant per-lane offset
+    // instead of a per-lane source select per slice: three constant offsets per row (own frame, next frame, previous frame), a wave-uniform
+    // choice per slice, the slice's position in the SGPR offset.
+    // SPECIAL = the launch has a fused temporal shift or a K that is not a multiple of 32: only then does the DMA
+    // issue path carry the per-slice source fix-ups (kept out of the common instantiation so the K loop is
+    // straight-line code between the MFMA groups).
     const int lr = lane >> 3;   // row within the 8-row group
     const int ls = lane & 7;    // LDS chunk slot
-    unsigned va[AI], vb[BI];    // LEAN: constant per-lane byte offsets of the activation / weight rows
-    unsigned vnx[LTSM ? AI : 1], vpv[LTSM ? AI : 1];   // LTSM: the same row in the next / previous frame, or out of range at a clip end
-    const float* lean_a = a.x;  // LEAN: wave-uniform base of the activation rows (PM: moved to the tile's first tap)
+    // The activation rows' per-lane state is declared by the form that uses it: a form that is off keeps ONE element, and every access sits
+    // under its form's flag (compile-time constants, so the other forms' code is never emitted).  The forms: lean, lean + shift (LTSM), the
+    // dense pointer walk, the tap gather (row-major and position-major).  The weight rows' state (lean: vb; otherwise pb / step_b / qb) is
+    // filled for both forms by one loop, and dead-code elimination drops the unused half: guarded by form, that loop changes the lean kernels.
+    constexpr bool WALK = !LEAN && DENSE, GATHER = !LEAN && !DENSE;
+    constexpr int LA = LEAN ? AI : 1, SA = LTSM ? AI : 1, WA = WALK ? AI : 1, GA = GATHER ? AI : 1;
+    // lean
+    unsigned va[LA];            // constant per-lane byte offsets of the activation rows
+    unsigned vb[BI];            // ... and of the weight rows
+    unsigned vnx[SA], vpv[SA];  // + shift: the same row in the next / previous frame, or out of range at a clip end
+    const float* lean_a = a.x;  // wave-uniform base of the activation rows (PM: moved to the tile's first tap)
     if (LEAN && PM) lean_a = a.x + ((long long)pm_iy0 * a.W + pm_ix0) * a.ldx;
-    const float* pa[AI];        // DENSE: running source pointer (or the zero block)
-    int step_a[AI];             // DENSE: pointer advance per slice (0 for the zero block)
-    long long boff[AI];         // generic: element offset of (image, oy*s-pad, ox*s-pad, chunk)
-    unsigned amask[AI];         // generic: bit t set <=> filter tap t is inside the image for this row
-    int tflag[AI];              // DENSE+TSM: bit0 has previous frame, bit1 has next frame, bit2 row valid
+    // dense pointer walk
+    const float* pa[WA];        // running source pointer (or the zero block)
+    int step_a[WA];             // pointer advance per slice (0 for the zero block)
+    // tap gather
+    long long boff[GA];         // element offset of (image, oy*s-pad, ox*s-pad, chunk)
+    unsigned amask[GA];         // bit t set <=> filter tap t is inside the image for this row
+    // dense pointer walk with a temporal shift
+    int tflag[WA];              // bit0 has previous frame, bit1 has next frame, bit2 row valid
+    // every form
     int qa[AI];                 // source chunk (swizzled) in floats
 #pragma unroll
     for (int j = 0; j < AI; ++j) {
@@ -669,15 +706,15 @@ void conv_gemm_glds_kernel(const ConvArgs a) {
         const int m = m0 + row;
         const bool ok = m < a.M;
         const int mm = ok ? m : 0;
-        qa[j] = (ls ^ ((row >> 1) & 7)) * 4;
-        pa[j] = a.zeros; step_a[j] = 0; boff[j] = 0; amask[j] = 0; tflag[j] = 0; va[j] = 0;
+        qa[j] = slice_chunk(row, ls) * 4;
+        if (WALK) { pa[j] = a.zeros; step_a[j] = 0; tflag[j] = 0; }
+        if (GATHER) { boff[j] = 0; amask[j] = 0; }
+        if (LEAN) va[j] = 0;
         if (LEAN) {
             int r = PM ? (m < a.pm_images ? m : 0) : mm;
             if (DENSE && a.stride != 1) {       // 1x1 / stride s (the downsample convs): output pixel -> input pixel, still one row per row
-                const int ohw = a.OH * a.OW;
-                const int img = mm / ohw, rem = mm - img * ohw;
-                const int oy = rem / a.OW, ox = rem - oy * a.OW;
-                r = (img * a.H + oy * a.stride) * a.W + ox * a.stride;
+                const OutPix px = out_pixel(a, mm);
+                r = (px.img * a.H + px.oy * a.stride) * a.W + px.ox * a.stride;
             }
             if constexpr ((CG_ABL & 32) != 0) r &= 1023;      // ablation: the activation rows of every tile come from the same 1024 rows (L2-resident)
             va[j] = (unsigned)(((size_t)r * (PM ? (size_t)a.H * a.W : (size_t)1) * a.ldx + qa[j]) * 4);
@@ -699,13 +736,9 @@ void conv_gemm_glds_kernel(const ConvArgs a) {
             boff[j] = ((long long)(iok ? img : 0) * a.H * a.W + (long long)pm_iy0 * a.W + pm_ix0) * a.ldx + qa[j];
             amask[j] = iok ? pm_mask : 0u;
         } else {
-            const int ohw = a.OH * a.OW;
-            const int img = mm / ohw;
-            const int rem = mm - img * ohw;
-            const int oy = rem / a.OW;
-            const int ox = rem - oy * a.OW;
-            const int iy0 = oy * a.stride - a.pad, ix0 = ox * a.stride - a.pad;
-            boff[j] = ((long long)img * a.H * a.W + (long long)iy0 * a.W + ix0) * a.ldx + qa[j];
+            const OutPix px = out_pixel(a, mm);
+            const int iy0 = px.oy * a.stride - a.pad, ix0 = px.ox * a.stride - a.pad;
+            boff[j] = ((long long)px.img * a.H * a.W + (long long)iy0 * a.W + ix0) * a.ldx + qa[j];
             unsigned mk = 0;
             for (int kh = 0; kh < a.KH; ++kh)
                 for (int kw = 0; kw < a.KW; ++kw)
@@ -714,6 +747,7 @@ void conv_gemm_glds_kernel(const ConvArgs a) {
             amask[j] = mk;
         }
     }
+    // weight rows of every form but lean: pointer walk (the weight loop fills both forms' state: guarding it changes the lean kernels)
     const float* pb[BI];
     int step_b[BI];
     int qb[BI];                 // weight-row source chunk (swizzled) in floats
@@ -734,7 +768,7 @@ void conv_gemm_glds_kernel(const ConvArgs a) {
         } else {
             const int row = (j * NW + wave) * 8 + lr;
             const int n = n0 + row;
-            const int q = (ls ^ ((row >> 1) & 7)) * 4;
+            const int q = slice_chunk(row, ls) * 4;
             qb[j] = q;
             vb[j] = (unsigned)(((size_t)(n < a.N ? n : 0) * a.K + q) * 4);
             if (n < a.N) { pb[j] = a.w + (size_t)n * a.K + q; step_b[j] = 32; }
@@ -749,7 +783,7 @@ void conv_gemm_glds_kernel(const ConvArgs a) {
     // per-slice wave-uniform state of the NEXT slice's DMA (set by prep)
     bool nx_tsm = false, nx_tail = false;
     int ltsm_ty = -1;           // LTSM: kind of the slice whose offsets are in vcur (0 next frame, 1 previous frame, 2 own frame)
-    unsigned vcur[LTSM ? AI : 1];
+    unsigned vcur[SA];
     int nx_kt = 0, nx_tap = 0, nx_c0 = 0, nx_kh = 0, nx_kw = 0;
     int nx_koff = 0;            // PM: offset of the slice inside a filter row (taps are skipped, so it is not 32 * kt)
     long long nx_toff = 0;
@@ -770,39 +804,14 @@ void conv_gemm_glds_kernel(const ConvArgs a) {
                 }
             }
         } else {
-            // one filter tap per slice (cin % 32 == 0); prep() is called for kt = 0, 1, 2, ... so the
-            // (tap, channel offset) pair is advanced incrementally -- scalar adds, no division
-            bool moved = false;
-            if (kt == 0) { nx_c0 = 0; nx_tap = 0; nx_kh = 0; nx_kw = 0; moved = true; }
-            else {
-                nx_c0 += 32;
-                if (nx_c0 == a.cin) {
-                    nx_c0 = 0;
-                    ++nx_tap;
-                    if (++nx_kw == a.KW) { nx_kw = 0; ++nx_kh; }
-                    moved = true;
-                }
-            }
-            if (PM && moved) {   // on to the next tap that touches the image (wave-uniform; the centre tap always does)
-                while (!((pm_walk >> nx_tap) & 1u)) {
-                    ++nx_tap;
-                    if (++nx_kw == a.KW) { nx_kw = 0; ++nx_kh; }
-                }
-            }
+            tap_walk_step<PM>(kt, a, pm_walk, nx_tap, nx_c0, nx_kh, nx_kw);
             nx_toff = ((long long)nx_kh * a.W + nx_kw) * a.ldx + nx_c0;
             if (PM) nx_koff = nx_tap * a.cin + nx_c0;
         }
     };
     // one DMA instruction: q < BI -> weight rows, else activation rows
     const unsigned smem_lds = (unsigned)(size_t)(lptr_t)smem;      // LDS byte address of the block's buffer
-    auto lean_dma = [&](const float* sbase, unsigned voff, const float* lds) {
-        const unsigned l = (unsigned)__builtin_amdgcn_readfirstlane(smem_lds + (unsigned)((lds - smem) * 4));
-        const unsigned long long b = (unsigned long long)sbase;     // wave-uniform by construction: pin it to SGPRs
-        const unsigned long long sb = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)(b >> 32)) << 32) |
-                                      (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)b);
-        // (s_nop: the M0 write -> LDS-DMA read hazard the compiler pads for its own builtin is ours to pad inside an asm block)
-        asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(l), "v"(voff), "s"(sb) : "memory", "m0");   // (m0 is named so that the compiler does not merge its own M0 initialisations across this block; the "reserved register" warning is expected)
-    };
+    auto lean_dma = [&](const float* sbase, unsigned voff, const float* lds) { lds_dma_sbase(sbase, voff, smem_lds + (unsigned)((lds - smem) * 4)); };
     auto issue_one = [&](int q, int buf) {
         if (LTSM && q >= BI) {
             // buffer_load_dwordx4 voffset, s[rsrc], soffset offen lds -- written out (the compiler's builtin for it makes the HOST pass drop
@@ -880,13 +889,18 @@ void conv_gemm_glds_kernel(const ConvArgs a) {
 #pragma unroll
     for (int j = 0; j < 2; ++j) foffb[j] = (lane & 31) * 16 + ((((2 * j + (lane >> 5)) ^ ((lane >> 2) & 3)) & 3) << 2);
 
+    // ==== schedule: one of three K loops ================================================================================================
+    // EMU = 0: v_mfma_f32_32x32x2_f32 (the default, exact fp32 FMA chain).  EMU = 6 / 9: the fragments are split into
+    // three bf16 parts after the LDS read and multiplied with 6 / 9 v_mfma_f32_32x32x16_bf16 per 16 k (see split3).
+    // BSP (split tiles only): the weights come pre-split as three bf16 planes (ConvArgs::wsp); their LDS image is
+    // [plane][BN rows][64 B] with the 16-byte chunk index XOR-ed with (row>>2)&3, and a fragment is one ds_read_b128.
     const int nk = PM ? __builtin_popcount(pm_walk) * (a.cin >> 5) : (a.K + 31) / 32;
     prep(0);
 #pragma unroll
     for (int q = 0; q < NI; ++q) issue_one(q, 0);
 
     if constexpr (EMU != 0 && BSP) {
-        // ---- production schedule of the split tiles: fragments always one k16 step ahead, ONE barrier per slice placed
+        // ---- schedule 1, the production schedule of the split tiles (EMU != 0, BSP): fragments always one k16 step ahead, ONE barrier per slice placed
         // between its two steps.  At the barrier T_k every wave has (a) read all of slice k out of LDS, (b) seen its own
         // DMA of slice k+1 land -- so after it buffer k&1 can take slice k+2 and slice k+1's first fragments can be read
         // while slice k's second step multiplies.
@@ -985,7 +999,7 @@ void conv_gemm_glds_kernel(const ConvArgs a) {
     }
 
     if constexpr (EMU == 0 && PIPE == 2) {
-        // ---- fp32 pipe, barrier between steps 2 and 3 of a slice: at T_k every wave has read all of slice k (step 3's
+        // ---- schedule 2, the fp32 pipe with the barrier between steps 2 and 3 of a slice (PIPE == 2; measured variant): at T_k every wave has read all of slice k (step 3's
         // fragments were fetched during step 2) and seen its DMA of slice k+1 land, so step 3 multiplies while the first
         // fragments of slice k+1 are already being read -- no LDS latency is exposed behind a barrier.  DMA of slice k+2:
         // first half during step 3 of slice k, second half during step 0 of slice k+1.
@@ -1002,11 +1016,7 @@ void conv_gemm_glds_kernel(const ConvArgs a) {
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int s4 = 0; s4 < 4; ++s4) {
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int j = 0; j < TN; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[cb][i][s4], bf[cb][j][s4], acc[i][j], 0, 0, 0);
+                mfma_step(acc, af[cb], bf[cb], s4);
                 if (dma) {
 #pragma unroll
                     for (int q = 0; q < NI; ++q)
@@ -1050,7 +1060,15 @@ void conv_gemm_glds_kernel(const ConvArgs a) {
         return;
     }
 
-    // the K loop runs in pairs of slices so that the stage a slice reads is a compile-time constant: the fragment reads are
+    // ---- schedule 3, the paired-slice loop (every other form: fp32, fp16 operands, splits on the fly).  PIPE = 0: the next slice's DMA at the
+    // top of a slice (kept for A/B), PIPE = 1: between the MFMA groups.
+    // DT (half-precision STORAGE, N2 / BASELINE config 5): bit 0 = fp16 output, bit 1 = fp16 residual, bit 2 = fp16 operands
+    // (x and w): a k slice is then 64 halfs -- the same 128 bytes per row, so the DMA, the LDS image and its swizzle are
+    // byte-identical and the loader simply counts in 32-bit words (the launcher halves K / cin / ldx); a lane's 16-byte
+    // fragment is exactly the 8 halfs one v_mfma_f32_32x32x16_f16 wants (lanes 0-31: k 0..7, lanes 32-63: k 8..15 of a
+    // 16-k step = chunk 2 kk + (lane >> 5), the f32 mapping).  Accumulation, BN and activation stay fp32.
+    // (Bit 2 is the (DT & 4) branch of the slice below; bits 0 and 1 go to the epilogue as its ET.)
+    // The K loop runs in pairs of slices so that the stage a slice reads is a compile-time constant: the fragment reads are
     // then ds_read_b128 at (loop-invariant VGPR) + immediate, with no address arithmetic per slice
     auto slice = [&](int kt, auto more_tag, auto stage_tag) {
         constexpr bool more = decltype(more_tag)::value;   // compile time: the last slice issues nothing
@@ -1142,11 +1160,7 @@ void conv_gemm_glds_kernel(const ConvArgs a) {
             } else {
 #pragma unroll
             for (int s4 = 0; s4 < 4; ++s4) {
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int j = 0; j < TN; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[cb][i][s4], bf[cb][j][s4], acc[i][j], 0, 0, 0);
+                mfma_step(acc, af[cb], bf[cb], s4);
                 if (PIPE && s4 < 2) {
                     // the DMA for the next slice is issued in the shadow of the MFMAs just queued: slot = 2*kk + s4
                     if (more) {
@@ -1175,6 +1189,7 @@ void conv_gemm_glds_kernel(const ConvArgs a) {
             slice(kt, std::false_type{}, S0{});
         }
     }
+    // ==== epilogue ======================================================================================================================
     __syncthreads();   // all fragment reads done before the slabs overwrite the stage buffers
     if constexpr (POOL) {
         conv_epilogue_pool<TM, TN, BM, BN, NW, DT == 4, DT == 6>(a, smem, acc, m0, n0, wm, wn, lane, wave, tile_m);
@@ -1259,26 +1274,19 @@ __global__ __launch_bounds__(256, N1 == 128 ? 2 : 3) void conv_fused_tail_kernel
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WGN, wn = wave % WGN;
 
-    int bid = blockIdx.x;
-    {
-        const int q = a.nblocks >> 3, r = a.nblocks & 7;
-        const int xcd = bid & 7, idx = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int bid = xcd_tile(blockIdx.x, a.nblocks);
     // row map of the tile
     int m0 = bid * BM, rstride = 1, roff = 0, rlimit = a.M;
     int pm_iy0 = 0, pm_ix0 = 0;
     unsigned pm_mask = 0;
     if (PM) {   // group-major order, as in conv_gemm_glds_kernel: an XCD's consecutive tiles are the pixels of the same images
-        const int ohw = a.OH * a.OW;
-        const int g = bid / ohw;
-        roff = bid - g * ohw;
-        m0 = g * fa.pm_gstride;                       // (128, or the largest multiple of the clip length below it: clips never straddle tiles)
-        rstride = ohw;
+        const OutPix px = out_pixel(a, bid);
+        roff = px.rem;
+        m0 = px.img * fa.pm_gstride;                  // (128, or the largest multiple of the clip length below it: clips never straddle tiles)
+        rstride = a.OH * a.OW;
         rlimit = a.pm_images < m0 + fa.pm_gstride ? a.pm_images : m0 + fa.pm_gstride;
-        const int oy = roff / a.OW, ox = roff - oy * a.OW;
-        pm_iy0 = oy * a.stride - a.pad;
-        pm_ix0 = ox * a.stride - a.pad;
+        pm_iy0 = px.oy * a.stride - a.pad;
+        pm_ix0 = px.ox * a.stride - a.pad;
         for (int kh = 0; kh < a.KH; ++kh)
             for (int kw = 0; kw < a.KW; ++kw)
                 if ((unsigned)(pm_iy0 + kh) < (unsigned)a.H && (unsigned)(pm_ix0 + kw) < (unsigned)a.W) pm_mask |= 1u << (kh * a.KW + kw);
@@ -1289,16 +1297,7 @@ __global__ __launch_bounds__(256, N1 == 128 ? 2 : 3) void conv_fused_tail_kernel
     typedef __attribute__((address_space(1))) char gchar;
     typedef __attribute__((address_space(1))) f32x4 gf32x4;
     const unsigned smem_lds = (unsigned)(size_t)(lptr_t)smem;
-    auto uni = [](unsigned long long v) {       // wave-uniform by construction: pin to SGPRs
-        return ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)(v >> 32)) << 32) |
-               (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)v);
-    };
-    // scalar-base LDS-DMA (see the LEAN note above conv_gemm_glds_kernel): constant lane offset, SALU-advanced base
-    auto lean_dma = [&](const float* sbase, unsigned voff, const float* lds) {
-        const unsigned l = (unsigned)__builtin_amdgcn_readfirstlane(smem_lds + (unsigned)((lds - smem) * 4));
-        const unsigned long long sb = uni((unsigned long long)sbase);
-        asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(l), "v"(voff), "s"(sb) : "memory", "m0");   // (m0 is named so that the compiler does not merge its own M0 initialisations across this block; the "reserved register" warning is expected)
-    };
+    auto lean_dma = [&](const float* sbase, unsigned voff, const float* lds) { lds_dma_sbase(sbase, voff, smem_lds + (unsigned)((lds - smem) * 4)); };
 
     // ---- phase 1: 3x3 implicit GEMM, tile 128 x 64, K = KH*KW*64 ------------------------------------------
     const int lr = lane >> 3, ls = lane & 7;
@@ -1317,13 +1316,9 @@ __global__ __launch_bounds__(256, N1 == 128 ? 2 : 3) void conv_fused_tail_kernel
         } else {
             const bool ok = m < a.M;
             const int mm = ok ? m : 0;
-            const int ohw = a.OH * a.OW;
-            const int img = mm / ohw;
-            const int rem = mm - img * ohw;
-            const int oy = rem / a.OW;
-            const int ox = rem - oy * a.OW;
-            const int iy0 = oy * a.stride - a.pad, ix0 = ox * a.stride - a.pad;
-            boff[j] = ((long long)img * a.H * a.W + (long long)iy0 * a.W + ix0) * a.ldx + qa;
+            const OutPix px = out_pixel(a, mm);
+            const int iy0 = px.oy * a.stride - a.pad, ix0 = px.ox * a.stride - a.pad;
+            boff[j] = ((long long)px.img * a.H * a.W + (long long)iy0 * a.W + ix0) * a.ldx + qa;
             unsigned mk = 0;
             for (int kh = 0; kh < a.KH; ++kh)
                 for (int kw = 0; kw < a.KW; ++kw)
@@ -1339,23 +1334,7 @@ __global__ __launch_bounds__(256, N1 == 128 ? 2 : 3) void conv_fused_tail_kernel
     int nx_tap = 0, nx_c0 = 0, nx_kh = 0, nx_kw = 0, nx_koff = 0;
     long long nx_toff = 0;
     auto prep = [&](int kt) {
-        bool moved = false;
-        if (kt == 0) { nx_c0 = 0; nx_tap = 0; nx_kh = 0; nx_kw = 0; moved = true; }
-        else {
-            nx_c0 += 32;
-            if (nx_c0 == a.cin) {
-                nx_c0 = 0;
-                ++nx_tap;
-                if (++nx_kw == a.KW) { nx_kw = 0; ++nx_kh; }
-                moved = true;
-            }
-        }
-        if (PM && moved) {      // on to the next tap that touches the image (the centre tap always does)
-            while (!((pm_mask >> nx_tap) & 1u)) {
-                ++nx_tap;
-                if (++nx_kw == a.KW) { nx_kw = 0; ++nx_kh; }
-            }
-        }
+        tap_walk_step<PM>(kt, a, pm_mask, nx_tap, nx_c0, nx_kh, nx_kw);
         nx_toff = ((long long)nx_kh * a.W + nx_kw) * a.ldx + nx_c0;
         nx_koff = nx_tap * a.cin + nx_c0;
     };
@@ -1427,8 +1406,8 @@ __global__ __launch_bounds__(256, N1 == 128 ? 2 : 3) void conv_fused_tail_kernel
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
         const size_t grow = (size_t)(m0 + wave * 32 + u * 8) * rstride + roff;
-        rbase[u] = uni((unsigned long long)fa.res + grow * fa.ldr * 4);
-        obase[u] = uni((unsigned long long)fa.out + grow * fa.n3 * 4);
+        rbase[u] = pin_sgpr((unsigned long long)fa.res + grow * fa.ldr * 4);
+        obase[u] = pin_sgpr((unsigned long long)fa.out + grow * fa.n3 * 4);
         row_ok[u] = m0 + wave * 32 + u * 8 + rsub < rlimit;
     }
     f32x4 rv[4];                             // identity rows of the coming conv3 pass (requested one pass ahead)
@@ -1474,9 +1453,7 @@ __global__ __launch_bounds__(256, N1 == 128 ? 2 : 3) void conv_fused_tail_kernel
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int s4 = 0; s4 < 4; ++s4) {
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-                    acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[cb][i][s4], bf[cb][0][s4], acc[i][0], 0, 0, 0);
+                mfma_step(acc, af[cb], bf[cb], s4);
                 if (s4 < 2) {
                     if (more) {
 #pragma unroll
@@ -1511,7 +1488,7 @@ __global__ __launch_bounds__(256, N1 == 128 ? 2 : 3) void conv_fused_tail_kernel
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int row = wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                A2[wn * (BM * 32) + row * 32 + ((kc ^ ((row >> 1) & 7)) << 2) + ke] = fmaxf(fmaf(acc[i][0][r], sc, bi) + 0.f, 0.f);
+                A2[wn * (BM * 32) + row * 32 + (slice_chunk(row, kc) << 2) + ke] = fmaxf(fmaf(acc[i][0][r], sc, bi) + 0.f, 0.f);
             }
     }
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -1620,11 +1597,7 @@ __global__ __launch_bounds__(256, N1 == 128 ? 2 : 3) void conv_fused_tail_kernel
 #pragma unroll
                 for (int j = 0; j < TN1; ++j) bf[j] = *reinterpret_cast<const f32x4*>(W1s + (wn * TN1 * 32 + j * 32) * 32 + foff[kk]);
 #pragma unroll
-                for (int s4 = 0; s4 < 4; ++s4)
-#pragma unroll
-                    for (int i = 0; i < TM; ++i)
-#pragma unroll
-                        for (int j = 0; j < TN1; ++j) acc1[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i][s4], bf[j][s4], acc1[i][j], 0, 0, 0);
+                for (int s4 = 0; s4 < 4; ++s4) mfma_step(acc1, af, bf, s4);
             }
             if (W3DB) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");    // single W3 buffer: its refill must have landed

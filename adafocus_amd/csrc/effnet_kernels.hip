@@ -177,15 +177,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K == 5 ? 3 
     const int tid = threadIdx.x;
     int bid = blockIdx.x;
     EF_STAMP(0);
-    {
-        // XCD-aware, bijective remap (the hardware places block b on XCD b % 8): every XCD gets a contiguous range of work
-        // items, so the channel slices of one tile -- which read interleaved 16 LPP-byte pieces of the same pixels -- and
-        // neighbouring tiles -- which share halo rows -- meet in ONE L2.  Measured before: the stride-2 layer of block 2
-        // fetched 2.2x its input from the fabric.
-        const int nb = gridDim.x, q = nb >> 3, r = nb & 7;
-        const int xcd = bid & 7, idx = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    // XCD-aware, bijective remap (xcd_tile: the hardware places block b on XCD b % 8): every XCD gets a contiguous range of work
+    // items, so the channel slices of one tile -- which read interleaved 16 LPP-byte pieces of the same pixels -- and
+    // neighbouring tiles -- which share halo rows -- meet in ONE L2.  Measured before: the stride-2 layer of block 2
+    // fetched 2.2x its input from the fabric.
+    bid = xcd_tile(bid, gridDim.x);
     const int slice = bid % a.slices; bid /= a.slices;
     const int tile = bid % a.tiles;
     const int img0 = (bid / a.tiles) * a.IMB;
