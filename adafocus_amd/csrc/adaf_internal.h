@@ -392,6 +392,7 @@ bool adaf_conv_tile_exists(int tile);   // is `tile` an id adaf_launch_conv_gemm
 void adaf_launch_conv_naive(const ConvArgs& a, hipStream_t s);
 // conv2 3x3 (64 -> 64) -> conv3 1x1 (+ identity, ReLU) [-> the next block's conv1 1x1] in one launch (stage 1 of the trunk);
 // returns 0 or < 0 when the shape is not eligible
+bool adaf_fused_tail_in_reach(const ConvArgs& c2, int n3);   // the 32-bit lane offsets of the launch reach every row of its operands
 bool adaf_fused_tail_shift_ok(const ConvArgs& c2, int n3, int ldr, int tsm_T1, int tsm_fold1);
 int adaf_launch_fused_tail(const ConvArgs& c2, const float* w3, const float* s3, const float* b3, const float* res, int ldr,
                            float* out, int n3, const float* w1n, const float* s1n, const float* b1n, float* out1, int n1,

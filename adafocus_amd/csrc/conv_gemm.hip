@@ -2144,6 +2144,13 @@ static bool fused_tail_pm(const ConvArgs& c2, int n3, int ldr, int* images_out, 
            (long long)groups * 128 * 100 <= (long long)images * (gstride == 128 ? 106 : 108) && (size_t)ohw * 8 * (size_t)(n3 > ldr ? n3 : ldr) * 4 < 0xffffff00ull;
 }
 
+// The fused tail addresses conv2's input, conv3's filters and its output / identity rows (n3 wide; the next conv1's 64 or 128 are fewer) with
+// 32-bit lane offsets from scalar bases: are they all within reach?  Asked by the trunk before it decides on the fused launch (beyond the
+// reach the block runs as conv2 / conv3 / next conv1, each planned by plan_conv) and by the launcher as its last line of defence.
+bool adaf_fused_tail_in_reach(const ConvArgs& c2, int n3) {
+    return (size_t)c2.M * c2.ldx * 4 < 0xffffff00ull && (size_t)c2.M * n3 * 4 < 0x3fffffffull * 4 && (size_t)n3 * 128 * 4 < 0xffffff00ull;
+}
+
 // images per tile group of the position-major tail whose next conv1 is shifted over clips of T frames: whole clips per tile
 static int fused_tail_gstride(int tsm_T1) { return tsm_T1 > 0 && tsm_T1 <= 128 ? (128 / tsm_T1) * tsm_T1 : 128; }
 
@@ -2160,9 +2167,7 @@ int adaf_launch_fused_tail(const ConvArgs& c2, const float* w3, const float* s3,
                            float* out, int n3, const float* w1n, const float* s1n, const float* b1n, float* out1, int n1,
                            hipStream_t s, int tsm_T1, int tsm_fold1) {
     if (c2.N != 64 || c2.cin != 64 || (c2.K & 31) || c2.KH * c2.KW > 32 || n3 % 32 || (n1 != 0 && n1 != 64 && n1 != 128)) return -1;
-    // scalar-base accesses: 32-bit lane offsets
-    if ((size_t)c2.M * c2.ldx * 4 >= 0xffffff00ull || (size_t)c2.M * n3 * 4 >= 0x3fffffffull * 4 || (size_t)n3 * 128 * 4 >= 0xffffff00ull)
-        return -1;
+    if (!adaf_fused_tail_in_reach(c2, n3)) return -1;      // scalar-base accesses: 32-bit lane offsets
     FusedTailArgs fa;
     fa.c2 = c2;
     fa.c2.tiles_n = 1;
@@ -2196,4 +2201,15 @@ int adaf_launch_fused_tail(const ConvArgs& c2, const float* w3, const float* s3,
         else hipLaunchKernelGGL((conv_fused_tail_kernel<128, false>), grid, block, 0, s, fa);
     }
     return 0;
+}
+
+// Debug hook (not in include/adafocus.h), without a device like adaf_conv_plan_debug: is the fused tail whose conv2 is `p` and whose conv3
+// has n3 outputs within its 32-bit reach (1 / 0), or the code with which the C ABI's validation refuses `p`.
+extern "C" int adaf_fused_tail_reach_debug(const adaf_conv_params* p, int n3) {
+    alignas(16) static const float operand[4] = {0.f, 0.f, 0.f, 0.f};
+    alignas(16) static float result[4];
+    adaf_handle host;
+    ConvArgs a;
+    const int rc = adaf_make_conv_args(&host, p, operand, operand, nullptr, nullptr, nullptr, result, &a);
+    return rc ? rc : (adaf_fused_tail_in_reach(a, n3) ? 1 : 0);
 }

@@ -312,13 +312,18 @@ int walk_trunk(adaf_resnet50* net, const float* x4, int n, int P, int tsm_T, int
             // (below ~1.5 row tiles of 128 pixels per CU the fused launch is a few dozen blocks that each run conv2, eight conv3 passes and
             //  the next conv1 one after the other -- 48-55 us at 8 patches against ~30 us for the three launches it replaces, each spread over
             //  more CUs; measured crossover between 64 and 96 patches of 96^2, tools/lat_plan_probe.py.  Bit-identical either way.)
-            const bool fusable = fuse && stage1_f32 && L2.cin == 64 && L2.cout == 64 && L2.stride == 1 &&
-                                 !net->tiles[i_c2] && !net->tiles[i_c3] && (net->fuse_stem_always || (long long)n * h1 * w1 * 2 >= 3ll * 128 * h->cus);
+            bool fusable = fuse && stage1_f32 && L2.cin == 64 && L2.cout == 64 && L2.stride == 1 &&
+                           !net->tiles[i_c2] && !net->tiles[i_c3] && (net->fuse_stem_always || (long long)n * h1 * w1 * 2 >= 3ll * 128 * h->cus);
+            const ConvLayer& L3 = net->convs[i_c3];
+            ConvArgs a2;
             if (fusable) {
-                const ConvLayer& L3 = net->convs[i_c3];
                 const adaf_conv_params p = layer_params(L2, n, h1, w1, ADAF_ACT_RELU);
-                ConvArgs a2;
                 if ((rc = adaf_make_conv_args(h, &p, t1, L2.w, L2.scale, L2.bias, nullptr, t2, &a2))) return rc;
+                // (the fused launch addresses its operands with 32-bit offsets: a batch whose stage-1 map is beyond that reach -- 4 GiB, 4096
+                //  patches of 128^2 -- takes the three launches below, each on the form plan_conv gives it.  Bit-identical either way.)
+                fusable = adaf_fused_tail_in_reach(a2, L3.cout);
+            }
+            if (fusable) {
                 // the next block's conv1 rides along unless it carries a temporal shift or a tile override
                 // ('block' placement: the next block reads a shifted COPY of this block's output, so its conv1 cannot ride; 'blockres': it rides
                 //  with the shift as a row offset inside the tile, whole clips per tile -- adaf_fused_tail_shift_ok)

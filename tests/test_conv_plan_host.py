@@ -229,6 +229,26 @@ def test_dma_reach_fallbacks():
     assert form(plan(tile=65, presplit=True, n=2, hw=8, cin=16384, cout=16384)) == (1, 0, 1, 0)
 
 
+def test_fused_tail_reach():
+    """adaf_fused_tail_in_reach, which the trunk asks before it takes the fused stage-1 tail (conv2 3x3 64 -> 64, conv3 to 256 channels):
+    the 256-channel map of every patch must lie within 32-bit byte offsets (0x3fffffff words), conv2's input within the DMA's 4 GB."""
+    import ctypes as C
+    _ensure_built()
+    fn = _lib.load_library().adaf_fused_tail_reach_debug
+    fn.argtypes, fn.restype = [C.c_void_p, C.c_int], C.c_int
+    assert "adaf_fused_tail_reach_debug" not in _lib.SYMBOLS
+
+    def reach(n, hw, n3=256, ldx=0):
+        p = _lib.ConvParams(n=n, h=hw, w=hw, cin=64, cout=64, kh=3, kw=3, stride=1, pad=1, act=_lib.ACT_RELU, tsm_segments=0, tsm_div=8,
+                            ldx=ldx, ldo=0, ldr=0, tile=0)
+        return fn(C.byref(p), n3)
+    assert (reach(4088, 32), reach(4096, 32)) == (1, 0)             # 128^2 patches: 0xff800000 and 2^32 bytes
+    assert (reach(7281, 24), reach(7282, 24)) == (1, 0)             # 96^2 patches: 7282 x 576 x 1 KiB = 2^32 + 131072
+    assert reach(4096, 32, n3=128) == 1 and reach(8192, 32, n3=128) == 0
+    # conv2's input rows through their pitch: 2^20 rows of 1020 floats are 0xff000000 bytes
+    assert (reach(1024, 32, ldx=1020), reach(1024, 32, ldx=1024)) == (1, 0)
+
+
 def test_pooled_epilogue_eligibility():
     last = dict(n=28, hw=3, cin=512, cout=2048, vec_epi=True)           # the trunk's last conv3 at 96^2 patches: 14 images per 126-row tile
     p = plan(pool_hw=9, **last)
