@@ -98,6 +98,9 @@ PROTOTYPES = {
     "adaf_bn_train_workspace_bytes": (sz, [ip, ip]),
     "adaf_bn_train_forward_f32": (ip, [vp, vp, ip, ip, vp, vp, fp, fp, vp, vp, ip, vp, vp, vp, vp, sz, vp]),
     "adaf_bn_train_backward_f32": (ip, [vp, vp, vp, vp, ip, ip] + [vp] * 7 + [sz, vp]),
+    "adaf_bn_map_workspace_bytes": (sz, [ip, ip]),
+    "adaf_bn_map_train_forward_f32": (ip, [vp, vp, ip, ip, vp, vp, fp, fp, vp, vp, vp, ip, vp, vp, vp, vp, sz, vp]),
+    "adaf_bn_map_train_backward_f32": (ip, [vp, vp, vp, vp, ip, ip] + [vp] * 7 + [sz, vp]),
     "adaf_ppo_encoder_bn_backward_workspace_bytes": (sz, [ip] * 7),
     "adaf_ppo_encoder_bn_backward_f32": (ip, [vp] * 5 + [ip] * 6 + [vp] * 17 + [sz, vp]),
     "adaf_crop_gather_nhwc4_f32": (ip, [vp, vp, ip, ip, ip, vp, ip, ip, ip, vp, vp, vp]),

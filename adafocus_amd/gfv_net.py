@@ -18,7 +18,10 @@ which reproduces the reference logits.  Stage-3 training (``tr
 train_stage 3: only ``classifier.*`` learns) runs the frozen part on the same HIP path and the classifier with a HIP backward
 (csrc/gru_bptt.hip).  Stage-2 training (``policy_train_mode()``: only ``focuser.policy.policy`` learns) runs the roll-out through
 ``one_step_act(training=True)`` and the PPO update through ``Focuser.update()`` with a HIP backward (csrc/ppo_train.hip; the loop body is
-``adafocus_amd.train.train_stage2_batch``; ``rollout_act`` is the T steps as one batched pass, the body of ``train_stage2_batch_fused``).  The other training branches (stages 0 and 1) are out of scope and raise.  ``GFV.one_step_act(training=False)`` -- the body of the
+``adafocus_amd.train.train_stage2_batch``; ``rollout_act`` is the T steps as one batched pass, the body of ``train_stage2_batch_fused``).
+Stage-0 training of the focuser's ResNet (``backbone_train_mode()``: the local CNN with its ``fc`` learns on whole frames, BatchNorm on
+batch statistics; csrc/bn_map.hip; the loop body is ``adafocus_amd.train.train_stage0_batch``).  What remains out of scope and
+raises: stage 0 for the glancer, stage 1, AMP.  ``GFV.one_step_act(training=False)`` -- the body of the
 stage-2 VALIDATION loop (ACT/main_dist.py:346-362), reward baseline included -- keeps the reference's
 per-step structure on the same HIP ops (round 6, pinned by G15).
 """
@@ -359,11 +362,13 @@ class GFV(nn.Module):
 
     def train_mode(self, args):
         """gfv_net.py:62-81 for train_stage == 3 (call after model.train(), as ACT/main_dist.py does): the glancer, the focuser and
-        both policies go to eval mode; only the classifier trains (dropout on, HIP backward).  Stages 0 and 1 (the backbones' training) are
-        out of scope and raise; stage 2 (the policy's training) is entered through `policy_train_mode()` and raises here too."""
+        both policies go to eval mode; only the classifier trains (dropout on, HIP backward).  Every other stage raises here: stage 2 (the
+        policy's training) is entered through `policy_train_mode()`, stage 0 for the focuser's ResNet through `backbone_train_mode()`;
+        stage 0 for the glancer and stage 1 are out of scope."""
         if args.train_stage != 3:
             raise NotImplementedError("train_mode: train_stage %r is not entered here (stage 3, classifier training, is; stage 2, policy "
-                                      "training, is entered with policy_train_mode(); stages 0 and 1 are out of scope)" % (args.train_stage,))
+                                      "training, is entered with policy_train_mode(); stage 0 for the focuser's ResNet with "
+                                      "backbone_train_mode(); stage 0 for the glancer and stage 1 are out of scope)" % (args.train_stage,))
         self.train()
         self.glancer.eval()
         self.focuser.eval()
@@ -380,6 +385,22 @@ class GFV(nn.Module):
         self.focuser.eval()
         self.focuser.policy.policy.train()
         self.focuser.policy.policy_old.train()
+
+    def backbone_train_mode(self, glancer=False):
+        """What the reference's train_mode does for train_stage == 0 (gfv_net.py:65-66), for the backbone stage 0 trains with
+        pretrain_glancer=False: the focuser's ResNet goes to train mode, trainable, with BatchNorm on batch statistics
+        (ResNet.set_bn_batch_stats); everything else goes to eval mode (nothing else runs in that branch, ACT/main_dist.py:544-548).
+        The loop body is `adafocus_amd.train.train_stage0_batch`.  glancer=True (pretrain_glancer) is out of scope."""
+        if glancer:
+            raise NotImplementedError("backbone_train_mode(glancer=True): stage 0 for the glancer needs the MobileNetV2 backward, which "
+                                      "is not implemented")
+        net = self.focuser.net
+        if not hasattr(net, "set_bn_batch_stats"):
+            raise NotImplementedError("backbone_train_mode: stage 0 trains a ResNet local CNN only (%s has no backward)" % type(net).__name__)
+        self.eval()
+        net.train()
+        net.set_trainable(True)
+        net.set_bn_batch_stats(True)
 
     @property
     def scale_size(self):

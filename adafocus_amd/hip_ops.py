@@ -464,6 +464,52 @@ def bn_train_backward(x, y, dy, gamma, mean, invstd):
     return dx, dgamma, dbeta
 
 
+def _map2d(t):
+    """A dense pixel-major map (..., cols) as (rows, cols)."""
+    t = t.contiguous()
+    return t.reshape(-1, t.shape[-1])
+
+
+def bn_map_train_forward(x, gamma, beta, running_mean=None, running_var=None, eps=1e-5, momentum=0.1, residual=None, relu=True):
+    """bn_train_forward for tall pixel-major maps (csrc/bn_map.hip): x (..., cols) dense, the statistics over every leading
+    axis [+ residual of x's shape] [+ ReLU]; running_mean / running_var are updated in place.  cols % 4 == 0.
+    -> (y of x's shape, mean (cols,), invstd (cols,))."""
+    L.need_gpu_f32(x, gamma, beta, running_mean, running_var, residual)
+    x2 = _map2d(x)
+    rows, cols = x2.shape
+    if rows < 2:
+        raise ValueError("Expected more than 1 value per channel when training, got input size %s" % (tuple(x.shape),))
+    if residual is not None and residual.shape != x.shape:
+        raise ValueError("bn_map_train_forward: the residual has another shape than x")
+    for r in (running_mean, running_var):
+        if r is not None and not r.is_contiguous():
+            raise ValueError("bn_map_train_forward: contiguous running statistics expected (they are updated in place)")
+    y = torch.empty(x.shape, device=x.device, dtype=torch.float32)
+    mean = torch.empty((cols,), device=x.device, dtype=torch.float32)
+    invstd = torch.empty((cols,), device=x.device, dtype=torch.float32)
+    ws, ws_bytes = _workspace("adaf_bn_map_workspace_bytes", x.device, rows, cols)
+    _call("adaf_bn_map_train_forward_f32", x, x2, rows, cols, gamma.contiguous(), beta.contiguous(), float(eps), float(momentum), running_mean,
+          running_var, _dense(residual), int(bool(relu)), y, mean, invstd, ws, ws_bytes)
+    return y, mean, invstd
+
+
+def bn_map_train_backward(x, y, dy, gamma, mean, invstd):
+    """Backward of bn_map_train_forward: y its output after ReLU (None: no ReLU, or dy has its mask applied) -> (dx of x's shape, dgamma,
+    dbeta).  A residual join's second gradient is added in front (relu_backward)."""
+    L.need_gpu_f32(x, y, dy, gamma, mean, invstd)
+    if dy.shape != x.shape or (y is not None and y.shape != x.shape):
+        raise ValueError("bn_map_train_backward: shapes differ")
+    x2 = _map2d(x)
+    rows, cols = x2.shape
+    dx = torch.empty(x.shape, device=x.device, dtype=torch.float32)
+    dgamma = torch.empty((cols,), device=x.device, dtype=torch.float32)
+    dbeta = torch.empty((cols,), device=x.device, dtype=torch.float32)
+    ws, ws_bytes = _workspace("adaf_bn_map_workspace_bytes", x.device, rows, cols)
+    _call("adaf_bn_map_train_backward_f32", x, x2, _dense(y), dy.contiguous(), rows, cols, gamma.contiguous(), mean.contiguous(),
+          invstd.contiguous(), dx, dgamma, dbeta, ws, ws_bytes)
+    return dx, dgamma, dbeta
+
+
 def ppo_encoder_backward(states, e1, e_bt, dx_bt, t, b, w_lin_pm, bn=None):
     """Backward of the policy's state encoder (1x1 conv -> [BatchNorm2d] ReLU -> flatten -> Linear -> [BatchNorm1d] ReLU) for 32 or 64
     conv outputs: states (T*B, h, w, C) pixel-major, e1 (T*B, h*w*cmid) and e_bt (B*T, H) its stored activations, dx_bt (B, T, H) the

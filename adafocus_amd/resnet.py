@@ -103,7 +103,8 @@ class ResNet(nn.Module):
         dev = next(iter(params.values())).device
         if dev.type != "cuda":
             raise RuntimeError("adafocus_amd.ResNet runs on MI355X only; move the module to the GPU (.cuda())")
-        sig = tuple((v.data_ptr(), v._version) for v in params.values())
+        # (the batch-statistics walk writes the running statistics from its kernels, which no tensor version sees: its own count)
+        sig = tuple((v.data_ptr(), v._version) for v in params.values()) + (getattr(self, "_stats_written", 0),)
         if self._trunk is None or self._trunk.device != dev or sig != self._sig:
             if self._trunk is None or self._trunk.device != dev:
                 self._trunk = hip_ops.ResNet50Trunk(dev)
@@ -148,13 +149,29 @@ class ResNet(nn.Module):
     def trainable(self):
         return getattr(self, "_trainable", False)
 
+    def set_bn_batch_stats(self, on):
+        """Opt-in (default off) to BatchNorm on BATCH statistics in the training walk: with set_trainable(True) and the module in train
+        mode, ``features_train_nhwc4`` normalises every layer with the statistics of its batch and moves the running statistics, as
+        the torch module in train mode does (stage 0 of the ActivityNet tree, ACT/main_dist.py:534-548).  In eval mode the
+        walk is the frozen one either way.  Off: train mode raises, as before."""
+        self._bn_batch_stats = bool(on)
+
+    @property
+    def bn_batch_stats(self):
+        return getattr(self, "_bn_batch_stats", False)
+
+    def _note_stats_written(self):
+        """The running statistics were written by a kernel: the next _sync folds them anew."""
+        self._stats_written = getattr(self, "_stats_written", 0) + 1
+
     def features_train_nhwc4(self, patches_nhwc4):
         """features_nhwc4 with an autograd graph into the trunk's parameters: BatchNorm on its running statistics (the module is in eval
         mode, as STH/stage3.py:313-317 puts the focuser), the same bits as the eval engine's features.  After optimizer.step() the
-        parameter versions change and the next features_nhwc4 re-packs the engine's weights (_sync)."""
+        parameter versions change and the next features_nhwc4 re-packs the engine's weights (_sync).  In train mode with
+        set_bn_batch_stats(True): BatchNorm on the statistics of the batch (trunk_train.walk_forward_batch)."""
         if not self.trainable:
             raise RuntimeError("adafocus_amd.ResNet: the training walk is off; call set_trainable(True) first")
-        if self.training:
+        if self.training and not self.bn_batch_stats:
             raise RuntimeError("adafocus_amd.ResNet trains with frozen BatchNorm statistics only (stage 3: the focuser is in eval mode); "
                                "BatchNorm in batch-statistics mode is not implemented")
         from . import trunk_train
@@ -191,6 +208,14 @@ class ResNet(nn.Module):
 
     def forward(self, x):
         return hip_ops.linear(self.get_featvec(x), self.fc.weight.detach(), self.fc.bias.detach())
+
+    def forward_train(self, x_nchw):
+        """forward with an autograd graph: (N, 3, H, W) frames -> (N, num_classes) logits through the training walk and ``fc`` (the Linear
+        and its backward of the Something-Something stage-3 head).  Needs set_trainable(True); which BatchNorm statistics the walk uses
+        follows the module's mode (features_train_nhwc4)."""
+        from .gfv_net_sth import _FcMeanPool
+        feat = self.features_train_nhwc4(nchw_to_nhwc4(x_nchw))
+        return _FcMeanPool.apply(feat, self.fc.weight, self.fc.bias, None, feat.shape[0])
 
     @property
     def feature_dim(self):

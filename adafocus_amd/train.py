@@ -14,13 +14,18 @@ backward, PyTorch's Adam step).
 
 ``train_stage3_batch_sth`` is the stage-3 loop body of the Something-Something tree (STH/stage3.py:339-375 without AMP): the classifier
 Linear and the local CNN learn (HIP forward and backward, PyTorch's SGD step on .grad); glancer and policy stay frozen.
+
+``train_stage0_batch`` is the stage-0 loop body of the ActivityNet tree for the focuser's ResNet (ACT/main_dist.py:544-548,
+pretrain_glancer=False, the branch without AMP): the local CNN and its ``fc`` learn on whole frames with BatchNorm on batch statistics
+(HIP forward and backward).
 """
 import torch
 import torch.nn.functional as F
 
 from . import hip_ops
 
-__all__ = ["get_reward", "train_stage2_batch", "train_stage2_batch_fused", "train_stage2_batch_sth", "train_stage3_batch_sth"]
+__all__ = ["get_reward", "train_stage2_batch", "train_stage2_batch_fused", "train_stage2_batch_sth", "train_stage3_batch_sth",
+           "train_stage0_batch"]
 
 
 def get_reward(args, confidence, confidence_last, baseline):
@@ -126,6 +131,23 @@ def train_stage3_batch_sth(model, glancer_images, focuser_images, target, args, 
     with torch.no_grad():
         global_feat_map, global_feat_logit = model.glance(glancer_images)
     pred, _ = model.action_stage3(frames, global_feat_map, global_feat_logit, 0, args, prev_local_patch=None, dropout_mask=dropout_mask)
+    loss = F.cross_entropy(pred, target)
+    loss.backward()
+    optimizer.step()
+    return pred.detach(), loss.detach()
+
+
+def train_stage0_batch(model, images, target, args, optimizer):
+    """One batch of stage-0 training of the focuser's ResNet (ACT/main_dist.py:544-548; `model.backbone_train_mode()` first, optimizer
+    over model.focuser.net's parameters).  images (B, T*3, H, W) normalised fp32 on the GPU, target (B,) int64.  The frames go through the
+    local CNN in train mode as one batch of B*T (BatchNorm statistics over all of them), the logits are averaged over T, then
+    cross-entropy, backward, optimizer.step(); the gradients are zeroed first (main_dist.py:473).
+    Returns (the prediction (B, C), the loss)."""
+    b, tc, hh, ww = images.shape
+    t = tc // 3
+    optimizer.zero_grad()
+    logits = model.focuser.net.forward_train(images.view(b * t, 3, hh, ww))
+    pred = logits.view(b, t, -1).mean(1, keepdim=True).squeeze(1)
     loss = F.cross_entropy(pred, target)
     loss.backward()
     optimizer.step()

@@ -656,6 +656,17 @@ int adaf_ppo_encoder_backward_f32(adaf_handle* h, const float* states, const flo
  *   ReLU): dbeta_out = sum dy_m, dgamma_out = sum dy_m * xhat, dx_out = gamma * invstd / rows * (rows * dy_m - dbeta - xhat * dgamma),
  *   xhat = (x - mean) * invstd recomputed from the forward's x, mean_out, invstd_out.
  *   Workspace of both: adaf_bn_train_workspace_bytes(rows, cols).
+ * adaf_bn_map_train_forward_f32 / adaf_bn_map_train_backward_f32 (csrc/bn_map.hip): the same two operations for TALL
+ *   pixel-major maps -- a layer of the local CNN in train mode, 10^5 ... 10^7 rows of 64 ... 2048 columns -- as HBM-bound strip walks with
+ *   16-byte accesses: x, y, dy, dx and residual are dense [rows, cols] and 16-byte aligned, cols % 4 == 0 (else ADAF_E_LAYOUT), offsets
+ *   are 64-bit (rows * cols * 4 may exceed 2^32).  The forward reads x ONCE for both statistics: per column the sums of (x - k) and
+ *   (x - k)^2 with k = x[0, column], in double, as row-slice partials (the slice count is a function of cols alone) that are added in slice
+ *   order in two levels; mean_out = k + S1 / rows, biased variance = (S2 - S1^2 / rows) / rows, both rounded once.  Then
+ *   y_out = (x - mean) * invstd * gamma + beta [+ residual when it is not NULL], then ReLU when relu != 0.  running_mean / running_var as
+ *   adaf_bn_train_forward_f32 (either may be NULL).  The backward has adaf_bn_train_backward_f32's operands and formulas (y == NULL: dy
+ *   as it is; the residual join's second gradient is NOT an operand: add it first, adaf_relu_backward_f32).  rows == 1 and non-positive
+ *   extents are ADAF_E_BADARG.  No atomics: the same inputs give the same bits.
+ *   Workspace of both: adaf_bn_map_workspace_bytes(rows, cols) (0 for extents the calls refuse); contents undefined on entry and exit.
  * adaf_ppo_wenc_grad_f32 (above) also takes conv_out == 64 in its streaming form and e1 == NULL (de1 has its mask applied).
  * adaf_ppo_encoder_bn_backward_f32: adaf_ppo_encoder_backward_f32 for 32 or 64 conv outputs, with or without BatchNorm.  With it (all
  *   of c1 ... dbeta2 given): c1 [T*B*map_pixels, conv_out] and l1 [T*B, hidden] are the raw conv / Linear outputs, gamma / mean / invstd
@@ -675,6 +686,13 @@ int adaf_bn_train_forward_f32(adaf_handle* h, const float* x, int rows, int cols
 int adaf_bn_train_backward_f32(adaf_handle* h, const float* x, const float* y, const float* dy, int rows, int cols, const float* gamma,
                                const float* mean, const float* invstd, float* dx_out, float* dgamma_out, float* dbeta_out, void* ws,
                                size_t ws_bytes, void* stream);
+size_t adaf_bn_map_workspace_bytes(int rows, int cols);
+int adaf_bn_map_train_forward_f32(adaf_handle* h, const float* x, int rows, int cols, const float* gamma, const float* beta, float eps,
+                                  float momentum, float* running_mean, float* running_var, const float* residual, int relu, float* y_out,
+                                  float* mean_out, float* invstd_out, void* ws, size_t ws_bytes, void* stream);
+int adaf_bn_map_train_backward_f32(adaf_handle* h, const float* x, const float* y, const float* dy, int rows, int cols, const float* gamma,
+                                   const float* mean, const float* invstd, float* dx_out, float* dgamma_out, float* dbeta_out, void* ws,
+                                   size_t ws_bytes, void* stream);
 size_t adaf_ppo_encoder_bn_backward_workspace_bytes(int steps, int batch, int map_pixels, int channels, int conv_out, int hidden, int with_bn);
 int adaf_ppo_encoder_bn_backward_f32(adaf_handle* h, const float* states, const float* e1, const float* e_bt, const float* dx_bt, int steps,
                                      int batch, int map_pixels, int channels, int conv_out, int hidden, const float* w_lin_pm,
