@@ -85,6 +85,8 @@ PROTOTYPES = {
     "adaf_ppo_sample_f32": (ip, [vp, vp, ip, ip, ip, vp, vp, vp, vp, vp]),
     "adaf_ppo_sample_actions_f32": (ip, [vp, vp, ip, ip, ip, ip, vp, vp, vp, vp, vp, vp]),
     "adaf_ppo_rewards_f32": (ip, [vp, vp, vp, vp, ip, ip, ip, ip, vp, vp, vp, vp]),
+    "adaf_ce_steps_workspace_bytes": (sz, [ip, ip]),
+    "adaf_ce_steps_f32": (ip, [vp, vp, vp, ip, ip, ip, vp, vp, vp, sz, vp]),
     "adaf_ppo_returns_f32": (ip, [vp, vp, ip, ip, fp, vp, vp]),
     "adaf_ppo_head_workspace_bytes": (sz, [ip, ip]),
     "adaf_ppo_head_f32": (ip, [vp, vp, ip, ip, ip, ip, vp, vp, vp, fp] + [vp] * 9 + [sz, vp]),

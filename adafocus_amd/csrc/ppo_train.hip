@@ -5,6 +5,8 @@
 //                            log-probabilities in the memory's (T, B) order, crop coordinates table[action] in the trunk's (B, T) order
 //   ppo_rewards_kernel       confidence = softmax probability of the target class per (clip, step), one wave per clip, and the reward of
 //                            main_dist.py:574-581 from it; ppo_ce_last_kernel the mean cross-entropy of the last step
+//   ce_steps_*_kernel        stage 1's loss (main_dist.py:479): the cross-entropy of every step's logits against the clip's label, one wave
+//                            per row with its gradient in the same pass, then the mean over the B*T rows in row order
 //   ppo_returns_kernel       R_t = r_t + gamma R_{t+1}, then (R - mean) / (std + 1e-5) over all T*B entries (unbiased std), one block
 //   ppo_head_kernel<Dist>    per row of the stacked head output [actor columns | critic value]: log-probability of the stored action and
 //                            entropy under the row's distribution, value, the clipped-surrogate loss terms AND d loss.mean() / d head in
@@ -150,6 +152,46 @@ __global__ __launch_bounds__(256) void ppo_ce_last_kernel(const float* logits, c
         __syncthreads();
     }
     if (tid == 0) *out = (float)(sum / (double)B);
+}
+
+// ---- the per-step cross-entropy of stage 1 (ACT/main_dist.py:479: every step's logits against the clip's label) ------------------------
+// One wave per row r = b * T + t, four rows per block: the row's loss log(sum exp(l - max)) - (l[target[b]] - max) into row_loss[r] and,
+// when asked for, d mean-loss / d logits = (exp(l - max) / sum - [c == target]) / rows.  A target outside [0, C) reads nothing out of
+// range: the row's loss and its gradient row are NaN
+__global__ __launch_bounds__(256) void ce_steps_rows_kernel(const float* logits, const long long* target, long long rows, int T, int C,
+                                                            float* row_loss, float* dlogits) {
+    const int lane = threadIdx.x & 63;
+    const long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= rows) return;
+    const long long tg = target[r / T];
+    const bool ok = tg >= 0 && tg < C;
+    const float* l = logits + (size_t)r * C;
+    float mx, total;
+    wave_softmax_stats(l, C, lane, &mx, &total);
+    if (lane == 0) row_loss[r] = ok ? logf(total) - (l[tg] - mx) : NAN;
+    if (dlogits) {
+        float* d = dlogits + (size_t)r * C;
+        const float n = (float)rows;
+        for (int c = lane; c < C; c += 64) d[c] = ok ? (expf(l[c] - mx) / total - (c == tg ? 1.f : 0.f)) / n : NAN;
+    }
+}
+
+// The mean of the per-row losses, added in row order in double (ppo_ce_last_kernel's comment has the measured reason) by one block: up to
+// 256 rows thread 0 adds them all; beyond that thread i first adds its run of ceil(rows / 256) consecutive rows, then thread 0 adds the
+// 256 partials in thread order -- two levels, each in row order
+__global__ __launch_bounds__(256) void ce_steps_mean_kernel(const float* row_loss, long long rows, float* loss) {
+    __shared__ double part[256];
+    const int tid = threadIdx.x;
+    const long long per = (rows + 255) / 256, r0 = tid * per, r1 = min(rows, r0 + per);
+    double s = 0.0;
+    for (long long r = r0; r < r1; ++r) s += (double)row_loss[r];
+    part[tid] = s;
+    __syncthreads();
+    if (tid == 0) {
+        double sum = 0.0;
+        for (int i = 0; i < 256; ++i) sum += part[i];
+        *loss = (float)(sum / (double)rows);
+    }
 }
 
 // ---- returns ----------------------------------------------------------------------------------------------------------------------------
@@ -541,6 +583,11 @@ size_t ppo_head_layout(void* ws, int steps, int batch, float** terms) {
     *terms = c.take<float>(2 * (size_t)steps * batch);      // the two per-row loss terms
     return c.off;
 }
+size_t ce_steps_layout(void* ws, int batch, int steps, float** row_loss) {
+    AdafCarver c(ws);
+    *row_loss = c.take<float>((size_t)batch * steps);       // the per-row losses
+    return c.off;
+}
 size_t wenc_layout(void* ws, int npix, int cin, int cmid, float** buf) {      // either form of adaf_ppo_wenc_grad_f32: the partials, or the masked gradient
     const size_t sk = wenc_sk_floats(npix, cin, cmid), chain = (size_t)npix * cmid;
     AdafCarver c(ws);
@@ -724,6 +771,29 @@ int adaf_ppo_rewards_f32(adaf_handle* h, const float* logits, const float* base_
     if (ce_last_out) hipLaunchKernelGGL(ppo_ce_last_kernel, dim3(1), dim3(256), 0, st, logits, tg, steps, batch, classes, ce_last_out);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? ADAF_OK : adaf_hip_fail(h, e, "ppo_rewards launch");
+}
+
+size_t adaf_ce_steps_workspace_bytes(int batch, int steps) {
+    float* row_loss;
+    return (batch <= 0 || steps <= 0) ? 0 : ce_steps_layout(nullptr, batch, steps, &row_loss);
+}
+
+int adaf_ce_steps_f32(adaf_handle* h, const float* logits, const int64_t* target, int batch, int steps, int classes, float* loss_out,
+                      float* dlogits_out, void* ws, size_t ws_bytes, void* stream) {
+    if (!h) return ADAF_E_BADARG;
+    if (!logits || !target || !loss_out || !ws) return adaf_fail(h, ADAF_E_BADARG, "ce_steps: null pointer");
+    if (batch <= 0 || steps <= 0 || classes <= 0) return adaf_fail(h, ADAF_E_BADARG, "ce_steps: non-positive extent");
+    const long long rows = (long long)batch * steps;
+    if ((rows + 3) / 4 > 0x7fffffffLL) return adaf_fail(h, ADAF_E_BADARG, "ce_steps: more than 2^33 rows");
+    float* row_loss;
+    int rc = adaf_check_ws(h, "ce_steps", ws, ws_bytes, ce_steps_layout(ws, batch, steps, &row_loss), ADAF_WS_ALIGN_FIRST);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(ce_steps_rows_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, logits, reinterpret_cast<const long long*>(target),
+                       rows, steps, classes, row_loss, dlogits_out);
+    hipLaunchKernelGGL(ce_steps_mean_kernel, dim3(1), dim3(256), 0, st, row_loss, rows, loss_out);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? ADAF_OK : adaf_hip_fail(h, e, "ce_steps launch");
 }
 
 int adaf_ppo_returns_f32(adaf_handle* h, const float* rewards, int steps, int batch, float gamma, float* returns_out, void* stream) {

@@ -20,8 +20,10 @@ train_stage 3: only ``classifier.*`` learns) runs the frozen part on the same HI
 ``one_step_act(training=True)`` and the PPO update through ``Focuser.update()`` with a HIP backward (csrc/ppo_train.hip; the loop body is
 ``adafocus_amd.train.train_stage2_batch``; ``rollout_act`` is the T steps as one batched pass, the body of ``train_stage2_batch_fused``).
 Stage-0 training of the focuser's ResNet (``backbone_train_mode()``: the local CNN with its ``fc`` learns on whole frames, BatchNorm on
-batch statistics; csrc/bn_map.hip; the loop body is ``adafocus_amd.train.train_stage0_batch``).  What remains out of scope and
-raises: stage 0 for the glancer, stage 1, AMP.  ``GFV.one_step_act(training=False)`` -- the body of the
+batch statistics; csrc/bn_map.hip; the loop body is ``adafocus_amd.train.train_stage0_batch``).
+Stage-1 training (``stage1_train_mode()``: the local CNN on one random crop per frame and the GRU classifier learn, the glancer stays
+frozen; the stage-1 form of ``forward`` in that state; the loop body is ``adafocus_amd.train.train_stage1_batch``).  What
+remains out of scope and raises: stage 0 for the glancer, stage 1 with the ``fc`` consensus, AMP.  ``GFV.one_step_act(training=False)`` -- the body of the
 stage-2 VALIDATION loop (ACT/main_dist.py:346-362), reward baseline included -- keeps the reference's
 per-step structure on the same HIP ops (round 6, pinned by G15).
 """
@@ -98,11 +100,15 @@ class GFV(nn.Module):
             x2 = x.view(b * (tc // 3), 3, hh, ww)
             net = self.glancer if kwargs.get("glancer") else self.focuser
             return net.predict(x2).view(b, tc // 3, -1)
+        if not kwargs.get("one_step") and self._in_stage1_train_state():
+            # (`training` is accepted and ignored here, as the random focuser ignores it: gfv_net.py:146, 317-327)
+            return self._stage1_train_forward(kwargs["input"], kwargs["scan"], kwargs.get("crop_actions"), kwargs.get("dropout_mask"))
         if kwargs.get("training"):
             raise NotImplementedError("only training=False (offline inference / validation) is implemented")
         if not kwargs.get("one_step"):
             if self.training:
-                raise NotImplementedError("the stage-1 form in train mode is stage-1 training: out of scope (stage 3 is one_step=True)")
+                raise NotImplementedError("the stage-1 form in train mode is stage-1 training: call stage1_train_mode() first (a plain "
+                                          ".train() is not its state; stage 3 is one_step=True)")
             # the stage-1 form (gfv_net.py:135-150) in eval mode, as validate() runs it at train_stage 1 (ACT/main_dist.py:334-340): glancer and
             # focuser over all B*T frames at once -- random crops when the model was built with random_patch (the stage-1 configuration),
             # else ONE policy step over the B*T frames as a batch, exactly as the reference's call does -- then the classifier
@@ -363,12 +369,13 @@ class GFV(nn.Module):
     def train_mode(self, args):
         """gfv_net.py:62-81 for train_stage == 3 (call after model.train(), as ACT/main_dist.py does): the glancer, the focuser and
         both policies go to eval mode; only the classifier trains (dropout on, HIP backward).  Every other stage raises here: stage 2 (the
-        policy's training) is entered through `policy_train_mode()`, stage 0 for the focuser's ResNet through `backbone_train_mode()`;
-        stage 0 for the glancer and stage 1 are out of scope."""
+        policy's training) is entered through `policy_train_mode()`, stage 0 for the focuser's ResNet through `backbone_train_mode()`,
+        stage 1 through `stage1_train_mode()`; stage 0 for the glancer is out of scope."""
         if args.train_stage != 3:
             raise NotImplementedError("train_mode: train_stage %r is not entered here (stage 3, classifier training, is; stage 2, policy "
                                       "training, is entered with policy_train_mode(); stage 0 for the focuser's ResNet with "
-                                      "backbone_train_mode(); stage 0 for the glancer and stage 1 are out of scope)" % (args.train_stage,))
+                                      "backbone_train_mode(); stage 1 with stage1_train_mode(); stage 0 for the glancer is out of scope)"
+                                      % (args.train_stage,))
         self.train()
         self.glancer.eval()
         self.focuser.eval()
@@ -385,6 +392,53 @@ class GFV(nn.Module):
         self.focuser.eval()
         self.focuser.policy.policy.train()
         self.focuser.policy.policy_old.train()
+
+    def stage1_train_mode(self):
+        """What the reference's train_mode does for train_stage == 1 (gfv_net.py:67-69): the model goes to train mode and the glancer to
+        eval mode; the focuser's ResNet becomes trainable with BatchNorm on batch statistics, as in `backbone_train_mode()`.  In this
+        state `forward(input=, scan=, backbone_pred=False, one_step=False)` is stage-1 training (gfv_net.py:135-150); the loop body is
+        `adafocus_amd.train.train_stage1_batch`.  Random-patch models with the GRU consensus and the fp32 ResNet local CNN only."""
+        net = self.focuser.net
+        if not self.focuser.random:
+            raise NotImplementedError("stage1_train_mode: stage 1 trains on random patches; this model is policy-driven "
+                                      "(random_patch=False: its training is stage 2 / 3)")
+        if not isinstance(self.classifier, RecurrentClassifier):
+            raise NotImplementedError("stage1_train_mode: consensus='fc' is out of scope (the reference's stage-1 loss, "
+                                      "ACT/main_dist.py:491, cannot take its output); the GRU consensus only")
+        if not hasattr(net, "set_bn_batch_stats"):
+            raise NotImplementedError("stage1_train_mode: stage 1 trains a ResNet local CNN only (%s has no backward)" % type(net).__name__)
+        if net.math != "f32":
+            raise NotImplementedError("stage1_train_mode: training the local CNN runs in fp32 only (local_math=%r has no backward)" % (net.math,))
+        self.train()
+        self.glancer.eval()
+        net.set_trainable(True)
+        net.set_bn_batch_stats(True)
+
+    def _in_stage1_train_state(self):
+        """The state `stage1_train_mode()` leaves: everything in train mode but the glancer, a random focuser whose ResNet walks on batch
+        statistics, the GRU classifier.  A plain .train() (glancer in train mode) is not it."""
+        net = self.focuser.net
+        return bool(self.training and not self.glancer.training and self.focuser.random and self.focuser.training and net.training
+                    and getattr(net, "trainable", False) and getattr(net, "bn_batch_stats", False) and self.classifier.training
+                    and isinstance(self.classifier, RecurrentClassifier))
+
+    def _stage1_train_forward(self, images, scan, crop_actions=None, dropout_mask=None):
+        """gfv_net.py:135-150 in train mode: the frozen glancer over the B*T scan frames without grad, one random crop per frame (origins
+        from PatchSampler.random_actions in the reference's draw order unless crop_actions (B*T, 2) gives the gather's actions), the
+        batch-statistics walk of the local CNN over all B*T patches as one batch, [global, local], the classifier in train mode
+        (dropout_mask (B, T, hidden): its multipliers; None: drawn).  -> (logits (B*T, C), last (B, C)) with a graph into the local CNN and
+        the classifier."""
+        b, tc, hh, ww = images.shape
+        t = tc // 3
+        frames = images.reshape(b * t, 3, hh, ww)
+        with torch.no_grad():
+            fvec = self.glancer(scan.reshape(b * t, 3, scan.shape[2], scan.shape[3]))[1] if self.with_glancer else None
+            if crop_actions is None:
+                crop_actions = self.focuser.patch_sampler.random_actions(frames)
+            patches = get_patch_nhwc4(frames, crop_actions, self.patch_size)
+        local = self.focuser.net.features_train_nhwc4(patches)
+        feature = torch.cat([fvec, local], dim=1) if self.with_glancer else local
+        return self.classifier(feature.view(b, t, -1), mask=dropout_mask)
 
     def backbone_train_mode(self, glancer=False):
         """What the reference's train_mode does for train_stage == 0 (gfv_net.py:65-66), for the backbone stage 0 trains with

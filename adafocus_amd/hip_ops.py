@@ -314,6 +314,40 @@ def ppo_rewards(logits, base_logits, target, steps, kind, want_conf=False, want_
     return out if len(out) > 1 else rewards
 
 
+def ce_steps(logits, target, steps, want_grad=True):
+    """The stage-1 loss (ACT/main_dist.py:479): logits (B*T, C) with rows b*T+t, target (B,) int64 -> (the mean over all B*T rows of the
+    cross-entropy of row b*T+t against class target[b] (1,), its gradient d loss / d logits (B*T, C) or None without want_grad).
+    `target.view(B, 1).expand(B, T).reshape(-1)` is never materialised.  Deterministic (same inputs, same bits)."""
+    L.need_gpu_f32(logits)
+    if target.dtype != torch.int64 or not target.is_cuda:
+        raise ValueError("ce_steps: int64 GPU target (B,) expected")
+    logits, target = logits.contiguous(), target.contiguous()
+    t, b = int(steps), target.numel()
+    if logits.dim() != 2 or t <= 0 or logits.shape[0] != t * b:
+        raise ValueError("ce_steps: logits (B*T, C) expected")
+    ws, ws_bytes = _workspace("adaf_ce_steps_workspace_bytes", logits.device, b, t)
+    loss = torch.empty((1,), device=logits.device, dtype=torch.float32)
+    dlogits = torch.empty_like(logits) if want_grad else None
+    _call("adaf_ce_steps_f32", logits, logits, target, b, t, logits.shape[1], loss, dlogits, ws, ws_bytes)
+    return loss, dlogits
+
+
+class CeStepsFn(torch.autograd.Function):
+    """apply(logits (B*T, C), target (B,), steps) -> the loss (1,) of `ce_steps`.  The forward keeps dlogits; the backward is
+    grad_out * dlogits."""
+
+    @staticmethod
+    def forward(ctx, logits, target, steps):
+        loss, dlogits = ce_steps(logits.detach(), target, steps)
+        ctx.save_for_backward(dlogits)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        dlogits, = ctx.saved_tensors
+        return grad_out * dlogits, None, None
+
+
 def ppo_returns(rewards, gamma):
     """rewards (T, B) -> discounted returns, normalised over all T*B entries (ACT/models/ppo.py:148-157)."""
     L.need_gpu_f32(rewards)

@@ -18,6 +18,10 @@ Linear and the local CNN learn (HIP forward and backward, PyTorch's SGD step on 
 ``train_stage0_batch`` is the stage-0 loop body of the ActivityNet tree for the focuser's ResNet (ACT/main_dist.py:544-548,
 pretrain_glancer=False, the branch without AMP): the local CNN and its ``fc`` learn on whole frames with BatchNorm on batch statistics
 (HIP forward and backward).
+
+``train_stage1_batch`` is the stage-1 loop body of the ActivityNet tree (ACT/main_dist.py:473-493 without AMP): the frozen glancer, one
+random crop per frame through the local CNN on batch statistics, the GRU classifier, and the cross-entropy of every step
+(``hip_ops.ce_steps``); the local CNN and the classifier learn.
 """
 import torch
 import torch.nn.functional as F
@@ -25,7 +29,7 @@ import torch.nn.functional as F
 from . import hip_ops
 
 __all__ = ["get_reward", "train_stage2_batch", "train_stage2_batch_fused", "train_stage2_batch_sth", "train_stage3_batch_sth",
-           "train_stage0_batch"]
+           "train_stage0_batch", "train_stage1_batch"]
 
 
 def get_reward(args, confidence, confidence_last, baseline):
@@ -152,3 +156,26 @@ def train_stage0_batch(model, images, target, args, optimizer):
     loss.backward()
     optimizer.step()
     return pred.detach(), loss.detach()
+
+
+def train_stage1_batch(model, images, target, args, optimizer, crop_actions=None, dropout_mask=None):
+    """One batch of stage-1 training (ACT/main_dist.py:473-493; `model.stage1_train_mode()` first, optimizer = main_dist.py:172-177's SGD
+    over model.focuser.parameters() and model.classifier.parameters(); focuser.net.fc takes no part and gets no gradient).  images
+    (B, T*3, H, W) normalised fp32 on the GPU, target (B,) int64.  zero_grad, `model.glancer_input`, the stage-1 form of the forward in
+    train mode (frozen glancer, one random crop per frame, the local CNN over the B*T patches as one batch on batch statistics, the GRU
+    classifier with dropout), the mean cross-entropy of all B*T steps against the clip's label (`hip_ops.ce_steps`: main_dist.py:479's
+    expanded target, not materialised), backward, optimizer.step().
+    The call form: the reference's non-AMP call (main_dist.py:486) omits `training=` while gfv_net.py:146 reads kwargs["training"], so
+    that branch cannot run as written; mirrored is the AMP branch's call (:477, training=True) with the loss of :479, without autocast
+    and the scaler.
+    crop_actions (B*T, 2) / dropout_mask (B, T, hidden) steer the crops (the gather's actions) and the dropout's multipliers (None: drawn
+    as the reference draws them / from torch's device generator).  Returns (the last step's prediction (B, C), the loss), detached."""
+    t = images.shape[1] // 3
+    optimizer.zero_grad()
+    input_prime = model.glancer_input(images)
+    output, pred = model(input=images, scan=input_prime, backbone_pred=False, one_step=False, training=True, crop_actions=crop_actions,
+                         dropout_mask=dropout_mask)
+    loss = hip_ops.CeStepsFn.apply(output, target, t)
+    loss.backward()
+    optimizer.step()
+    return pred.detach(), loss.detach()[0]

@@ -590,6 +590,15 @@ int adaf_gru_cls_backward_f32(adaf_handle* h, const float* x, int ldx, int batch
  *   conf_t.  conf_out [T, B] (may be NULL): the confidences.  ce_last_out [1] (may be NULL): the mean over clips of the cross-entropy of
  *   step T - 1, log(sum) - (l[target] - max) per clip, added over clips in index order.  A target outside [0, C) reads nothing out of
  *   range: that clip's rewards and confidences are NaN (and so is ce_last_out); other clips are untouched.  No workspace.
+ * adaf_ce_steps_f32: the stage-1 loss (ACT/main_dist.py:479), the cross-entropy of every step against its clip's label, with its
+ *   gradient.  logits [batch*steps, classes] contiguous with rows b * steps + t (the order adaf_gru_cls_train_forward_f32 writes), target
+ *   [batch] int64: row r has class target[r / steps] (the expanded target is never materialised).  loss_out [1]: the mean over all rows of
+ *   log(sum exp(l - max)) - (l[target] - max); dlogits_out [batch*steps, classes] (may be NULL: loss only):
+ *   (exp(l - max) / sum - [c == target]) / rows.  One wave per row, max and sum as adaf_ppo_rewards_f32 takes them (one device function);
+ *   the per-row losses go to the workspace and a second launch adds them in row order in double -- beyond 256 rows in two levels: 256
+ *   runs of ceil(rows / 256) consecutive rows, then the runs in order.  No atomics: the same inputs give the same bits.  A target outside
+ *   [0, classes) reads nothing out of range: the loss is NaN and that clip's `steps` rows of dlogits_out are NaN; every other row is
+ *   untouched.  Workspace: adaf_ce_steps_workspace_bytes(batch, steps) = batch * steps * 4 bytes.
  * adaf_ppo_returns_f32: rewards [T, B] -> R_t = r_t + gamma R_{t+1}, then (R - mean) / (std + 1e-5) over all T*B entries with the
  *   unbiased standard deviation (ppo.py:148-157), sums in a fixed order.  returns_out [T, B].
  * adaf_ppo_head_f32: per row of the stacked head output head [T*B, A + 1] (row b * T + t when head_batch_major, else t * B + b; columns
@@ -620,6 +629,9 @@ int adaf_ppo_sample_actions_f32(adaf_handle* h, const float* logits, int ld, int
                                 const float* table_yx, int64_t* action_out, float* logprob_out, float* coords_out, void* stream);
 int adaf_ppo_rewards_f32(adaf_handle* h, const float* logits, const float* base_logits, const int64_t* target, int steps, int batch,
                          int classes, int kind, float* rewards_out, float* conf_out, float* ce_last_out, void* stream);
+size_t adaf_ce_steps_workspace_bytes(int batch, int steps);
+int adaf_ce_steps_f32(adaf_handle* h, const float* logits, const int64_t* target, int batch, int steps, int classes, float* loss_out,
+                      float* dlogits_out, void* ws, size_t ws_bytes, void* stream);
 int adaf_ppo_returns_f32(adaf_handle* h, const float* rewards, int steps, int batch, float gamma, float* returns_out, void* stream);
 size_t adaf_ppo_head_workspace_bytes(int steps, int batch);
 int adaf_ppo_head_f32(adaf_handle* h, const float* head, int head_batch_major, int steps, int batch, int n_actions, const int64_t* actions,
