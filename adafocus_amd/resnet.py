@@ -152,8 +152,8 @@ class ResNet(nn.Module):
     def set_bn_batch_stats(self, on):
         """Opt-in (default off) to BatchNorm on BATCH statistics in the training walk: with set_trainable(True) and the module in train
         mode, ``features_train_nhwc4`` normalises every layer with the statistics of its batch and moves the running statistics, as
-        the torch module in train mode does (stage 0 of the ActivityNet tree, ACT/main_dist.py:534-548).  In eval mode the
-        walk is the frozen one either way.  Off: train mode raises, as before."""
+        the torch module in train mode does (stage 0 of the ActivityNet tree, ACT/main_dist.py:534-548): the one walk of
+        trunk_train.walk_forward in its batch-statistics form.  In eval mode the walk runs in the frozen form either way.  Off: train mode raises, as before."""
         self._bn_batch_stats = bool(on)
 
     @property
@@ -168,7 +168,8 @@ class ResNet(nn.Module):
         """features_nhwc4 with an autograd graph into the trunk's parameters: BatchNorm on its running statistics (the module is in eval
         mode, as STH/stage3.py:313-317 puts the focuser), the same bits as the eval engine's features.  After optimizer.step() the
         parameter versions change and the next features_nhwc4 re-packs the engine's weights (_sync).  In train mode with
-        set_bn_batch_stats(True): BatchNorm on the statistics of the batch (trunk_train.walk_forward_batch)."""
+        set_bn_batch_stats(True): BatchNorm on the statistics of the batch (the same walk, trunk_train.walk_forward, in its
+        batch-statistics form, trunk_train.BatchForm)."""
         if not self.trainable:
             raise RuntimeError("adafocus_amd.ResNet: the training walk is off; call set_trainable(True) first")
         if self.training and not self.bn_batch_stats:

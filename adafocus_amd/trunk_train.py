@@ -1,38 +1,42 @@
-"""Stage-3 training of the Something-Something local CNN: the differentiable walk of the ResNet trunk.
+"""Training of the ResNet local CNN: the differentiable walk of the trunk, stated once, and the two treatments of a conv + BatchNorm layer
+that run through it.  ``trunk_features`` is the network of ``adaf_resnet50_forward``, one launch per layer, with a HIP
+backward (csrc/conv_bwd.hip, csrc/bn_map.hip).
 
-STH/stage3.py:189-193 hands ``focuser.net.get_optim_policies()`` to the optimizer and :313-317 keeps the focuser in eval mode, so the
-shipped recipe fine-tunes every convolution and every BatchNorm affine parameter of the TSM-ResNet with FROZEN BatchNorm statistics.
-``trunk_features`` is that network, one launch per layer, with a HIP backward (csrc/conv_bwd.hip):
+THE WALK
+  forward   the stem, the max-pool, the Bottlenecks (conv1, conv2, the downsample branch, conv3 with the residual join) and the pool, with
+            the temporal shift where ``ResNet.shifted_blocks`` puts it: 'blockres' fused into conv1, 'block' in front of the whole block.
+            Every layer output is kept; the ReLU mask of the backward is ``y > 0`` of the stored output.
+  backward  the reverse walk: per layer the gradient goes through the layer's form, which hands back the gradient at the convolution's
+            output and the parameter gradients the layer wants; the data gradient runs on the forward engine with the filter transposed and
+            rotated (``hip_ops.conv2d_dgrad``).  Launches are skipped for parameters that do not require grad, and the data-gradient chain
+            stops at the earliest layer that has a trainable parameter.
 
-  forward   the stem on the trunk's stem kernel, the max-pool, the Bottlenecks through ``hip_ops.conv2d_bn_act`` and the pool, with the
-            folded BN affine, the residual and the temporal shift where ``ResNet.shifted_blocks`` puts it ('block': in front of the whole block) -- the fma chains of the
-            engine do not depend on the launch form, so the features are the eval engine's, bit for bit.  Every layer
-            output is kept; the ReLU mask of the backward is ``y > 0`` of the stored output.
-  backward  the reverse walk: per convolution the split-K weight gradient (unscaled), from it dW = s * G, dbeta and dgamma without a
-            pre-BN map (``hip_ops.conv_bn_param_grad``), and the data gradient on the forward engine with the filter transposed,
-            rotated and scaled.  Launches are skipped for parameters that do not require grad, and the data-gradient chain stops at the
-            earliest layer that has a trainable parameter.  BatchNorm running statistics are never touched.
+A LAYER FORM answers what differs between the treatments and nothing else: what is packed per layer, a layer's forward, the gradient
+through a layer, whether that needs the convolution's input, the filter of the data gradient, and what happens after the forward.  A new
+treatment of a layer is a new form, not a new walk.
 
-THE BATCH-STATISTICS FORM (stage 0 of the ActivityNet tree, ACT/main_dist.py:534-548, where the focuser's ResNet is in
-train mode): ``ResNet.set_bn_batch_stats(True)`` and the module in train mode select ``walk_forward_batch`` / ``TrunkBatchFn``.
+  FrozenForm  BatchNorm on its running statistics (stage 3 of the Something-Something tree: STH/stage3.py:189-193 hands
+              ``get_optim_policies()`` to the optimizer and :313-317 keeps the focuser in eval mode).  Forward: one ``conv2d_bn_act`` with the
+              folded affine, the activation, the residual and the fused shift, the stem on the trunk's stem kernel -- the fma chains of the
+              engine do not depend on the launch form, so the features are the eval engine's, bit for bit.  Backward: the ReLU
+              mask, the split-K weight gradient (unscaled), from it dW = s * G, dbeta and dgamma without a pre-BN map
+              (``hip_ops.conv_bn_param_grad``); the data gradient's filter is scaled.  Running statistics are never touched.
+  BatchForm   BatchNorm on the statistics of the batch (stage 0 and 1 of the ActivityNet tree, ACT/main_dist.py:534-548, where the
+              focuser's ResNet is in train mode; ``ResNet.set_bn_batch_stats(True)`` and the module in train mode select it).  Forward: the
+              convolution with the identity affine (the raw map), then ``hip_ops.bn_map_train_forward`` with the ReLU and, for conv3, the
+              residual; the stem runs on the generic engine too (its own kernel has the folded affine and the ReLU built in and hands out
+              no raw map).  Kept per layer: the raw map, mean and invstd -- twice the activation memory of the frozen form.  Running
+              statistics move once per forward; num_batches_tracked += 1.  Backward: ``hip_ops.bn_map_train_backward`` with the ReLU mask
+              inside gives the gradient at the convolution's output, dgamma and dbeta; ``conv2d_wgrad`` of that gradient IS dW, and the data
+              gradient's filter is packed with scale 1.
 
-  forward   per layer the convolution on the engine with the identity affine (no scale, no bias, no activation: the raw map), then
-            ``hip_ops.bn_map_train_forward`` with the ReLU and, for conv3, the residual; the stem runs on the generic engine too (its own
-            kernel has the folded affine and the ReLU built in and hands out no raw map).  The max-pool, the shift in both placements
-            and the pool are the frozen walk's.  Kept per layer: the raw map, the output after ReLU, mean and invstd -- twice the
-            activation memory of the frozen walk.  Running statistics move once per forward; num_batches_tracked += 1.
-  backward  the masked gradient goes through ``hip_ops.bn_map_train_backward`` (the ReLU mask of conv1 / conv2 / the stem inside it; the
-            residual join's two gradients are added by ``relu_backward`` first), which gives the gradient at the convolution's output,
-            dgamma and dbeta; ``conv2d_wgrad`` of that gradient IS dW, and ``conv2d_dgrad`` takes the filter packed with scale 1.  The
-            skipping rules are the frozen walk's.
-
-Math is fp32 only; generic over ``resnet.DEPTHS``.  Orchestration in Python over ``hip_ops`` and one ``torch.autograd.Function`` per form,
-as ``policy_train.py``."""
+Math is fp32 only; generic over ``resnet.DEPTHS``.  Orchestration in Python over ``hip_ops`` and one ``torch.autograd.Function``, as
+``policy_train.py``."""
 import torch
 
 from . import hip_ops
 
-__all__ = ["trunk_features", "TrunkFn", "TrunkBatchFn", "trunk_layers", "walk_forward", "walk_forward_batch"]
+__all__ = ["trunk_features", "TrunkFn", "trunk_layers", "walk_forward", "FrozenForm", "BatchForm"]
 
 BN_EPS = 1e-5      # the eps the engine folds with (csrc/resnet_trunk.hip)
 
@@ -68,27 +72,121 @@ def _flat(stem, blocks):
     return out
 
 
-class _Packed:
-    """The engine-layout operands of one layer, packed from the parameters as they are now."""
+# ---- the two layer forms --------------------------------------------------------------------------------------------------------------------
+class FrozenForm:
+    """conv + BatchNorm on its running statistics, folded into one launch.  pk: per layer (OHWI filter, folded scale, folded bias)."""
 
-    def __init__(self, layer):
+    def __init__(self):
+        self.pk = {}
+
+    def pack(self, layer):
         bn = layer.bn
-        self.w = hip_ops.pack_conv_weight(layer.conv.weight.detach())
-        self.scale, self.bias = hip_ops.fold_bn(bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var, BN_EPS)
+        self.pk[id(layer)] = (hip_ops.pack_conv_weight(layer.conv.weight.detach()),) + hip_ops.fold_bn(
+            bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var, BN_EPS)
+
+    def stem(self, layer, x4):
+        # (the stem on the trunk's own kernel: the generic engine adds its 147 products in another order)
+        _, scale, bias = self.pk[id(layer)]
+        return hip_ops.stem7x7_bn_relu(x4, layer.conv.weight.detach(), scale, bias)
+
+    def forward(self, layer, x, relu, residual=None, tsm=0, div=8):
+        w, scale, bias = self.pk[id(layer)]
+        return hip_ops.conv2d_bn_act(x, w, scale, bias, residual, layer.stride, layer.pad, hip_ops.ACT_RELU if relu else hip_ops.ACT_NONE,
+                                     tsm_segments=tsm, tsm_div=div)
+
+    def after_forward(self, net):
+        pass
+
+    def wants_input(self, need):
+        return any(need)            # dgamma and dbeta come from the weight gradient too
+
+    def relu_mask(self, g, y):
+        return hip_ops.relu_backward(g, y)
+
+    def backward(self, layer, g, x, y, need):
+        if not any(need):
+            return g, None
+        (w, scale, _), bn = self.pk[id(layer)], layer.bn
+        raw = hip_ops.conv2d_wgrad(x, g, tuple(w.shape), layer.stride, layer.pad)
+        return g, hip_ops.conv_bn_param_grad(g, raw, w, scale, bn.running_mean, bn.running_var, BN_EPS, layer.conv.weight.shape[1],
+                                             want_dw=need[0], want_affine=need[1] or need[2])
+
+    def dgrad_weight(self, layer):
+        w, scale, _ = self.pk[id(layer)]
+        return hip_ops.pack_conv_dgrad_weight(w, scale)
 
 
-def _conv(layer, pk, x, act, residual=None, tsm=0, div=8):
-    return hip_ops.conv2d_bn_act(x, pk.w, pk.scale, pk.bias, residual, layer.stride, layer.pad, act, tsm_segments=tsm, tsm_div=div)
+def _check_bn(bn):
+    if bn.momentum is None or not bn.track_running_stats or not bn.affine:
+        raise NotImplementedError("BatchNorm with momentum=None, without running statistics or without affine parameters")
 
 
-def walk_forward(net, x4):
-    """The training walk's forward: -> (features (N, 2048), the packed operands per layer, the stem's output, per block (block input as
-    the identity sees it, conv1's output, conv2's output, block output) -- all after ReLU --, the walk's description)."""
+class BatchForm:
+    """The raw convolution, then BatchNorm on the statistics of its map, as the module in train mode.  w: per layer the OHWI filter; kept:
+    per layer what the backward needs, (the raw conv map, mean, invstd)."""
+
+    def __init__(self):
+        self.w, self.kept = {}, {}
+
+    def pack(self, layer):
+        _check_bn(layer.bn)
+        self.w[id(layer)] = hip_ops.pack_conv_weight(layer.conv.weight.detach())
+
+    def stem(self, layer, x4):
+        # (the stem on the generic engine: the trunk's stem kernel folds the affine and the ReLU in and has no raw form)
+        return self.forward(layer, x4, True)
+
+    def forward(self, layer, x, relu, residual=None, tsm=0, div=8):
+        bn = layer.bn
+        raw = hip_ops.conv2d_bn_act(x, self.w[id(layer)], None, None, None, layer.stride, layer.pad, hip_ops.ACT_NONE, tsm_segments=tsm, tsm_div=div)
+        y, mean, invstd = hip_ops.bn_map_train_forward(raw, bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var, bn.eps,
+                                                       bn.momentum, residual=residual, relu=relu)
+        bn.num_batches_tracked += 1
+        self.kept[id(layer)] = (raw, mean, invstd)
+        return y
+
+    def after_forward(self, net):
+        net._note_stats_written()
+
+    def wants_input(self, need):
+        return need[0]
+
+    def relu_mask(self, g, y):
+        return g                             # (bn_map_train_backward applies it)
+
+    def backward(self, layer, g, x, y, need):
+        raw, mean, invstd = self.kept[id(layer)]
+        gc, dgamma, dbeta = hip_ops.bn_map_train_backward(raw, y, g, layer.bn.weight.detach(), mean, invstd)
+        dw = None
+        if need[0]:                          # the weight gradient of the raw convolution is dW itself
+            cin = layer.conv.weight.shape[1]
+            dw = hip_ops.conv2d_wgrad(x, gc, tuple(self.w[id(layer)].shape), layer.stride, layer.pad)[..., :cin].permute(0, 3, 1, 2).contiguous()
+        return gc, (dw, dgamma, dbeta)
+
+    def dgrad_weight(self, layer):
+        return hip_ops.pack_conv_dgrad_weight(self.w[id(layer)])
+
+
+# ---- the walk -------------------------------------------------------------------------------------------------------------------------------
+class Walk:
+    """What the forward leaves for the backward (and for the tests that read the device's ReLU branches): feat (N, 2048); stem_out; acts,
+    per block (block input as the identity sees it, conv1's output, conv2's output, block output) -- all after ReLU; stem and blocks of
+    trunk_layers; the shift (tsm segments, div, place); form, with its per-layer state."""
+
+    def __init__(self, **fields):
+        self.__dict__.update(fields)
+
+
+def walk_forward(net, x4, form=None):
+    """The training walk's forward -> Walk.  form: FrozenForm() or BatchForm(); None: as the net's mode says.  The batch-statistics form
+    moves every running statistic once."""
+    if form is None:
+        form = BatchForm() if (net.training and net.bn_batch_stats) else FrozenForm()
     stem, blocks = trunk_layers(net)
     tsm, div, place = int(net.tsm_segments), int(net.tsm_div), net.tsm_place
-    pk = {id(l): _Packed(l) for l in _flat(stem, blocks)}
-    # (the stem on the trunk's own kernel: the generic engine adds its 147 products in another order)
-    s = hip_ops.stem7x7_bn_relu(x4, stem.conv.weight.detach(), pk[id(stem)].scale, pk[id(stem)].bias)
+    for layer in _flat(stem, blocks):
+        form.pack(layer)
+    s = form.stem(stem, x4)
     y = hip_ops.maxpool3x3s2(s)
     acts = []
     for c1, c2, c3, ds, shifted in blocks:
@@ -96,28 +194,31 @@ def walk_forward(net, x4):
         if tsm and place == "block":
             xin = hip_ops.temporal_shift(y, tsm, div, hip_ops.LAYOUT_NHWC)
         fused = tsm if (tsm and place != "block" and shifted) else 0
-        z1 = _conv(c1, pk[id(c1)], xin, hip_ops.ACT_RELU, tsm=fused, div=div)
-        z2 = _conv(c2, pk[id(c2)], z1, hip_ops.ACT_RELU)
-        idn = xin if ds is None else _conv(ds, pk[id(ds)], xin, hip_ops.ACT_NONE)
-        y = _conv(c3, pk[id(c3)], z2, hip_ops.ACT_RELU, residual=idn)
+        z1 = form.forward(c1, xin, True, tsm=fused, div=div)
+        z2 = form.forward(c2, z1, True)
+        idn = xin if ds is None else form.forward(ds, xin, False)
+        y = form.forward(c3, z2, True, residual=idn)
         acts.append((xin, z1, z2, y))
-    return hip_ops.global_avgpool(y), pk, s, acts, (stem, blocks, tsm, div, place)
+    form.after_forward(net)
+    return Walk(feat=hip_ops.global_avgpool(y), stem_out=s, acts=acts, stem=stem, blocks=blocks, tsm=tsm, div=div, place=place, form=form)
 
 
 class TrunkFn(torch.autograd.Function):
-    """apply(patches_nhwc4, net, *params) -> (N, 2048); params = (conv.weight, bn.weight, bn.bias) of every layer in walk order, so the
-    gradients land in their .grad.  The patches take no gradient (the crop has integer origins)."""
+    """apply(patches_nhwc4, net, *params) -> (N, 2048), in the form the net's mode selects (walk_forward); params = (conv.weight,
+    bn.weight, bn.bias) of every layer in walk order, so the gradients land in their .grad.  The patches take no gradient (the crop has
+    integer origins)."""
 
     @staticmethod
     def forward(ctx, x4, net, *params):
-        feat, ctx.pk, ctx.s, ctx.acts, ctx.walk = walk_forward(net, x4)
+        wk = ctx.walk = walk_forward(net, x4)
         ctx.x4 = x4
+        feat, wk.feat = wk.feat, None           # (not kept on ctx: the output owns the node that owns ctx)
         return feat
 
     @staticmethod
     def backward(ctx, dfeat):
-        stem, blocks, tsm, div, place = ctx.walk
-        pk, acts = ctx.pk, ctx.acts
+        wk = ctx.walk
+        stem, blocks, acts, form, tsm, div = wk.stem, wk.blocks, wk.acts, wk.form, wk.tsm, wk.div
         flat = _flat(stem, blocks)
         need = {id(l): ctx.needs_input_grad[2 + 3 * i: 5 + 3 * i] for i, l in enumerate(flat)}
         grads = {}
@@ -125,18 +226,17 @@ class TrunkFn(torch.autograd.Function):
         def live(layer):
             return any(need[id(layer)])
 
-        def param_grads(layer, x, g):
-            if not live(layer):
-                return
-            nw, ng, nb = need[id(layer)]
-            p, bn = pk[id(layer)], layer.bn
-            raw = hip_ops.conv2d_wgrad(x, g, tuple(p.w.shape), layer.stride, layer.pad)
-            grads[id(layer)] = hip_ops.conv_bn_param_grad(g, raw, p.w, p.scale, bn.running_mean, bn.running_var, BN_EPS,
-                                                          layer.conv.weight.shape[1], want_dw=nw, want_affine=ng or nb)
+        def through(layer, g, x, y=None):
+            """The layer's backward for the gradient g at its output, after the form's relu_mask (x: the convolution's input; y: the
+            output whose ReLU mask a form that masks in its own backward still applies) -> the gradient at the convolution's output; keeps
+            the parameter gradients the layer wants.  Gradients and shifted inputs come in as temporaries and die with the call."""
+            gc, got = form.backward(layer, g, x, y, need[id(layer)])
+            if got is not None:
+                grads[id(layer)] = got
+            return gc
 
         def dgrad(layer, g, x_shape):
-            p = pk[id(layer)]
-            return hip_ops.conv2d_dgrad(g, hip_ops.pack_conv_dgrad_weight(p.w, p.scale), tuple(x_shape), layer.stride, layer.pad)
+            return hip_ops.conv2d_dgrad(g, form.dgrad_weight(layer), tuple(x_shape), layer.stride, layer.pad)
 
         # upstream[b]: some layer in front of block b (the stem or an earlier block) has a trainable parameter
         upstream, seen = [], live(stem)
@@ -155,177 +255,33 @@ class TrunkFn(torch.autograd.Function):
                 g3 = hip_ops.global_avgpool_backward(dfeat, tuple(y.shape), y)
             else:
                 g3 = hip_ops.relu_backward(g_out, y, g_idn)
-            param_grads(c3, z2, g3)
-            if ds is not None:
-                param_grads(ds, xin, g3)
-            g_out = g_idn = None
-            if upstream[b] or live(c1) or live(c2):
-                g2 = hip_ops.relu_backward(dgrad(c3, g3, z2.shape), z2)
-                param_grads(c2, z1, g2)
-                if upstream[b] or live(c1):
-                    g1 = hip_ops.relu_backward(dgrad(c2, g2, z1.shape), z1)
-                    fused = tsm and place != "block" and shifted
-                    if live(c1):
-                        param_grads(c1, hip_ops.temporal_shift(xin, tsm, div, hip_ops.LAYOUT_NHWC) if fused else xin, g1)
-                    if upstream[b]:
-                        g_out = dgrad(c1, g1, xin.shape)
-                        if fused:
-                            g_out = hip_ops.temporal_shift_backward(g_out, tsm, div, hip_ops.LAYOUT_NHWC)
-            if upstream[b]:
-                g_idn = g3 if ds is None else dgrad(ds, g3, xin.shape)
-                if tsm and place == "block":            # the whole block read the shifted map
-                    g_out = hip_ops.temporal_shift_backward(g_out, tsm, div, hip_ops.LAYOUT_NHWC)
-                    g_idn = hip_ops.temporal_shift_backward(g_idn, tsm, div, hip_ops.LAYOUT_NHWC)
-        else:
-            if live(stem):
-                # the pooled map is a maximum of ReLU outputs: where it is 0 its arg-max is a stem output of 0, which the stem's own ReLU
-                # mask zeroes anyway, so joining the two gradients under the mask `pooled > 0` changes nothing downstream
-                pooled = hip_ops.maxpool3x3s2(ctx.s)
-                gp = hip_ops.relu_backward(g_out, pooled, g_idn)
-                gs = hip_ops.relu_backward(hip_ops.maxpool3x3s2_backward(ctx.s, gp), ctx.s)
-                param_grads(stem, ctx.x4, gs)
-
-        out = []
-        for layer in flat:
-            got = grads.get(id(layer), (None, None, None))
-            nw, ng, nb = need[id(layer)]
-            out += [got[0] if nw else None, got[1] if ng else None, got[2] if nb else None]
-        return (None, None) + tuple(out)
-
-
-# ---- the batch-statistics form ------------------------------------------------------------------------------------------------------------
-class _Kept:
-    """What the backward needs of one conv + BatchNorm(batch statistics): the raw conv map and the statistics it was normalised with."""
-
-    def __init__(self, raw, mean, invstd):
-        self.raw, self.mean, self.invstd = raw, mean, invstd
-
-
-def _check_bn(bn):
-    if bn.momentum is None or not bn.track_running_stats or not bn.affine:
-        raise NotImplementedError("BatchNorm with momentum=None, without running statistics or without affine parameters")
-
-
-def _conv_raw(layer, w, x, tsm=0, div=8):
-    return hip_ops.conv2d_bn_act(x, w, None, None, None, layer.stride, layer.pad, hip_ops.ACT_NONE, tsm_segments=tsm, tsm_div=div)
-
-
-def _bn_batch(layer, raw, relu, residual=None):
-    """BatchNorm of `layer` on the statistics of `raw` [+ residual] [+ ReLU], as the module in train mode: -> (output, _Kept)."""
-    bn = layer.bn
-    y, mean, invstd = hip_ops.bn_map_train_forward(raw, bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var, bn.eps,
-                                                   bn.momentum, residual=residual, relu=relu)
-    bn.num_batches_tracked += 1
-    return y, _Kept(raw, mean, invstd)
-
-
-def walk_forward_batch(net, x4):
-    """walk_forward with BatchNorm on batch statistics: -> (features (N, 2048), the packed filter per layer, the stem's output, per block
-    (block input as the identity sees it, conv1's output, conv2's output, block output) -- all after ReLU --, the _Kept of every layer,
-    the walk's description).  Moves every running statistic once."""
-    stem, blocks = trunk_layers(net)
-    tsm, div, place = int(net.tsm_segments), int(net.tsm_div), net.tsm_place
-    flat = _flat(stem, blocks)
-    for l in flat:
-        _check_bn(l.bn)
-    w = {id(l): hip_ops.pack_conv_weight(l.conv.weight.detach()) for l in flat}
-    kept = {}
-    # (the stem on the generic engine: the trunk's stem kernel folds the affine and the ReLU in and has no raw form)
-    s, kept[id(stem)] = _bn_batch(stem, _conv_raw(stem, w[id(stem)], x4), True)
-    y = hip_ops.maxpool3x3s2(s)
-    acts = []
-    for c1, c2, c3, ds, shifted in blocks:
-        xin = y
-        if tsm and place == "block":
-            xin = hip_ops.temporal_shift(y, tsm, div, hip_ops.LAYOUT_NHWC)
-        fused = tsm if (tsm and place != "block" and shifted) else 0
-        z1, kept[id(c1)] = _bn_batch(c1, _conv_raw(c1, w[id(c1)], xin, fused, div), True)
-        z2, kept[id(c2)] = _bn_batch(c2, _conv_raw(c2, w[id(c2)], z1), True)
-        idn = xin
-        if ds is not None:
-            idn, kept[id(ds)] = _bn_batch(ds, _conv_raw(ds, w[id(ds)], xin), False)
-        y, kept[id(c3)] = _bn_batch(c3, _conv_raw(c3, w[id(c3)], z2), True, residual=idn)
-        acts.append((xin, z1, z2, y))
-    net._note_stats_written()
-    return hip_ops.global_avgpool(y), w, s, acts, kept, (stem, blocks, tsm, div, place)
-
-
-class TrunkBatchFn(torch.autograd.Function):
-    """TrunkFn for the batch-statistics form: the same operands and the same skipping rules."""
-
-    @staticmethod
-    def forward(ctx, x4, net, *params):
-        feat, ctx.w, ctx.s, ctx.acts, ctx.kept, ctx.walk = walk_forward_batch(net, x4)
-        ctx.x4 = x4
-        return feat
-
-    @staticmethod
-    def backward(ctx, dfeat):
-        stem, blocks, tsm, div, place = ctx.walk
-        w, acts, kept = ctx.w, ctx.acts, ctx.kept
-        flat = _flat(stem, blocks)
-        need = {id(l): ctx.needs_input_grad[2 + 3 * i: 5 + 3 * i] for i, l in enumerate(flat)}
-        grads = {}
-
-        def live(layer):
-            return any(need[id(layer)])
-
-        def through_bn(layer, x, g, y=None):
-            """BatchNorm backward of `layer` for the gradient g at its output (y: the output after ReLU whose mask g still needs), the
-            parameter gradients the layer wants (x: the convolution's input) -> the gradient at the convolution's output."""
-            k = kept[id(layer)]
-            gc, dgamma, dbeta = hip_ops.bn_map_train_backward(k.raw, y, g, layer.bn.weight.detach(), k.mean, k.invstd)
-            dw = None
-            if need[id(layer)][0]:           # the weight gradient of the raw convolution is dW itself
-                cin = layer.conv.weight.shape[1]
-                dw = hip_ops.conv2d_wgrad(x, gc, tuple(w[id(layer)].shape), layer.stride, layer.pad)[..., :cin].permute(0, 3, 1, 2).contiguous()
-            grads[id(layer)] = (dw, dgamma, dbeta)
-            return gc
-
-        def dgrad(layer, g, x_shape):
-            return hip_ops.conv2d_dgrad(g, hip_ops.pack_conv_dgrad_weight(w[id(layer)]), tuple(x_shape), layer.stride, layer.pad)
-
-        upstream, seen = [], live(stem)
-        for c1, c2, c3, ds, _ in blocks:
-            upstream.append(seen)
-            seen = seen or any(live(l) for l in (c1, c2, c3, ds) if l is not None)
-
-        dfeat = dfeat.contiguous().float()
-        g_out = g_idn = None
-        for b in range(len(blocks) - 1, -1, -1):
-            c1, c2, c3, ds, shifted = blocks[b]
-            xin, z1, z2, y = acts[b]
-            if not (upstream[b] or any(live(l) for l in (c1, c2, c3, ds) if l is not None)):
-                break
-            if b == len(blocks) - 1:
-                g3 = hip_ops.global_avgpool_backward(dfeat, tuple(y.shape), y)
-            else:
-                g3 = hip_ops.relu_backward(g_out, y, g_idn)
-            g_out = g_idn = None
             deeper = upstream[b] or live(c1) or live(c2)
-            gc3 = through_bn(c3, z2, g3) if (deeper or live(c3)) else None
-            gcd = through_bn(ds, xin, g3) if ds is not None and (upstream[b] or live(ds)) else None
+            gc3 = through(c3, g3, z2) if (deeper or live(c3)) else None
+            gcd = through(ds, g3, xin) if ds is not None and (upstream[b] or live(ds)) else None
+            g_out = g_idn = None
             if deeper:
-                gc2 = through_bn(c2, z1, dgrad(c3, gc3, z2.shape), z2)
+                gc2 = through(c2, form.relu_mask(dgrad(c3, gc3, z2.shape), z2), z1, z2)
                 if upstream[b] or live(c1):
-                    fused = tsm and place != "block" and shifted
-                    x1 = hip_ops.temporal_shift(xin, tsm, div, hip_ops.LAYOUT_NHWC) if (fused and need[id(c1)][0]) else xin
-                    gc1 = through_bn(c1, x1, dgrad(c2, gc2, z1.shape), z1)
+                    fused = tsm and wk.place != "block" and shifted
+                    shift_x = fused and form.wants_input(need[id(c1)])      # conv1 read the shifted map: materialised only for a weight gradient
+                    gc1 = through(c1, form.relu_mask(dgrad(c2, gc2, z1.shape), z1),
+                                  hip_ops.temporal_shift(xin, tsm, div, hip_ops.LAYOUT_NHWC) if shift_x else xin, z1)
                     if upstream[b]:
                         g_out = dgrad(c1, gc1, xin.shape)
                         if fused:
                             g_out = hip_ops.temporal_shift_backward(g_out, tsm, div, hip_ops.LAYOUT_NHWC)
             if upstream[b]:
                 g_idn = g3 if ds is None else dgrad(ds, gcd, xin.shape)
-                if tsm and place == "block":
+                if tsm and wk.place == "block":         # the whole block read the shifted map
                     g_out = hip_ops.temporal_shift_backward(g_out, tsm, div, hip_ops.LAYOUT_NHWC)
                     g_idn = hip_ops.temporal_shift_backward(g_idn, tsm, div, hip_ops.LAYOUT_NHWC)
         else:
             if live(stem):
-                # (the join under the mask `pooled > 0`: TrunkFn.backward says why that changes nothing downstream)
-                pooled = hip_ops.maxpool3x3s2(ctx.s)
+                # the pooled map is a maximum of ReLU outputs: where it is 0 its arg-max is a stem output of 0, which the stem's own ReLU
+                # mask zeroes anyway, so joining the two gradients under the mask `pooled > 0` changes nothing downstream
+                pooled = hip_ops.maxpool3x3s2(wk.stem_out)
                 gp = hip_ops.relu_backward(g_out, pooled, g_idn)
-                through_bn(stem, ctx.x4, hip_ops.maxpool3x3s2_backward(ctx.s, gp), ctx.s)
+                through(stem, form.relu_mask(hip_ops.maxpool3x3s2_backward(wk.stem_out, gp), wk.stem_out), ctx.x4, wk.stem_out)
 
         out = []
         for layer in flat:
@@ -344,5 +300,4 @@ def trunk_features(net, patches_nhwc4):
                                   "(the %s arithmetic has no backward)" % (net.math, net.math))
     stem, blocks = trunk_layers(net)
     params = [p for layer in _flat(stem, blocks) for p in layer.params()]
-    fn = TrunkBatchFn if (net.training and net.bn_batch_stats) else TrunkFn
-    return fn.apply(patches_nhwc4.contiguous(), net, *params)
+    return TrunkFn.apply(patches_nhwc4.contiguous(), net, *params)

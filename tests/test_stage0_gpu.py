@@ -16,12 +16,12 @@ import numpy as np
 import pytest
 import torch
 
-from adafocus_amd import resnet, synth, trunk_train
+from adafocus_amd import resnet, synth
 from adafocus_amd.train import train_stage0_batch
 from adafocus_amd.utils import nchw_to_nhwc4
 from tests import stage0_reference as R
 from tests.helpers import golden, rnd
-from tests.test_trunk_backward_gpu import SPREAD_FACTOR, _rel
+from tests.trunk_walk_harness import SPREAD_FACTOR, _device_branches, _rel, _run, check_features_and_gradients
 
 pytestmark = pytest.mark.gpu
 
@@ -88,64 +88,19 @@ def _net(tag, dev, batch_stats=True, train=True):
     return net
 
 
-def _run(net, x, dfeat, dev):
-    net.zero_grad(set_to_none=True)
-    feat = net.features_train_nhwc4(nchw_to_nhwc4(x.to(dev)))
-    feat.backward(dfeat.to(dev))
-    return feat.detach(), {k: v.grad for k, v in net.named_parameters()}
-
-
-def _device_branches(tag, dev):
-    """The ReLU masks of the device's batch-statistics walk (a second net from the same state dict: the walk moves running statistics),
-    checked against the float64 forward: a unit may differ only where the float64 input is within SPREAD_FACTOR x the fp32 forward error
-    of its map."""
-    ref = _case(tag)
-    pre64, pre32 = ref[torch.float64][2], ref[torch.float32][2]
-    with torch.no_grad():
-        _, _, s, acts, _, (_, blocks, _, _, _) = trunk_train.walk_forward_batch(_net(tag, dev), nchw_to_nhwc4(_inputs(tag)[1].to(dev)))
-    outs = {"stem": s}
-    for (c1, _, _, _, _), (_, z1, z2, y) in zip(blocks, acts):
-        q = c1.name.rsplit(".", 1)[0]
-        outs[q + ".z1"], outs[q + ".z2"], outs[q + ".y"] = z1, z2, y
-    assert set(outs) == set(pre64)
-    masks, differ = {}, 0
-    for k, z64 in pre64.items():
-        masks[k] = outs[k].permute(0, 3, 1, 2).cpu() > 0
-        d = masks[k] != (z64 > 0)
-        if d.any():
-            err = (pre32[k].double() - z64).abs().max().item()
-            worst = z64[d].abs().max().item()
-            print("%s %s: %d unit(s) on the other branch, |fp64 input| <= %.2e, fp32 forward error of the map %.2e" % (tag, k, int(d.sum()), worst, err))
-            assert worst <= SPREAD_FACTOR * err, (tag, k, worst, err)
-            differ += int(d.sum())
-    return masks, differ
-
-
 @pytest.mark.parametrize("tag", list(CASES))
 def test_features_gradients_and_statistics_against_fp64(dev, tag):
     sd, x, dfeat = _inputs(tag)
     ref = _case(tag)
     net = _net(tag, dev)
     feat, grads = _run(net, x, dfeat, dev)
-    f64, g64, _, s64 = ref[torch.float64]
-    f32, g32, _, s32 = ref[torch.float32]
-    masks, differ = _device_branches(tag, dev)
+    f64, g64, pre64, s64 = ref[torch.float64]
+    f32, g32, pre32, s32 = ref[torch.float32]
+    # (a second net from the same state dict: the walk moves running statistics)
+    masks, differ = _device_branches(tag, _net(tag, dev), x, dev, pre64, pre32)
     if differ:
         f64, g64, _, _ = _reference(tag, torch.float64, masks)
-    spread, err = _rel(f32, f64), _rel(feat, f64)
-    assert err <= SPREAD_FACTOR * spread, ("features", err, spread)
-    worst = []
-    for k, r64 in g64.items():
-        g = grads[k]
-        assert g is not None and torch.isfinite(g).all(), k
-        assert r64.abs().max() > 0, k
-        spread, err = _rel(g32[k], r64), _rel(g, r64)
-        worst.append((err / spread if spread > 0 else float("inf"), k, err, spread))
-    worst.sort(reverse=True)
-    print("%s: %d gradients; worst err / spread: %s" % (tag, len(worst), ", ".join("%s %.2e / %.2e" % w[1:] for w in worst[:4])))
-    assert grads["fc.weight"] is None and grads["fc.bias"] is None
-    bad = [(k, err, spread) for ratio, k, err, spread in worst if not err <= SPREAD_FACTOR * spread]
-    assert not bad, bad[:8]
+    check_features_and_gradients(tag, feat, grads, (f32, g32), (f64, g64), CASES[tag][3])
     # the running statistics moved once, as the module in train mode moves them
     stats = []
     for k, v in net.state_dict().items():
@@ -159,10 +114,6 @@ def test_features_gradients_and_statistics_against_fp64(dev, tag):
     print("%s: %d running statistics; worst err / spread: %s" % (tag, len(stats), ", ".join("%s %.2e / %.2e" % w[1:] for w in stats[:3])))
     bad = [(k, err, spread) for ratio, k, err, spread in stats if not err <= SPREAD_FACTOR * spread]
     assert not bad, bad[:8]
-    zero = CASES[tag][3]
-    if zero is not None:
-        assert grads[zero[0] + ".weight"][zero[1]].item() != 0.0        # the gamma = 0 channel still gets its dgamma
-        assert not grads[zero[0].replace("bn", "conv") + ".weight"][zero[1]].any()      # and passes no gradient to its filter
 
 
 def test_only_layer4_trainable_stops_the_chain(dev):

@@ -22,10 +22,10 @@ from adafocus_amd import resnet, synth
 from adafocus_amd.utils import nchw_to_nhwc4
 from tests.helpers import rnd
 from tests.test_f16_trunk import _shift
+from tests.trunk_walk_harness import SPREAD_FACTOR, _device_branches, _run, check_features_and_gradients  # noqa: F401 (SPREAD_FACTOR: tests/test_stage1_gpu.py)
 
 pytestmark = pytest.mark.gpu
 
-SPREAD_FACTOR = 50
 BN_EPS = 1e-5
 # tag -> (arch, patch size, temporal shift segments (0 = none), placement, a (BatchNorm, channel) whose gamma is set to exactly 0)
 CASES = {
@@ -114,53 +114,15 @@ def _case(tag):
     return _CACHE[tag]
 
 
-def _device_branches(tag, net, x, dev):
-    """The ReLU masks of the device's walk, checked against the fp64 forward: ({ReLU name: bool NCHW map}, units that differ).  A unit may
-    differ only where the fp64 pre-activation is within SPREAD_FACTOR x the fp32-vs-fp64 forward error of its map."""
-    from adafocus_amd import trunk_train
-    ref = _case(tag)[3]
-    pre64, pre32 = ref[torch.float64][2], ref[torch.float32][2]
-    with torch.no_grad():
-        _, _, s, acts, (_, blocks, _, _, _) = trunk_train.walk_forward(net, nchw_to_nhwc4(x.to(dev)))
-    outs = {"stem": s}
-    for (c1, _, _, _, _), (_, z1, z2, y) in zip(blocks, acts):
-        q = c1.name.rsplit(".", 1)[0]
-        outs[q + ".z1"], outs[q + ".z2"], outs[q + ".y"] = z1, z2, y
-    assert set(outs) == set(pre64)
-    masks, differ = {}, 0
-    for k, z64 in pre64.items():
-        masks[k] = outs[k].permute(0, 3, 1, 2).cpu() > 0
-        d = masks[k] != (z64 > 0)
-        if d.any():
-            err = (pre32[k].double() - z64).abs().max().item()
-            worst = z64[d].abs().max().item()
-            print("%s %s: %d unit(s) on the other branch, |fp64 input| <= %.2e, fp32 forward error of the map %.2e" % (tag, k, int(d.sum()), worst, err))
-            assert worst <= SPREAD_FACTOR * err, (tag, k, worst, err)
-            differ += int(d.sum())
-    return masks, differ
-
-
 def _net(tag, dev):
     arch, size, tsm, place, _ = CASES[tag]
-    sd = _case(tag)[0]
+    sd = _inputs(tag)[0]
     net = getattr(resnet, arch)()
     net.load_state_dict(sd, strict=True)
     net = net.eval().to(dev)
     net.set_math("f32")          # pinned: training is fp32 only, whatever default the session's other modules run the trunk with
     net.tsm_segments, net.tsm_div, net.tsm_place = tsm, 8, place
     return net
-
-
-def _run(net, x, dfeat, dev):
-    net.zero_grad(set_to_none=True)
-    net.set_trainable(True)
-    feat = net.features_train_nhwc4(nchw_to_nhwc4(x.to(dev)))
-    feat.backward(dfeat.to(dev))
-    return feat.detach(), {k: v.grad for k, v in net.named_parameters()}
-
-
-def _rel(got, ref64):
-    return ((got.double().cpu() - ref64).abs().max() / ref64.abs().max()).item()
 
 
 @pytest.mark.parametrize("tag", list(CASES))
@@ -172,33 +134,15 @@ def test_features_and_every_gradient_against_fp64(dev, tag):
     stats = {k: v.clone() for k, v in net.state_dict().items() if "running" in k}
     feat, grads = _run(net, x, dfeat, dev)
     assert torch.equal(feat, engine), "the training walk's features differ from the eval engine's in %d values" % int((feat != engine).sum())
-    f64, g64, _ = ref[torch.float64]
-    f32, g32, _ = ref[torch.float32]
-    masks, differ = _device_branches(tag, net, x, dev)
+    f64, g64, pre64 = ref[torch.float64]
+    f32, g32, pre32 = ref[torch.float32]
+    masks, differ = _device_branches(tag, net, x, dev, pre64, pre32)
     if differ:                       # the fp64 gradient on the branches the device took (module docstring)
         f64, g64, _ = _reference(tag, torch.float64, masks)
-    worst = []
-    spread, err = _rel(f32, f64), _rel(feat, f64)
-    assert err <= SPREAD_FACTOR * spread, ("features", err, spread)
-    for k, r64 in g64.items():
-        g = grads[k]
-        assert g is not None and torch.isfinite(g).all(), k
-        assert r64.abs().max() > 0, k
-        spread, err = _rel(g32[k], r64), _rel(g, r64)
-        worst.append((err / spread if spread > 0 else float("inf"), k, err, spread))
-    worst.sort(reverse=True)
-    print("%s: %d gradients; worst err / spread: %s" % (tag, len(worst), ", ".join("%s %.2e / %.2e" % w[1:] for w in worst[:4])))
-    assert grads["fc.weight"] is None and grads["fc.bias"] is None
-    bad = [(k, err, spread) for ratio, k, err, spread in worst if not err <= SPREAD_FACTOR * spread]
-    assert not bad, bad[:8]
+    check_features_and_gradients(tag, feat, grads, (f32, g32), (f64, g64), CASES[tag][4])
     for k, v in net.state_dict().items():
         if "running" in k:
             assert torch.equal(v, stats[k]), k                          # the BatchNorm statistics are never touched
-    zero = CASES[tag][4]
-    if zero is not None:
-        assert grads[zero[0] + ".weight"][zero[1]].item() != 0.0        # the gamma = 0 channel still gets its dgamma
-        conv = zero[0].replace("bn", "conv")
-        assert not grads[conv + ".weight"][zero[1]].any()               # and passes no gradient to its filter
 
 
 def test_only_layer4_trainable_stops_the_chain(dev):
