@@ -144,6 +144,14 @@ PROTOTYPES = {
     "adaf_temporal_shift_backward_f32": (ip, [vp, vp, ip, ip, ip, ip, ip, ip, vp, vp]),
     "adaf_conv_bn_param_grad_workspace_bytes": (sz, [ip]),
     "adaf_conv_bn_param_grad_f32": (ip, [vp, vp, ip, vp, vp, vp, vp, vp, fp, ip, ip, ip, ip, ip, vp, vp, vp, vp, sz, vp]),
+    "adaf_dwconv3x3_dgrad_f32": (ip, [vp, vp, ip, ip, ip, ip, ip, vp, vp, vp]),
+    "adaf_dwconv3x3_wgrad_workspace_bytes": (sz, [ip] * 5),
+    "adaf_dwconv3x3_wgrad_f32": (ip, [vp, vp, vp, ip, ip, ip, ip, ip, vp, vp, sz, vp]),
+    "adaf_bn_map_train_forward_act_f32": (ip, [vp, vp, ip, ip, vp, vp, fp, fp, vp, vp, vp, ip, vp, vp, vp, vp, sz, vp]),
+    "adaf_bn_map_train_backward_act_f32": (ip, [vp, vp, vp, ip, vp, ip, ip] + [vp] * 7 + [sz, vp]),
+    "adaf_add_f32": (ip, [vp, vp, vp, sz, vp, vp]),
+    "adaf_conv2d_wgrad_rows_workspace_bytes": (sz, [C.POINTER(ConvParams)]),
+    "adaf_conv2d_wgrad_rows_f32": (ip, [vp, C.POINTER(ConvParams), vp, vp, vp, vp, sz, vp]),
 }
 SYMBOLS = tuple(PROTOTYPES)
 

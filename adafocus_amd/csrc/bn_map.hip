@@ -10,8 +10,8 @@
 //                                x - k is exact in double
 //   bn_map_stat_final_kernel     the slices added in slice order, two levels: 32 groups of consecutive slices, then the 32 group sums;
 //                                mean, invstd = 1 / sqrt(biased variance + eps), the running statistics' update; rounded once
-//   bn_map_normalize_kernel      y = (x - mean) * invstd * gamma + beta [+ residual] [ReLU]
-//   bn_map_bwd_partial_kernel    per (slice, column): sum dy_m, sum dy_m (x - mean) in double; dy_m = dy where y > 0 (y == nullptr: dy)
+//   bn_map_normalize_kernel      y = (x - mean) * invstd * gamma + beta [+ residual] [clipped to [0, hi]: hi = +inf is ReLU, 6 is ReLU6]
+//   bn_map_bwd_partial_kernel    per (slice, column): sum dy_m, sum dy_m (x - mean) in double; dy_m = dy where 0 < y < hi (y == nullptr: dy)
 //   bn_map_bwd_final_kernel      dbeta, dgamma = invstd * sum dy_m (x - mean), the same two levels
 //   bn_map_bwd_dx_kernel         dx = gamma invstd / n (n dy_m - dbeta - xhat dgamma)
 //
@@ -151,7 +151,8 @@ __global__ __launch_bounds__(kThreads) void bn_map_stat_final_kernel(const doubl
 template <int CQ> __global__ __launch_bounds__(kThreads) void bn_map_normalize_kernel(const float* __restrict__ x, const float* __restrict__ mean,
                                                                                        const float* __restrict__ invstd, const float* __restrict__ gamma,
                                                                                        const float* __restrict__ beta, const float* __restrict__ res,
-                                                                                       int rows, int cols, int per, int relu, float* __restrict__ y) {
+                                                                                       int rows, int cols, int per, int relu, float hi,
+                                                                                       float* __restrict__ y) {
     const Strip s = strip_of<CQ>(rows, cols, per);
     if (s.c >= cols) return;
     const float4 m4 = col4(mean, s.c), i4 = col4(invstd, s.c), g4 = col4(gamma, s.c), b4 = col4(beta, s.c);
@@ -166,7 +167,7 @@ template <int CQ> __global__ __launch_bounds__(kThreads) void bn_map_normalize_k
         for (int j = 0; j < 4; ++j) {
             float t = (v[j] - m[j]) * is[j] * g[j] + b[j];
             if (res) t += rr[j];
-            o[j] = relu ? fmaxf(t, 0.f) : t;
+            o[j] = relu ? fminf(fmaxf(t, 0.f), hi) : t;      // (hi = +inf: the minimum changes nothing)
         }
         st4(y, r, cols, s.c, make_float4(o[0], o[1], o[2], o[3]));
     }
@@ -174,7 +175,8 @@ template <int CQ> __global__ __launch_bounds__(kThreads) void bn_map_normalize_k
 
 template <int CQ> __global__ __launch_bounds__(kThreads) void bn_map_bwd_partial_kernel(const float* __restrict__ x, const float* __restrict__ y,
                                                                                          const float* __restrict__ dy, const float* __restrict__ mean,
-                                                                                         int rows, int cols, int per, double* __restrict__ part) {
+                                                                                         int rows, int cols, int per, float hi,
+                                                                                         double* __restrict__ part) {
     const Strip s = strip_of<CQ>(rows, cols, per);
     double a[4] = {0.0, 0.0, 0.0, 0.0}, b[4] = {0.0, 0.0, 0.0, 0.0};
     if (s.c < cols) {
@@ -187,7 +189,7 @@ template <int CQ> __global__ __launch_bounds__(kThreads) void bn_map_bwd_partial
             const float v[4] = {v4.x, v4.y, v4.z, v4.w}, d[4] = {d4.x, d4.y, d4.z, d4.w}, yy[4] = {y4.x, y4.y, y4.z, y4.w};
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const double gd = yy[j] > 0.f ? d[j] : 0.f;
+                const double gd = yy[j] > 0.f && yy[j] < hi ? d[j] : 0.f;
                 a[j] += gd;
                 b[j] += gd * ((double)v[j] - m[j]);
             }
@@ -212,7 +214,7 @@ template <int CQ> __global__ __launch_bounds__(kThreads) void bn_map_bwd_dx_kern
                                                                                     const float* __restrict__ dy, const float* __restrict__ gamma,
                                                                                     const float* __restrict__ mean, const float* __restrict__ invstd,
                                                                                     const float* __restrict__ dgamma, const float* __restrict__ dbeta,
-                                                                                    int rows, int cols, int per, float* __restrict__ dx) {
+                                                                                    int rows, int cols, int per, float hi, float* __restrict__ dx) {
     const Strip s = strip_of<CQ>(rows, cols, per);
     if (s.c >= cols) return;
     const float4 m4 = col4(mean, s.c), i4 = col4(invstd, s.c), g4 = col4(gamma, s.c), a4 = col4(dgamma, s.c), b4 = col4(dbeta, s.c);
@@ -227,7 +229,7 @@ template <int CQ> __global__ __launch_bounds__(kThreads) void bn_map_bwd_dx_kern
         float o[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const float gd = yy[j] > 0.f ? d[j] : 0.f;
+            const float gd = yy[j] > 0.f && yy[j] < hi ? d[j] : 0.f;
             const float xh = (v[j] - m[j]) * is[j];
             o[j] = g[j] * is[j] / n * (n * gd - db[j] - xh * dg[j]);
         }
@@ -272,6 +274,48 @@ int bn_map_check(adaf_handle* h, const char* who, int rows, int cols, const void
     return adaf_check_ws(h, who, ws, ws_bytes, bn_map_layout(ws, cols, part), ADAF_WS_ALIGN_FIRST);
 }
 
+constexpr float kNoCeiling = __builtin_inff();      // the clip ceiling of ReLU: fminf(t, inf) and y < inf change nothing on a finite map
+
+// relu: clip to [0, hi]
+int bn_map_forward(adaf_handle* h, const char* who, const float* x, int rows, int cols, const float* gamma, const float* beta, float eps,
+                   float momentum, float* running_mean, float* running_var, const float* residual, int relu, float hi, float* y_out,
+                   float* mean_out, float* invstd_out, void* ws, size_t ws_bytes, void* stream) {
+    if (!x || !gamma || !beta || !y_out || !mean_out || !invstd_out || !ws) return adaf_fail(h, ADAF_E_BADARG, "%s: null pointer", who);
+    double* part;
+    const void* maps[3] = {x, residual, y_out};
+    int rc = bn_map_check(h, who, rows, cols, maps, 3, ws, ws_bytes, &part);
+    if (rc) return rc;
+    const hipStream_t st = (hipStream_t)stream;
+    const Launch l = launch_of(rows, cols);
+    BN_MAP_STRIP(bn_map_stat_partial_kernel, l, st, x, rows, cols, l.per, part);
+    hipLaunchKernelGGL(bn_map_stat_final_kernel, dim3((cols + 15) / 16), dim3(kThreads), 0, st, (const double*)part, x, rows, cols, l.slices, eps,
+                       momentum, mean_out, invstd_out, running_mean, running_var);
+    BN_MAP_STRIP(bn_map_normalize_kernel, l, st, x, (const float*)mean_out, (const float*)invstd_out, gamma, beta, residual, rows, cols, l.per,
+                 relu, hi, y_out);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? ADAF_OK : adaf_hip_fail(h, e, who);
+}
+
+// y == nullptr: no mask; else dy passes where 0 < y < hi
+int bn_map_backward(adaf_handle* h, const char* who, const float* x, const float* y, float hi, const float* dy, int rows, int cols,
+                    const float* gamma, const float* mean, const float* invstd, float* dx_out, float* dgamma_out, float* dbeta_out, void* ws,
+                    size_t ws_bytes, void* stream) {
+    if (!x || !dy || !gamma || !mean || !invstd || !dx_out || !dgamma_out || !dbeta_out || !ws) return adaf_fail(h, ADAF_E_BADARG, "%s: null pointer", who);
+    double* part;
+    const void* maps[4] = {x, y, dy, dx_out};
+    int rc = bn_map_check(h, who, rows, cols, maps, 4, ws, ws_bytes, &part);
+    if (rc) return rc;
+    const hipStream_t st = (hipStream_t)stream;
+    const Launch l = launch_of(rows, cols);
+    BN_MAP_STRIP(bn_map_bwd_partial_kernel, l, st, x, y, dy, mean, rows, cols, l.per, hi, part);
+    hipLaunchKernelGGL(bn_map_bwd_final_kernel, dim3((cols + 15) / 16), dim3(kThreads), 0, st, (const double*)part, invstd, cols, l.slices, dgamma_out,
+                       dbeta_out);
+    BN_MAP_STRIP(bn_map_bwd_dx_kernel, l, st, x, y, dy, gamma, mean, invstd, (const float*)dgamma_out, (const float*)dbeta_out, rows, cols, l.per,
+                 hi, dx_out);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? ADAF_OK : adaf_hip_fail(h, e, who);
+}
+
 }  // namespace
 
 size_t adaf_bn_map_workspace_bytes(int rows, int cols) {
@@ -282,38 +326,32 @@ size_t adaf_bn_map_workspace_bytes(int rows, int cols) {
 int adaf_bn_map_train_forward_f32(adaf_handle* h, const float* x, int rows, int cols, const float* gamma, const float* beta, float eps,
                                   float momentum, float* running_mean, float* running_var, const float* residual, int relu, float* y_out,
                                   float* mean_out, float* invstd_out, void* ws, size_t ws_bytes, void* stream) {
-    if (!x || !gamma || !beta || !y_out || !mean_out || !invstd_out || !ws) return adaf_fail(h, ADAF_E_BADARG, "bn_map_train_forward: null pointer");
-    double* part;
-    const void* maps[3] = {x, residual, y_out};
-    int rc = bn_map_check(h, "bn_map_train_forward", rows, cols, maps, 3, ws, ws_bytes, &part);
-    if (rc) return rc;
-    const hipStream_t st = (hipStream_t)stream;
-    const Launch l = launch_of(rows, cols);
-    BN_MAP_STRIP(bn_map_stat_partial_kernel, l, st, x, rows, cols, l.per, part);
-    hipLaunchKernelGGL(bn_map_stat_final_kernel, dim3((cols + 15) / 16), dim3(kThreads), 0, st, (const double*)part, x, rows, cols, l.slices, eps,
-                       momentum, mean_out, invstd_out, running_mean, running_var);
-    BN_MAP_STRIP(bn_map_normalize_kernel, l, st, x, (const float*)mean_out, (const float*)invstd_out, gamma, beta, residual, rows, cols, l.per,
-                 relu ? 1 : 0, y_out);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? ADAF_OK : adaf_hip_fail(h, e, "bn_map_train_forward launch");
+    return bn_map_forward(h, "bn_map_train_forward", x, rows, cols, gamma, beta, eps, momentum, running_mean, running_var, residual, relu ? 1 : 0,
+                          kNoCeiling, y_out, mean_out, invstd_out, ws, ws_bytes, stream);
+}
+
+int adaf_bn_map_train_forward_act_f32(adaf_handle* h, const float* x, int rows, int cols, const float* gamma, const float* beta, float eps,
+                                      float momentum, float* running_mean, float* running_var, const float* residual, int act, float* y_out,
+                                      float* mean_out, float* invstd_out, void* ws, size_t ws_bytes, void* stream) {
+    if (act != ADAF_ACT_NONE && act != ADAF_ACT_RELU && act != ADAF_ACT_RELU6)
+        return adaf_fail(h, ADAF_E_BADARG, "bn_map_train_forward_act: ADAF_ACT_NONE, ADAF_ACT_RELU or ADAF_ACT_RELU6 expected");
+    return bn_map_forward(h, "bn_map_train_forward_act", x, rows, cols, gamma, beta, eps, momentum, running_mean, running_var, residual,
+                          act != ADAF_ACT_NONE, act == ADAF_ACT_RELU6 ? 6.f : kNoCeiling, y_out, mean_out, invstd_out, ws, ws_bytes, stream);
 }
 
 int adaf_bn_map_train_backward_f32(adaf_handle* h, const float* x, const float* y, const float* dy, int rows, int cols, const float* gamma,
                                    const float* mean, const float* invstd, float* dx_out, float* dgamma_out, float* dbeta_out, void* ws,
                                    size_t ws_bytes, void* stream) {
-    if (!x || !dy || !gamma || !mean || !invstd || !dx_out || !dgamma_out || !dbeta_out || !ws)
-        return adaf_fail(h, ADAF_E_BADARG, "bn_map_train_backward: null pointer");
-    double* part;
-    const void* maps[4] = {x, y, dy, dx_out};
-    int rc = bn_map_check(h, "bn_map_train_backward", rows, cols, maps, 4, ws, ws_bytes, &part);
-    if (rc) return rc;
-    const hipStream_t st = (hipStream_t)stream;
-    const Launch l = launch_of(rows, cols);
-    BN_MAP_STRIP(bn_map_bwd_partial_kernel, l, st, x, y, dy, mean, rows, cols, l.per, part);
-    hipLaunchKernelGGL(bn_map_bwd_final_kernel, dim3((cols + 15) / 16), dim3(kThreads), 0, st, (const double*)part, invstd, cols, l.slices, dgamma_out,
-                       dbeta_out);
-    BN_MAP_STRIP(bn_map_bwd_dx_kernel, l, st, x, y, dy, gamma, mean, invstd, (const float*)dgamma_out, (const float*)dbeta_out, rows, cols, l.per,
-                 dx_out);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? ADAF_OK : adaf_hip_fail(h, e, "bn_map_train_backward launch");
+    return bn_map_backward(h, "bn_map_train_backward", x, y, kNoCeiling, dy, rows, cols, gamma, mean, invstd, dx_out, dgamma_out, dbeta_out, ws,
+                           ws_bytes, stream);
+}
+
+int adaf_bn_map_train_backward_act_f32(adaf_handle* h, const float* x, const float* y, int act, const float* dy, int rows, int cols,
+                                       const float* gamma, const float* mean, const float* invstd, float* dx_out, float* dgamma_out,
+                                       float* dbeta_out, void* ws, size_t ws_bytes, void* stream) {
+    if (act != ADAF_ACT_NONE && act != ADAF_ACT_RELU && act != ADAF_ACT_RELU6)
+        return adaf_fail(h, ADAF_E_BADARG, "bn_map_train_backward_act: ADAF_ACT_NONE, ADAF_ACT_RELU or ADAF_ACT_RELU6 expected");
+    if (act != ADAF_ACT_NONE && !y) return adaf_fail(h, ADAF_E_BADARG, "bn_map_train_backward_act: the mask of an activation needs y");
+    return bn_map_backward(h, "bn_map_train_backward_act", x, act == ADAF_ACT_NONE ? nullptr : y, act == ADAF_ACT_RELU6 ? 6.f : kNoCeiling, dy, rows,
+                           cols, gamma, mean, invstd, dx_out, dgamma_out, dbeta_out, ws, ws_bytes, stream);
 }

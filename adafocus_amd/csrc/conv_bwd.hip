@@ -17,12 +17,13 @@ namespace {
 
 inline unsigned blocks_for(size_t n, int per = 256) { return (unsigned)((n + per - 1) / per); }
 
-// the weight gradient's launch: M = cout as one or two sets of 32 filter rows per block, K = kh * kw * cin in chunks of 128.  The slices
-// are planned for the MI355X's 256 CUs whatever the device reports: the query needs no handle
+// the weight gradient's launch: M = cout as one or two sets of 32 filter rows per block (the last block's rows past cout are bounded off:
+// splitk_wgrad.h), K = kh * kw * cin in chunks of 128.  The slices are planned for the MI355X's 256 CUs whatever the device reports: the
+// query needs no handle
 struct WgradPlan { int mh; SkPlan sk; };
 WgradPlan wgrad_plan(long long npix, int cout, int K) {
     const int mh = cout % 64 == 0 ? 2 : 1;
-    return {mh, splitk_plan(npix, (long long)((K + 127) / 128) * (cout / (32 * mh)), kSkCus)};
+    return {mh, splitk_plan(npix, (long long)((K + 127) / 128) * ((cout + 32 * mh - 1) / (32 * mh)), kSkCus)};
 }
 
 // ---- data gradient -------------------------------------------------------------------------------------------------------------------
@@ -204,29 +205,26 @@ bool dgrad_shape_ok(const adaf_conv_params* p) {
     return p->stride == 2 && ((p->kh == 1 && p->pad == 0) || (p->kh == 3 && p->pad == 1));
 }
 
-}  // namespace
-
-extern "C" {
-
-size_t adaf_conv2d_wgrad_workspace_bytes(const adaf_conv_params* p) {
+// Both weight-gradient exports: cout a multiple of `cout_mult` -- 32, whole blocks of filter rows, or 4, the last block bounded.
+size_t wgrad_bytes(const adaf_conv_params* p, int cout_mult) {
     ConvGeom q;
-    if (conv_bwd_geom(nullptr, "", p, &q) || p->cout % 32) return 0;
+    if (conv_bwd_geom(nullptr, "", p, &q) || p->cout % cout_mult) return 0;
     float* part;
     return wgrad_layout(nullptr, wgrad_plan(q.npix_out, p->cout, q.K), p->cout, q.K, &part);
 }
 
-int adaf_conv2d_wgrad_f32(adaf_handle* h, const adaf_conv_params* p, const float* x, const float* g, float* dw_ohwi, void* ws,
-                          size_t ws_bytes, void* stream) {
+int wgrad_run(adaf_handle* h, const char* who, int cout_mult, const adaf_conv_params* p, const float* x, const float* g, float* dw_ohwi, void* ws,
+              size_t ws_bytes, void* stream) {
     if (!h) return ADAF_E_BADARG;
-    if (!x || !g || !dw_ohwi || !ws) return adaf_fail(h, ADAF_E_BADARG, "conv_wgrad: null pointer");
+    if (!x || !g || !dw_ohwi || !ws) return adaf_fail(h, ADAF_E_BADARG, "%s: null pointer", who);
     ConvGeom q;
-    int rc = conv_bwd_geom(h, "conv_wgrad", p, &q);
+    int rc = conv_bwd_geom(h, who, p, &q);
     if (rc) return rc;
-    if (p->cout % 32) return adaf_fail(h, ADAF_E_LAYOUT, "conv_wgrad: cout=%d must be a multiple of 32", p->cout);
-    if (!adaf_aligned16(x) || !adaf_aligned16(g) || !adaf_aligned16(dw_ohwi)) return adaf_fail(h, ADAF_E_LAYOUT, "conv_wgrad: 16-byte alignment");
+    if (p->cout % cout_mult) return adaf_fail(h, ADAF_E_LAYOUT, "%s: cout=%d must be a multiple of %d", who, p->cout, cout_mult);
+    if (!adaf_aligned16(x) || !adaf_aligned16(g) || !adaf_aligned16(dw_ohwi)) return adaf_fail(h, ADAF_E_LAYOUT, "%s: 16-byte alignment", who);
     const WgradPlan pl = wgrad_plan(q.npix_out, p->cout, q.K);
     float* part;
-    if ((rc = adaf_check_ws(h, "conv_wgrad", ws, ws_bytes, wgrad_layout(ws, pl, p->cout, q.K, &part), ADAF_WS_ALIGN_FIRST))) return rc;
+    if ((rc = adaf_check_ws(h, who, ws, ws_bytes, wgrad_layout(ws, pl, p->cout, q.K, &part), ADAF_WS_ALIGN_FIRST))) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int npix = (int)q.npix_out;
     auto launch = [&](const auto& src) {
@@ -241,7 +239,24 @@ int adaf_conv2d_wgrad_f32(adaf_handle* h, const adaf_conv_params* p, const float
         launch(SkWindow{x, g, p->cin, p->cout, p->h, p->w, q.oh, q.ow, p->kw, p->stride, p->pad});
     adaf_launch_slice_sum(part, pl.sk.used, (size_t)p->cout * q.K, dw_ohwi, st);
     hipError_t e = hipGetLastError();
-    return e == hipSuccess ? ADAF_OK : adaf_hip_fail(h, e, "conv_wgrad launch");
+    return e == hipSuccess ? ADAF_OK : adaf_hip_fail(h, e, who);
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t adaf_conv2d_wgrad_workspace_bytes(const adaf_conv_params* p) { return wgrad_bytes(p, 32); }
+size_t adaf_conv2d_wgrad_rows_workspace_bytes(const adaf_conv_params* p) { return wgrad_bytes(p, 4); }
+
+int adaf_conv2d_wgrad_f32(adaf_handle* h, const adaf_conv_params* p, const float* x, const float* g, float* dw_ohwi, void* ws,
+                          size_t ws_bytes, void* stream) {
+    return wgrad_run(h, "conv_wgrad", 32, p, x, g, dw_ohwi, ws, ws_bytes, stream);
+}
+
+int adaf_conv2d_wgrad_rows_f32(adaf_handle* h, const adaf_conv_params* p, const float* x, const float* g, float* dw_ohwi, void* ws,
+                               size_t ws_bytes, void* stream) {
+    return wgrad_run(h, "conv_wgrad_rows", 4, p, x, g, dw_ohwi, ws, ws_bytes, stream);
 }
 
 int adaf_pack_conv_dgrad_weight_f32(adaf_handle* h, const float* w_ohwi, const float* scale, int cout, int kh, int kw, int cin, float* w_dgrad,

@@ -2,12 +2,14 @@
 // reduction axis is the pixel axis, as ONE kernel for the PPO encoder's 1x1 conv (ppo_train.hip) and the trunk's convolutions
 // (conv_bwd.hip).  The callers differ in where a lane's operands come from; that is an operand source (below), everything else is here once.
 //
-// grid (ceil(K / (128 NQ)), M / (32 MH), slices), 512 threads.  A block owns pixels [slice * pps, (slice + 1) * pps), rows [32 MH blockIdx.y,
+// grid (ceil(K / (128 NQ)), ceil(M / (32 MH)), slices), 512 threads.  A block owns pixels [slice * pps, (slice + 1) * pps), rows [32 MH blockIdx.y,
 // ...) and columns [128 NQ blockIdx.x, ...).  Its pixels go to its 8 waves in groups of 8 (group g to wave g % 8, ascending); a wave walks its
 // groups with v_mfma_f32_32x32x2_f32 products: M = 32 rows, N = 32 lanes x 4 columns of a 16-byte load (MFMA q takes component q: output
 // column nl of accumulator 4 (mh NQ + j) + q is column 128 j + 4 nl + q of the block's chunk), K = 2 pixels per product (lane half = pixel
 // parity).  MH sets of 32 rows (row 32 mh + m is row m of the accumulators of set mh) are fed by the same B fragments.  Wave 0 writes the
 // block's partial into part[slice] ([slices, M, K]); adaf_launch_slice_sum adds the slices in slice order.  No atomics.
+// THE ROW BOUND: M need not fill the last block's rows.  A row >= M takes a zero row operand from a clamped address (row M - 1) and is
+// not stored; where M is a multiple of 32 MH the clamp and the bound never act.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -29,7 +31,7 @@ struct SkFrag {
 
 // ---- operand sources ----------------------------------------------------------------------------------------------------------------------
 // A source is passed to the kernel by value.  lane(kc) is what the lane keeps of its first column kc (clamped to a real column);
-// load(lane, pc, m, frag) requests the lane's operands of pixel pc (clamped into the slice) and row m (+ 32 mh).  Requests only: the
+// load(lane, pc, m, frag) requests the lane's operands of pixel pc (clamped into the slice) and row m (+ 32 mh, clamped below M).  Requests only: the
 // masks are applied by the kernel at product time, so nothing in load waits for memory.
 //
 // Pointwise: b[pixel, k] = x[pixel * K + k], the PPO encoder's states and a 1x1 stride-1 convolution (the window of output pixel p is input
@@ -50,8 +52,9 @@ struct SkPointwise {
         for (int j = 0; j < NQ; ++j) f.b[j] = *reinterpret_cast<const f32x4*>(xp + 128 * j);
 #pragma unroll
         for (int mh = 0; mh < MH; ++mh) {
-            f.d[mh] = g[(size_t)pc * M + m + 32 * mh];
-            f.gate[mh] = GATED ? e1[(size_t)pc * M + m + 32 * mh] : 1.f;
+            const int mc = min(m + 32 * mh, M - 1);
+            f.d[mh] = g[(size_t)pc * M + mc];
+            f.gate[mh] = GATED ? e1[(size_t)pc * M + mc] : 1.f;
         }
         f.okb = true;
     }
@@ -77,7 +80,7 @@ struct SkWindow {
         f.b[0] = *reinterpret_cast<const f32x4*>(x + (((size_t)img * H + iyc) * W + ixc) * cin + ln.ci);
 #pragma unroll
         for (int mh = 0; mh < MH; ++mh) {
-            f.d[mh] = g[(size_t)pc * M + m + 32 * mh];
+            f.d[mh] = g[(size_t)pc * M + min(m + 32 * mh, M - 1)];
             f.gate[mh] = 1.f;
         }
         f.okb = iy >= 0 && iy < H && ix >= 0 && ix < W;
@@ -128,7 +131,7 @@ __global__ __launch_bounds__(kSkThreads) void splitk_wgrad_kernel(const Src src,
                 for (int q = 0; q < 4; ++q) b[j][q] = st[u].okb ? st[u].b[j][q] : 0.f;
 #pragma unroll
             for (int mh = 0; mh < MH; ++mh) {
-                const float a = okp[u] && st[u].gate[mh] > 0.f ? st[u].d[mh] : 0.f;
+                const float a = okp[u] && st[u].gate[mh] > 0.f && m0 + nl + 32 * mh < M ? st[u].d[mh] : 0.f;
 #pragma unroll
                 for (int j = 0; j < NQ; ++j)
 #pragma unroll
@@ -177,7 +180,7 @@ __global__ __launch_bounds__(kSkThreads) void splitk_wgrad_kernel(const Src src,
                 for (int r = 0; r < 16; ++r) {
                     const int m = (r & 3) + 8 * (r >> 2) + 4 * half, k = 4 * (mh * NQ + j);
                     const f32x4 v = {acc[k][r], acc[k + 1][r], acc[k + 2][r], acc[k + 3][r]};
-                    *reinterpret_cast<f32x4*>(o + (size_t)(m0 + 32 * mh + m) * K + 128 * j) = v;
+                    if (m0 + 32 * mh + m < M) *reinterpret_cast<f32x4*>(o + (size_t)(m0 + 32 * mh + m) * K + 128 * j) = v;
                 }
     }
 }
@@ -201,7 +204,7 @@ constexpr int kSkCus = 256;     // workspaces are sized for the MI355X's 256 CUs
 
 template <int NQ, int MH, class Src>
 void splitk_wgrad_launch(const Src& src, float* part, int npix, int K, int M, const SkPlan& pl, hipStream_t st) {
-    const dim3 grid((K + 128 * NQ - 1) / (128 * NQ), M / (32 * MH), pl.used);
+    const dim3 grid((K + 128 * NQ - 1) / (128 * NQ), (M + 32 * MH - 1) / (32 * MH), pl.used);
     hipLaunchKernelGGL((splitk_wgrad_kernel<NQ, MH, Src>), grid, dim3(kSkThreads), 0, st, src, part, npix, K, M, pl.pps);
 }
 

@@ -370,11 +370,11 @@ class GFV(nn.Module):
         """gfv_net.py:62-81 for train_stage == 3 (call after model.train(), as ACT/main_dist.py does): the glancer, the focuser and
         both policies go to eval mode; only the classifier trains (dropout on, HIP backward).  Every other stage raises here: stage 2 (the
         policy's training) is entered through `policy_train_mode()`, stage 0 for the focuser's ResNet through `backbone_train_mode()`,
-        stage 1 through `stage1_train_mode()`; stage 0 for the glancer is out of scope."""
+        stage 1 through `stage1_train_mode()`; stage 0 for the glancer through `glancer_train_mode()`."""
         if args.train_stage != 3:
             raise NotImplementedError("train_mode: train_stage %r is not entered here (stage 3, classifier training, is; stage 2, policy "
                                       "training, is entered with policy_train_mode(); stage 0 for the focuser's ResNet with "
-                                      "backbone_train_mode(); stage 1 with stage1_train_mode(); stage 0 for the glancer is out of scope)"
+                                      "backbone_train_mode(); stage 1 with stage1_train_mode(); stage 0 for the glancer with glancer_train_mode())"
                                       % (args.train_stage,))
         self.train()
         self.glancer.eval()
@@ -440,14 +440,29 @@ class GFV(nn.Module):
         feature = torch.cat([fvec, local], dim=1) if self.with_glancer else local
         return self.classifier(feature.view(b, t, -1), mask=dropout_mask)
 
+    def glancer_train_mode(self):
+        """What the reference's train_mode does for train_stage == 0 (gfv_net.py:65-66) with pretrain_glancer=True: the glancer's
+        MobileNetV2 goes to train mode, trainable, with BatchNorm on batch statistics; everything else goes to eval mode (nothing else
+        runs in that branch, ACT/main_dist.py:544-548).  The loop body is `adafocus_amd.train.train_stage0_glancer_batch`."""
+        from .mobilenet import MobileNetV2
+        net = getattr(self.glancer, "net", None)
+        if not isinstance(net, MobileNetV2):
+            raise NotImplementedError("glancer_train_mode: stage 0 trains the ActivityNet glancer's MobileNetV2 only (%s has no backward)"
+                                      % type(net).__name__)
+        self.eval()
+        net.train()
+        net.set_trainable(True)
+        net.set_bn_batch_stats(True)
+
     def backbone_train_mode(self, glancer=False):
         """What the reference's train_mode does for train_stage == 0 (gfv_net.py:65-66), for the backbone stage 0 trains with
         pretrain_glancer=False: the focuser's ResNet goes to train mode, trainable, with BatchNorm on batch statistics
         (ResNet.set_bn_batch_stats); everything else goes to eval mode (nothing else runs in that branch, ACT/main_dist.py:544-548).
-        The loop body is `adafocus_amd.train.train_stage0_batch`.  glancer=True (pretrain_glancer) is out of scope."""
+        The loop body is `adafocus_amd.train.train_stage0_batch`.  glancer=True (pretrain_glancer) is another mode and another loop
+        body: `glancer_train_mode()`."""
         if glancer:
-            raise NotImplementedError("backbone_train_mode(glancer=True): stage 0 for the glancer needs the MobileNetV2 backward, which "
-                                      "is not implemented")
+            raise NotImplementedError("backbone_train_mode(glancer=True): this mode trains the focuser's ResNet; stage 0 for the glancer "
+                                      "(the MobileNetV2 backward) is entered with glancer_train_mode()")
         net = self.focuser.net
         if not hasattr(net, "set_bn_batch_stats"):
             raise NotImplementedError("backbone_train_mode: stage 0 trains a ResNet local CNN only (%s has no backward)" % type(net).__name__)

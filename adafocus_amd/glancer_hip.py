@@ -79,6 +79,11 @@ class GlancerEngine:
         self._net.set_fusion(self.fusion)
         return self._net
 
+    def mark_stale(self):
+        """A kernel wrote into the module's tensors (the training walk's running statistics): sync() keys on tensor versions, which such
+        a write does not move, so the packed copy is dropped by hand."""
+        self._sig = None
+
     def features(self, frames_nhwc4, tsm_segments=0, tsm_div=8, want_vec=True):
         if self.module.training:
             raise RuntimeError("adafocus_amd glancer: eval mode only")

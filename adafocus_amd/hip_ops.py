@@ -504,44 +504,77 @@ def _map2d(t):
     return t.reshape(-1, t.shape[-1])
 
 
-def bn_map_train_forward(x, gamma, beta, running_mean=None, running_var=None, eps=1e-5, momentum=0.1, residual=None, relu=True):
-    """bn_train_forward for tall pixel-major maps (csrc/bn_map.hip, DESIGN 3.14): x (..., cols) dense, the statistics over every leading
-    axis [+ residual of x's shape] [+ ReLU]; running_mean / running_var are updated in place.  cols % 4 == 0.
-    -> (y of x's shape, mean (cols,), invstd (cols,))."""
+def _bn_map_forward(who, sym, flag, x, gamma, beta, running_mean, running_var, eps, momentum, residual):
+    """Both forwards over maps: `sym` with `flag` (the relu flag, or an ACT_* value) in the activation's place."""
     L.need_gpu_f32(x, gamma, beta, running_mean, running_var, residual)
     x2 = _map2d(x)
     rows, cols = x2.shape
     if rows < 2:
         raise ValueError("Expected more than 1 value per channel when training, got input size %s" % (tuple(x.shape),))
     if residual is not None and residual.shape != x.shape:
-        raise ValueError("bn_map_train_forward: the residual has another shape than x")
+        raise ValueError("%s: the residual has another shape than x" % who)
     for r in (running_mean, running_var):
         if r is not None and not r.is_contiguous():
-            raise ValueError("bn_map_train_forward: contiguous running statistics expected (they are updated in place)")
+            raise ValueError("%s: contiguous running statistics expected (they are updated in place)" % who)
     y = torch.empty(x.shape, device=x.device, dtype=torch.float32)
     mean = torch.empty((cols,), device=x.device, dtype=torch.float32)
     invstd = torch.empty((cols,), device=x.device, dtype=torch.float32)
     ws, ws_bytes = _workspace("adaf_bn_map_workspace_bytes", x.device, rows, cols)
-    _call("adaf_bn_map_train_forward_f32", x, x2, rows, cols, gamma.contiguous(), beta.contiguous(), float(eps), float(momentum), running_mean,
-          running_var, _dense(residual), int(bool(relu)), y, mean, invstd, ws, ws_bytes)
+    _call(sym, x, x2, rows, cols, gamma.contiguous(), beta.contiguous(), float(eps), float(momentum), running_mean, running_var, _dense(residual),
+          int(flag), y, mean, invstd, ws, ws_bytes)
     return y, mean, invstd
 
 
-def bn_map_train_backward(x, y, dy, gamma, mean, invstd):
-    """Backward of bn_map_train_forward: y its output after ReLU (None: no ReLU, or dy has its mask applied) -> (dx of x's shape, dgamma,
-    dbeta).  A residual join's second gradient is added in front (relu_backward)."""
+def _bn_map_backward(who, sym, act, x, y, dy, gamma, mean, invstd):
+    """Both backwards over maps: act None is `sym` without an activation operand (the mask is y > 0 where y is given)."""
     L.need_gpu_f32(x, y, dy, gamma, mean, invstd)
     if dy.shape != x.shape or (y is not None and y.shape != x.shape):
-        raise ValueError("bn_map_train_backward: shapes differ")
+        raise ValueError("%s: shapes differ" % who)
     x2 = _map2d(x)
     rows, cols = x2.shape
     dx = torch.empty(x.shape, device=x.device, dtype=torch.float32)
     dgamma = torch.empty((cols,), device=x.device, dtype=torch.float32)
     dbeta = torch.empty((cols,), device=x.device, dtype=torch.float32)
     ws, ws_bytes = _workspace("adaf_bn_map_workspace_bytes", x.device, rows, cols)
-    _call("adaf_bn_map_train_backward_f32", x, x2, _dense(y), dy.contiguous(), rows, cols, gamma.contiguous(), mean.contiguous(),
+    _call(sym, x, x2, _dense(y), *(() if act is None else (int(act),)), dy.contiguous(), rows, cols, gamma.contiguous(), mean.contiguous(),
           invstd.contiguous(), dx, dgamma, dbeta, ws, ws_bytes)
     return dx, dgamma, dbeta
+
+
+def bn_map_train_forward(x, gamma, beta, running_mean=None, running_var=None, eps=1e-5, momentum=0.1, residual=None, relu=True):
+    """bn_train_forward for tall pixel-major maps (csrc/bn_map.hip, DESIGN 3.14): x (..., cols) dense, the statistics over every leading
+    axis [+ residual of x's shape] [+ ReLU]; running_mean / running_var are updated in place.  cols % 4 == 0.
+    -> (y of x's shape, mean (cols,), invstd (cols,))."""
+    return _bn_map_forward("bn_map_train_forward", "adaf_bn_map_train_forward_f32", bool(relu), x, gamma, beta, running_mean, running_var, eps,
+                           momentum, residual)
+
+
+def bn_map_train_backward(x, y, dy, gamma, mean, invstd):
+    """Backward of bn_map_train_forward: y its output after ReLU (None: no ReLU, or dy has its mask applied) -> (dx of x's shape, dgamma,
+    dbeta).  A residual join's second gradient is added in front (relu_backward)."""
+    return _bn_map_backward("bn_map_train_backward", "adaf_bn_map_train_backward_f32", None, x, y, dy, gamma, mean, invstd)
+
+
+_BN_MAP_ACTS = (ACT_NONE, ACT_RELU, ACT_RELU6)
+
+
+def bn_map_train_forward_act(x, gamma, beta, running_mean=None, running_var=None, eps=1e-5, momentum=0.1, residual=None, act=ACT_RELU6):
+    """bn_map_train_forward with an activation in place of the relu flag: act = ACT_NONE, ACT_RELU or ACT_RELU6 (y clipped to [0, 6],
+    MobileNetV2's activation) -> (y, mean, invstd).  ACT_NONE / ACT_RELU give bn_map_train_forward's bits."""
+    if act not in _BN_MAP_ACTS:
+        raise ValueError("bn_map_train_forward_act: act is ACT_NONE, ACT_RELU or ACT_RELU6")
+    return _bn_map_forward("bn_map_train_forward_act", "adaf_bn_map_train_forward_act_f32", act, x, gamma, beta, running_mean, running_var, eps,
+                           momentum, residual)
+
+
+def bn_map_train_backward_act(x, y, dy, gamma, mean, invstd, act=ACT_RELU6):
+    """Backward of bn_map_train_forward_act: y its output (read for ACT_RELU: dy passes where y > 0, and ACT_RELU6: where 0 < y < 6, ATen's
+    hardtanh_backward on the activation's input; not read for ACT_NONE) -> (dx of x's shape, dgamma, dbeta)."""
+    if act not in _BN_MAP_ACTS:
+        raise ValueError("bn_map_train_backward_act: act is ACT_NONE, ACT_RELU or ACT_RELU6")
+    if act != ACT_NONE and y is None:
+        raise ValueError("bn_map_train_backward_act: the mask of an activation needs the forward's output")
+    return _bn_map_backward("bn_map_train_backward_act", "adaf_bn_map_train_backward_act_f32", act, x, y, dy, gamma, mean, invstd)
 
 
 def ppo_encoder_backward(states, e1, e_bt, dx_bt, t, b, w_lin_pm, bn=None):
@@ -604,6 +637,64 @@ def conv2d_wgrad(x, g, w_shape, stride=1, pad=0):
     dw = torch.empty(tuple(w_shape), device=x.device, dtype=torch.float32)
     _call("adaf_conv2d_wgrad_f32", x, C.byref(p), x, g, dw, ws, ws_bytes)
     return dw
+
+
+def conv2d_wgrad_rows(x, g, w_shape, stride=1, pad=0):
+    """conv2d_wgrad for Cout % 4 == 0 (MobileNetV2's 16, 24 and 144 output channels): the same split-K launch with the last block's
+    filter rows bounded at Cout; for Cout % 32 == 0 conv2d_wgrad's bits."""
+    L.need_gpu_f32(x, g)
+    x, g = x.contiguous(), g.contiguous()
+    p, g_shape = _bwd_params(x.shape, w_shape, stride, pad)
+    if tuple(g.shape) != g_shape:
+        raise ValueError("conv2d_wgrad_rows: gradient of shape %s expected, got %s" % (g_shape, tuple(g.shape)))
+    ws, ws_bytes = _workspace("adaf_conv2d_wgrad_rows_workspace_bytes", x.device, C.byref(p))
+    dw = torch.empty(tuple(w_shape), device=x.device, dtype=torch.float32)
+    _call("adaf_conv2d_wgrad_rows_f32", x, C.byref(p), x, g, dw, ws, ws_bytes)
+    return dw
+
+
+def _dw_out_shape(x_shape, stride):
+    n, hh, ww, c = x_shape
+    return (n, (hh - 1) // stride + 1, (ww - 1) // stride + 1, c)
+
+
+def dwconv3x3_dgrad(g, w_33c, x_shape, stride=1):
+    """The gradient at the input of dwconv3x3_bn_act's convolution: g (N,OH,OW,C) the gradient at its output, w_33c of pack_dw_weight,
+    x_shape (N,H,W,C) -> (N,H,W,C).  A gather with a fixed tap order (csrc/dw_bwd.hip)."""
+    L.need_gpu_f32(g, w_33c)
+    g, w_33c = g.contiguous(), w_33c.contiguous()
+    n, hh, ww, c = x_shape
+    if tuple(g.shape) != _dw_out_shape(x_shape, stride) or tuple(w_33c.shape) != (3, 3, c):
+        raise ValueError("dwconv3x3_dgrad: gradient of shape %s and a (3,3,%d) filter expected, got %s and %s"
+                         % (_dw_out_shape(x_shape, stride), c, tuple(g.shape), tuple(w_33c.shape)))
+    dx = torch.empty(tuple(x_shape), device=g.device, dtype=torch.float32)
+    _call("adaf_dwconv3x3_dgrad_f32", g, g, n, hh, ww, c, int(stride), w_33c, dx)
+    return dx
+
+
+def dwconv3x3_wgrad(x, g, stride=1):
+    """The weight gradient of dwconv3x3_bn_act's convolution: x (N,H,W,C) its input, g (N,OH,OW,C) the gradient at its output ->
+    (C,1,3,3), PyTorch's layout.  Slice partials in double, added in a fixed order: the same inputs give the same bits."""
+    L.need_gpu_f32(x, g)
+    x, g = x.contiguous(), g.contiguous()
+    n, hh, ww, c = x.shape
+    if tuple(g.shape) != _dw_out_shape(x.shape, stride):
+        raise ValueError("dwconv3x3_wgrad: gradient of shape %s expected, got %s" % (_dw_out_shape(x.shape, stride), tuple(g.shape)))
+    ws, ws_bytes = _workspace("adaf_dwconv3x3_wgrad_workspace_bytes", x.device, n, hh, ww, c, int(stride))
+    dw = torch.empty((3, 3, c), device=x.device, dtype=torch.float32)
+    _call("adaf_dwconv3x3_wgrad_f32", x, x, g, n, hh, ww, c, int(stride), dw, ws, ws_bytes)
+    return dw.permute(2, 0, 1).reshape(c, 1, 3, 3).contiguous()
+
+
+def add(a, b):
+    """a + b of two dense maps of one shape: the join of two gradients where no activation masks it (relu_backward joins under a mask)."""
+    L.need_gpu_f32(a, b)
+    if a.shape != b.shape:
+        raise ValueError("add: shapes differ")
+    a, b = a.contiguous(), b.contiguous()
+    out = torch.empty_like(a)
+    _call("adaf_add_f32", a, a, b, a.numel(), out)
+    return out
 
 
 def pack_conv_dgrad_weight(w_ohwi, scale=None):

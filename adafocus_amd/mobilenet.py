@@ -63,6 +63,52 @@ class MobileNetV2(nn.Module):
         lin = self.classifier[-1]
         return hip_ops.linear(self.features_nhwc(x)[1], lin.weight.detach(), lin.bias.detach())
 
+    # ---- stage-0 training of the glancer (opt-in) -----------------------------
+    def set_trainable(self, on):
+        """Stage 0 with pretrain_glancer=true (ACT/main_dist.py:534-548): on = ``features_train_nhwc4`` / ``forward_train`` are available,
+        the walk of glancer_train.py with a HIP backward into every conv weight and BatchNorm weight / bias that requires grad.  Off (the
+        default) nothing changes: train mode raises "eval mode only" as before."""
+        self._trainable = bool(on)
+
+    @property
+    def trainable(self):
+        return getattr(self, "_trainable", False)
+
+    def set_bn_batch_stats(self, on):
+        """Opt-in (default off) to BatchNorm on BATCH statistics in the training walk, as the torch module in train mode: the only form
+        the walk has (stage 0 trains the whole network in train mode)."""
+        self._bn_batch_stats = bool(on)
+
+    @property
+    def bn_batch_stats(self):
+        return getattr(self, "_bn_batch_stats", False)
+
+    def _note_stats_written(self):
+        """The running statistics were written by a kernel, which moves no tensor version: the next eval forward folds them anew."""
+        self._engine.mark_stale()
+
+    def features_train_nhwc4(self, frames_nhwc4):
+        """(N,S,S,4) pixel-major frames -> (N,1280), the mean over pixels of the head's map, with an autograd graph into the parameters
+        of ``features``; BatchNorm on the statistics of the batch, running statistics moved once.  Needs set_trainable(True),
+        set_bn_batch_stats(True) and the module in train mode (GFV.glancer_train_mode() sets all three)."""
+        if not self.trainable:
+            raise RuntimeError("adafocus_amd.MobileNetV2: the training walk is off; call set_trainable(True) first")
+        if not (self.training and self.bn_batch_stats):
+            raise NotImplementedError("adafocus_amd.MobileNetV2 trains in train mode on batch statistics only (stage 0; "
+                                      "set_bn_batch_stats(True) and .train()): a walk on frozen statistics is not built")
+        from . import glancer_train
+        return glancer_train.glancer_features(self, frames_nhwc4)
+
+    def forward_train(self, x_nchw, dropout_mask=None):
+        """The module's forward in train mode with a backward (mobilenet.py:150-155): the training walk, Dropout(0.2), the Linear (its
+        forward and backward on the engine).  dropout_mask (N,1280), the multipliers 0 or 1 / (1 - p), replaces the dropout's own draw
+        from torch's device generator."""
+        from .gfv_net_sth import _FcMeanPool
+        feat = self.features_train_nhwc4(nchw_to_nhwc4(x_nchw))
+        drop, lin = self.classifier[0], self.classifier[-1]
+        feat = drop(feat) if dropout_mask is None else feat * dropout_mask.to(device=feat.device, dtype=feat.dtype)
+        return _FcMeanPool.apply(feat, lin.weight, lin.bias, None, feat.shape[0])
+
     def get_featmap(self, x):
         fmap, fvec = self.features_nhwc(x)
         return fmap.permute(0, 3, 1, 2), fvec

@@ -19,6 +19,9 @@ Linear and the local CNN learn (HIP forward and backward, PyTorch's SGD step on 
 pretrain_glancer=False, the branch without AMP): the local CNN and its ``fc`` learn on whole frames with BatchNorm on batch statistics
 (HIP forward and backward).
 
+``train_stage0_glancer_batch`` is the same loop body with pretrain_glancer=True: the glancer's MobileNetV2 and its classifier learn on
+whole frames in train mode (``GFV.glancer_train_mode()``; HIP forward and backward).
+
 ``train_stage1_batch`` is the stage-1 loop body of the ActivityNet tree (ACT/main_dist.py:473-493 without AMP): the frozen glancer, one
 random crop per frame through the local CNN on batch statistics, the GRU classifier, and the cross-entropy of every step
 (``hip_ops.ce_steps``); the local CNN and the classifier learn.
@@ -29,7 +32,7 @@ import torch.nn.functional as F
 from . import hip_ops
 
 __all__ = ["get_reward", "train_stage2_batch", "train_stage2_batch_fused", "train_stage2_batch_sth", "train_stage3_batch_sth",
-           "train_stage0_batch", "train_stage1_batch"]
+           "train_stage0_batch", "train_stage0_glancer_batch", "train_stage1_batch"]
 
 
 def get_reward(args, confidence, confidence_last, baseline):
@@ -151,6 +154,24 @@ def train_stage0_batch(model, images, target, args, optimizer):
     t = tc // 3
     optimizer.zero_grad()
     logits = model.focuser.net.forward_train(images.view(b * t, 3, hh, ww))
+    pred = logits.view(b, t, -1).mean(1, keepdim=True).squeeze(1)
+    loss = F.cross_entropy(pred, target)
+    loss.backward()
+    optimizer.step()
+    return pred.detach(), loss.detach()
+
+
+def train_stage0_glancer_batch(model, images, target, args, optimizer, dropout_mask=None):
+    """One batch of stage-0 training of the glancer's MobileNetV2 (ACT/main_dist.py:544-548 with pretrain_glancer=true;
+    `model.glancer_train_mode()` first, optimizer over model.glancer.net's parameters).  images (B, T*3, H, W) normalised fp32 on the GPU,
+    target (B,) int64.  The frames go through the MobileNetV2 in train mode as one batch of B*T (BatchNorm statistics over all of them,
+    Dropout(0.2) in front of the Linear), the logits are averaged over T, then cross-entropy, backward, optimizer.step(); the gradients
+    are zeroed first (main_dist.py:473).  dropout_mask (B*T, 1280) gives the dropout's multipliers (None: drawn from torch's device
+    generator).  Returns (the prediction (B, C), the loss), detached."""
+    b, tc, hh, ww = images.shape
+    t = tc // 3
+    optimizer.zero_grad()
+    logits = model.glancer.net.forward_train(images.view(b * t, 3, hh, ww), dropout_mask=dropout_mask)
     pred = logits.view(b, t, -1).mean(1, keepdim=True).squeeze(1)
     loss = F.cross_entropy(pred, target)
     loss.backward()

@@ -772,6 +772,44 @@ int adaf_conv_bn_param_grad_f32(adaf_handle* h, const float* g, int pixels, cons
                                 const float* mean, const float* var, float eps, int cout, int kh, int kw, int cin, int cin_pad, float* dw_oihw,
                                 float* dgamma, float* dbeta, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- stage-0 training of the glancer: what MobileNetV2's backward adds (csrc/dw_bwd.hip, csrc/bn_map.hip, csrc/conv_bwd.hip) ----
+ * ACT/main_dist.py:534-548 with pretrain_glancer=true trains the glancer's MobileNetV2 on whole frames in train mode.  fp32, no atomics:
+ * the same inputs give the same bits.  64-bit element offsets throughout.
+ *
+ * adaf_dwconv3x3_dgrad_f32: the data gradient of adaf_dwconv3x3_bn_act_f32's convolution (pad 1, stride 1 or 2), in its layouts:
+ *   dx[n, iy, ix, c] = sum over (kh, kw) of g[n, oy, ox, c] * w_33c[kh, kw, c] over the output pixels with oy s + kh - 1 = iy and
+ *   ox s + kw - 1 = ix.  g [n, oh, ow, c] with oh = (hh - 1) / s + 1, dx [n, hh, ww, c], c % 4 == 0 (else ADAF_E_LAYOUT), g, w_33c, dx
+ *   16-byte aligned.  A gather with a fixed tap order; no zero-inserted copy of g.
+ * adaf_dwconv3x3_wgrad_f32: dw_33c[kh, kw, c] = sum over (n, oy, ox) of g[n, oy, ox, c] * x[n, oy s + kh - 1, ox s + kw - 1, c], taps in the
+ *   padding skipped; the filter layout of adaf_pack_dw_weight_f32.  Slice partials of a strip walk over output pixels, carried in double
+ *   and added in slice order in two levels.  Workspace: adaf_dwconv3x3_wgrad_workspace_bytes(n, hh, ww, c, stride) (0 for a description the
+ *   call refuses); contents undefined on entry and exit.
+ * adaf_bn_map_train_forward_act_f32 / adaf_bn_map_train_backward_act_f32: adaf_bn_map_train_forward_f32 / adaf_bn_map_train_backward_f32
+ *   with an activation in place of the relu flag: ADAF_ACT_NONE, ADAF_ACT_RELU or ADAF_ACT_RELU6 (else ADAF_E_BADARG).  ReLU6 clips y to
+ *   [0, 6]; its backward passes dy where 0 < y < 6 on the stored output, which is 0 < x < 6 on the activation's input (ATen's
+ *   hardtanh_backward).  The backward reads y only for an activation (then it must not be NULL).  With ADAF_ACT_NONE / ADAF_ACT_RELU the
+ *   bits are those of the calls without _act.  Workspace: adaf_bn_map_workspace_bytes.
+ * adaf_conv2d_wgrad_rows_f32: adaf_conv2d_wgrad_f32 for cout % 4 == 0 (MobileNetV2's 16, 24 and 144 output channels): the same split-K
+ *   launch with the last block's filter rows bounded at cout.  For cout % 32 == 0 the bits of adaf_conv2d_wgrad_f32.
+ *   Workspace: adaf_conv2d_wgrad_rows_workspace_bytes(p).
+ * adaf_add_f32: out[i] = a[i] + b[i]: the identity's gradient joins the main path's at an InvertedResidual with use_res_connect (its
+ *   output has no activation; under a ReLU the join is adaf_relu_backward_f32's).  count % 4 == 0, 16-byte aligned; out may be a or b. */
+int adaf_dwconv3x3_dgrad_f32(adaf_handle* h, const float* g, int n, int hh, int ww, int c, int stride, const float* w_33c, float* dx,
+                             void* stream);
+size_t adaf_dwconv3x3_wgrad_workspace_bytes(int n, int hh, int ww, int c, int stride);
+int adaf_dwconv3x3_wgrad_f32(adaf_handle* h, const float* x, const float* g, int n, int hh, int ww, int c, int stride, float* dw_33c, void* ws,
+                             size_t ws_bytes, void* stream);
+int adaf_bn_map_train_forward_act_f32(adaf_handle* h, const float* x, int rows, int cols, const float* gamma, const float* beta, float eps,
+                                      float momentum, float* running_mean, float* running_var, const float* residual, int act, float* y_out,
+                                      float* mean_out, float* invstd_out, void* ws, size_t ws_bytes, void* stream);
+int adaf_bn_map_train_backward_act_f32(adaf_handle* h, const float* x, const float* y, int act, const float* dy, int rows, int cols,
+                                       const float* gamma, const float* mean, const float* invstd, float* dx_out, float* dgamma_out,
+                                       float* dbeta_out, void* ws, size_t ws_bytes, void* stream);
+int adaf_add_f32(adaf_handle* h, const float* a, const float* b, size_t count, float* out, void* stream);
+size_t adaf_conv2d_wgrad_rows_workspace_bytes(const adaf_conv_params* p);
+int adaf_conv2d_wgrad_rows_f32(adaf_handle* h, const adaf_conv_params* p, const float* x, const float* g, float* dw_ohwi, void* ws,
+                               size_t ws_bytes, void* stream);
+
 /* ---- a8: linear classifier + temporal mean ---------------------------------------------
  * nn.Linear + ConsensusModule('avg') (+ glancer mean logits) -- STH/models/gfv_net.py:164-174,
  * STH/ops/basic_ops.py:17-26.  feat [B*T, F]; global_logit [B, Tg, C] or NULL; out [B, C];

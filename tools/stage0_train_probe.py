@@ -99,13 +99,13 @@ def kernels(patches, rounds):
 
 
 class Split:
-    """HIP events around the hip_ops calls of a walk: category -> [(start, end)]."""
+    """HIP events around the hip_ops calls of a walk: category -> [(start, end)].  cats: hip_ops name -> category (None: CATS)."""
 
-    def __init__(self):
-        self.events, self.saved = collections.defaultdict(list), {}
+    def __init__(self, cats=None):
+        self.events, self.saved, self.cats = collections.defaultdict(list), {}, CATS if cats is None else cats
 
     def __enter__(self):
-        for name, cat in CATS.items():
+        for name, cat in self.cats.items():
             fn = self.saved[name] = getattr(hip_ops, name)
 
             def wrapped(*a, _fn=fn, _cat=cat, **k):
