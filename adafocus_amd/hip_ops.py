@@ -625,32 +625,29 @@ def stem7x7_bn_relu(patches_nhwc4, w_oihw, scale, bias):
     return out
 
 
-def conv2d_wgrad(x, g, w_shape, stride=1, pad=0):
-    """The UNSCALED weight gradient of a convolution: x (N,H,W,Cin), g (N,OH,OW,Cout) the gradient at the convolution's output, w_shape
-    (Cout,KH,KW,Cin) -> (Cout,KH,KW,Cin).  Deterministic (same inputs, same bits)."""
+def _conv2d_wgrad(who, x, g, w_shape, stride, pad):
+    """Both split-K weight gradients: the entry point adaf_<who>_f32 with its workspace query."""
     L.need_gpu_f32(x, g)
     x, g = x.contiguous(), g.contiguous()
     p, g_shape = _bwd_params(x.shape, w_shape, stride, pad)
     if tuple(g.shape) != g_shape:
-        raise ValueError("conv2d_wgrad: gradient of shape %s expected, got %s" % (g_shape, tuple(g.shape)))
-    ws, ws_bytes = _workspace("adaf_conv2d_wgrad_workspace_bytes", x.device, C.byref(p))
+        raise ValueError("%s: gradient of shape %s expected, got %s" % (who, g_shape, tuple(g.shape)))
+    ws, ws_bytes = _workspace("adaf_%s_workspace_bytes" % who, x.device, C.byref(p))
     dw = torch.empty(tuple(w_shape), device=x.device, dtype=torch.float32)
-    _call("adaf_conv2d_wgrad_f32", x, C.byref(p), x, g, dw, ws, ws_bytes)
+    _call("adaf_%s_f32" % who, x, C.byref(p), x, g, dw, ws, ws_bytes)
     return dw
+
+
+def conv2d_wgrad(x, g, w_shape, stride=1, pad=0):
+    """The UNSCALED weight gradient of a convolution: x (N,H,W,Cin), g (N,OH,OW,Cout) the gradient at the convolution's output, w_shape
+    (Cout,KH,KW,Cin) -> (Cout,KH,KW,Cin).  Deterministic (same inputs, same bits)."""
+    return _conv2d_wgrad("conv2d_wgrad", x, g, w_shape, stride, pad)
 
 
 def conv2d_wgrad_rows(x, g, w_shape, stride=1, pad=0):
     """conv2d_wgrad for Cout % 4 == 0 (MobileNetV2's 16, 24 and 144 output channels): the same split-K launch with the last block's
     filter rows bounded at Cout; for Cout % 32 == 0 conv2d_wgrad's bits."""
-    L.need_gpu_f32(x, g)
-    x, g = x.contiguous(), g.contiguous()
-    p, g_shape = _bwd_params(x.shape, w_shape, stride, pad)
-    if tuple(g.shape) != g_shape:
-        raise ValueError("conv2d_wgrad_rows: gradient of shape %s expected, got %s" % (g_shape, tuple(g.shape)))
-    ws, ws_bytes = _workspace("adaf_conv2d_wgrad_rows_workspace_bytes", x.device, C.byref(p))
-    dw = torch.empty(tuple(w_shape), device=x.device, dtype=torch.float32)
-    _call("adaf_conv2d_wgrad_rows_f32", x, C.byref(p), x, g, dw, ws, ws_bytes)
-    return dw
+    return _conv2d_wgrad("conv2d_wgrad_rows", x, g, w_shape, stride, pad)
 
 
 def _dw_out_shape(x_shape, stride):

@@ -9,7 +9,7 @@ from torch import nn
 
 from . import hip_ops
 from .glancer_hip import GlancerEngine
-from .utils import nchw_to_nhwc4
+from .utils import TrainOptIn, nchw_to_nhwc4
 
 __all__ = ["MobileNetV2", "mobilenet_v2", "InvertedResidual"]
 
@@ -35,7 +35,7 @@ class InvertedResidual(nn.Module):
         return x + self.conv(x) if self.use_res_connect else self.conv(x)
 
 
-class MobileNetV2(nn.Module):
+class MobileNetV2(TrainOptIn, nn.Module):
     def __init__(self, num_classes=1000):
         super().__init__()
         self.last_channel = 1280
@@ -64,25 +64,8 @@ class MobileNetV2(nn.Module):
         return hip_ops.linear(self.features_nhwc(x)[1], lin.weight.detach(), lin.bias.detach())
 
     # ---- stage-0 training of the glancer (opt-in) -----------------------------
-    def set_trainable(self, on):
-        """Stage 0 with pretrain_glancer=true (ACT/main_dist.py:534-548): on = ``features_train_nhwc4`` / ``forward_train`` are available,
-        the walk of glancer_train.py with a HIP backward into every conv weight and BatchNorm weight / bias that requires grad.  Off (the
-        default) nothing changes: train mode raises "eval mode only" as before."""
-        self._trainable = bool(on)
-
-    @property
-    def trainable(self):
-        return getattr(self, "_trainable", False)
-
-    def set_bn_batch_stats(self, on):
-        """Opt-in (default off) to BatchNorm on BATCH statistics in the training walk, as the torch module in train mode: the only form
-        the walk has (stage 0 trains the whole network in train mode)."""
-        self._bn_batch_stats = bool(on)
-
-    @property
-    def bn_batch_stats(self):
-        return getattr(self, "_bn_batch_stats", False)
-
+    # (the opt-ins set_trainable / set_bn_batch_stats: utils.TrainOptIn.  Stage 0 with pretrain_glancer=true,
+    #  ACT/main_dist.py:534-548, trains the whole network in train mode: batch statistics are the only form the walk of glancer_train.py has)
     def _note_stats_written(self):
         """The running statistics were written by a kernel, which moves no tensor version: the next eval forward folds them anew."""
         self._engine.mark_stale()

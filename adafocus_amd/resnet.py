@@ -12,7 +12,7 @@ import torch
 from torch import nn
 
 from . import hip_ops
-from .utils import nchw_to_nhwc4
+from .utils import TrainOptIn, nchw_to_nhwc4
 
 __all__ = ["ResNet", "resnet50", "resnet101", "resnet152", "Bottleneck", "DEPTHS"]
 
@@ -55,7 +55,7 @@ class Bottleneck(nn.Module):
         raise RuntimeError("Bottleneck is a parameter container; the block runs inside adaf_resnet50_forward")
 
 
-class ResNet(nn.Module):
+class ResNet(TrainOptIn, nn.Module):
     def __init__(self, num_classes=1000, layers=DEPTHS["resnet50"]):
         super().__init__()
         if tuple(layers) not in DEPTHS.values():
@@ -139,27 +139,9 @@ class ResNet(nn.Module):
         """The arithmetic the trunk runs with ("f32" | "split_bf16" | "f16")."""
         return getattr(self, "_math", None) or DEFAULT_MATH
 
-    def set_trainable(self, on):
-        """Stage-3 fine-tuning of the Something-Something tree (STH/stage3.py:189-193): on = ``features_train_nhwc4`` is available, the
-        walk of trunk_train.py with a HIP backward into every conv weight and BatchNorm weight / bias that requires grad.  Off (the
-        default) nothing changes.  fp32 only: with set_math("split_bf16" | "f16") the training walk raises NotImplementedError."""
-        self._trainable = bool(on)
-
-    @property
-    def trainable(self):
-        return getattr(self, "_trainable", False)
-
-    def set_bn_batch_stats(self, on):
-        """Opt-in (default off) to BatchNorm on BATCH statistics in the training walk: with set_trainable(True) and the module in train
-        mode, ``features_train_nhwc4`` normalises every layer with the statistics of its batch and moves the running statistics, as
-        the torch module in train mode does (stage 0 of the ActivityNet tree, ACT/main_dist.py:534-548): the one walk of
-        trunk_train.walk_forward in its batch-statistics form.  In eval mode the walk runs in the frozen form either way.  Off: train mode raises, as before."""
-        self._bn_batch_stats = bool(on)
-
-    @property
-    def bn_batch_stats(self):
-        return getattr(self, "_bn_batch_stats", False)
-
+    # (the opt-ins set_trainable / set_bn_batch_stats: utils.TrainOptIn.  Stage-3 fine-tuning of the Something-Something tree,
+    #  STH/stage3.py:189-193, walks on frozen statistics in eval mode; stage 0 of the ActivityNet tree, ACT/main_dist.py:534-548, DESIGN 3.14,
+    #  on batch statistics in train mode; in eval mode the walk runs in the frozen form either way)
     def _note_stats_written(self):
         """The running statistics were written by a kernel: the next _sync folds them anew."""
         self._stats_written = getattr(self, "_stats_written", 0) + 1

@@ -10,7 +10,7 @@ import torch
 from . import hip_ops
 from ._lib import LAYOUT_NCHW, LAYOUT_NHWC4
 
-__all__ = ["get_patch", "get_patch_nhwc4", "nchw_to_nhwc4"]
+__all__ = ["get_patch", "get_patch_nhwc4", "nchw_to_nhwc4", "TrainOptIn"]
 
 
 def get_patch(images, action_sequence, patch_size):
@@ -33,3 +33,26 @@ def nchw_to_nhwc4(x):
         raise ValueError("nchw_to_nhwc4: square images expected")
     zeros = torch.zeros((x.shape[0], 2), device=x.device, dtype=torch.float32)
     return hip_ops.crop_gather(x, zeros, x.shape[2], 1, LAYOUT_NHWC4)
+
+
+class TrainOptIn:
+    """Mixin of ResNet and MobileNetV2: the two opt-ins their ``features_train_nhwc4`` checks.  Both default to off, and off nothing
+    changes: train mode raises as before."""
+
+    def set_trainable(self, on):
+        """on = ``features_train_nhwc4`` is available: the network's training walk with a HIP backward into every conv weight and
+        BatchNorm weight / bias that requires grad."""
+        self._trainable = bool(on)
+
+    @property
+    def trainable(self):
+        return getattr(self, "_trainable", False)
+
+    def set_bn_batch_stats(self, on):
+        """on = with set_trainable(True) and the module in train mode the walk normalises every layer with the statistics of its batch and
+        moves the running statistics, as the torch module in train mode does (layer_train.BatchForm)."""
+        self._bn_batch_stats = bool(on)
+
+    @property
+    def bn_batch_stats(self):
+        return getattr(self, "_bn_batch_stats", False)
