@@ -76,6 +76,7 @@ PROTOTYPES = {
     "adaf_mobilenetv2_workspace_bytes": (sz, [vp, ip, ip, ip]),
     "adaf_mobilenetv2_forward": (ip, [vp, vp, ip, ip, ip, ip, vp, vp, ip, vp, sz, vp]),
     "adaf_mobilenetv2_set_fusion": (ip, [vp, ip]),
+    "adaf_mobilenetv2_block_forms": (ip, [vp, ip, ip, ip, C.POINTER(ip), ip]),
     "adaf_grid_actions_f32": (ip, [vp, vp, ip, ip, vp, vp, vp, vp]),
     "adaf_gru_seq_forward_f32": (ip, [vp, vp, ip, ip, ip, ip, ip, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
     "adaf_gru_cls_train_workspace_bytes": (sz, [ip, ip, ip]),

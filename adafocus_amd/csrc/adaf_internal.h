@@ -268,7 +268,7 @@ struct MbStemArgs {       // fused stem -> block 1 (t = 1: depthwise + project) 
     int tiles_x, tiles_y, total_tiles;
     const float* zeros;
 };
-void adaf_launch_mb_stem_b1(MbStemArgs a, hipStream_t s);
+void adaf_launch_mb_stem_b1_tile(MbStemArgs a, hipStream_t s);      // mbconv.hip: wave-private tiles (any size)
 bool adaf_mb_stem_b1_strip_ok(int S, int H1);                      // mbstrip.hip
 void adaf_launch_mb_stem_b1_strip(MbStemArgs a, hipStream_t s);
 bool adaf_mb_block_strip_ok(int cin, int hid, int cout, int stride, int h, int w);
@@ -278,7 +278,7 @@ void adaf_launch_mb_expand_dw_strip(MbFuseArgs a, hipStream_t s);
 bool adaf_mb_expand_dw_ok(int cin, int hid, int hw);
 void adaf_launch_mb_expand_dw(MbFuseArgs a, int stride, hipStream_t s);
 bool adaf_mb_block_ok(int cin, int hid, int cout, int stride, int hw);
-void adaf_launch_mb_block(MbFuseArgs a, hipStream_t s);
+void adaf_launch_mb_block_tile(MbFuseArgs a, hipStream_t s);         // stride 1 only (stride 2 has the strip form alone)
 
 #ifdef __HIPCC__
 // Sum over the 64 lanes of a wave; every lane ends up with the same bits.  A butterfly (1, 2, 4, 8, 16, 32) whose first four steps stay on

@@ -609,8 +609,8 @@ bool adaf_mb_block_ok(int cin, int hid, int cout, int stride, int hw) {
            cout <= 32 && hw >= 28;
 }
 
-void adaf_launch_mb_block(MbFuseArgs a, hipStream_t s) {
-    if (adaf_mb_block_strip_ok(a.cin, a.hid, a.cout, a.OH == a.H ? 1 : 2, a.H, a.W)) return adaf_launch_mb_block_strip(a, s);
+// (the wave-private tile form; the strip form is adaf_launch_mb_block_strip -- the caller has decided, mobilenetv2.hip block_form)
+void adaf_launch_mb_block_tile(MbFuseArgs a, hipStream_t s) {
     a.tiles_x = (a.OW + 7) / 8;
     a.tiles_y = (a.OH + 3) / 4;
     const long long tiles = (long long)a.n * a.tiles_x * a.tiles_y;
@@ -620,8 +620,7 @@ void adaf_launch_mb_block(MbFuseArgs a, hipStream_t s) {
     else hipLaunchKernelGGL((mb_block_w_kernel<32>), grid, block, 0, s, a);
 }
 
-void adaf_launch_mb_stem_b1(MbStemArgs a, hipStream_t s) {
-    if (adaf_mb_stem_b1_strip_ok(a.S, a.H1)) return adaf_launch_mb_stem_b1_strip(a, s);
+void adaf_launch_mb_stem_b1_tile(MbStemArgs a, hipStream_t s) {
     a.tiles_x = (a.H1 + 7) / 8;
     a.tiles_y = (a.H1 + 3) / 4;
     a.total_tiles = a.n * a.tiles_x * a.tiles_y;

@@ -134,6 +134,45 @@ MbWorkspace workspace_layout(const adaf_mobilenetv2* net, int n, int size, int t
     return w;
 }
 
+// The launch form of block `bidx` on a `hw` x `hw` input map, from the frame size, the map and the options alone.  THE decision: the forward
+// launches what it says and adaf_mobilenetv2_block_forms reports it (include/adafocus.h has the codes).  Block 0 stands for the stem + block 1
+// pair (hw = the stem's output side): one kernel, on strips or on wave-private tiles -- or the stem conv and block 1 as launches of their own.
+enum { MB_UNFUSED = 0, MB_TILE_XD = 1, MB_TILE_WHOLE = 2, MB_STRIP_WHOLE = 3, MB_STRIP_XD = 4 };
+enum { MB_SHIFT_NONE = 0, MB_SHIFT_STRIP = 1, MB_SHIFT_OPERAND = 2, MB_SHIFT_COPY = 3 };
+struct MbForm { int form, shift; };
+
+MbForm block_form(const adaf_mobilenetv2* net, size_t bidx, int size, int hw, int tsm_segments, int tsm_div) {
+    const MbBlock& b = net->blocks[bidx];
+    MbForm f = {MB_UNFUSED, MB_SHIFT_NONE};
+    if (bidx == 0) {
+        if (net->fuse && b.t == 1 && b.inp == 32 && b.oup == 16 && b.stride == 1) f.form = adaf_mb_stem_b1_strip_ok(size, hw) ? MB_STRIP_WHOLE : MB_TILE_WHOLE;
+        return f;
+    }
+    if (b.expand < 0) return f;
+    const int hid = b.inp * b.t;
+    const bool tile_xd = net->fuse && adaf_mb_expand_dw_ok(b.inp, hid, hw);
+    // the 14 x 14 blocks (64 / 96 input channels): expand -> depthwise on strips (mbstrip.hip), the project conv stays on the engine
+    const bool strip_xd = net->fuse && net->whole && !tile_xd && adaf_mb_expand_dw_strip_ok(b.inp, hid, b.stride, hw, hw);
+    if (tile_xd || strip_xd) {
+        // the whole block in one launch: neither expanded map reaches HBM
+        if (net->whole && adaf_mb_block_ok(b.inp, hid, b.oup, b.stride, hw) && net->convs[b.project].cin_pad == hid)
+            f.form = adaf_mb_block_strip_ok(b.inp, hid, b.oup, b.stride, hw, hw) ? MB_STRIP_WHOLE : MB_TILE_WHOLE;
+        else f.form = strip_xd ? MB_STRIP_XD : MB_TILE_XD;
+    }
+    if (tsm_segments > 0 && b.stride == 1 && b.inp == b.oup) {      // STH/models/gfv_net.py:238-241: residual blocks
+        // the expand -> depthwise strip kernel, whose lanes load whole 4-channel groups of one shift kind (fold % 4 == 0: the 64- / 96-channel blocks):
+        // the shift rides in their pixel loads (MbFuseArgs::tsm_T), nothing is materialised and the identity rows are the input itself
+        // (the whole-block strip kernel of the 32-channel blocks has no register left for the frame offset: 252 of 256; its input stays materialised)
+        // (the kernel gives a frame offset to the first CIN / 4 channels of a pixel only, mbstrip.hip dsh[]: both shifted folds must lie inside them
+        //  -- shift_div >= 8; a wider fold falls through to the materialised copy the whole-block strips read)
+        const int fold = b.inp / tsm_div;
+        if (f.form == MB_STRIP_XD && fold % 4 == 0 && 2 * fold <= b.inp / 4) f.shift = MB_SHIFT_STRIP;
+        else if (f.form == MB_UNFUSED && fold % 4 == 0) f.shift = MB_SHIFT_OPERAND;     // shift fused into the operand load
+        else f.shift = MB_SHIFT_COPY;   // fold not a multiple of 4 channels (24-channel block), or a fused kernel: materialise the shift once
+    }
+    return f;
+}
+
 int run_conv(adaf_mobilenetv2* net, const MbConv& L, const float* in, int n, int hh, int ww, int act, const float* res,
              float* out, int tsm_T, int tsm_div, hipStream_t st) {
     const int oh = cdiv_out(hh, L.k, L.stride, L.k / 2), ow = cdiv_out(ww, L.k, L.stride, L.k / 2);
@@ -197,6 +236,19 @@ size_t adaf_mobilenetv2_workspace_bytes(const adaf_mobilenetv2* net, int n, int 
     return (!net || n <= 0 || size <= 0) ? 0 : workspace_layout(net, n, size, tsm_segments, nullptr).bytes;
 }
 
+int adaf_mobilenetv2_block_forms(const adaf_mobilenetv2* net, int size, int tsm_segments, int tsm_div, int* forms, int count) {
+    if (!net || !forms) return ADAF_E_BADARG;
+    if (size < 32 || count < (int)net->blocks.size()) return adaf_fail(net->h, ADAF_E_BADARG, "mobilenetv2 block_forms: need size >= 32 and room for 17 entries");
+    if (tsm_segments > 0 && tsm_div <= 0) return adaf_fail(net->h, ADAF_E_BADARG, "mobilenetv2 block_forms: tsm_div <= 0");
+    int hw = cdiv_out(size, 3, 2, 1);
+    for (size_t bidx = 0; bidx < net->blocks.size(); ++bidx) {
+        const MbForm f = block_form(net, bidx, size, hw, tsm_segments, tsm_div);
+        forms[bidx] = f.form | (f.shift << 4);
+        hw = cdiv_out(hw, 3, net->blocks[bidx].stride, 1);
+    }
+    return ADAF_OK;
+}
+
 int adaf_mobilenetv2_forward(adaf_mobilenetv2* net, const float* frames_nhwc4, int n, int size, int tsm_segments,
                              int tsm_div, float* featmap, float* featvec, int ldvec, void* ws, size_t ws_bytes,
                              void* stream) {
@@ -219,16 +271,17 @@ int adaf_mobilenetv2_forward(adaf_mobilenetv2* net, const float* frames_nhwc4, i
         float* cur = bufA;
         float* nxt = bufB;
         size_t first_block = 0;
-        const MbBlock& b1 = net->blocks[0];
-        if (net->fuse && b1.t == 1 && b1.inp == 32 && b1.oup == 16 && b1.stride == 1) {
-            // stem + block 1 in one kernel: the two 32-channel maps at the stem's resolution never reach HBM
+        const int sform = block_form(net, 0, size, hw, tsm_segments, tsm_div).form;
+        if (sform != MB_UNFUSED) {      // stem + block 1 in one kernel: the two 32-channel maps at the stem's resolution never reach HBM
+            const MbBlock& b1 = net->blocks[0];
             const MbConv &S = net->convs[net->stem], &D = net->convs[b1.dw], &P = net->convs[b1.project];
             MbStemArgs sa;
             memset(&sa, 0, sizeof(sa));
             sa.x = frames_nhwc4 + (size_t)f0 * size * size * 4; sa.n = nc; sa.S = size; sa.H1 = hw;
             sa.ws = S.w; sa.ss = S.scale; sa.bs = S.bias; sa.wd = D.w; sa.sd = D.scale; sa.bd = D.bias;
             sa.wp = P.w; sa.sp = P.scale; sa.bp = P.bias; sa.out = bufA; sa.zeros = net->h->zeros;
-            adaf_launch_mb_stem_b1(sa, st);
+            if (sform == MB_STRIP_WHOLE) adaf_launch_mb_stem_b1_strip(sa, st);
+            else adaf_launch_mb_stem_b1_tile(sa, st);
             first_block = 1;
         } else if ((rc = run_conv(net, net->convs[net->stem], frames_nhwc4 + (size_t)f0 * size * size * 4, nc, size, size,
                                   ADAF_ACT_RELU6, nullptr, bufA, 0, 0, st)))
@@ -239,31 +292,15 @@ int adaf_mobilenetv2_forward(adaf_mobilenetv2* net, const float* frames_nhwc4, i
             const bool residual = b.stride == 1 && b.inp == b.oup;
             const float* dw_in = cur;
             const MbConv& D = net->convs[b.dw];
-            bool fused = false;
+            const MbForm f = block_form(net, bidx, size, hw, tsm_segments, tsm_div);      // (bidx 0: block 1 behind the stem conv, unfused)
+            const bool fused = f.form != MB_UNFUSED;
             if (b.expand >= 0) {
                 const MbConv& E = net->convs[b.expand];
-                const bool tsm = tsm_segments > 0 && residual;      // STH/models/gfv_net.py:238-241
-                fused = net->fuse && adaf_mb_expand_dw_ok(b.inp, hid, hw);
-                // the 14 x 14 blocks (64 / 96 input channels): expand -> depthwise on strips (mbstrip.hip), the project conv stays on the engine
-                const bool strip_xd = net->fuse && net->whole && !fused && adaf_mb_expand_dw_strip_ok(b.inp, hid, b.stride, hw, hw);
-                if (strip_xd) fused = true;
                 const float* ein = cur;
-                int fused_T = 0, strip_T = 0;
-                // the expand -> depthwise strip kernel, whose lanes load whole 4-channel groups of one shift kind (fold % 4 == 0: the 64- / 96-channel blocks):
-                // the shift rides in their pixel loads (MbFuseArgs::tsm_T), nothing is materialised and the identity rows are the input itself
-                // (the whole-block strip kernel of the 32-channel blocks has no register left for the frame offset: 252 of 256; its input stays materialised)
-                // (the kernel gives a frame offset to the first CIN / 4 channels of a pixel only, mbstrip.hip dsh[]: both shifted folds must lie inside them
-                //  -- shift_div >= 8; a wider fold falls through to the materialised copy the whole-block strips read)
-                const int fold = tsm_div > 0 ? b.inp / tsm_div : 0;
-                const bool strip_shift = tsm && strip_xd && fold % 4 == 0 && 2 * fold <= b.inp / 4;
-                if (strip_shift) strip_T = tsm_segments;
-                else if (tsm) {
-                    if (!fused && (b.inp / tsm_div) % 4 == 0) fused_T = tsm_segments;   // shift fused into the operand load
-                    else {   // fold not a multiple of 4 channels (24-channel block), or the fused kernel: materialise the shift once
-                        float* sh = fused ? bufE : bufD;
-                        adaf_launch_tshift(cur, nc, b.inp, hw * hw, tsm_segments, tsm_div, ADAF_LAYOUT_NHWC, sh, st);
-                        ein = sh;
-                    }
+                if (f.shift == MB_SHIFT_COPY) {      // into the slab the block's own launches leave free
+                    float* sh = fused ? bufE : bufD;
+                    adaf_launch_tshift(cur, nc, b.inp, hw * hw, tsm_segments, tsm_div, ADAF_LAYOUT_NHWC, sh, st);
+                    ein = sh;
                 }
                 if (fused) {
                     MbFuseArgs fa;
@@ -272,22 +309,22 @@ int adaf_mobilenetv2_forward(adaf_mobilenetv2* net, const float* frames_nhwc4, i
                     fa.we = E.w; fa.se = E.scale; fa.be = E.bias; fa.wd = D.w; fa.sd = D.scale; fa.bd = D.bias;
                     fa.out = bufD; fa.hid = hid; fa.OH = fa.OW = cdiv_out(hw, 3, b.stride, 1);
                     fa.zeros = net->h->zeros;
-                    fa.tsm_T = strip_T; fa.tsm_fold = strip_T ? b.inp / tsm_div : 0;
-                    const MbConv& P = net->convs[b.project];
-                    if (net->whole && adaf_mb_block_ok(b.inp, hid, b.oup, b.stride, hw) && P.cin_pad == hid) {
-                        // the whole block in one launch: neither expanded map reaches HBM
+                    fa.tsm_T = f.shift == MB_SHIFT_STRIP ? tsm_segments : 0; fa.tsm_fold = fa.tsm_T ? b.inp / tsm_div : 0;
+                    if (f.form == MB_STRIP_WHOLE || f.form == MB_TILE_WHOLE) {
+                        const MbConv& P = net->convs[b.project];
                         fa.wp = P.w; fa.sp = P.scale; fa.bp = P.bias; fa.cout = b.oup;
                         fa.res = residual ? cur : nullptr;
                         fa.out2 = nxt;
-                        adaf_launch_mb_block(fa, st);
+                        if (f.form == MB_STRIP_WHOLE) adaf_launch_mb_block_strip(fa, st);
+                        else adaf_launch_mb_block_tile(fa, st);
                         float* t = cur; cur = nxt; nxt = t;
                         hw = fa.OH;
                         continue;
                     }
-                    if (strip_xd) adaf_launch_mb_expand_dw_strip(fa, st);
+                    if (f.form == MB_STRIP_XD) adaf_launch_mb_expand_dw_strip(fa, st);
                     else adaf_launch_mb_expand_dw(fa, b.stride, st);
                 } else {
-                    if ((rc = run_conv(net, E, ein, nc, hw, hw, ADAF_ACT_RELU6, nullptr, bufE, fused_T, tsm_div, st)))
+                    if ((rc = run_conv(net, E, ein, nc, hw, hw, ADAF_ACT_RELU6, nullptr, bufE, f.shift == MB_SHIFT_OPERAND ? tsm_segments : 0, tsm_div, st)))
                         return adaf_fail(h, rc, "mobilenetv2: expand launch");
                     dw_in = bufE;
                 }

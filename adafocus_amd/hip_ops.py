@@ -1083,6 +1083,16 @@ class MobileNetV2Net(_NetEngine):
         # expand -> depthwise kernel + project launch instead of the whole-block kernel of b3 / b5 / b6 (A/B switches)
         self._call("set_fusion", int(on), stream=False)
 
+    def block_forms(self, size, tsm_segments=0, tsm_div=8):
+        """The launch form forward() takes per block at size x size frames under the current set_fusion bits and the global option
+        "mb_strip" (adaf_mobilenetv2_block_forms: the decision function of the forward itself; launches nothing).  17 ints: [0] the stem +
+        block 1 pair, [i] block b<i+1>.  Low nibble: 0 separate launches, 1 tile expand -> depthwise, 2 tile whole block, 3 strip whole
+        block, 4 strip expand -> depthwise; second nibble, the temporal shift: 0 none, 1 in the strip loads, 2 in the operand load,
+        3 materialised."""
+        forms = (C.c_int * 17)()
+        self._call("block_forms", int(size), int(tsm_segments), int(tsm_div), forms, 17, stream=False)
+        return list(forms)
+
     def forward(self, frames_nhwc4, tsm_segments=0, tsm_div=8, want_vec=True):
         """(N,S,S,4) -> featmap (N,S/32,S/32,1280) NHWC, featvec (N,1280) or None."""
         L.need_gpu_f32(frames_nhwc4)

@@ -407,6 +407,14 @@ int adaf_mobilenetv2_forward(adaf_mobilenetv2* net, const float* frames_nhwc4, i
  * of the 14 x 14 blocks b8 .. b13 (bit 3 set: b2 .. b6 and b8 .. b13 fall back to the wave-private kernels / separate launches).  Same bits as every
  * other combination. */
 int adaf_mobilenetv2_set_fusion(adaf_mobilenetv2* net, int on);
+/* Read-only: the launch form a forward of `size` x `size` frames takes for each block under the current set_fusion bits and the global
+ * option "mb_strip" -- the forward consults the same function, so this is what runs.  Writes 17 entries (count >= 17, else ADAF_E_BADARG):
+ * forms[0] the stem + block 1 pair, forms[i] block i + 1 (b2 .. b17).  Low nibble, the form: 0 separate launches (conv engine + depthwise
+ * kernel), 1 wave-private tile kernel expand -> depthwise + a project launch, 2 tile kernel for the whole block, 3 strip kernel for the
+ * whole block, 4 strip kernel expand -> depthwise + a project launch (the stem entry: 0, 2 or 3).  Second nibble ((forms[i] >> 4) & 15), the
+ * temporal shift of the block's input (tsm_segments > 0, residual blocks): 0 none, 1 inside the strip kernel's pixel loads, 2 inside the
+ * expand conv's operand load, 3 materialised by a copy in front of the block.  Launches nothing; needs no finalize. */
+int adaf_mobilenetv2_block_forms(const adaf_mobilenetv2* net, int size, int tsm_segments, int tsm_div, int* forms, int count);
 
 /* ---- N2 / BASELINE config 5: EfficientNet (MBConv with squeeze-and-excite) as the local CNN --------------------------
  * PARITY UNPINNED: the reference has no EfficientNet on a live path.  It names the third-party package

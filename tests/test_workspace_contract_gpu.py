@@ -284,6 +284,9 @@ M_CASES += [MCase(224, 4, 4, d, True, st) for d in (8, 4) for st in (0, 1)]     
 M_CASES += [MCase(96, 3, align=True)]
 M_CASES += [MCase(32, 520, 8, chunk=1024, big=True), MCase(32, 513, chunk=1024, big=True)]     # 512 <= n <= chunk: halves of 264 + 256 (whole clips), 257 + 256
 M_CASES += [MCase(32, 520, 8, big=True)]                               # the default chunk of 512: 512 + 8 frames side by side
+# odd maps (113: 57, 29, 15, 8, 4; 196: 98, 49, 25, 13, 7) and strip blocks handing over to tile kernels (168: 84, 42, 21, 11, 6): where cdiv_out and a
+# hand-written maximum could part ways (tests/test_glancer_sizes_gpu.py has the plans of these sizes)
+M_CASES += [MCase(s, 2, strip=st) for s in (113, 168, 196) for st in (0, 1)] + [MCase(168, 4, 2, 8)]
 
 
 def _mid(c):
