@@ -17,6 +17,7 @@ LAYOUT_NCHW, LAYOUT_NHWC, LAYOUT_NHWC4 = 0, 1, 2
 ACT_NONE, ACT_RELU, ACT_RELU6, ACT_SIGMOID, ACT_SWISH = 0, 1, 2, 3, 4
 MATH_F32, MATH_F32_SPLIT_BF16, MATH_F16 = 0, 1, 2
 DTYPE_F32, DTYPE_F16 = 0, 1
+STEM_FORM_AUTO, STEM_FORM_TILE4, STEM_FORM_TILE6, STEM_FORM_STRIP, STEM_FORM_UNFUSED = range(5)
 CONV_TILES = 4
 
 
@@ -134,6 +135,10 @@ PROTOTYPES = {
     "adaf_effnet_forward": (ip, [vp, vp, ip, ip, ip, ip, vp, vp, vp, ip, vp, sz, vp]),
     "adaf_stem7x7_workspace_bytes": (sz, []),
     "adaf_stem7x7_bn_relu_f32": (ip, [vp, vp, ip, ip, vp, vp, vp, vp, vp, sz, vp]),
+    "adaf_stem7x7_pool_form": (ip, [vp, ip, ip]),
+    "adaf_stem7x7_pool": (ip, [vp, vp, ip, ip, vp, vp, vp, ip, ip, vp, vp, C.POINTER(ip), vp, sz, vp]),
+    "adaf_stem7x7_pool_frames": (ip, [vp, vp, ip, ip, ip, ip, vp, ip, ip, ip, vp, vp, vp, ip, vp, vp, sz, vp]),
+    "adaf_maxpool3x3s2_f16out": (ip, [vp, vp, ip, ip, ip, ip, vp, vp]),
     "adaf_conv2d_wgrad_workspace_bytes": (sz, [C.POINTER(ConvParams)]),
     "adaf_conv2d_wgrad_f32": (ip, [vp, C.POINTER(ConvParams), vp, vp, vp, vp, sz, vp]),
     "adaf_pack_conv_dgrad_weight_f32": (ip, [vp, vp, vp, ip, ip, ip, ip, vp, vp]),

@@ -448,7 +448,11 @@ bool adaf_stem7x7_rows_ok(int P, int n, int cus);   // the strip-walking stem + 
 // the same launch gathering its own windows from planar frames [n, 3, H, W] at floor(action * (H - P)) (get_patch folded in); false = not available
 // out16: the pooled map is stored as fp16 (one rounding of the fp32 result; ADAF_MATH_F16), `out` then holds halfs
 bool adaf_launch_stem7x7_pool_frames(const float* frames, bool pixel_major, int nframes, const float* act, int fpa, int H, int W, int n, int P,
-                                     const float* wr, const float* scale, const float* bias, float* out, int cus, hipStream_t s, bool out16 = false);
+                                     const float* wr, const float* scale, const float* bias, float* out, int cus, hipStream_t s, bool out16 = false,
+                                     bool any_n = false);   // any_n (the adaf_stem7x7_pool_frames export): also below one image per CU
 bool adaf_stem7x7_pool_pays(int P);     // does the fused stem + max-pool launch beat the two separate ones at this patch size
-void adaf_launch_stem7x7_pool(const float* x4, int n, int P, const float* wr, const float* scale, const float* bias, float* out,
-                              int cus, hipStream_t s, bool out16 = false);
+// the stem's launch form for n patches of P^2 (ADAF_STEM_FORM_STRIP / TILE6 / TILE4 / UNFUSED, include/adafocus.h): the one decision of the walk and of adaf_stem7x7_pool
+int adaf_stem7x7_plan(int P, int n, int cus, bool fuse, bool fuse_always);
+// form: ADAF_STEM_FORM_AUTO, or one kernel forced (STRIP / TILE4 / TILE6) at any n; false = a forced strip form at a size without one
+bool adaf_launch_stem7x7_pool(const float* x4, int n, int P, const float* wr, const float* scale, const float* bias, float* out,
+                              int cus, hipStream_t s, bool out16 = false, int form = 0);

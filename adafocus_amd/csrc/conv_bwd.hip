@@ -383,6 +383,88 @@ int adaf_stem7x7_bn_relu_f32(adaf_handle* h, const float* patches_nhwc4, int n, 
     return e == hipSuccess ? ADAF_OK : adaf_hip_fail(h, e, "stem7x7 launch");
 }
 
+// The pooled forms of the stem, each on its own: the launchers of the trunk's walk (stem.hip) with the form of adaf_stem7x7_plan or a forced one.
+int adaf_stem7x7_pool_form(const adaf_handle* h, int n, int patch) {
+    if (!h || n <= 0 || patch <= 0) return 0;
+    return adaf_stem7x7_plan(patch, n, h->cus, true, false);
+}
+
+static int stem_pool_operands(adaf_handle* h, const char* who, const void* x, const float* w_oihw, const float* scale, const float* bias, int out_dtype,
+                              const void* out, void* ws, size_t ws_bytes) {
+    if (!x || !w_oihw || !scale || !bias || !out || !ws) return adaf_fail(h, ADAF_E_BADARG, "%s: null pointer", who);
+    if (out_dtype != ADAF_DTYPE_F32 && out_dtype != ADAF_DTYPE_F16) return adaf_fail(h, ADAF_E_BADARG, "%s: out_dtype %d", who, out_dtype);
+    if (!adaf_aligned16(x) || !adaf_aligned16(out) || !adaf_aligned16(scale) || !adaf_aligned16(bias)) return adaf_fail(h, ADAF_E_LAYOUT, "%s: 16-byte alignment", who);
+    return adaf_check_ws(h, who, ws, ws_bytes, adaf_stem7x7_workspace_bytes(), ADAF_WS_ALIGN_FIRST);
+}
+
+int adaf_stem7x7_pool(adaf_handle* h, const float* patches_nhwc4, int n, int patch, const float* w_oihw, const float* scale, const float* bias,
+                      int form, int out_dtype, void* out, float* conv_map, int* form_used, void* ws, size_t ws_bytes, void* stream) {
+    if (!h) return ADAF_E_BADARG;
+    if (n <= 0 || patch <= 0) return adaf_fail(h, ADAF_E_BADARG, "stem7x7_pool: non-positive extent");
+    if ((long long)n * patch * patch > 0x7fffffffLL) return adaf_fail(h, ADAF_E_BADARG, "stem7x7_pool: too many pixels");
+    if (form < ADAF_STEM_FORM_AUTO || form > ADAF_STEM_FORM_UNFUSED) return adaf_fail(h, ADAF_E_BADARG, "stem7x7_pool: form %d", form);
+    int rc = stem_pool_operands(h, "stem7x7_pool", patches_nhwc4, w_oihw, scale, bias, out_dtype, out, ws, ws_bytes);
+    if (rc) return rc;
+    if (form == ADAF_STEM_FORM_AUTO) form = adaf_stem7x7_pool_form(h, n, patch);
+    if (form == ADAF_STEM_FORM_STRIP && patch != 64 && patch != 96 && patch != 128 && patch != 144)
+        return adaf_fail(h, ADAF_E_BADARG, "stem7x7_pool: the strip kernel exists for patches of 64, 96, 128 and 144, not %d", patch);
+    if (form == ADAF_STEM_FORM_UNFUSED && (!conv_map || !adaf_aligned16(conv_map)))
+        return adaf_fail(h, ADAF_E_BADARG, "stem7x7_pool: the unfused form needs a 16-byte aligned conv_map [n, oh, oh, 64]");
+    hipStream_t st = (hipStream_t)stream;
+    const bool f16 = out_dtype == ADAF_DTYPE_F16;
+    const float* wr = static_cast<const float*>(ws);
+    adaf_launch_pack_stem_weight(w_oihw, static_cast<float*>(ws), st);
+    if (form == ADAF_STEM_FORM_UNFUSED) {
+        const int oh = (patch - 1) / 2 + 1;
+        adaf_launch_stem7x7(patches_nhwc4, n, patch, wr, scale, bias, conv_map, h->cus, st);
+        if (f16) adaf_launch_maxpool_f16out(conv_map, n, oh, oh, 64, out, st);
+        else adaf_launch_maxpool(conv_map, n, oh, oh, 64, static_cast<float*>(out), st);
+    } else if (!adaf_launch_stem7x7_pool(patches_nhwc4, n, patch, wr, scale, bias, static_cast<float*>(out), h->cus, st, f16, form)) {
+        return adaf_fail(h, ADAF_E_LAUNCH, "stem7x7_pool: no kernel of form %d at patch %d", form, patch);
+    }
+    if (form_used) *form_used = form;
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? ADAF_OK : adaf_hip_fail(h, e, "stem7x7_pool launch");
+}
+
+int adaf_stem7x7_pool_frames(adaf_handle* h, const float* frames, int frames_layout, int n_frames, int height, int width, const float* action_yx,
+                             int n_actions, int frames_per_action, int patch, const float* w_oihw, const float* scale, const float* bias,
+                             int out_dtype, void* out, void* ws, size_t ws_bytes, void* stream) {
+    if (!h) return ADAF_E_BADARG;
+    if (!action_yx || n_frames <= 0 || n_actions <= 0 || frames_per_action <= 0 || height <= 0 || width <= 0)
+        return adaf_fail(h, ADAF_E_BADARG, "stem7x7_pool_frames: null pointer or empty batch");
+    if (frames_layout != ADAF_LAYOUT_NCHW && frames_layout != ADAF_LAYOUT_NHWC4)
+        return adaf_fail(h, ADAF_E_LAYOUT, "stem7x7_pool_frames: frames must be NCHW (3 planes) or NHWC4");
+    if (n_frames % frames_per_action) return adaf_fail(h, ADAF_E_BADARG, "stem7x7_pool_frames: n_frames %% frames_per_action != 0");
+    const int per_set = n_frames / frames_per_action;
+    if (n_actions % per_set)
+        return adaf_fail(h, ADAF_E_BADARG, "stem7x7_pool_frames: n_actions=%d is not a multiple of n_frames / frames_per_action=%d", n_actions, per_set);
+    if (width < height) return adaf_fail(h, ADAF_E_BADARG, "stem7x7_pool_frames: width %d < height %d (get_patch scales both axes by H - P)", width, height);
+    if (patch != 64 && patch != 96 && patch != 128 && patch != 144)
+        return adaf_fail(h, ADAF_E_BADARG, "stem7x7_pool_frames: the strip kernel exists for patches of 64, 96, 128 and 144, not %d", patch);
+    if (patch > height) return adaf_fail(h, ADAF_E_BADARG, "stem7x7_pool_frames: patch %d larger than the frames' height %d", patch, height);
+    const long long n = (long long)(n_actions / per_set) * n_frames;        // one patch per (action set, frame)
+    if (n * patch * patch > 0x7fffffffLL || (long long)n_frames * height * width > 0x7fffffffLL) return adaf_fail(h, ADAF_E_BADARG, "stem7x7_pool_frames: too many pixels");
+    int rc = stem_pool_operands(h, "stem7x7_pool_frames", frames, w_oihw, scale, bias, out_dtype, out, ws, ws_bytes);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    adaf_launch_pack_stem_weight(w_oihw, static_cast<float*>(ws), st);
+    if (!adaf_launch_stem7x7_pool_frames(frames, frames_layout == ADAF_LAYOUT_NHWC4, n_frames, action_yx, frames_per_action, height, width, (int)n, patch,
+                                         static_cast<const float*>(ws), scale, bias, static_cast<float*>(out), h->cus, st, out_dtype == ADAF_DTYPE_F16, true))
+        return adaf_fail(h, ADAF_E_LAUNCH, "stem7x7_pool_frames: no gathering kernel for this geometry");
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? ADAF_OK : adaf_hip_fail(h, e, "stem7x7_pool_frames launch");
+}
+
+int adaf_maxpool3x3s2_f16out(adaf_handle* h, const float* x, int n, int hh, int ww, int c, void* out_f16, void* stream) {
+    if (!h) return ADAF_E_BADARG;
+    if (!x || !out_f16 || n <= 0 || hh <= 0 || ww <= 0 || c <= 0) return adaf_fail(h, ADAF_E_BADARG, "maxpool_f16out: bad arguments");
+    if (c % 4 || !adaf_aligned16(x) || ((uintptr_t)out_f16 & 7)) return adaf_fail(h, ADAF_E_LAYOUT, "maxpool_f16out: c %% 4, 16-byte aligned x and 8-byte aligned out required");
+    adaf_launch_maxpool_f16out(x, n, hh, ww, c, out_f16, (hipStream_t)stream);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? ADAF_OK : adaf_hip_fail(h, e, "maxpool_f16out launch");
+}
+
 size_t adaf_conv_bn_param_grad_workspace_bytes(int cout) {
     if (cout <= 0) return 0;
     AdafCarver c(nullptr);

@@ -210,13 +210,15 @@ int walk_trunk(adaf_resnet50* net, const float* x4, int n, int P, int tsm_T, int
     const double stem_flops = 2.0 * (double)n * s1 * s1 * 64 * 147;
     const double stem_in = 4.0 * ((double)n * P * P * 3 + 64.0 * 147), conv_map = 4.0 * (double)n * s1 * s1 * 64, pool_map = eb * (double)n * ph * ph * 64;
     const bool stem_kernel = net->tiles[0] == 0;   // (a tile override != 0 runs the stem on the generic engine instead; set_tiles refuses one for the fp16 trunk)
+    // one launch (the strip or the tile kernel: the conv map never reaches HBM) or two: adaf_stem7x7_plan decides, here and for adaf_stem7x7_pool
+    const int stem_form = stem_kernel ? adaf_stem7x7_plan(P, n, h->cus, fuse, net->fuse_stem_always) : ADAF_STEM_FORM_UNFUSED;
     int rc;
     bool gathered = false;
     if (src) {
         // the patches are windows of resident frames at floor(action * (H - P)) (get_patch, ACT/models/utils.py:37-51).  The strip-walking
         // stem kernel gathers them itself -- no gather launch, no patch tensor; where it does not apply (other patch sizes, small batches,
         // fusion off, a stem tile override) the gather runs into a free workspace slab first: same values either way.
-        if (stem_kernel && fuse && adaf_stem7x7_rows_ok(P, n, h->cus)) {
+        if (stem_form == ADAF_STEM_FORM_STRIP) {
             mark(stem_flops, stem_in + pool_map, 94);
             gathered = adaf_launch_stem7x7_pool_frames(src->frames, src->pixel_major, src->nframes, src->act, src->fpa, src->H, src->W, n, P,
                                                        net->stem_w, L0.scale, L0.bias, buf[1], h->cus, st, f16);
@@ -235,9 +237,10 @@ int walk_trunk(adaf_resnet50* net, const float* x4, int n, int P, int tsm_T, int
         }
     }
     if (gathered) {
-    } else if (stem_kernel && fuse && (adaf_stem7x7_pool_pays(P) || adaf_stem7x7_rows_ok(P, n, h->cus) || net->fuse_stem_always)) {   // both in one launch: the conv map never reaches HBM
+    } else if (stem_form != ADAF_STEM_FORM_UNFUSED) {
         mark(stem_flops, stem_in + pool_map, 90);
-        adaf_launch_stem7x7_pool(x4, n, P, net->stem_w, L0.scale, L0.bias, buf[1], h->cus, st, f16);
+        if (!adaf_launch_stem7x7_pool(x4, n, P, net->stem_w, L0.scale, L0.bias, buf[1], h->cus, st, f16, stem_form))
+            return adaf_fail(h, ADAF_E_LAUNCH, "resnet50%s: no strip stem kernel at patch %d", tag, P);
     } else {
         if (stem_kernel) {   // specialised stem kernel
             mark(stem_flops, stem_in + conv_map, 40);

@@ -541,30 +541,46 @@ bool adaf_stem7x7_pool_pays(int P) {
 }
 
 // the strip-walking form: instantiated patch sizes, and a block owns whole images -- below one image per CU the tile form spreads better
+static bool rows_size(int P) { return P == 64 || P == 96 || P == 128 || P == 144; }
 bool adaf_stem7x7_rows_ok(int P, int n, int cus) {
     const int mode = adaf_options().stem_rows;      // 0 = off, 1 = default, 2 = at every image count (tests)
     if (!mode) return false;
-    return (P == 64 || P == 96 || P == 128 || P == 144) && (n >= cus || mode == 2);
+    return rows_size(P) && (n >= cus || mode == 2);
+}
+
+// The stem's launch form, decided once: the trunk's walk and the adaf_stem7x7_pool export both ask here.  Fusion off: two launches.  Else the
+// strip kernel where it applies, else the tile kernel where its 6-row tiles are the cheaper cover (adaf_stem7x7_pool_pays: the fused launch
+// wins there) -- or, with `fuse_always` (tests), at every size with the cheaper of the two tile heights -- else two launches.
+int adaf_stem7x7_plan(int P, int n, int cus, bool fuse, bool fuse_always) {
+    if (!fuse) return ADAF_STEM_FORM_UNFUSED;
+    if (adaf_stem7x7_rows_ok(P, n, cus)) return ADAF_STEM_FORM_STRIP;
+    if (adaf_stem7x7_pool_pays(P)) return ADAF_STEM_FORM_TILE6;
+    return fuse_always ? ADAF_STEM_FORM_TILE4 : ADAF_STEM_FORM_UNFUSED;
 }
 
 bool adaf_launch_stem7x7_pool_frames(const float* frames, bool pixel_major, int nframes, const float* act, int fpa, int H, int W, int n, int P,
-                                     const float* wr, const float* scale, const float* bias, float* out, int cus, hipStream_t s, bool out16) {
-    if (!adaf_stem7x7_rows_ok(P, n, cus) || !act || fpa < 1 || nframes < 1 || H < P || W < P) return false;
+                                     const float* wr, const float* scale, const float* bias, float* out, int cus, hipStream_t s, bool out16,
+                                     bool any_n) {
+    if (!(any_n ? rows_size(P) : adaf_stem7x7_rows_ok(P, n, cus)) || !act || fpa < 1 || nframes < 1 || H < P || W < P) return false;
     StemArgs a;
     a.x = frames; a.act = act; a.fpa = fpa; a.H = H; a.W = W; a.nframes = nframes; a.w = wr; a.scale = scale; a.bias = bias; a.out = out;
     a.n = n; a.P = P; a.OH = P / 2; a.OW = a.OH; a.PH = a.OH / 2; a.PW = a.PH; a.tiles_y = a.tiles_x = a.ntiles = 0;
     return pixel_major ? launch_rows_for<2>(a, cus, s, out16) : launch_rows_for<1>(a, cus, s, out16);
 }
 
-// conv 7x7/2 + BN + ReLU + max-pool 3x3/2/1 in one launch: out [n, PH, PW, 64] with PH = (OH - 1) / 2 + 1
-void adaf_launch_stem7x7_pool(const float* x4, int n, int P, const float* wr, const float* scale, const float* bias, float* out,
-                              int cus, hipStream_t s, bool out16) {
+// conv 7x7/2 + BN + ReLU + max-pool 3x3/2/1 in one launch: out [n, PH, PW, 64] with PH = (OH - 1) / 2 + 1.  `form`: ADAF_STEM_FORM_AUTO = the
+// strip kernel where adaf_stem7x7_rows_ok, else the cheaper tile height; STRIP / TILE4 / TILE6 = that kernel at any n (false: no strip kernel
+// at this patch size, nothing launched)
+bool adaf_launch_stem7x7_pool(const float* x4, int n, int P, const float* wr, const float* scale, const float* bias, float* out,
+                              int cus, hipStream_t s, bool out16, int form) {
     StemArgs a;
     a.x = x4; a.w = wr; a.scale = scale; a.bias = bias; a.out = out; a.act = nullptr; a.fpa = 1; a.H = a.W = 0; a.nframes = n;
     a.n = n; a.P = P; a.OH = (P + 6 - 7) / 2 + 1; a.OW = a.OH; a.PH = (a.OH - 1) / 2 + 1; a.PW = a.PH;
-    if (adaf_stem7x7_rows_ok(P, n, cus) && launch_rows_for<0>(a, cus, s, out16)) return;
+    if (form == ADAF_STEM_FORM_STRIP) return launch_rows_for<0>(a, cus, s, out16);
+    if (form == ADAF_STEM_FORM_AUTO && adaf_stem7x7_rows_ok(P, n, cus) && launch_rows_for<0>(a, cus, s, out16)) return true;
     // rows of pooled pixels per tile: 4 (5 waves) or 6 (7 waves), whichever computes fewer conv pixels for this map
-    const int cost4 = ((a.PH + 3) / 4) * PoolCfg<4>::NWV, cost6 = ((a.PH + 5) / 6) * PoolCfg<6>::NWV;
-    if (cost6 < cost4) launch_pool<6>(a, cus, s, out16);
+    const bool six = form == ADAF_STEM_FORM_AUTO ? adaf_stem7x7_pool_pays(P) : form == ADAF_STEM_FORM_TILE6;
+    if (six) launch_pool<6>(a, cus, s, out16);
     else launch_pool<4>(a, cus, s, out16);
+    return true;
 }

@@ -625,6 +625,66 @@ def stem7x7_bn_relu(patches_nhwc4, w_oihw, scale, bias):
     return out
 
 
+STEM_FORMS = {"auto": L.STEM_FORM_AUTO, "tile4": L.STEM_FORM_TILE4, "tile6": L.STEM_FORM_TILE6, "strip": L.STEM_FORM_STRIP,
+              "unfused": L.STEM_FORM_UNFUSED}
+_STEM_FORM_NAMES = {v: k for k, v in STEM_FORMS.items()}
+
+
+def stem7x7_pool_form(n, patch, device=None):
+    """The form the trunk's walk takes for n patches of patch^2 with fusion on: 'strip', 'tile4', 'tile6' or 'unfused'."""
+    dev = _current(device)
+    return _STEM_FORM_NAMES[L.load_library().adaf_stem7x7_pool_form(L.handle(dev), int(n), int(patch))]
+
+
+def stem7x7_pool(patches_nhwc4, w_oihw, scale, bias, form="auto", half=False, return_form=False):
+    """The trunk's stem + max-pool, one form at a time (adaf_stem7x7_pool; a test surface): (N,P,P,4) patches -> the pooled map
+    (N,PH,PH,64), fp32 or (half) fp16.  form: 'auto' (the walk's own choice), 'tile4', 'tile6', 'strip' (P 64 / 96 / 128 / 144 only)
+    or 'unfused'.  return_form: -> (map, the name of the form that ran)."""
+    L.need_gpu_f32(patches_nhwc4, w_oihw, scale, bias)
+    x, w, scale, bias = (t.contiguous() for t in (patches_nhwc4, w_oihw, scale, bias))
+    n, p, p2, c = x.shape
+    if c != 4 or p != p2 or tuple(w.shape) != (64, 3, 7, 7):
+        raise ValueError("stem7x7_pool: square (N,P,P,4) patches and a (64,3,7,7) filter expected")
+    code = STEM_FORMS[form]
+    oh = (p - 1) // 2 + 1
+    ph = (oh - 1) // 2 + 1
+    ws, ws_bytes = _workspace("adaf_stem7x7_workspace_bytes", x.device)
+    resolved = code or STEM_FORMS[stem7x7_pool_form(n, p, x.device)]
+    conv_map = torch.empty((n, oh, oh, 64), device=x.device, dtype=torch.float32) if resolved == L.STEM_FORM_UNFUSED else None
+    out = torch.empty((n, ph, ph, 64), device=x.device, dtype=torch.float16 if half else torch.float32)
+    used = C.c_int(-1)
+    _call("adaf_stem7x7_pool", x, x, n, p, w, scale, bias, code, DTYPE_F16 if half else DTYPE_F32, out, conv_map, C.byref(used), ws, ws_bytes)
+    return (out, _STEM_FORM_NAMES[used.value]) if return_form else out
+
+
+def stem7x7_pool_frames(frames, actions, patch, w_oihw, scale, bias, frames_per_action=1, half=False):
+    """The strip kernel gathering its own windows (adaf_stem7x7_pool_frames; a test surface): frames (N,3,H,W) planar or (N,H,W,4)
+    pixel-major, actions (k * N / frames_per_action, 2) fp32 (y, x) -> the pooled map (k * N, PH, PH, 64) of the patches get_patch cuts."""
+    L.need_gpu_f32(frames, actions, w_oihw, scale, bias)
+    x, act, w, scale, bias = (t.contiguous() for t in (frames, actions, w_oihw, scale, bias))
+    layout, nf, ch, hh, ww = _frame_geometry(x)
+    fpa, p = int(frames_per_action), int(patch)
+    if ch != 3 or act.dim() != 2 or act.shape[1] != 2 or tuple(w.shape) != (64, 3, 7, 7) or fpa < 1 or nf % fpa or act.shape[0] % (nf // fpa):
+        raise ValueError("stem7x7_pool_frames: 3-channel frames, (k * N / frames_per_action, 2) actions and a (64,3,7,7) filter expected")
+    n = act.shape[0] // (nf // fpa) * nf
+    ph = p // 4
+    ws, ws_bytes = _workspace("adaf_stem7x7_workspace_bytes", x.device)
+    out = torch.empty((n, ph, ph, 64), device=x.device, dtype=torch.float16 if half else torch.float32)
+    _call("adaf_stem7x7_pool_frames", x, x, layout, nf, hh, ww, act, act.shape[0], fpa, p, w, scale, bias, DTYPE_F16 if half else DTYPE_F32, out,
+          ws, ws_bytes)
+    return out
+
+
+def maxpool3x3s2_f16out(x):
+    """nn.MaxPool2d(3, 2, 1) of an fp32 NHWC map with an fp16 store (one rounding of the fp32 maximum): the fp16 trunk's unfused front."""
+    L.need_gpu_f32(x)
+    x = x.contiguous()
+    n, hh, ww, c = x.shape
+    out = torch.empty((n, (hh - 1) // 2 + 1, (ww - 1) // 2 + 1, c), device=x.device, dtype=torch.float16)
+    _call("adaf_maxpool3x3s2_f16out", x, x, n, hh, ww, c, out)
+    return out
+
+
 def _conv2d_wgrad(who, x, g, w_shape, stride, pad):
     """Both split-K weight gradients: the entry point adaf_<who>_f32 with its workspace query."""
     L.need_gpu_f32(x, g)

@@ -762,6 +762,33 @@ int adaf_ppo_encoder_bn_backward_f32(adaf_handle* h, const float* states, const 
 size_t adaf_stem7x7_workspace_bytes(void);
 int adaf_stem7x7_bn_relu_f32(adaf_handle* h, const float* patches_nhwc4, int n, int patch, const float* w_oihw, const float* scale,
                              const float* bias, float* out, void* ws, size_t ws_bytes, void* stream);
+/* The pooled forms of the same stem, each as a launch of its own: a read-only test surface over the launchers the adaf_resnet50_* walk uses
+ * (tests/test_stem_forms_gpu.py holds every form to float64).  All compute
+ *     max_pool2d(relu(conv2d(x[..., :3], w, stride 2, pad 3) * scale + bias), 3, 2, 1)
+ * into out [n, ph, ph, 64], ph = (oh - 1) / 2 + 1, as fp32 (out_dtype ADAF_DTYPE_F32) or fp16 (ADAF_DTYPE_F16: ONE round-to-nearest-even
+ * of the fp32 pooled value, the ADAF_MATH_F16 trunk's store).  Lane 3 of the NHWC4 input is not read.  Workspace:
+ * adaf_stem7x7_workspace_bytes(), the same packed filter bank.
+ * adaf_stem7x7_pool_form: the form the walk takes for n patches of patch^2 with fusion on (adaf_resnet50_set_fusion(1)) and the global
+ *   options as they are: one of ADAF_STEM_FORM_TILE4 .. ADAF_STEM_FORM_UNFUSED.  Host arithmetic; 0 for a non-positive extent.
+ * adaf_stem7x7_pool: patches_nhwc4 [n, patch, patch, 4].  form: ADAF_STEM_FORM_AUTO = adaf_stem7x7_pool_form's; TILE4 / TILE6 = the tile
+ *   kernel with 4 / 6 pooled rows per tile at any patch size; STRIP = the strip-walking kernel, at any n (its n >= CUs rule is a performance
+ *   choice), patch 64 / 96 / 128 / 144 only -- any other size is ADAF_E_BADARG, never another kernel; UNFUSED = adaf_stem7x7_bn_relu_f32's
+ *   launch into conv_map [n, oh, oh, 64] fp32, then the stand-alone max-pool.  conv_map is read and written by the UNFUSED form only (NULL
+ *   there is ADAF_E_BADARG) and may be NULL otherwise.  *form_used (may be NULL) receives the form that ran.
+ * adaf_stem7x7_pool_frames: the strip kernel gathering its own windows, addressed as adaf_resnet50_forward_frames: frames [n_frames, 3, H, W]
+ *   (ADAF_LAYOUT_NCHW) or [n_frames, H, W, 4] (ADAF_LAYOUT_NHWC4), action_yx [n_actions, 2], n_actions = k * n_frames / frames_per_action;
+ *   out [k * n_frames, ph, ph, 64].  At any n.  What the kernel cannot do is refused: patch not 64 / 96 / 128 / 144, patch > height,
+ *   width < height, n_frames not a multiple of frames_per_action, n_actions not a multiple of n_frames / frames_per_action.
+ * adaf_maxpool3x3s2_f16out: adaf_maxpool3x3s2_f32 with the fp16 store of the ADAF_MATH_F16 trunk's unfused front: x fp32, out_f16
+ *   [n, oh, ow, c] = one rounding of the fp32 maximum.  c % 4 == 0, 16-byte aligned x, 8-byte aligned out. */
+enum { ADAF_STEM_FORM_AUTO = 0, ADAF_STEM_FORM_TILE4 = 1, ADAF_STEM_FORM_TILE6 = 2, ADAF_STEM_FORM_STRIP = 3, ADAF_STEM_FORM_UNFUSED = 4 };
+int adaf_stem7x7_pool_form(const adaf_handle* h, int n, int patch);
+int adaf_stem7x7_pool(adaf_handle* h, const float* patches_nhwc4, int n, int patch, const float* w_oihw, const float* scale, const float* bias,
+                      int form, int out_dtype, void* out, float* conv_map, int* form_used, void* ws, size_t ws_bytes, void* stream);
+int adaf_stem7x7_pool_frames(adaf_handle* h, const float* frames, int frames_layout, int n_frames, int height, int width, const float* action_yx,
+                             int n_actions, int frames_per_action, int patch, const float* w_oihw, const float* scale, const float* bias,
+                             int out_dtype, void* out, void* ws, size_t ws_bytes, void* stream);
+int adaf_maxpool3x3s2_f16out(adaf_handle* h, const float* x, int n, int hh, int ww, int c, void* out_f16, void* stream);
 size_t adaf_conv2d_wgrad_workspace_bytes(const adaf_conv_params* p);
 int adaf_conv2d_wgrad_f32(adaf_handle* h, const adaf_conv_params* p, const float* x, const float* g, float* dw_ohwi, void* ws,
                           size_t ws_bytes, void* stream);

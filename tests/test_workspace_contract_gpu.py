@@ -592,6 +592,67 @@ def test_ppo_encoder_backward_workspace(dev, ops, t, b):
     contract("ppo", "ppo_encoder_backward T%d B%d" % (t, b), dev, need, call, spec, wrapper, align=(t == 5))
 
 
+def _stem_params(dev):
+    w = rnd((64, 3, 7, 7), 1030, 147 ** -0.5).to(dev)
+    return w, (rnd((64,), 1031, 0.2) + 1.0).to(dev), rnd((64,), 1032, 0.1).to(dev)
+
+
+@pytest.mark.parametrize("form,p,half", [("tile4", 50, False), ("tile6", 37, True), ("strip", 64, False), ("strip", 96, True), ("unfused", 33, False),
+                                         ("unfused", 33, True), ("auto", 96, False), ("auto", 100, True)])
+def test_stem_pool_workspace(dev, ops, form, p, half):
+    """adaf_stem7x7_pool, every form: the workspace is adaf_stem7x7_bn_relu_f32's packed filter bank (no size query of its own)."""
+    lib, h = L.load_library(), L.handle(dev)
+    n = 3
+    x = [_x4(n, p, 1033 + i, dev) for i in (0, 1)]
+    w, scale, bias = _stem_params(dev)
+    oh = (p - 1) // 2 + 1
+    ph = (oh - 1) // 2 + 1
+    need = lib.adaf_stem7x7_workspace_bytes()
+    assert need == 2 * 74 * 64 * 4
+    conv_map = torch.empty((n, oh, oh, 64), device=dev)
+    dtype = torch.float16 if half else torch.float32
+
+    def call(ws, nb, o, alt):
+        return lib.adaf_stem7x7_pool(h, L.ptr(x[alt]), n, p, L.ptr(w), L.ptr(scale), L.ptr(bias), ops.STEM_FORMS[form], L.DTYPE_F16 if half else L.DTYPE_F32,
+                                     L.ptr(o["out"]), L.ptr(conv_map), None, L.ptr(ws), nb, L.stream_ptr())
+    contract("stem", "stem7x7_pool %s P%d %s" % (form, p, dtype), dev, need, call, {"out": ((n, ph, ph, 64), dtype)},
+             lambda: {"out": ops.stem7x7_pool(x[0], w, scale, bias, form=form, half=half)}, align=(form == "strip" and not half))
+
+
+@pytest.mark.parametrize("layout,half", [("nchw", False), ("nhwc4", True)])
+def test_stem_pool_frames_workspace(dev, ops, layout, half):
+    lib, h = L.load_library(), L.handle(dev)
+    nf, hw, p, fpa, k = 4, 80, 64, 2, 2
+    fr = [rnd((nf, 3, hw, hw), 1040 + i).to(dev) for i in (0, 1)]
+    if layout == "nhwc4":
+        from adafocus_amd.utils import nchw_to_nhwc4
+        fr = [nchw_to_nhwc4(f).contiguous() for f in fr]
+    act = torch.from_numpy(np.random.Generator(np.random.PCG64(1042)).random((k * nf // fpa, 2), dtype=np.float32)).to(dev)
+    w, scale, bias = _stem_params(dev)
+    need = lib.adaf_stem7x7_workspace_bytes()
+    code = L.LAYOUT_NHWC4 if layout == "nhwc4" else L.LAYOUT_NCHW
+    dtype = torch.float16 if half else torch.float32
+
+    def call(ws, nb, o, alt):
+        return lib.adaf_stem7x7_pool_frames(h, L.ptr(fr[alt]), code, nf, hw, hw, L.ptr(act), act.shape[0], fpa, p, L.ptr(w), L.ptr(scale), L.ptr(bias),
+                                            L.DTYPE_F16 if half else L.DTYPE_F32, L.ptr(o["out"]), L.ptr(ws), nb, L.stream_ptr())
+    contract("stem", "stem7x7_pool_frames %s %s" % (layout, dtype), dev, need, call, {"out": ((k * nf, p // 4, p // 4, 64), dtype)},
+             lambda: {"out": ops.stem7x7_pool_frames(fr[0], act, p, w, scale, bias, frames_per_action=fpa, half=half)}, align=not half)
+
+
+def test_stem_conv_workspace(dev, ops):
+    """adaf_stem7x7_bn_relu_f32, the training walk's stem: the same workspace."""
+    lib, h = L.load_library(), L.handle(dev)
+    n, p = 3, 33
+    x = [_x4(n, p, 1050 + i, dev) for i in (0, 1)]
+    w, scale, bias = _stem_params(dev)
+    need = lib.adaf_stem7x7_workspace_bytes()
+
+    def call(ws, nb, o, alt):
+        return lib.adaf_stem7x7_bn_relu_f32(h, L.ptr(x[alt]), n, p, L.ptr(w), L.ptr(scale), L.ptr(bias), L.ptr(o["out"]), L.ptr(ws), nb, L.stream_ptr())
+    contract("stem", "stem7x7_bn_relu P%d" % p, dev, need, call, {"out": (n, 17, 17, 64)}, lambda: {"out": ops.stem7x7_bn_relu(x[0], w, scale, bias)}, align=True)
+
+
 # ------------------------------------------------------------------------------------------------------------------ non-positive extents
 def test_queries_return_zero_for_non_positive_extents_and_the_calls_are_refused(dev, ops):
     lib, h = L.load_library(), L.handle(dev)
